@@ -7,7 +7,13 @@ B=1024 rows per GPU, H=HH=128, C=21, times=arange(101), 30 % NaN observations ->
 coefficients (1024, 100, 84), dt=1 -> N=100 Euler steps, ts=[0, 100], Brownian increments from the
 in-kernel Philox generator, inputs resident in HBM.  value = rows x solver-steps x K / wall time.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, runs W warm-up solves, times K solves and prints the result line (`value`, `ms_per_step` = wall time
+of one timed solve).  --dump-outputs DIR writes what the last timed solve returned (the solver states `ys`, float32) as
+DIR/ys.npy (DIR/ys_rank<r>.npy per rank when N > 1); the inputs are seeded, so two builds can be compared output for output.
+--full adds everything else: HIP-event timing spreads and the roofline of the solve kernel, the CPU baseline and the
+`extra` legs below, and writes the full record.
 
 --gpus N > 1 run as plain `python bench.py --gpus N` re-executes itself under
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1` (one process per GPU over
@@ -512,18 +518,20 @@ LINE_LIMIT = 4096      # the driver keeps a bounded tail of stdout: r05's 21 KB 
 
 
 def compact_line(out):
-    """The ONE JSON line of the bench contract: contract keys, the roofline / cpu_baseline objects and the per-leg `summary` - numbers
-    only, no prose (the full record with every `extra` leg, timing spreads and provenance notes goes to a file, see main)."""
-    r = out["roofline"]
+    """The ONE JSON line of the bench contract: contract keys and, with --full, the roofline / cpu_baseline objects and the per-leg
+    `summary` - numbers only, no prose (the full record with every `extra` leg, timing spreads and provenance notes goes to a file,
+    see main)."""
     line = {k: out[k] for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                                 "vs_baseline", "dtype", "data")}
     line["config"] = {k: out["config"][k] for k in ("workload", "rows_per_gpu", "solver_steps", "global_rows", "parallelism", "kernel",
                                                     "prepare")}
-    line["roofline"] = {"bound": r["bound"], "achieved": round(r["achieved"], 3), "peak": r["peak"], "unit": r["unit"],
-                        "frac": round(r["frac"], 4), "traffic": r["traffic"], "kernel_ms": round(r["kernel_ms"], 5),
-                        "executed_frac": round(r["executed_frac"], 4), "flop_per_rowstep": r["flop_per_rowstep"],
-                        "bytes_per_rowstep": r["bytes_per_rowstep"], "hbm_frac": round(r["hbm_frac"], 5),
-                        "launched_path": r["launched_path"]}
+    if "roofline" in out:
+        r = out["roofline"]
+        line["roofline"] = {"bound": r["bound"], "achieved": round(r["achieved"], 3), "peak": r["peak"], "unit": r["unit"],
+                            "frac": round(r["frac"], 4), "traffic": r["traffic"], "kernel_ms": round(r["kernel_ms"], 5),
+                            "executed_frac": round(r["executed_frac"], 4), "flop_per_rowstep": r["flop_per_rowstep"],
+                            "bytes_per_rowstep": r["bytes_per_rowstep"], "hbm_frac": round(r["hbm_frac"], 5),
+                            "launched_path": r["launched_path"]}
     if "cpu_baseline" in out:
         c = out["cpu_baseline"]
         line["cpu_baseline"] = {"value": round(c["value"], 1), "unit": c["unit"], "cores": c["cores"], "kind": c["kind"],
@@ -568,10 +576,14 @@ def main():
     ap.add_argument('--steps', type=int, default=50)
     ap.add_argument('--warmup', type=int, default=10)
     ap.add_argument('--kernel', default='auto')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extra', action='store_true', help='skip the K3 / K5 strong-scaling legs')
+    ap.add_argument('--full', action='store_true', help='also measure the timing spreads, roofline, CPU baseline and extra legs')
+    ap.add_argument('--dump-outputs', metavar='DIR', help="write the last timed solve's outputs as DIR/<name>.npy")
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-extra', action='store_true', help='with --full: skip the extra legs')
     ap.add_argument('--exact-order', action='store_true', help='keep the unfused emb(linear_in) operation order')
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         self_launch(args)
@@ -617,20 +629,24 @@ def main():
         call.launch(stream)          # the engine's call, as sdeint makes it: prepare launch (weight pack + time table) + fused solve
     barrier()
     elapsed = maxr(time.perf_counter() - t0)
+    ys = call.ys.cpu().numpy()            # what the last timed solve returned (the --full launches below overwrite call.ys)
+    assert bool(np.isfinite(ys).all()), 'non-finite solver output'
+    if args.dump_outputs:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, 'ys.npy' if world == 1 else f'ys_rank{rank}.npy'), ys)
 
-    # per-solve HIP-event timings on the launch stream: the whole call, and the dominant kernel alone (prepared
-    # workspace reused)
-    t_call_prep = event_times_ms(lambda: call.launch(stream), stream, max(50, args.steps), 10)     # as timed in `value`
-    t_call = event_times_ms(lambda: call.launch(stream, auto_reuse=True), stream, 50, 10)          # evaluation epochs: prepared workspace reused
-    t_kern = event_times_ms(lambda: call.launch(stream, reuse_prepared=True), stream, 50, 10)
-    kern_ms = float(np.median(t_kern))
-    ys = call.ys
-    assert bool(torch.isfinite(ys).all()), 'non-finite solver output'
+    if args.full:
+        # per-solve HIP-event timings on the launch stream: the whole call, and the dominant kernel alone (prepared
+        # workspace reused)
+        t_call_prep = event_times_ms(lambda: call.launch(stream), stream, max(50, args.steps), 10)     # as timed in `value`
+        t_call = event_times_ms(lambda: call.launch(stream, auto_reuse=True), stream, 50, 10)          # evaluation epochs: prepared workspace reused
+        t_kern = event_times_ms(lambda: call.launch(stream, reuse_prepared=True), stream, 50, 10)
+        kern_ms = float(np.median(t_kern))
 
     # `extra`: the widened rows first, the BASELINE.json configurations LAST, and a compact `summary` of the latter as the very last
     # key of the line - a record that keeps only the tail of stdout still carries every BASELINE leg
     extra = {}
-    if not args.no_extra:
+    if args.full and not args.no_extra:
         if world == 1:
             extra["tutorial_field"] = tutorial_field(dev, stream)
             extra["K1_tutorial_lsde"] = tutorial_field(dev, stream, kind='lsde', rows=256, hh=32, n=50)
@@ -652,11 +668,6 @@ def main():
     if rank == 0:
         rowsteps = B * NSTEP
         value = world * rowsteps * args.steps / elapsed
-        ach_tf = rowsteps * FLOP_PER_ROWSTEP / (kern_ms * 1e-3) / 1e12
-        exe_tf = rowsteps * EXECUTED_FLOP_PER_ROWSTEP / (kern_ms * 1e-3) / 1e12
-        ach_gbs = rowsteps * BYTES_PER_ROWSTEP / (kern_ms * 1e-3) / 1e9
-        launched = S.engine.forward_path(model, B, L, NSTEP, kernel=args.kernel)
-        traffic = HBM_TRAFFIC_BYTES_PER_LAUNCH if launched == HBM_TRAFFIC_KERNEL[0] and not args.exact_order else None
         out = {
             "metric": "SDE solver steps/sec (batch x steps / s), forward solve",
             "value": value, "unit": "row-steps/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
@@ -667,33 +678,42 @@ def main():
                        "rows_per_gpu": B, "solver_steps": NSTEP, "global_rows": world * B,
                        "parallelism": f"row-shard x{world}, no collective in the solver", "kernel": args.kernel,
                        "prepare": "every call (weight pack + time table launch inside the timed region, as r01-r04)"},
-            "timing": {"solve_call": spread(t_call), "solve_call_with_prepare": spread(t_call_prep), "solve_kernel": spread(t_kern),
-                       "note": "solve_call_with_prepare: SolveCall.launch as timed in `value` (prepare launch + solve kernel, what sdeint "
-                               "does per call; r05 timed the reuse form); solve_call: launch(auto_reuse=True) - the prepared workspace "
-                               "(packed weights, time table) reused while the parameter block's version counter stands (evaluation epochs)",
-                       "method": "HIP events on the launch stream, one pair per solve, after 10 warm-ups (SURVEY 8d)"},
-            "roofline": {"bound": "mfma", "achieved": ach_tf, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
-                         "frac": ach_tf / PEAK_FP32_TFLOPS, "traffic": traffic,
-                         "traffic_source": HBM_TRAFFIC_SOURCE if traffic else f"none: the launched path {launched!r} is not the profiled one",
-                         "launched_path": launched, "profiled_kernel": HBM_TRAFFIC_KERNEL[1],
-                         "kernel_ms": kern_ms, "flop_per_rowstep": FLOP_PER_ROWSTEP, "bytes_per_rowstep": BYTES_PER_ROWSTEP,
-                         "executed_flop_per_rowstep": EXECUTED_FLOP_PER_ROWSTEP, "executed_frac": exe_tf / PEAK_FP32_TFLOPS,
-                         "mfma_issue_cycles_per_simd_step": MFMA_CYCLES_PER_STEP,
-                         "kernel_ns_per_step": kern_ms * 1e6 / NSTEP,
-                         "hbm_frac": ach_gbs / PEAK_HBM_GBS, "hbm_achieved_GBs": ach_gbs,
-                         "note": "fp32 FMA/MFMA roof binds (intensity ~490 FLOP/B); frac counts the reference's algorithmic "
-                                 "FLOPs, executed_frac the MFMA FLOPs the kernel issues (folded first layer); the kernel issues "
-                                 "1664 MFMA cycles per SIMD and step (two waves x 104 x 8) - measured MFMA-busy share and clock: "
-                                 "profiles/r06_pmc_counters.txt (SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE); hbm_* = algorithmic 346 B/row-step"},
         }
+        if args.full:
+            ach_tf = rowsteps * FLOP_PER_ROWSTEP / (kern_ms * 1e-3) / 1e12
+            exe_tf = rowsteps * EXECUTED_FLOP_PER_ROWSTEP / (kern_ms * 1e-3) / 1e12
+            ach_gbs = rowsteps * BYTES_PER_ROWSTEP / (kern_ms * 1e-3) / 1e9
+            launched = S.engine.forward_path(model, B, L, NSTEP, kernel=args.kernel)
+            traffic = HBM_TRAFFIC_BYTES_PER_LAUNCH if launched == HBM_TRAFFIC_KERNEL[0] and not args.exact_order else None
+            out["timing"] = {"solve_call": spread(t_call), "solve_call_with_prepare": spread(t_call_prep), "solve_kernel": spread(t_kern),
+                             "note": "solve_call_with_prepare: SolveCall.launch as timed in `value` (prepare launch + solve kernel, what "
+                                     "sdeint does per call; r05 timed the reuse form); solve_call: launch(auto_reuse=True) - the prepared "
+                                     "workspace (packed weights, time table) reused while the parameter block's version counter stands "
+                                     "(evaluation epochs)",
+                             "method": "HIP events on the launch stream, one pair per solve, after 10 warm-ups (SURVEY 8d)"}
+            out["roofline"] = {"bound": "mfma", "achieved": ach_tf, "peak": PEAK_FP32_TFLOPS, "unit": "TFLOP/s",
+                               "frac": ach_tf / PEAK_FP32_TFLOPS, "traffic": traffic,
+                               "traffic_source": HBM_TRAFFIC_SOURCE if traffic else f"none: the launched path {launched!r} is not the profiled one",
+                               "launched_path": launched, "profiled_kernel": HBM_TRAFFIC_KERNEL[1],
+                               "kernel_ms": kern_ms, "flop_per_rowstep": FLOP_PER_ROWSTEP, "bytes_per_rowstep": BYTES_PER_ROWSTEP,
+                               "executed_flop_per_rowstep": EXECUTED_FLOP_PER_ROWSTEP, "executed_frac": exe_tf / PEAK_FP32_TFLOPS,
+                               "mfma_issue_cycles_per_simd_step": MFMA_CYCLES_PER_STEP,
+                               "kernel_ns_per_step": kern_ms * 1e6 / NSTEP,
+                               "hbm_frac": ach_gbs / PEAK_HBM_GBS, "hbm_achieved_GBs": ach_gbs,
+                               "note": "fp32 FMA/MFMA roof binds (intensity ~490 FLOP/B); frac counts the reference's algorithmic "
+                                       "FLOPs, executed_frac the MFMA FLOPs the kernel issues (folded first layer); the kernel issues "
+                                       "1664 MFMA cycles per SIMD and step (two waves x 104 x 8) - measured MFMA-busy share and clock: "
+                                       "profiles/r06_pmc_counters.txt (SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE); hbm_* = algorithmic "
+                                       "346 B/row-step"}
         if extra:
             out["extra"] = extra
-        if not args.no_cpu_baseline and world == 1:     # reported at N = 1 only (the other ranks would idle behind it)
+        if args.full and not args.no_cpu_baseline and world == 1:     # reported at N = 1 only (the other ranks would idle behind it)
             out["cpu_baseline"] = cpu_baseline(pr, params)
             out["speedup_vs_cpu"] = value / world / out["cpu_baseline"]["value"]
         if extra:
             out["summary"] = summary_of(out, extra)
-        out["full_record"] = write_full_record(out)
+        if args.full:
+            out["full_record"] = write_full_record(out)
         line = compact_line(out)
     else:
         line = None

@@ -64,3 +64,13 @@ def test_bench_line_without_extra_legs_or_cpu_baseline():
         out.pop(k)
     line = json.loads(bench.compact_line(out))
     assert "roofline" in line and "cpu_baseline" not in line and "summary" not in line
+
+
+def test_plain_run_line_carries_the_contract_keys_without_the_full_figures():
+    out = canned()
+    for k in ("timing", "roofline", "extra", "summary", "cpu_baseline", "speedup_vs_cpu", "full_record"):
+        out.pop(k)
+    line = json.loads(bench.compact_line(out))
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step", "steps", "warmup", "n_gpus", "config"):
+        assert k in line, k
+    assert not {"roofline", "cpu_baseline", "summary", "full_record"} & set(line)

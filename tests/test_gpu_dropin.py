@@ -485,7 +485,7 @@ def test_uninstantiated_hidden_sizes_run_zero_padded_on_the_mfma_kernels(ci, mon
 
 
 def test_bench_runs_its_rccl_branch_on_one_gpu_and_emits_the_contract_line():
-    """`python bench.py` with SNSDE_BENCH_FORCE_DIST=1: the process group (nccl = RCCL), the barrier / max-over-ranks timing and
+    """`python bench.py --full` with SNSDE_BENCH_FORCE_DIST=1: the process group (nccl = RCCL), the barrier / max-over-ranks timing and
     the K5 gradient all-reduce run at world size 1; the last stdout line is the contract's JSON with roofline objects on the
     headline and on the strong-scaling legs."""
     import json
@@ -493,7 +493,7 @@ def test_bench_runs_its_rccl_branch_on_one_gpu_and_emits_the_contract_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, SNSDE_BENCH_FORCE_DIST='1', MASTER_ADDR='127.0.0.1', MASTER_PORT='29533', HSA_ENABLE_IPC_MODE_LEGACY='0')
-    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--steps', '5', '--warmup', '2', '--no-cpu-baseline'],
+    r = subprocess.run([sys.executable, os.path.join(root, 'bench.py'), '--full', '--steps', '5', '--warmup', '2', '--no-cpu-baseline'],
                        capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     text = r.stdout.strip().splitlines()[-1]
@@ -507,3 +507,33 @@ def test_bench_runs_its_rccl_branch_on_one_gpu_and_emits_the_contract_line():
     assert full['roofline']['traffic_source'] and full['value'] == line['value']
     for leg in ('K3_strong', 'K5_strong_train'):
         assert 0.0 < full['extra'][leg]['roofline']['frac'] < 1.0, leg
+
+
+def test_plain_bench_run_times_the_given_steps_and_dumps_what_the_last_step_computed(tmp_path):
+    """`python bench.py` without --full: the result line carries the contract keys and none of the --full figures, `steps` is the
+    number asked for, and --dump-outputs writes the last timed solve's states - the same array whatever the step count (seeded
+    inputs, fixed Philox seed) and the one a direct SolveCall on bench.py's inputs returns."""
+    import json
+    import bench
+    dumps = []
+    for steps in (3, 7):
+        d = tmp_path / f'steps{steps}'
+        r = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '1', '--dump-outputs', str(d)],
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        line = json.loads(r.stdout.strip().splitlines()[-1])
+        assert line['steps'] == steps and line['warmup'] == 1 and line['n_gpus'] == 1 and line['dtype'] == 'f32'
+        assert line['unit'] == 'row-steps/s' and line['higher_is_better'] is True and line['value'] > 1e7
+        assert abs(line['value'] - bench.B * bench.NSTEP / (line['ms_per_step'] * 1e-3)) <= 1e-6 * line['value']
+        assert not {'roofline', 'cpu_baseline', 'summary', 'full_record'} & set(line), sorted(line)
+        assert sorted(os.listdir(d)) == ['ys.npy']
+        ys = np.load(d / 'ys.npy')
+        assert ys.dtype == np.float32 and ys.shape == (2, bench.B, bench.H) and np.isfinite(ys).all()
+        dumps.append(ys)
+    assert np.array_equal(dumps[0], dumps[1])
+    dev = torch.device(DEV)
+    pr, _, flat, coeffs, y0 = bench.build_inputs(dev, 0)
+    model = S.engine.model_struct(bench.C, bench.H, bench.H, bench.NL, bench.IO, bench.NO)
+    grid = S.engine.step_grid(np.array([0.0, float(bench.NSTEP)], np.float32), 1.0, pr['times'], dev)
+    ys = S.engine.SolveCall(model, flat, coeffs, grid, y0, method='euler', seed=2024).launch()
+    assert np.array_equal(ys.cpu().numpy(), dumps[0])

@@ -184,4 +184,8 @@ def test_package_training_loop_reproduces_the_reference_common_sde_loop_trace():
     np.testing.assert_allclose(trace, gold['trainloop/trace'], rtol=2e-5, atol=2e-6)
     sd = model.state_dict()
     for k in sd:
-        np.testing.assert_allclose(sd[k].numpy(), gold['trainloop/final_sd/' + k], rtol=2e-4, atol=2e-6, err_msg=k)
+        # model.linear.0 feeds a training-mode BatchNorm, so its bias has a zero gradient in exact arithmetic: the ~1e-7 it gets is
+        # round-off, which Adam scales to steps of up to lr = 1e-2 in a direction set by the host's CPU kernels (instruction set,
+        # thread count: measured up to 2e-5 apart between hosts).  It is held to 1 % of one such step, the rest to fp32 round-off.
+        atol = 1e-4 if k == 'model.linear.0.bias' else 2e-6
+        np.testing.assert_allclose(sd[k].numpy(), gold['trainloop/final_sd/' + k], rtol=2e-4, atol=atol, err_msg=k)

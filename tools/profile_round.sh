@@ -4,10 +4,10 @@
 tag=${1:-r02}
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/$tag; mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python $R/bench.py --steps 50 --no-cpu-baseline --no-extra > $O/bench_prof.json 2> $O/bench_prof.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python $R/bench.py --full --steps 50 --no-cpu-baseline --no-extra > $O/bench_prof.json 2> $O/bench_prof.err
 cp $(find $O/stats -name '*kernel_stats.csv' | head -1) $O/${tag}_kernel_stats.csv
 for c in FETCH_SIZE WRITE_SIZE GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_INSTS_MFMA SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE; do
-  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o run -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra > /dev/null 2>&1
+  rocprofv3 --kernel-trace --pmc $c --output-format csv -d $O/pmc_$c -o run -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra > /dev/null 2>&1
 done
 python - <<PY > $O/${tag}_pmc_counters.txt
 import csv, glob
