@@ -4,7 +4,7 @@
 #include <stdio.h>
 #include <string.h>
 
-#include "snsde_internal.h"
+#include "snsde_mfma_kernels.h"      // (MfmaPlan: host side only, no kernel is instantiated here)
 
 namespace {
 
@@ -137,6 +137,34 @@ int snsde_build_net(const snsde_model& m, int32_t n_steps, SnsdeNet* net) {
     net->gt_tab = (no == 12 || no == 13 || no == 16 || no == 17) ? net->packed_floats : -1;
     (void)n_steps;
     return SNSDE_OK;
+}
+
+// field variants beyond the reference's Diffusion_model (tutorial fields): served by the lean 4-row-tile MFMA kernel only
+static bool is_variant(const snsde_model& m) {
+    return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0;
+}
+
+int snsde_flavor_hint(const snsde_solve* s) {
+    if (is_variant(s->model) || s->noise_table) return 1;      // tutorial-style fields: 4-row tiles only
+    return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
+}
+
+// Which kernel runs the forward solve of a descriptor (SNSDE_PATH_*): the one decision behind snsde_solve_forward and
+// snsde_forward_path.  An MFMA path carries the plan snsde_mfma_launch runs (the plan names the kernel).
+struct ForwardRoute { int path; snsde_mfma::MfmaPlan plan; };
+
+static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
+    ForwardRoute r{};      // (SNSDE_PATH_NONE)
+    const int k = s->kernel;
+    const bool variant = is_variant(s->model) || s->noise_table;
+    const int generic = s->method == SNSDE_SRK ? SNSDE_PATH_GENERIC_SRK : SNSDE_PATH_GENERIC;
+    if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
+    if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
+    if (k == SNSDE_KERNEL_GENERIC) { r.path = generic; return r; }
+    r.plan = make_plan(s, net, snsde_flavor_hint(s));
+    // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor
+    r.path = r.plan.ok ? snsde_mfma_path(r.plan) : (k == SNSDE_KERNEL_AUTO && !variant ? generic : SNSDE_PATH_NONE);
+    return r;
 }
 
 extern "C" {
@@ -307,11 +335,6 @@ int snsde_grid_srk_build(const float* step_tab, int32_t n_steps, const float* ti
     return SNSDE_OK;
 }
 
-// field variants beyond the reference's Diffusion_model (tutorial fields): served by the lean 4-row-tile MFMA kernel only
-static bool is_variant(const snsde_model& m) {
-    return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0;
-}
-
 static int validate_solve(const snsde_solve* s, bool eval) {
     if (!s) return SNSDE_ERR_NULL;
     if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;      // stale binding: refuse before reading any field
@@ -353,38 +376,18 @@ size_t snsde_workspace_bytes(const snsde_solve* s) {
 int snsde_solve_forward(const snsde_solve* s, void* hip_stream) {
     int rc = validate_solve(s, false);
     if (rc) return rc;
+    if (s->kernel < SNSDE_KERNEL_AUTO || s->kernel > SNSDE_KERNEL_MFMA_W4) return SNSDE_ERR_OPTION;
     if (s->workspace_bytes < snsde_workspace_bytes(s)) return SNSDE_ERR_WORKSPACE;
     SnsdeNet net;
     rc = snsde_build_net(s->model, s->n_steps, &net);
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    if (is_variant(s->model) || s->noise_table) {      // tutorial-style fields: the 4-row-tile MFMA kernels or nothing
-        if (s->kernel == SNSDE_KERNEL_GENERIC || s->kernel == SNSDE_KERNEL_MFMA_M16) return SNSDE_ERR_UNSUPPORTED;
-        return snsde_mfma_launch(s, net, st, 1);
-    }
-    if (s->method == SNSDE_SRK) {   // SRK: MFMA variant (M4 tiles) where instantiated, else the generic (all-options) family
-        if (s->kernel == SNSDE_KERNEL_MFMA_M16) return snsde_mfma_launch(s, net, st, 0);     // (H = 64 / 128, elementwise diffusions)
-        if (s->kernel == SNSDE_KERNEL_MFMA_M4) return snsde_mfma_launch(s, net, st, 1);
-        if (s->kernel == SNSDE_KERNEL_MFMA_W4) return snsde_mfma_launch(s, net, st, 2);
-        if (s->kernel == SNSDE_KERNEL_MFMA) return snsde_mfma_launch(s, net, st, -1);
-        if (s->kernel == SNSDE_KERNEL_AUTO && snsde_mfma_supported(s, net)) return snsde_mfma_launch(s, net, st, -1);
-        if (s->kernel != SNSDE_KERNEL_AUTO && s->kernel != SNSDE_KERNEL_GENERIC) return SNSDE_ERR_OPTION;
-        if (s->z0_weight && (rc = snsde_z0_launch(s, st)) != SNSDE_OK) return rc;
-        return snsde_srk_launch(s, net, st);
-    }
-    switch (s->kernel) {
-        case SNSDE_KERNEL_AUTO:
-            if (snsde_mfma_supported(s, net)) return snsde_mfma_launch(s, net, st, -1);
-            break;
-        case SNSDE_KERNEL_GENERIC: break;
-        case SNSDE_KERNEL_MFMA: return snsde_mfma_launch(s, net, st, -1);
-        case SNSDE_KERNEL_MFMA_M16: return snsde_mfma_launch(s, net, st, 0);
-        case SNSDE_KERNEL_MFMA_M4: return snsde_mfma_launch(s, net, st, 1);
-        case SNSDE_KERNEL_MFMA_W4: return snsde_mfma_launch(s, net, st, 2);
-        default: return SNSDE_ERR_OPTION;
-    }
+    const ForwardRoute r = route_forward(s, net);
+    if (r.path == SNSDE_PATH_NONE) return SNSDE_ERR_UNSUPPORTED;
+    if (r.plan.ok) return snsde_mfma_launch(s, net, r.plan, st);
     if (s->z0_weight && (rc = snsde_z0_launch(s, st)) != SNSDE_OK) return rc;
-    return snsde_generic_launch(s, net, static_cast<hipStream_t>(hip_stream), 0, nullptr, nullptr, nullptr, nullptr);
+    if (r.path == SNSDE_PATH_GENERIC_SRK) return snsde_srk_launch(s, net, st);
+    return snsde_generic_launch(s, net, st, 0, nullptr, nullptr, nullptr, nullptr);
 }
 
 // Host-only query: the kernel family snsde_solve_forward would launch for this descriptor (needs model, batch, knots,
@@ -392,28 +395,10 @@ int snsde_solve_forward(const snsde_solve* s, void* hip_stream) {
 // (snsde_solve_forward returns SNSDE_ERR_UNSUPPORTED and the host layer takes its tensor loop).
 int snsde_forward_path(const snsde_solve* s) {
     if (!s || s->struct_size != sizeof(snsde_solve) || validate_model(&s->model) || s->batch <= 0 || s->knots < 2 || s->n_steps <= 0) return SNSDE_PATH_NONE;
-    const int no = s->model.noise_option;
-    if (s->method == SNSDE_MILSTEIN && no == 7) return SNSDE_PATH_NONE;
+    if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return SNSDE_PATH_NONE;
     SnsdeNet net;
     if (snsde_build_net(s->model, s->n_steps, &net)) return SNSDE_PATH_NONE;
-    const bool variant = is_variant(s->model) || s->noise_table;
-    if (variant) {
-        if (s->kernel == SNSDE_KERNEL_GENERIC || s->kernel == SNSDE_KERNEL_MFMA_M16) return SNSDE_PATH_NONE;
-        return snsde_mfma_path(s, net, 1);
-    }
-    const int hint = s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
-    if (s->method == SNSDE_SRK) {
-        if (s->kernel == SNSDE_KERNEL_MFMA_M16) return snsde_mfma_path(s, net, 0);
-        if (s->kernel == SNSDE_KERNEL_MFMA_M4) return snsde_mfma_path(s, net, 1);
-        if (s->kernel == SNSDE_KERNEL_MFMA_W4) return snsde_mfma_path(s, net, 2);
-        if (s->kernel == SNSDE_KERNEL_MFMA) return snsde_mfma_path(s, net, -1);
-        if (s->kernel == SNSDE_KERNEL_AUTO && snsde_mfma_supported(s, net)) return snsde_mfma_path(s, net, -1);
-        return SNSDE_PATH_GENERIC_SRK;
-    }
-    if (s->kernel == SNSDE_KERNEL_GENERIC) return SNSDE_PATH_GENERIC;
-    const int path = snsde_mfma_path(s, net, hint);
-    if (path != SNSDE_PATH_NONE || s->kernel != SNSDE_KERNEL_AUTO) return path;
-    return SNSDE_PATH_GENERIC;
+    return route_forward(s, net).path;
 }
 
 int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, float* f_out, float* g_out,
@@ -538,7 +523,7 @@ int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* wor
     rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
     if (rc) return rc;
     if (snsde_backward_supported(&b->fwd) != 1) return SNSDE_ERR_UNSUPPORTED;
-    if (!b->delta_save && !snsde_mfma_w4_fused(b, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
+    if (!b->delta_save && !snsde_mfma_w4_fused_solve(&b->fwd, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
     // the adjoint's workspace is an INPUT of this pass (its per-workgroup diffusion-side sums; on the wave-group path the per-tile
     // weight-gradient blocks themselves): the descriptor must still carry it, at the size the adjoint was given
     if (!b->workspace) return SNSDE_ERR_NULL;
@@ -561,7 +546,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
     if (rc) return rc;
     if (snsde_backward_supported(&b->fwd) != 1) return SNSDE_ERR_UNSUPPORTED;
-    if (!b->delta_save && !snsde_mfma_w4_fused(b, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
+    if (!b->delta_save && !snsde_mfma_w4_fused_solve(&b->fwd, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
     if (b->workspace_bytes < snsde_backward_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
     if (pg_workspace_bytes < snsde_param_gradients_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);

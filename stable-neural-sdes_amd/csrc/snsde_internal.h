@@ -55,11 +55,15 @@ int snsde_generic_backward_launch(const snsde_backward* b, const SnsdeNet& net, 
 int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
 int snsde_time_table_srk_launch(const float* params, const float* srk_tab, float* gt, const SnsdeNet& net, int H, int no,
                                 int n_rows, hipStream_t stream);
-// launchers (snsde_mfma.hip)
-bool snsde_mfma_supported(const snsde_solve* s, const SnsdeNet& net);
-int snsde_mfma_path(const snsde_solve* s, const SnsdeNet& net, int flavor_hint);
+// tile-flavour hint of s->kernel (-1: chosen from the batch, 0: 16-row tiles, 1: 4-row tiles, 2: wave pairs), the same for the
+// forward's route and every backward query (snsde_api.hip)
+int snsde_flavor_hint(const snsde_solve* s);
+// launchers (snsde_mfma.hip); the plan (snsde_mfma_kernels.h) names the forward kernel
+namespace snsde_mfma { struct MfmaPlan; }
+snsde_mfma::MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint);
+int snsde_mfma_path(const snsde_mfma::MfmaPlan& p);
 size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
-int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int flavor_hint);
+int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream);
 bool snsde_mfma_backward_supported(const snsde_solve* s, const SnsdeNet& net);
 size_t snsde_mfma_backward_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream);
@@ -79,7 +83,6 @@ int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, fl
                                 const float* dth_part, hipStream_t stream);
 // (snsde_mfma.hip) does the backward of this solve take the wave-pair adjoint with fused weight gradients?  -> offsets (floats) of
 // the per-tile blocks and of the theta partial sums inside the backward workspace
-bool snsde_mfma_w4_fused(const snsde_backward* b, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off);
 bool snsde_mfma_w4_fused_solve(const snsde_solve* s, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off);
 // launchers (snsde_wgrad.hip)
 size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net);

@@ -720,6 +720,10 @@ int dispatch_lean_h32(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_lean_h64(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_lean_h128(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_lean_h128_two_tile(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);   // snsde_m4t_kernel.h
-int dispatch_lean_h256(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st, bool stream_all);   // snsde_m4s_kernel.h / snsde_m4s2_kernel.h
+int dispatch_lean_h256(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);            // snsde_m4s_kernel.h
+int dispatch_lean_h256_two_tile(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);   // snsde_m4s2_kernel.h
+// host-side mirrors of the two-tile instantiation lists (make_plan); save = training mode (act_save, traj or dW_out)
+bool m4t_instantiated(int nhid, int kuxt, bool save);
+bool m4s2_instantiated(int nhid, int kuxt, bool save);
 
 }  // namespace snsde_mfma

@@ -251,13 +251,14 @@ __global__ void snsde_srk_expand_kernel(const float* __restrict__ step_tab, cons
     o[10] = raw_time ? tn[0] : tn[1]; o[11] = raw_time ? 0.0f : tn[2];
 }
 
+}  // namespace
+
 // tutorial-style fields (variant switches of snsde_model / a caller-supplied noise table): the lean 4-row-tile kernels only
 static bool variant_of(const snsde_solve* s) {
     const snsde_model& m = s->model;
     return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0 || s->noise_table != nullptr;
 }
 
-// Which configurations the fast path is instantiated for.
 // Wave-owns-rows forward (snsde_w4.hip): forced by hint 2; under `auto` up to 6144 rows
 static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     // measured at the K4 shape (tools/time_w4.py, profiles/r05_time_w4.txt): 2048 rows 109 us against 156 (4-row tiles) / 216 (16-row
@@ -266,6 +267,7 @@ static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint)
     return (flavor_hint == 2 || (flavor_hint == -1 && (s->batch <= 6144 || s->method == SNSDE_SRK))) && snsde_w4_supported(s, net);
 }
 
+// The forward's plan: does the MFMA fast path take this descriptor (ok), its workspace layout, and the kernel that runs it
 MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     MfmaPlan p{};
     const int hint_in = flavor_hint;
@@ -334,7 +336,8 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     p.SRK = srk ? 1 : 0;
     if ((srk && !srk_m16_ok) || m4n) p.FL = 1;
     // the wave-pair kernels (snsde_w4.hip) take the forward AND the Euler adjoint: their per-tile partial sums are per 4 rows
-    if (hint_in < 0 && w4_takes(s, net, -1)) p.FL = 1;
+    const bool w4 = w4_takes(s, net, hint_in);
+    if (w4) p.FL = 1;
     p.M4N = m4n ? 1 : 0; p.KUXN = kuxn;
     p.FOLD = (emb && (nhid > 1 || p.KUX > 2 || srk || noise_net || !(s->flags & SNSDE_FLAG_EXACT_ORDER))) ? 1 : 0;   // exact order: NL <= 2, C <= 32 only
     // lean M4 kernel (snsde_m4_kernel.h): 4-row tiles, Euler / Milstein, elementwise diffusions, 32 <= H <= 128; the time
@@ -452,11 +455,19 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
         const bool kernel_ok = (p.LEAN && H <= 128 && !srk) || (srk && p.FL == 1 && !m4n);
         if (!shape_ok || !kernel_ok) return p;
     }
+    // the kernel; the two-tile lean kernels (relu fields with a y input) where instantiated, same results as the one-tile kernels they
+    // stand in for: at H = 256 unless SNSDE_FLAG_STREAM_ALL asks for the fully streamed one, at H = 128 under SNSDE_FLAG_TWO_TILE
+    const bool save = s->act_save || s->traj || s->dW_out, two_tile = m.activation == SNSDE_ACT_RELU && io != 0;
+    if (w4 || m4n || !p.LEAN) p.kernel = w4 ? FwdKernel::w4 : (m4n ? FwdKernel::m4n : (p.FL ? FwdKernel::general_m4 : FwdKernel::general_m16));
+    else if (H == 256) p.kernel = two_tile && !(s->flags & SNSDE_FLAG_STREAM_ALL) && m4s2_instantiated(nhid, kuxt, save)
+                                      ? FwdKernel::lean_two_tile_h256 : FwdKernel::lean_streamed_h256;
+    else p.kernel = two_tile && H == 128 && (s->flags & SNSDE_FLAG_TWO_TILE) && s->kl_column1 == 0 && m4t_instantiated(nhid, kuxt, save)
+                        ? FwdKernel::lean_two_tile_h128 : FwdKernel::lean;
     p.ok = true;
     return p;
 }
 
-RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& fp) {
+static RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& fp) {
     RevPlan p{};
     p.ok = false;
     if (!fp.ok || (s->method != SNSDE_EULER && s->method != SNSDE_MILSTEIN && s->method != SNSDE_SRK)) return p;
@@ -544,29 +555,17 @@ RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
     return p;
 }
 
-}  // namespace
-
-
 // time table kernel lives in snsde_generic.hip
 
-bool snsde_mfma_supported(const snsde_solve* s, const SnsdeNet& net) { return make_plan(s, net, -1).ok; }
-
-// adjoint on the wave groups: Euler or SRK (SRID2) with a diffusion net, 4-row-tile plan, every a_n or dL/dy0 only
-static bool w4_rev_takes(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& fp, const RevPlan& p, int hint) {
-    // (p.NW >= 4: the per-tile theta partials - four floats per 4-row tile - live in the plan's dth block of nwg x NW floats)
-    const bool method_ok = s->method == SNSDE_SRK ? (p.SRK && p.M4N == 1 && p.NW >= 4) : (!p.M4N && !p.SRK);
-    return hint != 0 && hint != 1 && p.ok && p.FL == 1 && method_ok && fp.NN > 0 && s->kl_column1 == 0 &&
-           (hint == 2 || s->batch <= 6144) && snsde_w4_rev_supported(s, net);
-}
-
-// which MFMA kernel family a forward launch of this descriptor takes (SNSDE_PATH_*; 0: none)
-int snsde_mfma_path(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
-    const MfmaPlan p = make_plan(s, net, flavor_hint);
+// the MFMA kernel family a forward launch of this plan takes (SNSDE_PATH_*; 0: none).  The two-tile lean kernels report the family
+// of the kernel they stand in for
+int snsde_mfma_path(const MfmaPlan& p) {
     if (!p.ok) return SNSDE_PATH_NONE;
-    if (flavor_hint != 0 && flavor_hint != 1 && w4_takes(s, net, flavor_hint)) return SNSDE_PATH_MFMA_W4;
+    if (p.kernel == FwdKernel::w4) return SNSDE_PATH_MFMA_W4;
     if (p.SRK) return SNSDE_PATH_MFMA_SRK;
-    if (p.LEAN) return p.H == 256 ? SNSDE_PATH_LEAN_STREAMED : SNSDE_PATH_LEAN;
-    return p.FL ? SNSDE_PATH_MFMA_M4 : SNSDE_PATH_MFMA_M16;
+    if (p.kernel == FwdKernel::lean || p.kernel == FwdKernel::lean_two_tile_h128) return SNSDE_PATH_LEAN;
+    if (p.kernel == FwdKernel::lean_two_tile_h256 || p.kernel == FwdKernel::lean_streamed_h256) return SNSDE_PATH_LEAN_STREAMED;
+    return p.kernel == FwdKernel::general_m16 ? SNSDE_PATH_MFMA_M16 : SNSDE_PATH_MFMA_M4;      // (M4: also the diffusion-net kernels)
 }
 
 size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net) {
@@ -580,14 +579,10 @@ size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net) {
     return need;
 }
 
-int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int flavor_hint) {
-    MfmaPlan p = make_plan(s, net, flavor_hint);
+int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& p, hipStream_t stream) {
     if (!p.ok) return SNSDE_ERR_UNSUPPORTED;
-    // the kernels form their per-step save offsets from 32-bit uniform factors (uoff): slots x B x H must fit
-    if ((uint64_t)16 * (uint64_t)s->batch * (uint64_t)s->model.hidden_channels >= (1ull << 32)) return SNSDE_ERR_UNSUPPORTED;
     float* ws = static_cast<float*>(s->workspace);
-    const bool w4 = w4_takes(s, net, flavor_hint);
-    if (flavor_hint == 2 && !w4) return SNSDE_ERR_UNSUPPORTED;
+    const bool w4 = p.kernel == FwdKernel::w4;
     if (w4 && !s->act_save) {
         // inference on the wave-owns-rows kernel: it reads the nn.Linear layout of `params` itself - no packing, no tables
         if (s->z0_weight) { const int rc = snsde_z0_launch(s, stream); if (rc) return rc; }
@@ -659,7 +654,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t str
     a.method = s->method; a.no = s->model.noise_option;
     a.off_theta = net.off_theta; a.gt_off = p.gt_off; a.bias_off = p.bias_off;
     for (int i = 0; i < p.n_layers; ++i) a.w_off[i] = p.layer[i].dst;
-    if (p.M4N) {
+    if (p.kernel == FwdKernel::m4n) {
         a.lean_geo = (p.IO == 5 || p.IO == 6) ? 1 : 0;
         a.act = s->model.activation; a.f_out = s->model.drift_output; a.g_out = s->model.diffusion_output;
         a.raw_time = s->model.time_feature;
@@ -676,11 +671,9 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t str
         a.lean_geo = (io == 5 || io == 6) ? 1 : 0;
         a.act = s->model.activation; a.f_out = s->model.drift_output; a.g_out = s->model.diffusion_output;
         a.raw_time = s->model.time_feature; a.gt_ext = s->noise_table;
-        if (p.H == 256) return dispatch_lean_h256(p, a, stream, (s->flags & SNSDE_FLAG_STREAM_ALL) != 0);
-        if (p.H == 128 && (s->flags & SNSDE_FLAG_TWO_TILE)) {
-            const int rc = dispatch_lean_h128_two_tile(p, a, stream);
-            if (rc != SNSDE_ERR_UNSUPPORTED) return rc;
-        }
+        if (p.kernel == FwdKernel::lean_two_tile_h256) return dispatch_lean_h256_two_tile(p, a, stream);
+        if (p.kernel == FwdKernel::lean_streamed_h256) return dispatch_lean_h256(p, a, stream);
+        if (p.kernel == FwdKernel::lean_two_tile_h128) return dispatch_lean_h128_two_tile(p, a, stream);
         if (p.H == 128) return dispatch_lean_h128(p, a, stream);
         if (p.H == 64) return dispatch_lean_h64(p, a, stream);
         if (p.H == 32) return dispatch_lean_h32(p, a, stream);
@@ -708,18 +701,29 @@ const float* snsde_mfma_gt_table(const snsde_solve* s, const SnsdeNet& net) {
     return (p.ok && p.gt_off >= 0 && s->workspace) ? static_cast<const float*>(s->workspace) + p.gt_off : nullptr;
 }
 
-bool snsde_mfma_backward_supported(const snsde_solve* s, const SnsdeNet& net) {
-    return make_rev_plan(s, net, make_plan(s, net, variant_of(s) ? 1 : -1)).ok;
+// The adjoint of this solve: the forward's plan (the forward launch's flavour hint), the adjoint's plan, and whether the wave-pair
+// adjoint with the weight gradients inside takes it (Euler or SRK (SRID2) with a diffusion net, 4-row tiles, every a_n or dL/dy0 only)
+struct BackwardChoice { MfmaPlan fp; RevPlan rp; bool w4; };
+
+static BackwardChoice backward_choice(const snsde_solve* s, const SnsdeNet& net) {
+    const int hint = snsde_flavor_hint(s);
+    BackwardChoice c;
+    c.fp = make_plan(s, net, hint);
+    c.rp = make_rev_plan(s, net, c.fp);
+    const RevPlan& p = c.rp;
+    // (p.NW >= 4: the per-tile theta partials - four floats per 4-row tile - live in the plan's dth block of nwg x NW floats)
+    const bool method_ok = s->method == SNSDE_SRK ? (p.SRK && p.M4N == 1 && p.NW >= 4) : (!p.M4N && !p.SRK);
+    c.w4 = hint != 0 && hint != 1 && p.ok && p.FL == 1 && method_ok && c.fp.NN > 0 && s->kl_column1 == 0 &&
+           (hint == 2 || s->batch <= 6144) && snsde_w4_rev_supported(s, net);
+    return c;
 }
 
-static int flavor_hint_of(const snsde_solve* s) {
-    if (variant_of(s)) return 1;      // tutorial-style fields: 4-row tiles only (snsde_solve_forward launches them that way)
-    return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
-}
+bool snsde_mfma_backward_supported(const snsde_solve* s, const SnsdeNet& net) { return backward_choice(s, net).rp.ok; }
 
 bool snsde_mfma_backward_partials(const snsde_solve* s, const SnsdeNet& net, int* nwg, int* waves, size_t* ds_off,
                                   size_t* dth_off) {
-    RevPlan p = make_rev_plan(s, net, make_plan(s, net, flavor_hint_of(s)));
+    const BackwardChoice c = backward_choice(s, net);
+    const RevPlan& p = c.rp;
     if (!p.ok || p.dth_off == 0) return false;
     *nwg = p.nwg; *waves = p.NW; *ds_off = p.ds_off; *dth_off = p.dth_off;
     return true;
@@ -728,39 +732,29 @@ bool snsde_mfma_backward_partials(const snsde_solve* s, const SnsdeNet& net, int
 static size_t w4_gpart_off(const RevPlan& p) { return ((size_t)p.total_floats + 63) & ~(size_t)63; }
 
 size_t snsde_mfma_backward_workspace_floats(const snsde_solve* s, const SnsdeNet& net) {
-    const int hint = flavor_hint_of(s);
-    const MfmaPlan fp = make_plan(s, net, hint);
-    RevPlan p = make_rev_plan(s, net, fp);
-    if (!p.ok) return 0;
-    if (w4_rev_takes(s, net, fp, p, hint)) return w4_gpart_off(p) + snsde_w4_grad_floats(s);
-    return (size_t)p.total_floats;
-}
-
-bool snsde_mfma_w4_fused(const snsde_backward* b, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off) {
-    return snsde_mfma_w4_fused_solve(&b->fwd, net, gpart_off, dth_off);
+    const BackwardChoice c = backward_choice(s, net);
+    if (!c.rp.ok) return 0;
+    return c.w4 ? w4_gpart_off(c.rp) + snsde_w4_grad_floats(s) : (size_t)c.rp.total_floats;
 }
 
 bool snsde_mfma_w4_fused_solve(const snsde_solve* s, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off) {
-    const int hint = flavor_hint_of(s);
-    const MfmaPlan fp = make_plan(s, net, hint);
-    const RevPlan p = make_rev_plan(s, net, fp);
-    if (!w4_rev_takes(s, net, fp, p, hint)) return false;
-    if (gpart_off) *gpart_off = w4_gpart_off(p);
-    if (dth_off) *dth_off = p.dth_off;
+    const BackwardChoice c = backward_choice(s, net);
+    if (!c.w4) return false;
+    if (gpart_off) *gpart_off = w4_gpart_off(c.rp);
+    if (dth_off) *dth_off = c.rp.dth_off;
     return true;
 }
 
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream) {
     const snsde_solve* s = &b->fwd;
-    const int hint = flavor_hint_of(s);
-    MfmaPlan fp = make_plan(s, net, hint);
-    RevPlan p = make_rev_plan(s, net, fp);
-    if (!p.ok) return SNSDE_ERR_UNSUPPORTED;
-    if ((uint64_t)16 * (uint64_t)s->batch * (uint64_t)s->model.hidden_channels >= (1ull << 32)) return SNSDE_ERR_UNSUPPORTED;   // (uoff)
+    const BackwardChoice c = backward_choice(s, net);
+    const MfmaPlan& fp = c.fp;
+    const RevPlan& p = c.rp;
+    if (!p.ok) return SNSDE_ERR_UNSUPPORTED;      // (the plans also refuse what overflows the kernels' 32-bit save offsets)
     float* ws = static_cast<float*>(b->workspace);
-    if (w4_rev_takes(s, net, fp, p, hint)) {
+    if (c.w4) {
         // the wave-pair adjoint reads the nn.Linear layout of `params` itself (columns of the weights): no fold, no pack launch;
-        // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (snsde_mfma_w4_fused)
+        // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (snsde_mfma_w4_fused_solve)
         if (!(s->dW_out ? s->dW_out : s->dW) && s->seed_dev) return SNSDE_ERR_NULL;
         return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + w4_gpart_off(p), stream);
     }

@@ -1805,8 +1805,12 @@ int launch_rev_srk(const RevArgs& a, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
+// the forward kernel a plan runs (set by make_plan only; snsde_mfma_path reports it, snsde_mfma_launch dispatches on it)
+enum class FwdKernel { w4, m4n, lean, lean_two_tile_h128, lean_two_tile_h256, lean_streamed_h256, general_m4, general_m16 };
+
 struct MfmaPlan {
     bool ok;
+    FwdKernel kernel;
     int H, KUX, NHID, IO, FL, TPW, NW, FOLD, NN, SRK;
     int LEAN, KUXT;    // lean M4 kernel (snsde_m4_kernel.h) and its 16-wide k-blocks of [X(t) | sin t, cos t]
     int M4N, KUXN;     // diffusion nets under SRK / Milstein (snsde_m4n_kernel.h) and its control k-blocks (0: latent-only drift)

@@ -869,7 +869,7 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, float* grad
                        hipStream_t stream) {
     {   // wave-pair adjoint with fused weight gradients (snsde_w4_kernel.h): the sums are in the BACKWARD workspace, per tile
         size_t gpart_off = 0, dth_off = 0;
-        if (snsde_mfma_w4_fused(b, net, &gpart_off, &dth_off)) {
+        if (snsde_mfma_w4_fused_solve(&b->fwd, net, &gpart_off, &dth_off)) {
             float* bws = static_cast<float*>(b->workspace);
             return snsde_w4_grad_reduce_launch(b, net, grad_params, n_params, bws + gpart_off, bws + dth_off, stream);
         }
