@@ -82,7 +82,15 @@ enum {
     /* H = 128 on 4-row tiles (Euler / Milstein, elementwise diffusions, relu fields): four waves of two tiles, one wave per SIMD with
      * the whole register file (snsde_m4t_kernel.h), instead of the eight-wave lean kernel.  Same results bit for bit.  An A/B switch:
      * measured slower at the K2 shape, so it is opt-in. */
-    SNSDE_FLAG_TWO_TILE = 8
+    SNSDE_FLAG_TWO_TILE = 8,
+    /* Inference only, opt-in: bf16 MFMA operands on the lean 4-row-tile kernel (SNSDE_PATH_LEAN_BF16; the reference's
+     * Diffusion_model fields with elementwise diffusions, Euler / Milstein, H = 64 / 128).  Only the two operands of every
+     * matrix instruction are rounded to bf16 (nearest even): the layer weights and the layer inputs [X(t) | sin t, cos t], y and
+     * the hidden activations.  The state, accumulators, biases, tanh, the diffusion, Milstein's term, the increments, X(t), the
+     * update and the output interpolation stay f32.  SNSDE_ERR_UNSUPPORTED (never an f32 kernel instead) for any other
+     * configuration, with training outputs (act_save, stage_save, traj, dW_out, dU_out), and from every backward entry point
+     * (snsde_backward_supported returns 0). */
+    SNSDE_FLAG_BF16_OPERANDS = 16
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -333,7 +341,8 @@ enum { SNSDE_PATH_NONE = 0,          /* no kernel: snsde_solve_forward returns S
        SNSDE_PATH_LEAN_STREAMED = 5, /* MFMA, 4-row tiles, lean kernel with L2 -> LDS streamed weights (H = 256)     */
        SNSDE_PATH_GENERIC_SRK = 6,   /* SRK on the generic family                                                   */
        SNSDE_PATH_MFMA_SRK = 7,      /* SRK on the MFMA 4-row tiles                                                 */
-       SNSDE_PATH_MFMA_W4 = 8 };     /* MFMA, 4 rows per wave pair (csrc/snsde_w4_kernel.h: H = 64, diffusion nets, Euler / SRK) */
+       SNSDE_PATH_MFMA_W4 = 8,       /* MFMA, 4 rows per wave pair (csrc/snsde_w4_kernel.h: H = 64, diffusion nets, Euler / SRK) */
+       SNSDE_PATH_LEAN_BF16 = 9 };   /* the lean kernel with bf16 MFMA operands (SNSDE_FLAG_BF16_OPERANDS, H = 64 / 128)      */
 SNSDE_API int snsde_forward_path(const snsde_solve* s);
 
 /* Readout head of the wrappers in one launch (inference; replaces the 4-5 tensor ops of `self.linear(z)`,

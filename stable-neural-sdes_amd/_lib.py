@@ -17,8 +17,9 @@ FLAG_REUSE_PREPARED = 1
 FLAG_EXACT_ORDER = 2
 FLAG_STREAM_ALL = 4
 FLAG_TWO_TILE = 8
+FLAG_BF16_OPERANDS = 16     # inference only: bf16 MFMA operands on the lean 4-row-tile kernel (include/snsde.h)
 BWD_ADJ0_ONLY = 1
-PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4')
+PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4', 'lean-bf16')
 KERNELS = {'auto': KERNEL_AUTO, 'generic': KERNEL_GENERIC, 'mfma': KERNEL_MFMA, 'mfma16': 3, 'mfma4': 4, 'w4': 5}
 
 

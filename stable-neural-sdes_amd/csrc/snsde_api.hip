@@ -160,10 +160,12 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     const int generic = s->method == SNSDE_SRK ? SNSDE_PATH_GENERIC_SRK : SNSDE_PATH_GENERIC;
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
-    if (k == SNSDE_KERNEL_GENERIC) { r.path = generic; return r; }
+    if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS)) r.path = generic; return r; }
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
     // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor
     r.path = r.plan.ok ? snsde_mfma_path(r.plan) : (k == SNSDE_KERNEL_AUTO && !variant ? generic : SNSDE_PATH_NONE);
+    // bf16 operands: the bf16 lean kernel or nothing (no f32 kernel stands in for it)
+    if ((s->flags & SNSDE_FLAG_BF16_OPERANDS) && r.path != SNSDE_PATH_LEAN_BF16) r = ForwardRoute{};
     return r;
 }
 
@@ -458,6 +460,7 @@ int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_p
 
 int snsde_backward_supported(const snsde_solve* s) {
     if (!s || s->struct_size != sizeof(snsde_solve) || validate_model(&s->model)) return 0;
+    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return 0;     // an inference-only forward: no adjoint of any kind
     if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return 0;     // no forward kernel either (validate_solve)
     SnsdeNet net;
     if (snsde_build_net(s->model, s->n_steps, &net)) return 0;
@@ -483,6 +486,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
+    if (b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;

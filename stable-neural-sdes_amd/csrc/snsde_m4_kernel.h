@@ -23,6 +23,8 @@
 // order of the final update  y + g dW + f h  (was y + f h + g dW): both inside the parity tolerance (tests/helpers.py).
 // Reference semantics: benchmark_classification/models_sde/neuralsde.py:295-307 (f, g), SURVEY.md A3-A6 (stepping).
 #pragma once
+#include <type_traits>
+
 #include "snsde_mfma_kernels.h"
 
 namespace snsde_mfma {
@@ -221,6 +223,105 @@ __device__ __forceinline__ void lean_gemm(const float (&w)[KU * 4], LeanB<KU>& b
     lean_gemm_from<Y, KU, 0>(w, b, c, d);
 }
 
+// ---- bf16 operands (SNSDE_FLAG_BF16_OPERANDS; instantiated as CfgBf16<CfgL<..>> in snsde_m4b_h*.hip) ----------------------
+// Only the two MFMA operands are bf16 (round to nearest even): the resident weights and the LDS copies of the layer inputs
+// [X(t) | sin t, cos t], y and the hidden activations.  Accumulators, biases, the diffusion, the update and every value a lane
+// keeps in registers stay f32.  One v_mfma_f32_4x4x4_16b_bf16 takes the four k-slots e = 0..3 of a 16-wide k-block that four
+// chained 4x4x1 f32 MFMAs take in the f32 kernel (same lane / k-slot map: k(u, s, e) = 16u + 4s + e), so a layer is KU MFMAs
+// instead of 4 KU, and a k-block's B operand is 8 bytes: one ds_read_b64 by lanes 0-15, broadcast by the MFMA (blgp:4).
+// The LDS buffers keep the f32 kernel's float layout (same bases, same row strides counted in elements), half of each row used.
+typedef short s16x4 __attribute__((ext_vector_type(4)));
+typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
+template <class CF> struct CfgBf16 : CF { static constexpr bool BF = true; };
+template <class CF, class = void> struct lean_bf : std::false_type {};
+template <class CF> struct lean_bf<CF, std::void_t<decltype(CF::BF)>> : std::bool_constant<CF::BF> {};
+template <int KU> struct LeanBh { s16x4 v[KU]; };
+template <bool BF, int KU> using LeanWt = std::conditional_t<BF, s16x4[KU], float[KU * 4]>;    // resident weights of one layer
+template <bool BF, int KU> using LeanBt = std::conditional_t<BF, LeanBh<KU>, LeanB<KU>>;        // B operands of one layer
+template <bool BF> using LeanOp = std::conditional_t<BF, __bf16, float>;                        // LDS operand element
+
+__device__ __forceinline__ s16x4 lean_bf16x4(f32x4 v) {      // (v_cvt_pk_bf16_f32: round to nearest even, NaN stays NaN)
+    const bf16x4 b = {(__bf16)v[0], (__bf16)v[1], (__bf16)v[2], (__bf16)v[3]};
+    return __builtin_bit_cast(s16x4, b);
+}
+template <int KU>
+__device__ __forceinline__ void lean_load_w(s16x4 (&w)[KU], const float* __restrict__ g, int wave, int lane) {
+#pragma unroll
+    for (int u = 0; u < KU; ++u) w[u] = lean_bf16x4(*reinterpret_cast<const f32x4*>(g + (((size_t)wave * KU + u) * 64 + lane) * 4));
+}
+// LDS byte address of operand element (row offset + column) of a buffer (f32 kernel: the expression it always used)
+template <bool BF>
+__device__ __forceinline__ uint32_t lean_op_addr(const float* buf, int roff, int col) {
+    if constexpr (BF) return lean_lds_addr(buf) + (uint32_t)((roff + col) * 2);
+    else return lean_lds_addr(buf + roff + col);
+}
+#define LEAN_RB(i, o) "\n\tds_read_b64 %" #i ", %[a] offset:" #o
+#define LEAN_RB_PRE "s_mov_b64 exec, 0xffff"
+#define LEAN_RB_POST "\n\ts_mov_b64 exec, -1"
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<1>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB_POST : "=&v"(b.v[0]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<2>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB_POST : "=&v"(b.v[0]), "=&v"(b.v[1]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<3>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB_POST
+                 : "=&v"(b.v[0]), "=&v"(b.v[1]), "=&v"(b.v[2]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<4>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB(3, 96) LEAN_RB_POST
+                 : "=&v"(b.v[0]), "=&v"(b.v[1]), "=&v"(b.v[2]), "=&v"(b.v[3]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<6>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB(3, 96) LEAN_RB(4, 128) LEAN_RB(5, 160) LEAN_RB_POST
+                 : "=&v"(b.v[0]), "=&v"(b.v[1]), "=&v"(b.v[2]), "=&v"(b.v[3]), "=&v"(b.v[4]), "=&v"(b.v[5]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b(uint32_t a, LeanBh<8>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB(3, 96) LEAN_RB(4, 128) LEAN_RB(5, 160)
+                 LEAN_RB(6, 192) LEAN_RB(7, 224) LEAN_RB_POST
+                 : "=&v"(b.v[0]), "=&v"(b.v[1]), "=&v"(b.v[2]), "=&v"(b.v[3]), "=&v"(b.v[4]), "=&v"(b.v[5]), "=&v"(b.v[6]),
+                   "=&v"(b.v[7]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b_carried(uint32_t a, LeanBh<1>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB_POST : "+v"(b.v[0]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b_carried(uint32_t a, LeanBh<2>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB_POST : "+v"(b.v[0]), "+v"(b.v[1]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b_carried(uint32_t a, LeanBh<3>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB_POST
+                 : "+v"(b.v[0]), "+v"(b.v[1]), "+v"(b.v[2]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_b_carried(uint32_t a, LeanBh<6>& b) {
+    asm volatile(LEAN_RB_PRE LEAN_RB(0, 0) LEAN_RB(1, 32) LEAN_RB(2, 64) LEAN_RB(3, 96) LEAN_RB(4, 128) LEAN_RB(5, 160) LEAN_RB_POST
+                 : "+v"(b.v[0]), "+v"(b.v[1]), "+v"(b.v[2]), "+v"(b.v[3]), "+v"(b.v[4]), "+v"(b.v[5]) : [a] "v"(a));
+}
+#undef LEAN_RB
+#undef LEAN_RB_PRE
+#undef LEAN_RB_POST
+template <int CNT> __device__ __forceinline__ void lean_wait2(s16x4& x, s16x4& y) {
+    asm volatile("s_waitcnt lgkmcnt(%2)" : "+v"(x), "+v"(y) : "n"(CNT < 15 ? CNT : 15));
+}
+template <int CNT> __device__ __forceinline__ void lean_wait1(s16x4& x) {
+    asm volatile("s_waitcnt lgkmcnt(%1)" : "+v"(x) : "n"(CNT < 15 ? CNT : 15));
+}
+// c/d += W . b: one bf16 MFMA per k-block, even blocks on c, odd on d; consumed in pairs as their reads land (as above)
+template <int Y, int KU, int U>
+__device__ __forceinline__ void lean_gemm_from(const s16x4 (&w)[KU], LeanBh<KU>& b, f32x4& c, f32x4& d) {
+    if constexpr (U < KU) {
+        if constexpr (U + 1 < KU) lean_wait2<Y + KU - 2 - U>(b.v[U], b.v[U + 1]);
+        else lean_wait1<Y>(b.v[U]);
+        c = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(w[U], b.v[U], c, 0, 0, 4);
+        if constexpr (U + 1 < KU) d = __builtin_amdgcn_mfma_f32_4x4x4bf16_1k(w[U + 1], b.v[U + 1], d, 0, 0, 4);
+        __builtin_amdgcn_sched_barrier(0);
+        lean_gemm_from<Y, KU, U + 2>(w, b, c, d);
+    }
+}
+template <int Y, int KU>
+__device__ __forceinline__ void lean_gemm(const s16x4 (&w)[KU], LeanBh<KU>& b, f32x4& c, f32x4& d) {
+    lean_gemm_from<Y, KU, 0>(w, b, c, d);
+}
+
 // Cycle timeline (development builds, -DLEAN_TRACE): s_memtime stamps at LT(i) are left in flight (no s_waitcnt) and collected
 // in three groups behind the step's barriers (whose own s_waitcnt lgkmcnt(0) has already drained the queue there), so they do
 // not drain the LDS queue the way TRACE() does.  The kernel has no registers to spare (251 of 256 VGPRs, SGPRs at the limit, and
@@ -260,6 +361,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     constexpr int H = CF::H, NT = CF::NT, NHID = CF::NHID, KUH = CF::KUH, KUXT = CF::KUXT;
     constexpr int LDY = CF::LDY, LDX = CF::LDX, LDA = CF::LDA, RS = CF::RS;
     constexpr bool YIN = CF::YIN, SAVE = CF::SAVE;
+    constexpr bool BF = lean_bf<CF>::value;                 // bf16 MFMA operands (CfgBf16)
+    using OpT = LeanOp<BF>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ybuf = lds;                       // [4][LDY]  y
     float* xbuf = ybuf + 4 * LDY;            // [2][4][LDX]  X(t) (xc) | sin t, cos t | 0..   (step parity)
@@ -291,7 +394,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
 
     // ---- resident weights, bias fragments ---------------------------------------------------------------------
     int li = 0;
-    float wxt[(KUXT > 0 ? KUXT : 1) * 4], wy[KUH * 4], wh[NHID > 0 ? NHID : 1][KUH * 4], wo[KUH * 4];
+    LeanWt<BF, (KUXT > 0 ? KUXT : 1)> wxt;
+    LeanWt<BF, KUH> wy, wh[NHID > 0 ? NHID : 1], wo;
     if constexpr (KUXT > 0) lean_load_w<KUXT>(wxt, a.ws + a.w_off[li++], wave, lane);
     if constexpr (YIN) lean_load_w<KUH>(wy, a.ws + a.w_off[li++], wave, lane);
 #pragma unroll
@@ -330,7 +434,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     const int rslot = a.row_out ? a.row_out[rowc] : -1;
 
     float yv = a.y0[goff];
-    ybuf[r * LDY + fo] = yv;
+    reinterpret_cast<OpT*>(ybuf)[r * LDY + fo] = (OpT)yv;
     if (row_ok) {
         a.ys[(size_t)row * H + fo] = yv;
         if constexpr (SAVE) { if (a.traj) a.traj[(size_t)row * H + fo] = yv; }
@@ -394,7 +498,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
                     v = ca[i] + (cb[i] + (0.5f * cc[i] + q3) * frac) * frac;
                 }
                 v = xkind[i] == 0 ? v : (xkind[i] == 1 ? sn : cs);
-                if (xdst[i] >= 0) xb[xdst[i]] = v;
+                if (xdst[i] >= 0) reinterpret_cast<OpT*>(xb)[xdst[i]] = (OpT)v;
             }
         }
     };
@@ -467,19 +571,19 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     if constexpr (LEAN_PRIO_MODE == 2) { if (__builtin_amdgcn_readfirstlane(tid) < NT / 2 && CF::NW >= 8) __builtin_amdgcn_s_setprio(1); }
 
     // B-operand read addresses (LDS byte offsets; only lanes 0-15 read: q = 0 there)
-    const uint32_t yrow = lean_lds_addr(ybuf + r * LDY + 4 * s);
-    const uint32_t xrow = lean_lds_addr(xbuf + r * LDX + 4 * s);      // + 4 * LDX floats on odd steps
-    const uint32_t arow = lean_lds_addr(bufA + r * LDA + 4 * s);
-    const uint32_t brow = lean_lds_addr(bufB + r * LDA + 4 * s);
-    float* const aown = bufA + r * LDA + fo;
-    float* const bown = bufB + r * LDA + fo;
+    const uint32_t yrow = lean_op_addr<BF>(ybuf, r * LDY, 4 * s);
+    const uint32_t xrow = lean_op_addr<BF>(xbuf, r * LDX, 4 * s);      // + 4 * LDX floats on odd steps
+    const uint32_t arow = lean_op_addr<BF>(bufA, r * LDA, 4 * s);
+    const uint32_t brow = lean_op_addr<BF>(bufB, r * LDA, 4 * s);
+    OpT* const aown = reinterpret_cast<OpT*>(bufA) + r * LDA + fo;
+    OpT* const bown = reinterpret_cast<OpT*>(bufB) + r * LDA + fo;
     const f32x4 zero4 = {0.f, 0.f, 0.f, 0.f};
     // (round 4, measured and dropped: the trajectory plane stored TILE-WIDE out of ybuf by one wave of the younger half - H lanes x 16
     //  bytes = the tile's 4 H contiguous bytes, instead of one dword per lane from all eight waves: 216.7 -> 217.8 us for the training-
     //  mode forward at K2.  With the counted-vmcnt experiment at vm_wait this rules out both the store instruction count / segment
     //  width and the acknowledgement drain as the source of the ~4 us per plane and 100 steps that every per-step store costs here.)
 
-    LeanB<(KUXT > 0 ? KUXT : 1)> bx{};    // [X(t_n) | tau_n] operands of the step about to start
+    LeanBt<BF, (KUXT > 0 ? KUXT : 1)> bx{};    // [X(t_n) | tau_n] operands of the step about to start
     if constexpr (KUXT > 0) lean_read_b_carried(xrow, bx);
     LT_DECL
     // Outer loop over the requested outputs, inner loop over the solver steps up to each of them (out_step[k] = the step
@@ -509,7 +613,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         LT(0)
         // ---- top: the first layer's B operands, then the table quads of the coming steps (asm: the compiler never waits
         //      on them; they have landed once the first layer's last s_waitcnt has passed) ------------------------------------
-        LeanB<KUH> by;
+        LeanBt<BF, KUH> by;
         if constexpr (YIN) lean_read_b(yrow, by);
         asm volatile("" : "+v"(qa), "+v"(qb));      // (read before the closing barrier of the previous step: landed)
         const float h = qa[0];
@@ -529,7 +633,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         {
             const float pre = m4_reduce_scatter(c + d);
             const float o = CF::SWISH ? lean_swish(pre, act_scale) : fmaxf(pre, 0.0f);
-            *aown = o;
+            *aown = (OpT)o;
             if constexpr (SAVE) {
                 if (a.act_save && row_ok) {
                     lean_gstore(o, goff4, act_n);
@@ -555,7 +659,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
 #pragma unroll
         for (int l = 0; l < NHID; ++l) {
             const bool toB = (l % 2 == 0);
-            LeanB<KUH> bh;
+            LeanBt<BF, KUH> bh;
             lean_read_b(cur, bh);
             __builtin_amdgcn_sched_barrier(0);
             if (l == 0) prep();
@@ -565,7 +669,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
             lean_gemm<0, KUH>(wh[l], bh, c, d);
             const float pre = m4_reduce_scatter(c + d);
             const float o = CF::SWISH ? lean_swish(pre, act_scale) : fmaxf(pre, 0.0f);
-            *(toB ? bown : aown) = o;
+            *(toB ? bown : aown) = (OpT)o;
             if constexpr (SAVE) {
                 if (a.act_save && row_ok) {
                     lean_gstore(o, goff4, act_n + uoff(0, 0, 1 + l, (uint32_t)BH));
@@ -580,7 +684,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         }
         // ---- output layer, f, update -------------------------------------------------------------------------------
         {
-            LeanB<KUH> bo;
+            LeanBt<BF, KUH> bo;
             lean_read_b(cur, bo);
             __builtin_amdgcn_sched_barrier(0);
             if (NHID == 0) prep();
@@ -621,7 +725,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         const float ynew = fmaf(f, h, ypart);
         yold = yv;
         yv = ynew;
-        ybuf[r * LDY + fo] = ynew;
+        reinterpret_cast<OpT*>(ybuf)[r * LDY + fo] = (OpT)ynew;
         if constexpr (SAVE) {
             if (row_ok) {
                 if (a.traj) lean_gstore(ynew, goff4, a.traj + uoff((int)nu + 1, (uint32_t)BH));
@@ -722,6 +826,8 @@ int dispatch_lean_h128(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_lean_h128_two_tile(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);   // snsde_m4t_kernel.h
 int dispatch_lean_h256(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);            // snsde_m4s_kernel.h
 int dispatch_lean_h256_two_tile(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);   // snsde_m4s2_kernel.h
+int dispatch_lean_bf16_h64(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);        // snsde_m4b_kernel.h: bf16 operands
+int dispatch_lean_bf16_h128(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 // host-side mirrors of the two-tile instantiation lists (make_plan); save = training mode (act_save, traj or dW_out)
 bool m4t_instantiated(int nhid, int kuxt, bool save);
 bool m4s2_instantiated(int nhid, int kuxt, bool save);

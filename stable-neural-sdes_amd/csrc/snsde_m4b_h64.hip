@@ -1,0 +1,8 @@
+// Lean 4-row-tile forward kernel with bf16 MFMA operands (snsde_m4b_kernel.h) instantiated for hidden size 64.
+#include "snsde_m4b_kernel.h"
+
+namespace snsde_mfma {
+
+int dispatch_lean_bf16_h64(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st) { return dispatch_lean_bf16<64>(p, a, st); }
+
+}  // namespace snsde_mfma

@@ -270,6 +270,10 @@ static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint)
 // The forward's plan: does the MFMA fast path take this descriptor (ok), its workspace layout, and the kernel that runs it
 MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     MfmaPlan p{};
+    // bf16 MFMA operands (SNSDE_FLAG_BF16_OPERANDS): the lean 4-row-tile kernel only, so `auto` plans 4-row tiles; whatever the
+    // plan below arrives at other than that kernel is no plan (never an f32 kernel in its place)
+    const bool bf16 = (s->flags & SNSDE_FLAG_BF16_OPERANDS) != 0;
+    if (bf16 && flavor_hint == -1) flavor_hint = 1;
     const int hint_in = flavor_hint;
     if (flavor_hint == 2) flavor_hint = 1;      // (the wave-owns-rows forward, snsde_w4.hip: every plan-side decision as for 4-row tiles)
     const snsde_model& m = s->model;
@@ -463,6 +467,11 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
                                       ? FwdKernel::lean_two_tile_h256 : FwdKernel::lean_streamed_h256;
     else p.kernel = two_tile && H == 128 && (s->flags & SNSDE_FLAG_TWO_TILE) && s->kl_column1 == 0 && m4t_instantiated(nhid, kuxt, save)
                         ? FwdKernel::lean_two_tile_h128 : FwdKernel::lean;
+    if (bf16) {      // inference on the reference's Diffusion_model fields, H = 64 / 128 (snsde_m4b_kernel.h)
+        const bool train = save || s->stage_save || s->dU_out;
+        if (p.kernel != FwdKernel::lean || !(H == 64 || H == 128) || variant || train || s->kl_column1 != 0 || srk) return p;
+        p.kernel = FwdKernel::lean_bf16;
+    }
     p.ok = true;
     return p;
 }
@@ -564,6 +573,7 @@ int snsde_mfma_path(const MfmaPlan& p) {
     if (p.kernel == FwdKernel::w4) return SNSDE_PATH_MFMA_W4;
     if (p.SRK) return SNSDE_PATH_MFMA_SRK;
     if (p.kernel == FwdKernel::lean || p.kernel == FwdKernel::lean_two_tile_h128) return SNSDE_PATH_LEAN;
+    if (p.kernel == FwdKernel::lean_bf16) return SNSDE_PATH_LEAN_BF16;
     if (p.kernel == FwdKernel::lean_two_tile_h256 || p.kernel == FwdKernel::lean_streamed_h256) return SNSDE_PATH_LEAN_STREAMED;
     return p.kernel == FwdKernel::general_m16 ? SNSDE_PATH_MFMA_M16 : SNSDE_PATH_MFMA_M4;      // (M4: also the diffusion-net kernels)
 }
@@ -674,6 +684,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         if (p.kernel == FwdKernel::lean_two_tile_h256) return dispatch_lean_h256_two_tile(p, a, stream);
         if (p.kernel == FwdKernel::lean_streamed_h256) return dispatch_lean_h256(p, a, stream);
         if (p.kernel == FwdKernel::lean_two_tile_h128) return dispatch_lean_h128_two_tile(p, a, stream);
+        if (p.kernel == FwdKernel::lean_bf16) return p.H == 128 ? dispatch_lean_bf16_h128(p, a, stream) : dispatch_lean_bf16_h64(p, a, stream);
         if (p.H == 128) return dispatch_lean_h128(p, a, stream);
         if (p.H == 64) return dispatch_lean_h64(p, a, stream);
         if (p.H == 32) return dispatch_lean_h32(p, a, stream);

@@ -1806,7 +1806,7 @@ int launch_rev_srk(const RevArgs& a, hipStream_t stream) {
 }
 
 // the forward kernel a plan runs (set by make_plan only; snsde_mfma_path reports it, snsde_mfma_launch dispatches on it)
-enum class FwdKernel { w4, m4n, lean, lean_two_tile_h128, lean_two_tile_h256, lean_streamed_h256, general_m4, general_m16 };
+enum class FwdKernel { w4, m4n, lean, lean_two_tile_h128, lean_two_tile_h256, lean_streamed_h256, general_m4, general_m16, lean_bf16 };
 
 struct MfmaPlan {
     bool ok;

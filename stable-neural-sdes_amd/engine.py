@@ -148,15 +148,37 @@ _MFMA_SIZES = (16, 32, 64, 128, 256)
 _PAD_CACHE = {}
 
 
-def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False):
+PRECISIONS = ('fp32', 'bf16')
+
+
+def precision_flags(precision):
+    """SNSDE_FLAG_* bits of an operand precision ('fp32': none; 'bf16': SNSDE_FLAG_BF16_OPERANDS)."""
+    if precision not in PRECISIONS:
+        raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
+    return _lib.FLAG_BF16_OPERANDS if precision == 'bf16' else 0
+
+
+def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32'):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query)."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
+    s.flags = precision_flags(precision)
     s.noise_table = C.c_void_p(16) if table else None
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
+
+
+def check_bf16(model, batch, knots, n_steps, method='euler', kernel='auto'):
+    """Raise ValueError unless the bf16-operand kernel takes this inference solve (there is no fp32 stand-in for it)."""
+    if method == 'srk':
+        raise ValueError("precision='bf16' covers Euler and Milstein only, not SRK")
+    if forward_path(model, batch, knots, n_steps, method, kernel, precision='bf16') != 'lean-bf16':
+        raise ValueError(f"precision='bf16' does not cover this configuration (hidden_channels={model.hidden_channels}, "
+                         f"num_hidden_layers={model.num_hidden_layers}, input_option={model.input_option}, "
+                         f"noise_option={model.noise_option}, method={method!r}, kernel={kernel!r}): it runs the lean 4-row-tile "
+                         "kernel at H = 64 / 128 on the reference's Diffusion_model fields only")
 
 
 def padding_plan(model, batch, knots, n_steps, method):
@@ -440,7 +462,7 @@ class SolveCall:
 
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
-                 noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False):
+                 noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32'):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -475,6 +497,7 @@ class SolveCall:
         #  whether it needs delta planes at all - depends on them)
         s.kernel = _lib.KERNELS[kernel]
         self.base_flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_STREAM_ALL if stream_all else 0) | (_lib.FLAG_TWO_TILE if two_tile else 0)
+        self.base_flags |= precision_flags(precision)      # bf16: inference only (the library refuses training outputs and every backward)
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -493,7 +516,8 @@ class SolveCall:
         self.cfg_key = (model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
-                        dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed))
+                        dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
+                        precision)
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:

@@ -152,6 +152,20 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     default_names = names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
                                       and not (set(names) - {'drift', 'diffusion'}))
     rec = engine.recognise(sde) if default_names else None
+    # options={'precision': 'bf16'}: inference on the bf16-operand kernel (engine.check_bf16), or a ValueError - never fp32 instead
+    precision = options.get('precision', 'fp32')
+    engine.precision_flags(precision)
+    if precision == 'bf16':
+        if backend == 'torch':
+            raise ValueError("precision='bf16' is a HIP kernel option; backend='torch' has no bf16 solve")
+        params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
+        if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)):
+            raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad (use torch.no_grad(), "
+                             "requires_grad_(False) or precision='fp32')")
+        if rec is None:
+            raise ValueError("precision='bf16' needs an sde honouring the Diffusion_model contract (the fused HIP solve)")
+        if not y0.is_cuda:
+            raise ValueError("precision='bf16' needs CUDA (ROCm) tensors")
     want_hip = backend == 'hip' or (backend == 'auto' and rec is not None and y0.is_cuda)
     if 'z0_linear' in options and not (want_hip and rec is not None and y0.is_cuda):
         y0 = _materialise_z0(sde, y0, ts, options)      # only the fused solve evaluates the initial state itself
@@ -262,7 +276,14 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     if row_out is not None:     # per-row output selection fused into the solve: the result is (B, H)
         row_out = row_out.to(device=dev, dtype=torch.int32).contiguous()
         options = dict(options, row_out=row_out)
-    if options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute'):
+    precision = options.get('precision', 'fp32')
+    if precision == 'bf16':
+        if needs_grad or (z0_lin is not None and torch.is_grad_enabled() and any(p.requires_grad for p in z0_lin.parameters())):
+            raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad")
+        if options.get('save_traj', False):
+            raise ValueError("precision='bf16' is inference only: save_traj is a training output")
+        engine.check_bf16(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method, options.get('kernel', 'auto'))
+    if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute'):
         pad = engine.padding_plan(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method)
         if pad is not None:       # a hidden size without MFMA instantiation: solve the zero-padded model (exact)
             if z0_lin is not None:
@@ -290,10 +311,13 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                             row_offset=int(options.get('row_offset', 0)), kernel=options.get('kernel', 'auto'),
                             save_traj=bool(options.get('save_traj', False)),
                             exact_order=bool(options.get('exact_order', False)), dU=dU, row_out=row_out,
-                            z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()))
+                            z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
+                            precision=precision)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
+        if precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
+            raise ValueError(f"precision='bf16': the solve was refused ({exc})") from exc
         # a valid request no kernel covers (Milstein with noise_option 7, sqrt(y)): same behaviour as the gradient path, the
         # unfused tensor-op loop, unless strict
         # (-6, SNSDE_ERR_LDS: a hidden size whose per-tile buffers exceed the LDS budget of the only kernel family that covers
