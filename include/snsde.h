@@ -90,7 +90,10 @@ enum {
      * update and the output interpolation stay f32.  SNSDE_ERR_UNSUPPORTED (never an f32 kernel instead) for any other
      * configuration, with training outputs (act_save, stage_save, traj, dW_out, dU_out), and from every backward entry point
      * (snsde_backward_supported returns 0). */
-    SNSDE_FLAG_BF16_OPERANDS = 16
+    SNSDE_FLAG_BF16_OPERANDS = 16,
+    /* Run the lean 4-row-tile kernel's general instantiation even where a compile-time specialised one covers the launch
+     * (snsde_lean_variant).  Same results bit for bit; exists for A/B measurements and the bit-identity test. */
+    SNSDE_FLAG_LEAN_GENERAL = 32
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -344,6 +347,12 @@ enum { SNSDE_PATH_NONE = 0,          /* no kernel: snsde_solve_forward returns S
        SNSDE_PATH_MFMA_W4 = 8,       /* MFMA, 4 rows per wave pair (csrc/snsde_w4_kernel.h: H = 64, diffusion nets, Euler / SRK) */
        SNSDE_PATH_LEAN_BF16 = 9 };   /* the lean kernel with bf16 MFMA operands (SNSDE_FLAG_BF16_OPERANDS, H = 64 / 128)      */
 SNSDE_API int snsde_forward_path(const snsde_solve* s);
+/* Host-only query next to snsde_forward_path: which instantiation of the lean kernel (SNSDE_PATH_LEAN, one 4-row tile per
+ * workgroup) snsde_solve_forward would launch.  SNSDE_LEAN_GENERAL = the instantiation that tests the field's options at run
+ * time; SNSDE_LEAN_SPECIALISED = one compiled for exactly this field's options (csrc/snsde_m4_kernel.h: CfgSpec), the same
+ * results bit for bit.  SNSDE_LEAN_NONE when the forward runs on another kernel. */
+enum { SNSDE_LEAN_NONE = 0, SNSDE_LEAN_GENERAL = 1, SNSDE_LEAN_SPECIALISED = 2 };
+SNSDE_API int snsde_lean_variant(const snsde_solve* s);
 
 /* Readout head of the wrappers in one launch (inference; replaces the 4-5 tensor ops of `self.linear(z)`,
  * benchmark_classification/models_sde/neuralsde.py:59-61,119; benchmark_forecasting/models_sde/neuralsde.py:186; torch_ists

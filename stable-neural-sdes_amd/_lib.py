@@ -18,6 +18,8 @@ FLAG_EXACT_ORDER = 2
 FLAG_STREAM_ALL = 4
 FLAG_TWO_TILE = 8
 FLAG_BF16_OPERANDS = 16     # inference only: bf16 MFMA operands on the lean 4-row-tile kernel (include/snsde.h)
+FLAG_LEAN_GENERAL = 32      # the lean kernel's general instantiation where a specialised one covers the launch (A/B, bit-identity test)
+LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 BWD_ADJ0_ONLY = 1
 PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4', 'lean-bf16')
 KERNELS = {'auto': KERNEL_AUTO, 'generic': KERNEL_GENERIC, 'mfma': KERNEL_MFMA, 'mfma16': 3, 'mfma4': 4, 'w4': 5}
@@ -81,7 +83,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_spline_evaluate', 'snsde_eval_fg', 'snsde_act_slots', 'snsde_backward_supported',
            'snsde_backward_workspace_bytes', 'snsde_solve_backward', 'snsde_spline_workspace_bytes',
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
-           'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_readout_head', 'snsde_save_layout',
+           'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward')
 
 
@@ -137,6 +139,7 @@ def lib():
     L.snsde_backward_with_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snsde_backward_supported.argtypes = [C.POINTER(Solve)]
     L.snsde_forward_path.argtypes = [C.POINTER(Solve)]
+    L.snsde_lean_variant.argtypes = [C.POINTER(Solve)]
     L.snsde_readout_head.argtypes = [C.POINTER(Head), C.c_void_p]
     L.snsde_affine_compose.argtypes = [C.POINTER(AffineJob), C.c_int32, C.c_void_p, C.c_void_p]
     L.snsde_affine_compose_backward.argtypes = [C.POINTER(AffineJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]

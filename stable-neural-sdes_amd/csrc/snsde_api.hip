@@ -403,6 +403,15 @@ int snsde_forward_path(const snsde_solve* s) {
     return route_forward(s, net).path;
 }
 
+int snsde_lean_variant(const snsde_solve* s) {
+    if (snsde_forward_path(s) != SNSDE_PATH_LEAN) return SNSDE_LEAN_NONE;
+    SnsdeNet net;
+    if (snsde_build_net(s->model, s->n_steps, &net)) return SNSDE_LEAN_NONE;
+    const ForwardRoute r = route_forward(s, net);
+    if (r.plan.kernel != snsde_mfma::FwdKernel::lean) return SNSDE_LEAN_NONE;
+    return r.plan.LEAN_SPEC ? SNSDE_LEAN_SPECIALISED : SNSDE_LEAN_GENERAL;
+}
+
 int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, float* f_out, float* g_out,
                   void* hip_stream) {
     int rc = validate_solve(s, true);

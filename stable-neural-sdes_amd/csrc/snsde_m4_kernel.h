@@ -322,6 +322,20 @@ __device__ __forceinline__ void lean_gemm(const s16x4 (&w)[KU], LeanBh<KU>& b, f
     lean_gemm_from<Y, KU, 0>(w, b, c, d);
 }
 
+// ---- compile-time mode (instantiated as CfgSpec<CfgL<..>, GEO> where make_plan sets MfmaPlan::LEAN_SPEC) ----------------------
+// The general instantiation tests the noise family, the method, the drift output, the increment source, the data sources and the
+// field variant at run time, inside the step loop.  CfgSpec fixes them for the reference's Diffusion_model fields the benchmarks
+// run: table x y noise (noise_option 3 / 6 / 11 / 13 / 17), Euler, relu, tanh drift (with z *= tanh(y) when GEO: input_option 6),
+// in-kernel Philox increments, a control path in the first layer, no accumulator column.  Same arithmetic on every value; only
+// the tests, the selects they feed and the branches around them are gone.
+template <class CF, int GEO_> struct CfgSpec : CF { static constexpr bool SPEC = true, SPEC_GEO = GEO_ != 0; };
+template <class CF, class = void> struct lean_spec : std::false_type {};
+template <class CF> struct lean_spec<CF, std::void_t<decltype(CF::SPEC)>> : std::bool_constant<CF::SPEC> {};
+template <class CF> constexpr bool lean_spec_geo() {
+    if constexpr (lean_spec<CF>::value) return CF::SPEC_GEO;
+    else return false;
+}
+
 // Cycle timeline (development builds, -DLEAN_TRACE): s_memtime stamps at LT(i) are left in flight (no s_waitcnt) and collected
 // in three groups behind the step's barriers (whose own s_waitcnt lgkmcnt(0) has already drained the queue there), so they do
 // not drain the LDS queue the way TRACE() does.  The kernel has no registers to spare (251 of 256 VGPRs, SGPRs at the limit, and
@@ -362,6 +376,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     constexpr int LDY = CF::LDY, LDX = CF::LDX, LDA = CF::LDA, RS = CF::RS;
     constexpr bool YIN = CF::YIN, SAVE = CF::SAVE;
     constexpr bool BF = lean_bf<CF>::value;                 // bf16 MFMA operands (CfgBf16)
+    constexpr bool SP = lean_spec<CF>::value;               // compile-time mode (CfgSpec)
+    static_assert(!SP || (!BF && !CF::ACC && !CF::SWISH && KUXT > 0 && 16 * KUXT + 16 <= LDX), "CfgSpec: f32 relu fields with a control path");
     using OpT = LeanOp<BF>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ybuf = lds;                       // [4][LDY]  y
@@ -387,10 +403,10 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     float* zstash = zstash_all + wave * CF::ZSTASH;
     const uint32_t fo4 = (uint32_t)(fo * sizeof(float)), goff4 = (uint32_t)(goff * sizeof(float));
     const int xc = a.lean_xc;                              // control channels in the xt block (0: drift without X)
-    const bool time_on = a.lean_time != 0, geo = a.lean_geo != 0;
+    const bool time_on = a.lean_time != 0, geo = SP ? lean_spec_geo<CF>() : a.lean_geo != 0;
     const float act_scale = a.act == SNSDE_ACT_LIPSWISH ? 0.909f : 1.0f;
-    const int f_out = a.f_out;                             // SNSDE_DRIFT_*: tanh(z) | z | z * y
-    const bool g_raw = a.g_out == SNSDE_DIFFUSION_RAW;     // g = raw instead of tanh(sigmoid(theta) nan_to_num(raw))
+    const int f_out = SP ? (int)SNSDE_DRIFT_TANH : a.f_out;            // SNSDE_DRIFT_*: tanh(z) | z | z * y
+    const bool g_raw = !SP && a.g_out == SNSDE_DIFFUSION_RAW;          // g = raw instead of tanh(sigmoid(theta) nan_to_num(raw))
 
     // ---- resident weights, bias fragments ---------------------------------------------------------------------
     int li = 0;
@@ -423,12 +439,12 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
 
     const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
     const int no = a.no;
-    const bool tab = a.gt_off >= 0;
+    const bool tab = SP || a.gt_off >= 0;
     const float* gt = a.gt_ext ? a.gt_ext : a.ws + (tab ? a.gt_off : 0);
-    const bool mul_y = (no == 13 || no == 17 || no == 3 || no == 6 || no == 11);
-    const bool yfun = (no >= 7 && no <= 10);
-    const bool mil = a.method == SNSDE_MILSTEIN;
-    const bool phx = a.dW == nullptr;
+    const bool mul_y = SP || (no == 13 || no == 17 || no == 3 || no == 6 || no == 11);
+    const bool yfun = !SP && (no >= 7 && no <= 10);
+    const bool mil = !SP && a.method == SNSDE_MILSTEIN;
+    const bool phx = SP || a.dW == nullptr;
     const uint32_t grow = (uint32_t)(a.row_offset + row);
     const uint64_t seed = a.seed_dev ? *a.seed_dev : a.seed;
     const int rslot = a.row_out ? a.row_out[rowc] : -1;
@@ -456,12 +472,14 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         const int li_ = lane + 64 * i, it = wave * xquota + li_;
         const bool ok = KUXT > 0 && li_ < xquota && it < 4 * xw;
         const int rr = ok ? it / xw : 0, col = ok ? it - rr * xw : 0;
-        xdst[i] = ok ? rr * LDX + col : -1;
+        // (CfgSpec: no exec-masked store per step - the lanes without an entry write into the rows' padding past the k-blocks,
+        //  one slot per lane, never read)
+        xdst[i] = ok ? rr * LDX + col : (SP ? (lane & 3) * LDX + 16 * KUXT + (lane >> 2) : -1);
         xkind[i] = col < xc ? 0 : (col == xc ? 1 : 2);
         const int gr = row0 + rr < B ? rr : B - 1 - row0, ch = col < xc ? col : 0;
         cvo[i] = (uint32_t)((gr * cstride + ch) * sizeof(float));
     }
-    const bool has_x = KUXT > 0 && xc > 0;
+    const bool has_x = SP || (KUXT > 0 && xc > 0);
     const float* ctile = a.coeffs + (size_t)row0 * cstride;
     const uint32_t cstep = (uint32_t)(C * sizeof(float));
     const uint32_t cidx = (uint32_t)(4 * C * sizeof(float));       // bytes per spline interval
@@ -498,7 +516,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
                     v = ca[i] + (cb[i] + (0.5f * cc[i] + q3) * frac) * frac;
                 }
                 v = xkind[i] == 0 ? v : (xkind[i] == 1 ? sn : cs);
-                if (xdst[i] >= 0) reinterpret_cast<OpT*>(xb)[xdst[i]] = (OpT)v;
+                if (SP || xdst[i] >= 0) reinterpret_cast<OpT*>(xb)[xdst[i]] = (OpT)v;
             }
         }
     };
@@ -507,7 +525,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     // in this wave's LDS stash; else the supplied increments)
     auto next_dw = [&](int i, float sqh) -> float {
         if (__builtin_expect(phx, 1)) {
-            const int k = i % (4 * CF::ZB);
+            const int k = (int)((uint32_t)i % (uint32_t)(4 * CF::ZB));      // (i >= 0: a mask, not a signed remainder)
             if (__builtin_expect(k == 0, 0)) {
                 float zq[4 * CF::ZB];
 #pragma unroll
@@ -652,7 +670,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
             {
                 const int n1 = more ? n + 1 : n;          // (the last step prefetches its own inputs again: never used)
                 dw_nxt = next_dw(n1, qa[1]);
-                if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)n1 * H);
+                // (the row base on the scalar unit: n1 is uniform, and formed in VGPRs its 64-bit product costs ~5 VALU per step)
+                if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane(n1) * H);
             }
         };
         uint32_t cur = arow;
@@ -769,10 +788,30 @@ int launch_lean(const MfmaArgs& a, hipStream_t stream) {
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
+// The (H, NHID, KUXT) shapes with a CfgSpec instantiation (relu, y input; inference and training mode, GEO 0 and 1): K2 and the
+// GSDE shards of K3.  Shapes that do not pay for the build time stay on the general instantiation.
+#define SNSDE_LEAN_SPEC_LIST(X) X(128, 1, 2)
+__host__ __device__ constexpr bool lean_spec_instantiated(int h, int nhid, int kuxt) {
+#define SNSDE_LEAN_SPEC_HAS(H_, NH_, KX_) if (h == H_ && nhid == NH_ && kuxt == KX_) return true;
+    SNSDE_LEAN_SPEC_LIST(SNSDE_LEAN_SPEC_HAS)
+#undef SNSDE_LEAN_SPEC_HAS
+    return false;
+}
+
 // KUXT = 16-wide k-blocks of [X(t) | sin t, cos t]; YIN = 0 only for input_option 0
 template <int H>
 int dispatch_lean(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st) {
     const bool save = a.act_save || a.traj || a.dW_out;
+    if (p.LEAN_SPEC) {                  // compile-time mode (make_plan decided it covers the launch): 1 tanh drift, 2 with geo
+#define SNSDE_LEAN_SPEC_CASE(H_, NH_, KX_) \
+        if constexpr (H == H_) { if (p.NHID == NH_ && p.KUXT == KX_) { \
+            if (p.LEAN_SPEC == 2) return save ? launch_lean<CfgSpec<CfgL<H_, NH_, KX_, 1, 1>, 1>>(a, st) \
+                                              : launch_lean<CfgSpec<CfgL<H_, NH_, KX_, 1, 0>, 1>>(a, st); \
+            return save ? launch_lean<CfgSpec<CfgL<H_, NH_, KX_, 1, 1>, 0>>(a, st) : launch_lean<CfgSpec<CfgL<H_, NH_, KX_, 1, 0>, 0>>(a, st); } }
+        SNSDE_LEAN_SPEC_LIST(SNSDE_LEAN_SPEC_CASE)
+#undef SNSDE_LEAN_SPEC_CASE
+        return SNSDE_ERR_UNSUPPORTED;
+    }
     if (a.acc_col >= 0) {               // the LatentSDE mapping (fields.compose_latent): relu, one control k-block, y-dependent drift
 #ifndef SNSDE_DEV_SUBSET
 #define SNSDE_LEAN_ACC(NH_) \

@@ -472,6 +472,12 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
         if (p.kernel != FwdKernel::lean || !(H == 64 || H == 128) || variant || train || s->kl_column1 != 0 || srk) return p;
         p.kernel = FwdKernel::lean_bf16;
     }
+    // the lean kernel's compile-time mode (snsde_m4_kernel.h: CfgSpec) where one is instantiated and covers the launch: the
+    // reference's fields with table x y noise, Euler, Philox increments, a control path; SNSDE_FLAG_LEAN_GENERAL keeps the general one
+    if (p.kernel == FwdKernel::lean && !(s->flags & SNSDE_FLAG_LEAN_GENERAL) && lean_spec_instantiated(H, nhid, kuxt) && !variant &&
+        (io == 2 || io == 4 || io == 6) && m.input_channels > 0 && (no == 3 || no == 6 || no == 11 || no == 13 || no == 17) &&
+        s->method == SNSDE_EULER && !s->dW && s->kl_column1 == 0)
+        p.LEAN_SPEC = io == 6 ? 2 : 1;
     p.ok = true;
     return p;
 }

@@ -1813,6 +1813,7 @@ struct MfmaPlan {
     FwdKernel kernel;
     int H, KUX, NHID, IO, FL, TPW, NW, FOLD, NN, SRK;
     int LEAN, KUXT;    // lean M4 kernel (snsde_m4_kernel.h) and its 16-wide k-blocks of [X(t) | sin t, cos t]
+    int LEAN_SPEC;     // kernel == lean: 0 general instantiation, 1 / 2 the compile-time mode CfgSpec<.., GEO = 0 / 1>
     int M4N, KUXN;     // diffusion nets under SRK / Milstein (snsde_m4n_kernel.h) and its control k-blocks (0: latent-only drift)
     int srk_tab_off;   // expanded (3N-row) step table of the SRK variant inside the workspace
     int n_bias_rows;

@@ -462,7 +462,8 @@ class SolveCall:
 
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
-                 noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32'):
+                 noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
+                 lean_general=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -498,6 +499,8 @@ class SolveCall:
         s.kernel = _lib.KERNELS[kernel]
         self.base_flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_STREAM_ALL if stream_all else 0) | (_lib.FLAG_TWO_TILE if two_tile else 0)
         self.base_flags |= precision_flags(precision)      # bf16: inference only (the library refuses training outputs and every backward)
+        if lean_general:    # (SNSDE_FLAG_LEAN_GENERAL: the lean kernel's general instantiation; same results bit for bit)
+            self.base_flags |= _lib.FLAG_LEAN_GENERAL
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -576,6 +579,12 @@ class SolveCall:
         if not capturing:             # a recorded prepare launch has not run: it prepared nothing an eager launch could reuse
             self._prep_key = key
         return self.ys
+
+
+def lean_variant(call):
+    """Which instantiation of the lean kernel the call's forward launches: 'general' (the field's options tested at run time),
+    'specialised' (compiled for exactly those options, csrc/snsde_m4_kernel.h: CfgSpec) or 'none' (another kernel)."""
+    return _lib.LEAN_VARIANTS[_lib.lib().snsde_lean_variant(C.byref(call.desc))]
 
 
 def backward_supported(call):
