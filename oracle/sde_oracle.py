@@ -507,7 +507,7 @@ def step_grid(ts, dt):
 # differential equations", SIAM J. Numer. Anal. 48(3), 2010, section 5 (order (3.0, 1.5) for scalar / diagonal noise, four stages).
 # torchsde 0.2.5 carries it as `_core/methods/tableaus/srid2.py` and `SRK.diagonal_or_scalar_step` (method='srk', the only SRK
 # torchsde has for non-additive noise) walks it: the names below are srid2.py's.  torchsde's source is not in the reference tree
-# (parity unpinned); what pins the TRANSCRIPTION is tests/golden/make_srk_golden.py, which evaluates the published table
+# (parity unpinned); what pins the TRANSCRIPTION is tests/golden/make_exact_golden.py, which evaluates the published table
 # in exact rational arithmetic without importing this file (tests/test_oracle_golden.py, tests/test_gpu_parity.py check both against
 # its vectors), and tests/test_oracle_analytic.py checks Roessler's order conditions on every row.
 #   row by row (Roessler's Butcher array  c(0) | A(0) | B(0)  over  c(1) | A(1) | B(1)  over  alpha | beta(1) beta(2) | beta(3) beta(4)):

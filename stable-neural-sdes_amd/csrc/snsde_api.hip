@@ -139,13 +139,8 @@ int snsde_build_net(const snsde_model& m, int32_t n_steps, SnsdeNet* net) {
     return SNSDE_OK;
 }
 
-// field variants beyond the reference's Diffusion_model (tutorial fields): served by the lean 4-row-tile MFMA kernel only
-static bool is_variant(const snsde_model& m) {
-    return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0;
-}
-
 int snsde_flavor_hint(const snsde_solve* s) {
-    if (is_variant(s->model) || s->noise_table) return 1;      // tutorial-style fields: 4-row tiles only
+    if (snsde_solve_variant(s)) return 1;      // tutorial-style fields: 4-row tiles only
     return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
 }
 
@@ -156,7 +151,7 @@ struct ForwardRoute { int path; snsde_mfma::MfmaPlan plan; };
 static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     ForwardRoute r{};      // (SNSDE_PATH_NONE)
     const int k = s->kernel;
-    const bool variant = is_variant(s->model) || s->noise_table;
+    const bool variant = snsde_solve_variant(s);
     const int generic = s->method == SNSDE_SRK ? SNSDE_PATH_GENERIC_SRK : SNSDE_PATH_GENERIC;
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
@@ -167,6 +162,30 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     // bf16 operands: the bf16 lean kernel or nothing (no f32 kernel stands in for it)
     if ((s->flags & SNSDE_FLAG_BF16_OPERANDS) && r.path != SNSDE_PATH_LEAN_BF16) r = ForwardRoute{};
     return r;
+}
+
+// The adjoint of a descriptor: the one decision behind every backward entry point (snsde_mfma_kernels.h: BackwardRoute).  Both plans
+// are made here, once, with the forward launch's flavour hint, and handed down: the launchers do not plan.
+// mode 1: MFMA adjoint kernel (forward on the MFMA path with act_save); 2: generic adjoint kernel (forward on the generic kernel,
+// traj + dW_out only); 0: no fused backward for this configuration
+static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const SnsdeNet& net) {
+    snsde_mfma::BackwardRoute r{};
+    const int hint = snsde_flavor_hint(s), k = s->kernel;
+    r.fp = make_plan(s, net, hint);
+    r.rp = make_rev_plan(s, net, r.fp, hint);
+    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return r;     // an inference-only forward: no adjoint of any kind
+    if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return r;     // no forward kernel either (validate_solve)
+    const bool variant = snsde_solve_variant(s);      // tutorial-style fields: the 4-row-tile MFMA adjoint or nothing
+    if (r.rp.ok && k != SNSDE_KERNEL_GENERIC && !(variant && k == SNSDE_KERNEL_MFMA_M16)) r.mode = 1;
+    else if (!variant && snsde_generic_backward_supported(s)) r.mode = 2;
+    return r;
+}
+
+// (the generic adjoints pack their own weights / tables)
+static size_t backward_workspace_bytes(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r) {
+    size_t f = r.rp.ok ? r.rp.workspace_floats : 0, g = 0;
+    snsde_generic_workspace_floats(&b->fwd, net, &g);
+    return ((f > g ? f : g) + 64) * sizeof(float);
 }
 
 extern "C" {
@@ -340,7 +359,6 @@ int snsde_grid_srk_build(const float* step_tab, int32_t n_steps, const float* ti
 static int validate_solve(const snsde_solve* s, bool eval) {
     if (!s) return SNSDE_ERR_NULL;
     if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;      // stale binding: refuse before reading any field
-    if (!s) return SNSDE_ERR_NULL;
     int rc = validate_model(&s->model);
     if (rc) return rc;
     if (s->batch <= 0 || s->knots < 2) return SNSDE_ERR_DIMS;
@@ -417,7 +435,7 @@ int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, f
     int rc = validate_solve(s, true);
     if (rc) return rc;
     if (!step_row || !y || !f_out || !g_out) return SNSDE_ERR_NULL;
-    if (is_variant(s->model) || s->noise_table) return SNSDE_ERR_UNSUPPORTED;
+    if (snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
     snsde_solve tmp = *s;
     tmp.n_steps = 1;
     tmp.n_out = 2;
@@ -434,11 +452,10 @@ int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, f
 int snsde_act_slots(const snsde_model* m) {
     int rc = validate_model(m);
     if (rc) return rc;
-    const int no = m->noise_option;   // + the diffusion net's activations (hidden for 18/19, output)
+    const int nn = snsde_noise_net_layers(m->noise_option);   // + the diffusion net's activations (hidden for 18/19, output)
     // smooth activations (tutorial fields): the pre-activations of the NL activated layers as well (their derivative)
     // (+ the hidden pre-activation of a two-layer diffusion net, the last slot)
-    return m->num_hidden_layers + 1 + ((no == 18 || no == 19) ? 2 : ((no == 14 || no == 15) ? 1 : 0)) +
-           (m->activation != SNSDE_ACT_RELU ? m->num_hidden_layers + ((no == 18 || no == 19) ? 1 : 0) : 0);
+    return m->num_hidden_layers + 1 + nn + (m->activation != SNSDE_ACT_RELU ? m->num_hidden_layers + (nn == 2 ? 1 : 0) : 0);
 }
 
 int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_planes, int32_t* delta_slots) {
@@ -446,8 +463,7 @@ int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_p
     if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;
     int slots = snsde_act_slots(&s->model);
     if (slots < 0) return slots;
-    const int no = s->model.noise_option;
-    const int nn = (no == 18 || no == 19) ? 2 : ((no == 14 || no == 15) ? 1 : 0);
+    const int nn = snsde_noise_net_layers(s->model.noise_option);
     int planes = 1;
     if (s->method == SNSDE_SRK && nn > 0) {
         slots += nn; planes = 3;
@@ -460,34 +476,26 @@ int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_p
         *delta_slots = slots + ((s->method == SNSDE_MILSTEIN && nn > 0) ? (nn == 2 ? 3 : 1) : 0);
         // 0: the adjoint of this solve accumulates the weight gradients itself (wave-pair adjoint, snsde_w4_kernel.h): no delta planes
         SnsdeNet net;
-        if (nn > 0 && s->batch > 0 && s->n_steps > 0 && snsde_build_net(s->model, s->n_steps, &net) == SNSDE_OK &&
-            snsde_backward_supported(s) == 1 && snsde_mfma_w4_fused_solve(s, net, nullptr, nullptr))
-            *delta_slots = 0;
+        if (nn > 0 && s->batch > 0 && s->n_steps > 0 && snsde_build_net(s->model, s->n_steps, &net) == SNSDE_OK) {
+            const snsde_mfma::BackwardRoute r = route_backward(s, net);
+            if (r.mode == 1 && r.rp.kernel == snsde_mfma::RevKernel::w4_fused) *delta_slots = 0;
+        }
     }
     return SNSDE_OK;
 }
 
 int snsde_backward_supported(const snsde_solve* s) {
     if (!s || s->struct_size != sizeof(snsde_solve) || validate_model(&s->model)) return 0;
-    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return 0;     // an inference-only forward: no adjoint of any kind
-    if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return 0;     // no forward kernel either (validate_solve)
     SnsdeNet net;
     if (snsde_build_net(s->model, s->n_steps, &net)) return 0;
-    if (is_variant(s->model) || s->noise_table)                // tutorial-style fields: the 4-row-tile MFMA adjoint or nothing
-        return (s->kernel != SNSDE_KERNEL_GENERIC && s->kernel != SNSDE_KERNEL_MFMA_M16 && snsde_mfma_backward_supported(s, net)) ? 1 : 0;
-    // 1: MFMA adjoint kernel (forward on the MFMA path with act_save); 2: generic adjoint kernel (forward on the
-    // generic kernel, traj + dW_out only); 0: no fused backward for this configuration
-    if (snsde_mfma_backward_supported(s, net) && s->kernel != SNSDE_KERNEL_GENERIC) return 1;
-    return snsde_generic_backward_supported(s) ? 2 : 0;
+    return route_backward(s, net).mode;
 }
 
 size_t snsde_backward_workspace_bytes(const snsde_backward* b) {
     if (!b || b->struct_size != sizeof(snsde_backward) || b->fwd.struct_size != sizeof(snsde_solve)) return 0;
     SnsdeNet net;
     if (snsde_build_net(b->fwd.model, b->fwd.n_steps, &net)) return 0;
-    size_t f = snsde_mfma_backward_workspace_floats(&b->fwd, net), g = 0;
-    snsde_generic_workspace_floats(&b->fwd, net, &g);      // the generic adjoints pack their own weights / tables
-    return ((f > g ? f : g) + 64) * sizeof(float);
+    return backward_workspace_bytes(b, net, route_backward(&b->fwd, net));
 }
 
 int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
@@ -502,26 +510,40 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     SnsdeNet net;
     rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
     if (rc) return rc;
-    const int mode = snsde_backward_supported(&b->fwd);
-    if (mode == 0) return SNSDE_ERR_UNSUPPORTED;
-    if (mode == 2) {
+    const snsde_mfma::BackwardRoute r = route_backward(&b->fwd, net);
+    if (r.mode == 0) return SNSDE_ERR_UNSUPPORTED;
+    if (r.mode == 2) {
         if (!b->fwd.dW_out) return SNSDE_ERR_NULL;
         if (b->flags & SNSDE_BWD_ADJ0_ONLY) return SNSDE_ERR_OPTION;     // (its parameter pass reads every a_n)
         if (b->delta_save) return SNSDE_ERR_UNSUPPORTED;    // the generic adjoint writes adjoints only
-        if (b->workspace_bytes < snsde_backward_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
+        if (b->workspace_bytes < backward_workspace_bytes(b, net, r)) return SNSDE_ERR_WORKSPACE;
         return snsde_generic_backward_launch(b, net, static_cast<hipStream_t>(hip_stream));
     }
     if (!b->fwd.act_save) return SNSDE_ERR_NULL;
-    if (b->workspace_bytes < snsde_backward_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
-    return snsde_mfma_backward_launch(b, net, static_cast<hipStream_t>(hip_stream));
+    if (b->workspace_bytes < backward_workspace_bytes(b, net, r)) return SNSDE_ERR_WORKSPACE;
+    return snsde_mfma_backward_launch(b, net, r, static_cast<hipStream_t>(hip_stream));
 }
 
 size_t snsde_param_gradients_workspace_bytes(const snsde_backward* b) {
     if (!b || b->struct_size != sizeof(snsde_backward) || b->fwd.struct_size != sizeof(snsde_solve)) return 0;
     SnsdeNet net;
     if (snsde_build_net(b->fwd.model, b->fwd.n_steps, &net)) return 0;
-    if (snsde_backward_supported(&b->fwd) != 1) return 0;
+    if (route_backward(&b->fwd, net).mode != 1) return 0;
     return snsde_wgrad_workspace_floats(b, net) * sizeof(float);
+}
+
+// The checks the two parameter-gradient entry points share once the descriptor's pointers are in: the route (MFMA adjoint only),
+// the delta planes, the two workspaces
+static int route_param_gradients(const snsde_backward* b, const SnsdeNet& net, size_t pg_workspace_bytes, snsde_mfma::BackwardRoute* r) {
+    *r = route_backward(&b->fwd, net);
+    if (r->mode != 1) return SNSDE_ERR_UNSUPPORTED;
+    if (!b->delta_save && r->rp.kernel != snsde_mfma::RevKernel::w4_fused) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
+    // the adjoint's workspace is an INPUT of the parameter pass (its per-workgroup diffusion-side sums; on the wave-group path the
+    // per-tile weight-gradient blocks themselves): the descriptor must still carry it, at the size the adjoint was given
+    if (!b->workspace) return SNSDE_ERR_NULL;
+    if (b->workspace_bytes < backward_workspace_bytes(b, net, *r)) return SNSDE_ERR_WORKSPACE;
+    if (pg_workspace_bytes < snsde_wgrad_workspace_floats(b, net) * sizeof(float)) return SNSDE_ERR_WORKSPACE;
+    return SNSDE_OK;
 }
 
 int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* workspace, size_t workspace_bytes,
@@ -535,14 +557,10 @@ int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* wor
     SnsdeNet net;
     rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
     if (rc) return rc;
-    if (snsde_backward_supported(&b->fwd) != 1) return SNSDE_ERR_UNSUPPORTED;
-    if (!b->delta_save && !snsde_mfma_w4_fused_solve(&b->fwd, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
-    // the adjoint's workspace is an INPUT of this pass (its per-workgroup diffusion-side sums; on the wave-group path the per-tile
-    // weight-gradient blocks themselves): the descriptor must still carry it, at the size the adjoint was given
-    if (!b->workspace) return SNSDE_ERR_NULL;
-    if (b->workspace_bytes < snsde_backward_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
-    if (workspace_bytes < snsde_param_gradients_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
-    return snsde_wgrad_launch(b, net, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(workspace),
+    snsde_mfma::BackwardRoute r;
+    rc = route_param_gradients(b, net, workspace_bytes, &r);
+    if (rc) return rc;
+    return snsde_wgrad_launch(b, net, r, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(workspace),
                               static_cast<hipStream_t>(hip_stream));
 }
 
@@ -558,14 +576,13 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     SnsdeNet net;
     rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
     if (rc) return rc;
-    if (snsde_backward_supported(&b->fwd) != 1) return SNSDE_ERR_UNSUPPORTED;
-    if (!b->delta_save && !snsde_mfma_w4_fused_solve(&b->fwd, net, nullptr, nullptr)) return SNSDE_ERR_NULL;      // (delta_slots == 0: no planes)
-    if (b->workspace_bytes < snsde_backward_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
-    if (pg_workspace_bytes < snsde_param_gradients_workspace_bytes(b)) return SNSDE_ERR_WORKSPACE;
-    hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    rc = snsde_mfma_backward_launch(b, net, st);
+    snsde_mfma::BackwardRoute r;
+    rc = route_param_gradients(b, net, pg_workspace_bytes, &r);
     if (rc) return rc;
-    return snsde_wgrad_launch(b, net, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(pg_workspace), st);
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    rc = snsde_mfma_backward_launch(b, net, r, st);
+    if (rc) return rc;
+    return snsde_wgrad_launch(b, net, r, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(pg_workspace), st);
 }
 
 int snsde_spline_evaluate(const float* coeffs, int32_t batch, int32_t knots, int32_t channels, int32_t index,

@@ -43,8 +43,21 @@ struct SnsdeDims {
     int32_t B, H, HH, C, L, NL, io, no, N, T, method;
 };
 
-// host-side helpers (snsde_api.cpp)
+// host-side helpers (snsde_api.hip)
 int snsde_build_net(const snsde_model& m, int32_t n_steps, SnsdeNet* net);
+
+// field variants beyond the reference's Diffusion_model (tutorial-style fields: the variant switches of snsde_model, or - for the
+// solve - a caller-supplied noise table): served by the 4-row-tile MFMA kernels only
+inline bool snsde_model_variant(const snsde_model& m) {
+    return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0;
+}
+inline bool snsde_solve_variant(const snsde_solve* s) { return snsde_model_variant(s->model) || s->noise_table != nullptr; }
+// families of noise_option (neuralsde.py:233-288).  Layers of the diffusion net on [sin t, cos t | y]: 14/15 one, 18/19 two
+inline int snsde_noise_net_layers(int no) { return (no == 18 || no == 19) ? 2 : ((no == 14 || no == 15) ? 1 : 0); }
+// table noise: raw = (row of a per-step table) x {1, y}: the time-only noise MLPs and the closed forms in t, sigma
+inline bool snsde_table_noise(int no) { return (no >= 1 && no <= 6) || no == 11 || no == 12 || no == 13 || no == 16 || no == 17; }
+// y noise: raw = phi(y): sqrt y, y^3, sigmoid y, relu y
+inline bool snsde_y_noise(int no) { return no >= 7 && no <= 10; }
 
 // launchers (snsde_generic.hip)
 int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, size_t* floats);
@@ -58,19 +71,15 @@ int snsde_time_table_srk_launch(const float* params, const float* srk_tab, float
 // tile-flavour hint of s->kernel (-1: chosen from the batch, 0: 16-row tiles, 1: 4-row tiles, 2: wave pairs), the same for the
 // forward's route and every backward query (snsde_api.hip)
 int snsde_flavor_hint(const snsde_solve* s);
-// launchers (snsde_mfma.hip); the plan (snsde_mfma_kernels.h) names the forward kernel
-namespace snsde_mfma { struct MfmaPlan; }
+// launchers (snsde_mfma.hip); the plans (snsde_mfma_kernels.h) name the forward and the adjoint kernel.  The backward launchers take
+// the route their entry point decided (route_backward, snsde_api.hip) and do not plan
+namespace snsde_mfma { struct MfmaPlan; struct RevPlan; struct BackwardRoute; }
 snsde_mfma::MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint);
+snsde_mfma::RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& fp, int flavor_hint);
 int snsde_mfma_path(const snsde_mfma::MfmaPlan& p);
 size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
 int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream);
-bool snsde_mfma_backward_supported(const snsde_solve* s, const SnsdeNet& net);
-size_t snsde_mfma_backward_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
-int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream);
-const float* snsde_mfma_gt_table(const snsde_solve* s, const SnsdeNet& net);
-const float* snsde_mfma_srk_pass_table(const snsde_solve* s, const SnsdeNet& net);   // (3N, SNSDE_STEP_STRIDE) or null
-bool snsde_mfma_backward_partials(const snsde_solve* s, const SnsdeNet& net, int* nwg, int* waves, size_t* ds_off,
-                                  size_t* dth_off);
+int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net);
 int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
@@ -81,13 +90,10 @@ int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth
 size_t snsde_w4_grad_floats(const snsde_solve* s);
 int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* gpart,
                                 const float* dth_part, hipStream_t stream);
-// (snsde_mfma.hip) does the backward of this solve take the wave-pair adjoint with fused weight gradients?  -> offsets (floats) of
-// the per-tile blocks and of the theta partial sums inside the backward workspace
-bool snsde_mfma_w4_fused_solve(const snsde_solve* s, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off);
 // launchers (snsde_wgrad.hip)
 size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net);
-int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* ws,
-                       hipStream_t stream);
+int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, float* grad_params,
+                       int32_t n_params, float* ws, hipStream_t stream);
 int snsde_z0_launch(const snsde_solve* s, hipStream_t stream);   // y0 = z0_weight . X(ts[0]) + z0_bias (stand-alone launch)
 int snsde_spline_launch(const float* coeffs, int32_t B, int32_t L, int32_t C, int32_t index, float frac,
                         int32_t derivative, float* out, hipStream_t stream);
@@ -101,7 +107,7 @@ int snsde_spline_launch(const float* coeffs, int32_t B, int32_t L, int32_t C, in
 // coefficients torchsde 0.2.5 ships as _core/methods/tableaus/srid2.py and SRK.diagonal_or_scalar_step walks).  The kernels spell the
 // stage formulas out, so only the rows with more than one possible transcription are named here; the whole tableau is in
 // oracle/sde_oracle.py (SRK_*), checked term by term against an exact-rational evaluation of the published table
-// (tests/golden/make_srk_golden.py).  Rounds 1 - 5 carried B(1) / beta(2) of SRI1W1 (srid1) in these two places: a valid order-1.5
+// (tests/golden/make_exact_golden.py).  Rounds 1 - 5 carried B(1) / beta(2) of SRI1W1 (srid1) in these two places: a valid order-1.5
 // scheme, but not torchsde's trajectory on the same draws.
 //   c(1) = (0, 1/4, 1, 1/4)     A(1) = [1/4; 1 0; 0 0 1/4]     B(1) = [-1/2; 1 0; 2 -1 1/2]
 //   H1_1 = y + f0 h/4 + B1_10 g0 sqrt h        H1_2 = y + f0 h + B1_20 g0 sqrt h

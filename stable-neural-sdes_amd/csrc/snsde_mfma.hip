@@ -253,12 +253,6 @@ __global__ void snsde_srk_expand_kernel(const float* __restrict__ step_tab, cons
 
 }  // namespace
 
-// tutorial-style fields (variant switches of snsde_model / a caller-supplied noise table): the lean 4-row-tile kernels only
-static bool variant_of(const snsde_solve* s) {
-    const snsde_model& m = s->model;
-    return m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0 || s->noise_table != nullptr;
-}
-
 // Wave-owns-rows forward (snsde_w4.hip): forced by hint 2; under `auto` up to 6144 rows
 static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     // measured at the K4 shape (tools/time_w4.py, profiles/r05_time_w4.txt): 2048 rows 109 us against 156 (4-row tiles) / 216 (16-row
@@ -288,38 +282,35 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     // launchers accept
     if ((uint64_t)16 * (uint64_t)(s->batch > 0 ? s->batch : 0) * (uint64_t)H >= (1ull << 32)) return p;
     const bool srk = s->method == SNSDE_SRK;
+    const bool variant = snsde_solve_variant(s);
+    const int nn = snsde_noise_net_layers(no);
+    const bool noise_net = nn > 0, tab_noise = snsde_table_noise(no), y_noise = snsde_y_noise(no);
     // SRK: 4-row tiles; 16-row tiles for the elementwise diffusions at H = 64 / 128, C <= 32 (large batches)
-    const bool srk_m16_ok = srk && (H == 64 || H == 128) && !(no == 14 || no == 15 || no == 18 || no == 19) && m.input_channels <= 32 &&
-                            m.activation == 0 && m.drift_output == 0 && m.diffusion_output == 0 && m.time_feature == 0 && !s->noise_table;
+    const bool srk_m16_ok = srk && (H == 64 || H == 128) && !noise_net && m.input_channels <= 32 && !variant;
     if (srk && flavor_hint == 0 && !srk_m16_ok) return p;
     if (!(H == 256 || H == 128 || H == 64 || H == 32 || H == 16)) return p;
     if (!(io >= 0 && io <= 6)) return p;
-    const bool noise_net = (no == 14 || no == 15 || no == 18 || no == 19);
-    // table noise: raw = (row of a per-step table) x {1, y}: the time-only noise MLPs and the closed forms in t, sigma
-    const bool tab_noise = (no >= 1 && no <= 6) || no == 11 || no == 12 || no == 13 || no == 16 || no == 17;
-    const bool y_noise = (no >= 7 && no <= 10);      // raw = phi(y): sqrt y, y^3, sigmoid y, relu y
     if (!(no == 0 || tab_noise || y_noise || noise_net)) return p;
     // SRK / Milstein through a diffusion net: the 4-row-tile kernels of snsde_m4n_kernel.h (embedded or latent-only drifts)
-    const bool variant_m = m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0;
     const int kuxn = (io == 2 || io == 4 || io == 6) ? (m.input_channels > 32 ? 5 : 2) : 0;
     // Euler with a net takes them too where the general kernel has no (spill-free) instantiation: a wide control path behind
     // the embedding (C > 32, e.g. the sepsis channels), and H = 128 on 4-row tiles (its five resident matrices spill there)
-    bool m4n = noise_net && (s->method != SNSDE_EULER || variant_m);      // (field variants with a net: these kernels, every method)
+    bool m4n = noise_net && (s->method != SNSDE_EULER || snsde_model_variant(m));      // (field variants with a net: these kernels, every method)
     if (noise_net && !m4n && io != 0 && flavor_hint != 0 && m.num_hidden_layers <= 4 &&
-        m4n_instantiated(H, kuxn, m.num_hidden_layers - 1, no >= 18 ? 2 : 1, SNSDE_EULER)) {
+        m4n_instantiated(H, kuxn, m.num_hidden_layers - 1, nn, SNSDE_EULER)) {
         const long r4 = ((s->batch + 3) / 4 + 255) / 256, r16 = ((s->batch + 15) / 16 + 255) / 256;
         const bool m4_tiles = flavor_hint == 1 || 10 * r4 <= 22 * r16;
         if (kuxn == 5 || (H == 128 && m4_tiles)) m4n = true;
     }
     if (m4n && (flavor_hint == 0 || io == 0 || m.num_hidden_layers > 4 ||
-                !m4n_instantiated(H, kuxn, m.num_hidden_layers - 1, no >= 18 ? 2 : 1, s->method)))
+                !m4n_instantiated(H, kuxn, m.num_hidden_layers - 1, nn, s->method)))
         return p;
     if (noise_net && !m4n && (io == 0 || io == 2 || io == 4 || io == 6) && m.input_channels > 32) return p;   // nets + wide control: generic
     if (srk && m.input_channels > 32 && (io == 0 || m.num_hidden_layers > 3)) return p;   // wide control under SRK: embedded drifts, NL <= 3
     const bool emb = (io == 2 || io == 4 || io == 6);
     const int nhid = m.num_hidden_layers - 1;
     if (nhid > 3) return p;
-    p.NN = noise_net ? (no >= 18 ? 2 : 1) : 0;
+    p.NN = nn;
     if ((emb || io == 0) && m.input_channels > 80) return p;
     p.H = H; p.IO = io; p.NHID = nhid;
     p.KUX = (emb || io == 0) ? (m.input_channels > 32 ? 5 : 2) : 1;    // 16-wide k-blocks of the control channels (C <= 32 / <= 80)
@@ -352,8 +343,6 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     if (kuxt == 4 || kuxt == 5) kuxt = 6;        // instantiated: 0, 1, 2, 3, 6 blocks
     p.KUXT = kuxt;
     p.LEAN = (p.FL == 1 && !srk && !m4n && p.NN == 0 && (!emb || p.FOLD) && kuxt <= 6 && lean_fits(H, nhid, kuxt, io != 0)) ? 1 : 0;
-    const bool variant = m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0 ||
-                         s->noise_table != nullptr;
     // tutorial-style fields: lean kernel instantiations with an activation switch (Euler / Milstein), or the general kernel's
     // SRK variant (embedded drifts, C <= 32, H <= 128, a supplied table at the four stage times or no diffusion)
     if (variant && m4n && (s->noise_table || io == 0)) return p;
@@ -482,39 +471,40 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     return p;
 }
 
-static RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& fp) {
+// The adjoint's plan: does an MFMA adjoint kernel take the solve the forward plan fp ran (ok), its workspace layout, and the kernel
+// that runs it.  flavor_hint: the forward launch's (snsde_flavor_hint)
+RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& fp, int flavor_hint) {
     RevPlan p{};
     p.ok = false;
     if (!fp.ok || (s->method != SNSDE_EULER && s->method != SNSDE_MILSTEIN && s->method != SNSDE_SRK)) return p;
-    // diffusion nets: Euler on the general adjoint kernel, SRK on snsde_m4n_rev_kernel.h (Milstein: the generic adjoint)
-    const bool m4n_rev = fp.M4N && !variant_of(s) &&
-                         ((s->method == SNSDE_SRK && m4n_rev_instantiated(fp.H, fp.NHID, fp.NN)) ||
-                          (s->method == SNSDE_MILSTEIN && m4n_mil_rev_instantiated(fp.H, fp.NHID, fp.NN)));
-    // ... field variants under SRK / Milstein on the VAR instantiations of the same two kernels (two-layer nets: NeuralSDEFunc; round 5)
-    const bool variant_srk_net_rev = fp.M4N && variant_of(s) && (s->method == SNSDE_SRK || s->method == SNSDE_MILSTEIN) && fp.H <= 128 &&
-                                     fp.IO != 0 && fp.NN == 2 && fp.NHID <= 2 && !s->noise_table &&
-                                     s->model.diffusion_output != SNSDE_DIFFUSION_TANH && s->model.drift_output != SNSDE_DRIFT_TIMES_Y &&
-                                     (s->method == SNSDE_SRK ? m4n_rev_instantiated(fp.H, fp.NHID, fp.NN)
-                                                             : m4n_mil_rev_instantiated(fp.H, fp.NHID, fp.NN));
-    if (fp.NN != 0 && s->method != SNSDE_EULER && !m4n_rev && !variant_srk_net_rev) return p;
-    // field variants with a net (NeuralSDEFunc-shaped, fields.py): Euler on the general adjoint kernel's 4-row tiles
-    const bool variant_net_rev = fp.M4N && variant_of(s) && s->method == SNSDE_EULER && fp.FL == 1 && fp.H <= 128 && fp.IO != 0 &&
-                                 !s->noise_table && s->model.diffusion_output != SNSDE_DIFFUSION_TANH &&
-                                 s->model.drift_output != SNSDE_DRIFT_TIMES_Y;
-    if (fp.M4N && variant_of(s) && !variant_net_rev && !variant_srk_net_rev) return p;
-    p.M4N = (m4n_rev || variant_srk_net_rev) ? (s->method == SNSDE_SRK ? 1 : 2) : 0;
-    // tutorial-style fields under SRK (the general kernel's SRK variant ran the forward): the SRK adjoint kernel carries the
-    // switches; a raw diffusion from a supplied table (rows = the four stage times of every step) or none
-    const bool variant_srk_rev = fp.SRK && s->method == SNSDE_SRK && variant_of(s) && !fp.M4N && fp.FL == 1 && fp.H <= 128 &&
-                                 fp.IO != 5 && fp.IO != 6 && fp.IO != 0 &&
-                                 ((s->model.diffusion_output == SNSDE_DIFFUSION_RAW && s->noise_table != nullptr) ||
-                                  s->model.noise_option == 0);
-    // tutorial-style fields: the register-resident lean forward (its training-mode instantiations), Euler / Milstein
-    if (variant_of(s) && !variant_net_rev && !variant_srk_net_rev && !variant_srk_rev && !(fp.LEAN && fp.FL == 1 && fp.H <= 128 && !fp.SRK && s->method != SNSDE_SRK &&
-                           (s->model.activation == SNSDE_ACT_RELU || lean_act_save_fits(fp.H, fp.NHID, fp.KUXT)) &&
-                           (s->model.diffusion_output == SNSDE_DIFFUSION_RAW || s->model.noise_option == 0) &&
-                           (s->noise_table != nullptr || s->model.noise_option == 0)))
-        return p;      // (a raw diffusion from a supplied table, or none: theta and noise_t take no part)
+    const snsde_model& m = s->model;
+    const bool variant = snsde_solve_variant(s), srk = s->method == SNSDE_SRK;
+    // the field variants the diffusion-net adjoints carry switches for (NeuralSDEFunc-shaped fields, fields.py)
+    const bool variant_net_ok = fp.H <= 128 && fp.IO != 0 && !s->noise_table && m.diffusion_output != SNSDE_DIFFUSION_TANH &&
+                                m.drift_output != SNSDE_DRIFT_TIMES_Y;
+    if (fp.M4N && s->method != SNSDE_EULER) {
+        // SRK / Milstein through a diffusion net: snsde_m4n_rev_kernel.h / snsde_m4n_mil_rev_kernel.h; field variants on the VAR
+        // instantiations of the same two kernels (two-layer nets: NeuralSDEFunc; round 5)
+        if (!(srk ? m4n_rev_instantiated(fp.H, fp.NHID, fp.NN) : m4n_mil_rev_instantiated(fp.H, fp.NHID, fp.NN))) return p;
+        if (variant && !(variant_net_ok && fp.NN == 2 && fp.NHID <= 2)) return p;
+        p.M4N = srk ? 1 : 2;
+    } else if (variant && fp.M4N) {
+        // field variants with a net under Euler: the general adjoint kernel's 4-row tiles
+        if (!(variant_net_ok && fp.FL == 1)) return p;
+    } else if (variant && srk) {
+        // tutorial-style fields under SRK (the general kernel's SRK variant ran the forward): the SRK adjoint kernel carries the
+        // switches; a raw diffusion from a supplied table (rows = the four stage times of every step) or none
+        if (!(fp.FL == 1 && fp.H <= 128 && fp.IO != 5 && fp.IO != 6 && fp.IO != 0 &&
+              ((m.diffusion_output == SNSDE_DIFFUSION_RAW && s->noise_table != nullptr) || m.noise_option == 0)))
+            return p;
+    } else if (variant) {
+        // tutorial-style fields: the register-resident lean forward (its training-mode instantiations), Euler / Milstein;
+        // a raw diffusion from a supplied table, or none: theta and noise_t take no part
+        if (!(fp.LEAN && fp.FL == 1 && fp.H <= 128 && (m.activation == SNSDE_ACT_RELU || lean_act_save_fits(fp.H, fp.NHID, fp.KUXT)) &&
+              (m.diffusion_output == SNSDE_DIFFUSION_RAW || m.noise_option == 0) && (s->noise_table != nullptr || m.noise_option == 0)))
+            return p;
+    }
+    // (everything else is the reference's own fields: diffusion nets under Euler and the elementwise diffusions on the general adjoint)
     p.SRK = fp.SRK;
     const int H = fp.H, io = fp.IO;
     if (p.SRK && io == 0) return p;      // (the SRK adjoint kernel has no y-free variant: the generic adjoint takes it)
@@ -558,14 +548,30 @@ static RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const Mf
     p.total_floats = packed + (p.emb ? H * net.in.K + H : 0) + 16;
     p.nwg = (s->batch + (p.FL ? 4 : 16) - 1) / (p.FL ? 4 : 16);
     p.ds_off = p.dth_off = 0;
-    const int no_ = s->model.noise_option;
-    if (fp.gt_off >= 0 || p.NN > 0 || (no_ >= 7 && no_ <= 10)) {     // the adjoint kernel also leaves the diffusion-side parameter sums
+    if (fp.gt_off >= 0 || p.NN > 0 || snsde_y_noise(m.noise_option)) {     // the adjoint kernel also leaves the diffusion-side parameter sums
         size_t o = ((size_t)p.total_floats + 3) & ~(size_t)3;
         if (fp.gt_off >= 0) { p.ds_off = o; o += (size_t)p.nwg * s->n_steps * H * (p.SRK ? 4 : 1); }   // time-only noise MLP: d/d s_n
         p.dth_off = o; o += (size_t)p.nwg * p.NW;                                    // d/d sigmoid(theta)
         if (o + 16 > 0x7fffffff) return p;
         p.total_floats = (int)(o + 16);
     }
+    // the kernel.  Wave pairs with the weight gradients inside (snsde_w4_kernel.h) where `w4` or `auto` ran the forward on them: Euler
+    // or SRK (SRID2) with a diffusion net, every a_n or dL/dy0 only; forced by hint 2, under `auto` up to 6144 rows (w4_takes)
+    // (p.NW >= 4: the per-tile theta partials - four floats per 4-row tile - live in the plan's dth block of nwg x NW floats)
+    const bool w4_method = srk ? (p.M4N == 1 && p.NW >= 4) : !p.M4N;
+    if ((flavor_hint == 2 || (flavor_hint == -1 && s->batch <= 6144)) && p.FL == 1 && w4_method && fp.NN > 0 && s->kl_column1 == 0 &&
+        snsde_w4_rev_supported(s, net))
+        p.kernel = RevKernel::w4_fused;
+    else if (p.M4N) p.kernel = p.M4N == 1 ? RevKernel::m4n_srk : RevKernel::m4n_milstein;
+    else if (p.SRK) p.kernel = RevKernel::general_srk;
+    // two tiles per wave at H = 256 (round 6) unless SNSDE_FLAG_STREAM_ALL asks for the streamed weights: the reference's own fields
+    // on 4-row tiles, elementwise diffusions, y-dependent drifts, no path-integral column (dispatch_rev_h256_two_tile)
+    else if (H == 256 && !(s->flags & SNSDE_FLAG_STREAM_ALL) && p.FL == 1 && !p.IO0 && p.NN == 0 && !variant && s->kl_column1 == 0 &&
+             m4s2_rev_instantiated(p.NHID, p.GEO != 0))
+        p.kernel = RevKernel::two_tile_h256;
+    else p.kernel = RevKernel::general;
+    p.w4_gpart_off = p.kernel == RevKernel::w4_fused ? ((size_t)p.total_floats + 63) & ~(size_t)63 : 0;
+    p.workspace_floats = p.kernel == RevKernel::w4_fused ? p.w4_gpart_off + snsde_w4_grad_floats(s) : (size_t)p.total_floats;
     p.ok = true;
     return p;
 }
@@ -707,73 +713,17 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
 
 // ---- backward host side ---------------------------------------------------------------------------------
 
-const float* snsde_mfma_srk_pass_table(const snsde_solve* s, const SnsdeNet& net) {
-    MfmaPlan p = make_plan(s, net, -1);
-    return (p.ok && p.SRK && s->workspace) ? static_cast<const float*>(s->workspace) + p.srk_tab_off : nullptr;
-}
-
-const float* snsde_mfma_gt_table(const snsde_solve* s, const SnsdeNet& net) {
-    if (s->noise_table) return s->noise_table;
-    MfmaPlan p = make_plan(s, net, -1);
-    return (p.ok && p.gt_off >= 0 && s->workspace) ? static_cast<const float*>(s->workspace) + p.gt_off : nullptr;
-}
-
-// The adjoint of this solve: the forward's plan (the forward launch's flavour hint), the adjoint's plan, and whether the wave-pair
-// adjoint with the weight gradients inside takes it (Euler or SRK (SRID2) with a diffusion net, 4-row tiles, every a_n or dL/dy0 only)
-struct BackwardChoice { MfmaPlan fp; RevPlan rp; bool w4; };
-
-static BackwardChoice backward_choice(const snsde_solve* s, const SnsdeNet& net) {
-    const int hint = snsde_flavor_hint(s);
-    BackwardChoice c;
-    c.fp = make_plan(s, net, hint);
-    c.rp = make_rev_plan(s, net, c.fp);
-    const RevPlan& p = c.rp;
-    // (p.NW >= 4: the per-tile theta partials - four floats per 4-row tile - live in the plan's dth block of nwg x NW floats)
-    const bool method_ok = s->method == SNSDE_SRK ? (p.SRK && p.M4N == 1 && p.NW >= 4) : (!p.M4N && !p.SRK);
-    c.w4 = hint != 0 && hint != 1 && p.ok && p.FL == 1 && method_ok && c.fp.NN > 0 && s->kl_column1 == 0 &&
-           (hint == 2 || s->batch <= 6144) && snsde_w4_rev_supported(s, net);
-    return c;
-}
-
-bool snsde_mfma_backward_supported(const snsde_solve* s, const SnsdeNet& net) { return backward_choice(s, net).rp.ok; }
-
-bool snsde_mfma_backward_partials(const snsde_solve* s, const SnsdeNet& net, int* nwg, int* waves, size_t* ds_off,
-                                  size_t* dth_off) {
-    const BackwardChoice c = backward_choice(s, net);
-    const RevPlan& p = c.rp;
-    if (!p.ok || p.dth_off == 0) return false;
-    *nwg = p.nwg; *waves = p.NW; *ds_off = p.ds_off; *dth_off = p.dth_off;
-    return true;
-}
-
-static size_t w4_gpart_off(const RevPlan& p) { return ((size_t)p.total_floats + 63) & ~(size_t)63; }
-
-size_t snsde_mfma_backward_workspace_floats(const snsde_solve* s, const SnsdeNet& net) {
-    const BackwardChoice c = backward_choice(s, net);
-    if (!c.rp.ok) return 0;
-    return c.w4 ? w4_gpart_off(c.rp) + snsde_w4_grad_floats(s) : (size_t)c.rp.total_floats;
-}
-
-bool snsde_mfma_w4_fused_solve(const snsde_solve* s, const SnsdeNet& net, size_t* gpart_off, size_t* dth_off) {
-    const BackwardChoice c = backward_choice(s, net);
-    if (!c.w4) return false;
-    if (gpart_off) *gpart_off = w4_gpart_off(c.rp);
-    if (dth_off) *dth_off = c.rp.dth_off;
-    return true;
-}
-
-int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream) {
+int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const BackwardRoute& r, hipStream_t stream) {
     const snsde_solve* s = &b->fwd;
-    const BackwardChoice c = backward_choice(s, net);
-    const MfmaPlan& fp = c.fp;
-    const RevPlan& p = c.rp;
-    if (!p.ok) return SNSDE_ERR_UNSUPPORTED;      // (the plans also refuse what overflows the kernels' 32-bit save offsets)
+    const MfmaPlan& fp = r.fp;
+    const RevPlan& p = r.rp;
+    if (r.mode != 1) return SNSDE_ERR_UNSUPPORTED;      // (the plans also refuse what overflows the kernels' 32-bit save offsets)
     float* ws = static_cast<float*>(b->workspace);
-    if (c.w4) {
+    if (p.kernel == RevKernel::w4_fused) {
         // the wave-pair adjoint reads the nn.Linear layout of `params` itself (columns of the weights): no fold, no pack launch;
-        // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (snsde_mfma_w4_fused_solve)
+        // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (RevPlan::w4_gpart_off)
         if (!(s->dW_out ? s->dW_out : s->dW) && s->seed_dev) return SNSDE_ERR_NULL;
-        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + w4_gpart_off(p), stream);
+        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + p.w4_gpart_off, stream);
     }
     // first_y = emb[:, 0:H] . linear_in (all columns; the pack step picks the y columns).  A forward that ran with the folded first
     // layer left exactly this product in ITS workspace (piece `in` of snsde_prepare_kernel, same (H, K_in) layout): the pack
@@ -816,7 +766,7 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hip
     a.adj0_only = (b->flags & SNSDE_BWD_ADJ0_ONLY) ? 1 : 0;
     a.acc_col = s->kl_column1 - 1; a.acc_a = s->kl_prior_a; a.acc_b = s->kl_prior_b;
     if (a.acc_col >= 0 && (p.FL != 1 || p.M4N || p.H > 128)) return SNSDE_ERR_UNSUPPORTED;      // (the 4-row-tile Euler / SRK adjoints carry it)
-    if (a.adj0_only && p.M4N == 2) return SNSDE_ERR_OPTION;      // (its weight-gradient jobs read every a_n)
+    if (a.adj0_only && p.kernel == RevKernel::m4n_milstein) return SNSDE_ERR_OPTION;      // (its weight-gradient jobs read every a_n)
     if (p.SRK) {
         if (!s->dU_out) return SNSDE_ERR_NULL;
         a.dU = s->dU_out;
@@ -825,30 +775,33 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, hip
     a.dth_part = p.dth_off ? ws + p.dth_off : nullptr;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = s->model.noise_option; a.off_theta = net.off_theta; a.method = s->method;
     for (int i = 0; i < p.n_layers; ++i) a.w_off[i] = p.layer[i].dst;
-    if (p.M4N == 2) {
-        a.geo = p.GEO;
-        if (p.H == 128) return dispatch_m4n_mil_rev_h128(p, a, stream);
-        if (p.H == 64) return dispatch_m4n_mil_rev_h64(p, a, stream);
-        if (p.H == 32) return dispatch_m4n_mil_rev_h32(p, a, stream);
-        if (p.H == 16) return dispatch_m4n_mil_rev_h16(p, a, stream);
-        return SNSDE_ERR_UNSUPPORTED;
+    // one dispatcher per kernel: what it answers is the launch's answer (a plan and a dispatcher that disagree are an error, never
+    // a run of another kernel)
+    switch (p.kernel) {
+        case RevKernel::w4_fused: break;      // (launched above)
+        case RevKernel::m4n_milstein:
+            a.geo = p.GEO;
+            if (p.H == 128) return dispatch_m4n_mil_rev_h128(p, a, stream);
+            if (p.H == 64) return dispatch_m4n_mil_rev_h64(p, a, stream);
+            if (p.H == 32) return dispatch_m4n_mil_rev_h32(p, a, stream);
+            if (p.H == 16) return dispatch_m4n_mil_rev_h16(p, a, stream);
+            break;
+        case RevKernel::m4n_srk:
+            a.geo = p.GEO;
+            if (p.H == 128) return dispatch_m4n_rev_h128(p, a, stream);
+            if (p.H == 64) return dispatch_m4n_rev_h64(p, a, stream);
+            if (p.H == 32) return dispatch_m4n_rev_h32(p, a, stream);
+            if (p.H == 16) return dispatch_m4n_rev_h16(p, a, stream);
+            break;
+        case RevKernel::two_tile_h256: return dispatch_rev_h256_two_tile(p, a, stream);
+        case RevKernel::general_srk:      // (dispatch_rev: launch_rev_srk where the plan says SRK)
+        case RevKernel::general:
+            if (p.H == 256) return dispatch_rev_h256(p, a, stream);
+            if (p.H == 128) return dispatch_rev_h128(p, a, stream);
+            if (p.H == 64) return dispatch_rev_h64(p, a, stream);
+            if (p.H == 32) return dispatch_rev_h32(p, a, stream);
+            if (p.H == 16) return dispatch_rev_h16(p, a, stream);
+            break;
     }
-    if (p.M4N) {
-        a.geo = p.GEO;
-        if (p.H == 128) return dispatch_m4n_rev_h128(p, a, stream);
-        if (p.H == 64) return dispatch_m4n_rev_h64(p, a, stream);
-        if (p.H == 32) return dispatch_m4n_rev_h32(p, a, stream);
-        if (p.H == 16) return dispatch_m4n_rev_h16(p, a, stream);
-        return SNSDE_ERR_UNSUPPORTED;
-    }
-    if (p.H == 256 && !(s->flags & SNSDE_FLAG_STREAM_ALL)) {      // two tiles per wave, a quarter of the transposed weights resident (round 6)
-        const int rc = dispatch_rev_h256_two_tile(p, a, stream);
-        if (rc != SNSDE_ERR_UNSUPPORTED) return rc;
-    }
-    if (p.H == 256) return dispatch_rev_h256(p, a, stream);
-    if (p.H == 128) return dispatch_rev_h128(p, a, stream);
-    if (p.H == 64) return dispatch_rev_h64(p, a, stream);
-    if (p.H == 32) return dispatch_rev_h32(p, a, stream);
-    if (p.H == 16) return dispatch_rev_h16(p, a, stream);
     return SNSDE_ERR_UNSUPPORTED;
 }

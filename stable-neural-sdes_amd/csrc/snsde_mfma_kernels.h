@@ -1823,14 +1823,32 @@ struct MfmaPlan {
     int bias_off, gt_off, total_floats;
 };
 
+// the adjoint kernel a plan runs (set by make_rev_plan only; snsde_mfma_backward_launch dispatches on it)
+enum class RevKernel {
+    w4_fused,        // wave-pair adjoint with the weight gradients inside (snsde_w4_rev_launch): no delta planes
+    m4n_srk,         // SRK through a diffusion net (snsde_m4n_rev_kernel.h)
+    m4n_milstein,    // Milstein through a diffusion net (snsde_m4n_mil_rev_kernel.h)
+    general_srk,     // SRK adjoint of the general kernel (launch_rev_srk, 4-row tiles)
+    two_tile_h256,   // H = 256, two tiles per wave, a quarter of the transposed weights resident (snsde_m4s2_rev_kernel.h)
+    general          // Euler / Milstein adjoint of the general kernel on 4- or 16-row tiles (dispatch_rev)
+};
+
 struct RevPlan {
     bool ok;
+    RevKernel kernel;
     int H, NHID, GEO, FL, NW, NN, SRK, IO0, n_layers, fold_tmp, total_floats, emb;
-    int M4N;                    // SRK through a diffusion net: snsde_m4n_rev_kernel.h
+    int M4N;                    // weight layout of the diffusion-net adjoints: 1 m4n_srk, 2 m4n_milstein (+ the forward-layout net), 0 else
     int nwg;                    // workgroups of the adjoint launch
     size_t ds_off, dth_off;     // diffusion-side partial sums inside the backward workspace (0 = none)
+    size_t w4_gpart_off;        // kernel == w4_fused: the per-tile weight-gradient blocks, behind the plan's own floats
+    size_t workspace_floats;    // the whole backward workspace (total_floats, + the blocks at w4_gpart_off)
     MfmaLayerPack layer[MAXL];
 };
+
+// The adjoint of a solve, decided once per entry point (route_backward, snsde_api.hip): the mode snsde_backward_supported reports
+// (0 none, 1 MFMA adjoint, 2 generic adjoint), the forward's plan - the one its launch ran with - and the adjoint's plan.
+// Mode 1 runs rp; the plans are filled in whatever the mode (snsde_backward_workspace_bytes sizes for rp wherever it is ok).
+struct BackwardRoute { int mode; MfmaPlan fp; RevPlan rp; };
 
 // Which 4-row-tile configurations the lean kernel (snsde_m4_kernel.h) takes: its resident weights plus one layer's B
 // operands must fit the 256-register budget of two waves per SIMD WITHOUT spilling (its asm-issued loads land in
@@ -1959,6 +1977,7 @@ int dispatch_fwd_m16_h16(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_fwd_m4_h16(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_rev_h16(const RevPlan& p, const RevArgs& a, hipStream_t st);
 int dispatch_rev_h256_two_tile(const RevPlan& p, const RevArgs& a, hipStream_t st);   // snsde_m4s2_rev_kernel.h
+bool m4s2_rev_instantiated(int nhid, bool geo);                                         // (its instantiation list)
 int dispatch_fwd_m16_h32(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_fwd_m4_h32(const MfmaPlan& p, const MfmaArgs& a, hipStream_t st);
 int dispatch_rev_h32(const RevPlan& p, const RevArgs& a, hipStream_t st);

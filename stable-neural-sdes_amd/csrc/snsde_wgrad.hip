@@ -20,7 +20,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "snsde_internal.h"
+#include "snsde_mfma_kernels.h"      // (MfmaPlan / RevPlan of the route: host side only, no kernel of it is instantiated here)
 
 namespace {
 
@@ -681,7 +681,7 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     const int nhid = s.model.num_hidden_layers - 1;
     const bool emb = (io == 2 || io == 4 || io == 6), timef = io >= 3, io0 = io == 0;
     const bool usex = emb || io0;                       // X(t) is an input of the first layer
-    const int nn = (no == 18 || no == 19) ? 2 : ((no == 14 || no == 15) ? 1 : 0);
+    const int nn = snsde_noise_net_layers(no);
     const int ts = timef ? 2 : 0;
     const int xt = (timef || nn > 0) ? 2 : 0;          // time columns present in the xaux rows
     // xaux row = [sin t, cos t | X(t)] in the drift's order; a time-free embedded drift with a diffusion net (input_option 2)
@@ -814,13 +814,13 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     }
     w->sums_floats = (off + 3) & ~(size_t)3;
     w->part_floats = (size_t)nparts * TILE_FLOATS;
-    w->tnoise = (no >= 1 && no <= 6) || no == 11 || no == 12 || no == 13 || no == 16 || no == 17;   // table noise: ds wanted
+    w->tnoise = snsde_table_noise(no);   // ds wanted
     const bool two = (no == 16 || no == 17);
     size_t o = w->sums_floats + w->part_floats;
     const size_t NH = (size_t)n_trow * H;
     w->n_pass = n_pass; w->n_trow = n_trow;
     w->ds_off = o; o += w->tnoise ? NH : 0;
-    w->has_dth = w->tnoise || nn > 0 || (no >= 7 && no <= 10);
+    w->has_dth = w->tnoise || nn > 0 || snsde_y_noise(no);
     w->t_col0 = t_col0; w->x_col0 = x_col0; w->x_cols = usex ? C : 0;
     w->nact = nhid + 2 + nn + (srknet ? nn : 0);      // act_save slots per pass (snsde_save_layout)
     w->ndelta = w->nact + (milnet ? (nn == 2 ? 3 : 1) : 0);      // delta_save slots per pass
@@ -865,14 +865,15 @@ size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net
 //   3. snsde_epilogue_kernel     the small products (folded first layer, noise MLP) + the assembly of the flat gradient;
 // (+ snsde_sigma_grad_kernel for the closed-form table noises 1..6).  No events, no second stream: a cross-queue event round trip
 // costs 7 - 12 us on this runtime (rocprofv3 timeline of the round-3 pass), more than the small kernels it overlapped.
-int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* ws,
-                       hipStream_t stream) {
-    {   // wave-pair adjoint with fused weight gradients (snsde_w4_kernel.h): the sums are in the BACKWARD workspace, per tile
-        size_t gpart_off = 0, dth_off = 0;
-        if (snsde_mfma_w4_fused_solve(&b->fwd, net, &gpart_off, &dth_off)) {
-            float* bws = static_cast<float*>(b->workspace);
-            return snsde_w4_grad_reduce_launch(b, net, grad_params, n_params, bws + gpart_off, bws + dth_off, stream);
-        }
+int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, float* grad_params,
+                       int32_t n_params, float* ws, hipStream_t stream) {
+    using snsde_mfma::RevKernel;
+    const snsde_mfma::MfmaPlan& fp = r.fp;      // (the forward's: where its launch left the tables in the forward workspace)
+    const snsde_mfma::RevPlan& rp = r.rp;       // (the adjoint's: where its launch left the partial sums in the backward workspace)
+    if (r.mode != 1) return SNSDE_ERR_UNSUPPORTED;
+    if (rp.kernel == RevKernel::w4_fused) {   // fused weight gradients (snsde_w4_kernel.h): the sums are in the BACKWARD workspace, per tile
+        float* bws = static_cast<float*>(b->workspace);
+        return snsde_w4_grad_reduce_launch(b, net, grad_params, n_params, bws + rp.w4_gpart_off, bws + rp.dth_off, stream);
     }
     WPlan plan;
     WPlan* wp = &plan;
@@ -885,20 +886,20 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, float* grad
     const bool srk = s.method == SNSDE_SRK;
     const float* pass_tab = s.step_tab;            // one row per drift pass: time features and spline interval
     if (srk) {
-        pass_tab = snsde_mfma_srk_pass_table(&s, net);
-        if (!pass_tab || !s.stage_save || !s.srk_tab) return SNSDE_ERR_NULL;
+        if (!s.workspace || !s.stage_save || !s.srk_tab) return SNSDE_ERR_NULL;
+        pass_tab = static_cast<const float*>(s.workspace) + fp.srk_tab_off;      // (3N, SNSDE_STEP_STRIDE): the forward's expanded table
         a.traj = s.stage_save;                     // first-layer inputs = the stage states
     }
     const bool smooth = s.model.activation != SNSDE_ACT_RELU;      // act_save then also holds the NL pre-activations per step
     a.B = s.batch; a.H = H; a.N = wp->n_pass; a.NG = wp->ndelta;
-    a.NSAVE = wp->nact + (smooth ? s.model.num_hidden_layers + ((no == 18 || no == 19) ? (srk ? 2 : 1) : 0) : 0);      // (SRK: + the fourth evaluation's)
+    a.NSAVE = wp->nact + (smooth ? s.model.num_hidden_layers + (snsde_noise_net_layers(no) == 2 ? (srk ? 2 : 1) : 0) : 0);      // (SRK: + the fourth evaluation's)
     a.adj = b->adj;
     a.R = wp->n_pass * s.batch; a.ntiles = wp->ntiles; a.NP = wp->NP;
     for (int i = 0; i < wp->ntiles; ++i) a.tile[i] = wp->tile[i];
     a.x = XInfo{s.coeffs, pass_tab, s.batch, C, s.knots - 1, wp->t_col0, wp->xt, wp->x_col0, wp->x_cols,
                 s.model.time_feature == SNSDE_TIME_RAW ? 1 : 0, wp->n_col0};
     AArgs aa = wp->aa;
-    const float* gt = snsde_mfma_gt_table(&s, net);
+    const float* gt = s.noise_table ? s.noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s.workspace) + fp.gt_off : nullptr);
     float* ds = ws + wp->ds_off;
     aa.params = s.params; aa.sums = ws; aa.ds = ds; aa.dth = ws + wp->dth_off;
     aa.dz1 = ws + wp->dz1_off; aa.dz2 = ws + wp->dz2_off; aa.a1 = ws + wp->a1_off;
@@ -911,14 +912,12 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, float* grad
     if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_wgrad_kernel), lds_bytes, lds_attr)) return rc;
     a.dsum_blocks = 0;
     if (wp->has_dth) {
-        int nwg = 0, waves = 0; size_t ds_off = 0, dth_off = 0;
-        if ((wp->tnoise && !gt) || !b->workspace || !snsde_mfma_backward_partials(&s, net, &nwg, &waves, &ds_off, &dth_off))
-            return SNSDE_ERR_UNSUPPORTED;
+        if ((wp->tnoise && !gt) || !b->workspace || rp.dth_off == 0) return SNSDE_ERR_UNSUPPORTED;
         const float* bws = static_cast<const float*>(b->workspace);
         DArgs& d = a.dsum;
-        d.ds_part = bws + ds_off; d.dth_part = bws + dth_off; d.ds = ds; d.dth = ws + wp->dth_off;
+        d.ds_part = bws + rp.ds_off; d.dth_part = bws + rp.dth_off; d.ds = ds; d.dth = ws + wp->dth_off;
         if (s.noise_table && b->grad_noise_table) d.ds = b->grad_noise_table;     // dL/d(supplied table): the caller's to propagate
-        d.nwg = nwg; d.n_dth = nwg * waves; d.NH = wp->tnoise ? wp->n_trow * H : 0;
+        d.nwg = rp.nwg; d.n_dth = rp.nwg * rp.NW; d.NH = wp->tnoise ? wp->n_trow * H : 0;
         a.dsum_blocks = (d.NH + 63) / 64 + 1;
     }
     int gx = wp->max_split;
