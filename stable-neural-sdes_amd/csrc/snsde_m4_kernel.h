@@ -328,9 +328,23 @@ __device__ __forceinline__ void lean_gemm(const s16x4 (&w)[KU], LeanBh<KU>& b, f
 // run: table x y noise (noise_option 3 / 6 / 11 / 13 / 17), Euler, relu, tanh drift (with z *= tanh(y) when GEO: input_option 6),
 // in-kernel Philox increments, a control path in the first layer, no accumulator column.  Same arithmetic on every value; only
 // the tests, the selects they feed and the branches around them are gone.
-template <class CF, int GEO_> struct CfgSpec : CF { static constexpr bool SPEC = true, SPEC_GEO = GEO_ != 0; };
+//
+// Spline batches.  The general loop evaluates the tile's 4 x (xc + 2) entries of [X(t_{n+1}) | sin, cos] every step, one entry per
+// lane: at K2 twelve lanes of each wave work, all 64 pay the ~15 VALU instructions and the four loads.  The specialised loop evaluates XB = 4 steps at once,
+// every fourth step: lane 16 k + e takes entry e of its wave for X(t_{n+1+k}), k = 0..3, with the frac / sin / cos / interval of its
+// own step from the LDS step table, and xbuf becomes a ring of XB slots (slot m & 3 holds X(t_m)).  Same operations on every value.
+template <class CF, int GEO_> struct CfgSpec : CF {
+    static constexpr bool SPEC = true, SPEC_GEO = GEO_ != 0;
+    static constexpr int XB = 4;
+    static constexpr int LDS_FLOATS = CF::LDS_FLOATS + 4 * (XB - 2) * CF::LDX;
+    static_assert(CF::XI == 1 && 4 * 16 * CF::KUXT <= 16 * CF::NW && CF::ROWCH % XB == 0, "CfgSpec: one spline entry per lane, 16 lanes per step of a batch");
+};
 template <class CF, class = void> struct lean_spec : std::false_type {};
 template <class CF> struct lean_spec<CF, std::void_t<decltype(CF::SPEC)>> : std::bool_constant<CF::SPEC> {};
+template <class CF> constexpr int lean_xslots() {           // [X(t) | sin t, cos t] buffers in LDS
+    if constexpr (lean_spec<CF>::value) return CF::XB;
+    else return 2;
+}
 template <class CF> constexpr bool lean_spec_geo() {
     if constexpr (lean_spec<CF>::value) return CF::SPEC_GEO;
     else return false;
@@ -343,15 +357,17 @@ template <class CF> constexpr bool lean_spec_geo() {
 // per-lane LDS slot with a fire-and-forget ds_add_u32 (conflict-free, 12 x NT words behind the kernel's own LDS); phase i =
 // sum_i - sum_{i-1} (mod 2^32); the wrap-around phase 9 -> 0 from the sums of stamp 0 over steps >= 1 and stamp 9 over steps
 // <= N - 2 (slots 10 / 11).  Cost: 2 instructions per stamp and step (the traced kernel runs ~15 % slower than the plain one).
+// The f32 instantiations only: in the bf16 ones hipcc keeps the stamps in VGPRs across the loop and cannot copy them back for the
+// "+s" ties ("illegal VGPR to SGPR copy"), so there the stamps compile to nothing and the trace build stays buildable.
 #ifdef LEAN_TRACE
 #define LT_DECL unsigned long long lt[10]; uint32_t* const ltl = reinterpret_cast<uint32_t*>(lds + CF::LDS_FLOATS) + tid; \
-    for (int i_ = 0; i_ < 12; ++i_) ltl[i_ * NT] = 0u;
-#define LT(i) asm volatile("s_memtime %0" : "=s"(lt[i]));
+    if constexpr (!BF) { for (int i_ = 0; i_ < 12; ++i_) ltl[i_ * NT] = 0u; }
+#define LT(i) if constexpr (!BF) { asm volatile("s_memtime %0" : "=s"(lt[i])); }
 #define LT_ADD(slot, i) __hip_atomic_fetch_add(ltl + (slot) * NT, (uint32_t)lt[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-#define LT_COLLECT_A { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[0]), "+s"(lt[1]), "+s"(lt[2]), "+s"(lt[3])); \
+#define LT_COLLECT_A if constexpr (!BF) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[0]), "+s"(lt[1]), "+s"(lt[2]), "+s"(lt[3])); \
     LT_ADD(0, 0) LT_ADD(1, 1) LT_ADD(2, 2) LT_ADD(3, 3) if (n > 0) LT_ADD(10, 0) }
-#define LT_COLLECT_B { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[4]), "+s"(lt[5]), "+s"(lt[6])); LT_ADD(4, 4) LT_ADD(5, 5) LT_ADD(6, 6) }
-#define LT_COLLECT { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[7]), "+s"(lt[8]), "+s"(lt[9])); LT_ADD(7, 7) LT_ADD(8, 8) LT_ADD(9, 9) \
+#define LT_COLLECT_B if constexpr (!BF) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[4]), "+s"(lt[5]), "+s"(lt[6])); LT_ADD(4, 4) LT_ADD(5, 5) LT_ADD(6, 6) }
+#define LT_COLLECT if constexpr (!BF) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(lt[7]), "+s"(lt[8]), "+s"(lt[9])); LT_ADD(7, 7) LT_ADD(8, 8) LT_ADD(9, 9) \
     if (n + 1 < N) LT_ADD(11, 9) }
 #define LT_LDS_EXTRA (12 * CF::NT * sizeof(uint32_t))
 #else
@@ -363,6 +379,26 @@ template <class CF> constexpr bool lean_spec_geo() {
 #define LT_LDS_EXTRA 0
 #endif
 
+// Development bound (build.py variant NAME -DLEAN_KNOCKOUT; timing only, never a product build): the specialised step loop without
+// its chain-independent work - no spline evaluation, no coefficient prefetch, no Philox generation after the first block.  The
+// results are wrong but finite (X stays at X(t_0) / 0, the first 16 steps' normals repeat).  Its kernel time bounds from below what
+// moving that work off the compute waves could reach (profiles/helper_waves_knockout.txt).
+#ifdef LEAN_KNOCKOUT
+#define LEAN_KO(SP) (SP)
+#else
+#define LEAN_KO(SP) false
+#endif
+// Development probe (hipcc -DSNSDE_DEV_SUBSET -DLEAN_SPEC_WPS=3 -Rpass-analysis=kernel-resource-usage -c csrc/snsde_m4_h128.hip): the
+// specialised instantiations compiled for LEAN_SPEC_WPS waves per SIMD instead of CF::WPS = 2.  Three waves per SIMD (<= 168
+// registers) is what an extra helper wave beside the two compute waves would need; the probe shows what the compute path spills there
+// (profiles/helper_waves_knockout.txt).  Never run: a lean kernel that spills is wrong (build.py: check_lean_resources).
+#if (defined(LEAN_KNOCKOUT) || defined(LEAN_SPEC_WPS)) && !defined(SNSDE_DEV_SUBSET)
+#error "LEAN_KNOCKOUT / LEAN_SPEC_WPS are development switches (build.py variant): never part of a product build"
+#endif
+#ifndef LEAN_SPEC_WPS
+#define LEAN_SPEC_WPS CF::WPS
+#endif
+
 #ifndef LEAN_TANH_F
 #define LEAN_TANH_F lean_tanh_rel<false>
 #endif
@@ -371,7 +407,7 @@ template <class CF> constexpr bool lean_spec_geo() {
 #endif
 
 template <class CF>
-__global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
+__global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS : CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     constexpr int H = CF::H, NT = CF::NT, NHID = CF::NHID, KUH = CF::KUH, KUXT = CF::KUXT;
     constexpr int LDY = CF::LDY, LDX = CF::LDX, LDA = CF::LDA, RS = CF::RS;
     constexpr bool YIN = CF::YIN, SAVE = CF::SAVE;
@@ -381,8 +417,16 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     using OpT = LeanOp<BF>;
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* ybuf = lds;                       // [4][LDY]  y
-    float* xbuf = ybuf + 4 * LDY;            // [2][4][LDX]  X(t) (xc) | sin t, cos t | 0..   (step parity)
-    float* bufA = xbuf + 8 * LDX;            // [4][LDA]
+    constexpr int XS = lean_xslots<CF>();
+    float* xbuf = ybuf + 4 * LDY;            // [XS][4][LDX]  X(t) (xc) | sin t, cos t | 0..   (general: step parity)
+    // CfgSpec: a ring, X(t_m) in slot m & 3.  Slots (n + 1 .. n + 4) & 3 are written at the top of step n when n % 4 == 0, before the
+    // step's first barrier.  X(t_m), m >= 1, is read once, between the update and the closing barrier of step m - 1
+    // (lean_read_b_carried); X(t_0) is written in the prologue, read after the prologue's second barrier, and that read is closed
+    // by a third prologue barrier of its own.  So X(t_{n+1}) is complete a barrier before its read in step n (as in the general
+    // loop), X(t_{n+2..n+4}) earlier still.  The slots a batch overwrites last held X(t_{n-3+k}), k = 0..3: for n >= 4 they were read
+    // in steps n - 4 .. n - 1, all closed by their closing barriers; for the first batch (n = 0) only slot 0 held anything, X(t_0),
+    // and the third prologue barrier stands between every wave's read of it and any wave's store of X(t_4).
+    float* bufA = xbuf + 4 * XS * LDX;       // [4][LDA]
     float* bufB = bufA + 4 * LDA;            // [4][LDA]
     float* rowtab = bufB + 4 * LDA;          // [ROWCH + 3][RS]  step i: (h_i, sqrt h_{i+1}, -, - | sin t, cos t, frac of step i+1, idx of step i+2)
     float* zstash_all = rowtab + (CF::ROWCH + 3) * RS;
@@ -424,7 +468,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         for (int i = 0; i < 4; ++i) bfr[l][i] = (s == 0) ? a.ws[a.bias_off + l * H + wave * 16 + 4 * q + i] : 0.0f;
 
     // ---- LDS init; the step table is re-cut into the two quads per step this kernel reads -------------------------
-    for (int i = tid; i < 4 * (LDY + 2 * LDX + 2 * LDA); i += NT) lds[i] = 0.0f;
+    for (int i = tid; i < 4 * (LDY + XS * LDX + 2 * LDA); i += NT) lds[i] = 0.0f;
     auto fill_rows = [&](int base) {
         for (int i = tid; i < (CF::ROWCH + 3) * RS; i += NT) {
             const int j = i % RS;
@@ -467,9 +511,12 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     uint32_t cvo[CF::XI];                                   // byte offset of (tile row, channel) from the tile's first row
     int xdst[CF::XI], xkind[CF::XI];                        // LDS float offset inside an xbuf half (-1: none); 0 spline, 1 sin, 2 cos
     const size_t cstride = (size_t)(a.L - 1) * 4 * C;       // floats per batch row
+    // CfgSpec: lane 16 k + e evaluates entry e of this wave for step n + 1 + k of a batch (k = q), into ring slot (1 + k) & 3
+    // (xslot: that slot's float offset; store_xt takes the slot's base, xdst[] is the offset inside a slot)
+    [[maybe_unused]] const int xslot = SP ? ((1 + q) & 3) * (4 * LDX) : 0;
 #pragma unroll
     for (int i = 0; i < CF::XI; ++i) {
-        const int li_ = lane + 64 * i, it = wave * xquota + li_;
+        const int li_ = SP ? (lane & 15) : lane + 64 * i, it = wave * xquota + li_;
         const bool ok = KUXT > 0 && li_ < xquota && it < 4 * xw;
         const int rr = ok ? it / xw : 0, col = ok ? it - rr * xw : 0;
         // (CfgSpec: no exec-masked store per step - the lanes without an entry write into the rows' padding past the k-blocks,
@@ -526,7 +573,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
     auto next_dw = [&](int i, float sqh) -> float {
         if (__builtin_expect(phx, 1)) {
             const int k = (int)((uint32_t)i % (uint32_t)(4 * CF::ZB));      // (i >= 0: a mask, not a signed remainder)
-            if (__builtin_expect(k == 0, 0)) {
+            if (__builtin_expect(k == 0 && !(LEAN_KO(SP) && i > 0), 0)) {
                 float zq[4 * CF::ZB];
 #pragma unroll
                 for (int bb = 0; bb < CF::ZB; ++bb)
@@ -573,9 +620,13 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         load_coeffs(__float_as_int(g0[5]));
         float dummy = 0.0f;
         vm_wait(dummy, gt_cur);
-        store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);
+        store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);     // X(t_0): slot 0 (CfgSpec: the four lanes of an entry store the same value)
         dw_cur = next_dw(0, g0[6]);
         if (tab) lean_gload(gt_cur, fo4, gt);
+        if constexpr (SP) {      // the pieces of X(t_{1+k}) for the batch of step 0
+            const int m = 1 + q < N - 1 ? 1 + q : N - 1;
+            load_coeffs(__float_as_int(a.step_tab[(size_t)m * SNSDE_STEP_STRIDE + 5]));
+        } else
         load_coeffs(__float_as_int(a.step_tab[(size_t)(N > 1 ? 1 : 0) * SNSDE_STEP_STRIDE + 5]));
         vm_wait(dw_cur, gt_cur);
         qa = *reinterpret_cast<const f32x4*>(rowtab);
@@ -590,7 +641,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
 
     // B-operand read addresses (LDS byte offsets; only lanes 0-15 read: q = 0 there)
     const uint32_t yrow = lean_op_addr<BF>(ybuf, r * LDY, 4 * s);
-    const uint32_t xrow = lean_op_addr<BF>(xbuf, r * LDX, 4 * s);      // + 4 * LDX floats on odd steps
+    const uint32_t xrow = lean_op_addr<BF>(xbuf, r * LDX, 4 * s);      // + 4 * LDX floats on odd steps (CfgSpec: per ring slot)
     const uint32_t arow = lean_op_addr<BF>(bufA, r * LDA, 4 * s);
     const uint32_t brow = lean_op_addr<BF>(bufB, r * LDA, 4 * s);
     OpT* const aown = reinterpret_cast<OpT*>(bufA) + r * LDA + fo;
@@ -603,6 +654,13 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
 
     LeanBt<BF, (KUXT > 0 ? KUXT : 1)> bx{};    // [X(t_n) | tau_n] operands of the step about to start
     if constexpr (KUXT > 0) lean_read_b_carried(xrow, bx);
+    if constexpr (SP) {
+        // the first batch (step 0) stores X(t_4) into slot 0: every wave's read of X(t_0) out of it has landed first
+        if constexpr (KUXT == 1) asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bx.v[0]));
+        else asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(bx.v[0]), "+v"(bx.v[1]));
+        static_assert(KUXT <= 2, "tie every fragment of bx to the wait");
+        __syncthreads();
+    }
     LT_DECL
     // Outer loop over the requested outputs, inner loop over the solver steps up to each of them (out_step[k] = the step
     // after which output k + 1 is due): the step loop itself carries no output bookkeeping.
@@ -642,8 +700,23 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         if constexpr (KUXT > 0) lean_gemm<15, KUXT>(wxt, bx, c, d);
         // ---- in the shadow of those reads: diffusion, y + g dW; X(t_{n+1}) and the fetch of X(t_{n+2})'s pieces -----------
         const float ypart = gpart(yv, gt_cur, dw_cur, h);
-        store_xt(xbuf + ((n + 1) & 1) * (4 * LDX), qb[2], qb[0], qb[1]);       // (past the last step: a clamped row, never read)
-        load_coeffs(__float_as_int(qb[3]));
+        if constexpr (SP) {
+            // every fourth step: X(t_{n+1+k}) out of the pieces fetched four steps ago, with (sin, cos, frac) of step n + 1 + k from table
+            // row n + k; then the pieces of X(t_{n+5+k}), whose interval is in row n + 3 + k (rows past the last step repeat it:
+            // clamped, never read; n - rbase <= ROWCH - 4 at a batch, so the rows are inside the chunk's ROWCH + 3)
+            if constexpr (!LEAN_KO(SP)) {
+                if ((n & (CF::XB - 1)) == 0) {
+                    const float* rp = rowtab + (n - rbase + q) * RS;
+                    const f32x4 qk = *reinterpret_cast<const f32x4*>(rp + 4);
+                    const float ik = rp[3 * RS + 7];
+                    store_xt(xbuf + xslot, qk[2], qk[0], qk[1]);
+                    load_coeffs(__float_as_int(ik));
+                }
+            }
+        } else {
+            store_xt(xbuf + ((n + 1) & 1) * (4 * LDX), qb[2], qb[0], qb[1]);   // (past the last step: a clamped row, never read)
+            load_coeffs(__float_as_int(qb[3]));
+        }
         __builtin_amdgcn_sched_barrier(0);
         LT(1)
         if constexpr (YIN) lean_gemm<0, KUH>(wy, by, c, d);
@@ -756,7 +829,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4_kernel(MfmaArgs a) {
         // land before the closing barrier releases (its s_waitcnt lgkmcnt(0))
         asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16"
                      : "+v"(qa), "+v"(qb) : "v"(lean_lds_addr(rowtab + (n + 1 - rbase) * RS)));
-        if constexpr (KUXT > 0) lean_read_b_carried(xrow + ((n + 1) & 1) * (4 * LDX * 4), bx);
+        if constexpr (KUXT > 0) lean_read_b_carried(xrow + ((n + 1) & (XS - 1)) * (4 * LDX * 4), bx);
         LT(9)
         __syncthreads();
         LT_COLLECT
