@@ -170,7 +170,8 @@ typedef struct snsde_solve {
     int32_t  flags;        /* SNSDE_FLAG_*                                                       */
     int32_t  reserved;     /* must be 0                                                          */
     int64_t  row_offset;   /* global index of local row 0 (batch shards keep the global Philox   */
-                           /* stream: counter = (row_offset + row, step, col/4, 0))              */
+                           /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
+                           /* sees the local batch unless `global_rows` (below) is set           */
     uint64_t seed;         /* Philox key                                                         */
     const float*   params;    /* device, snsde_param_numel floats                                */
     const float*   coeffs;    /* device (B, L-1, 4C) = cat[a, b, two_c, three_d]                  */
@@ -224,6 +225,16 @@ typedef struct snsde_solve {
     float          kl_prior_a;
     float          kl_prior_b;
     int32_t        reserved2;  /* must be 0                                                          */
+    /* Rows of the WHOLE problem this call is a batch shard of (rows row_offset .. row_offset + batch - 1 of it), or 0: this call
+     * is the whole problem.  When set (>= row_offset + batch, SNSDE_ERR_DIMS otherwise) every choice between kernels whose
+     * results are not bit-identical to each other - 16-row / 4-row tiles, the wave-pair kernels, the wave-pair adjoint - is made as
+     * for `global_rows` rows on one device, by every entry point that plans (snsde_forward_path, snsde_lean_variant,
+     * snsde_backward_supported, snsde_save_layout, the workspace queries, both launches): the shards of a problem then run the
+     * kernel the unsharded problem runs and reproduce its states, trajectory, saved planes, per-row adjoints and dL/dy0 bit for
+     * bit (parameter gradients: per-shard sums, equal within rounding).  Grids, ragged tails, workspace sizes and the 32-bit
+     * save-offset guards stay per shard.  A shard the global plan's kernel cannot run (fewer than 4 rows under a wave-pair plan)
+     * is SNSDE_ERR_UNSUPPORTED: never another kernel. */
+    int64_t        global_rows;
 } snsde_solve;
 
 SNSDE_API size_t snsde_workspace_bytes(const snsde_solve* s);

@@ -139,6 +139,11 @@ int snsde_build_net(const snsde_model& m, int32_t n_steps, SnsdeNet* net) {
     return SNSDE_OK;
 }
 
+// global_rows (snsde.h): 0, or the rows of the whole problem - this shard's rows row_offset .. row_offset + batch - 1 lie inside it
+static bool global_rows_ok(const snsde_solve* s) {
+    return s->global_rows == 0 || (s->global_rows > 0 && s->row_offset >= 0 && s->global_rows - s->row_offset >= (int64_t)s->batch);
+}
+
 int snsde_flavor_hint(const snsde_solve* s) {
     if (snsde_solve_variant(s)) return 1;      // tutorial-style fields: 4-row tiles only
     return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
@@ -156,9 +161,12 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
     if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS)) r.path = generic; return r; }
+    if (!global_rows_ok(s)) return r;
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
-    // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor
-    r.path = r.plan.ok ? snsde_mfma_path(r.plan) : (k == SNSDE_KERNEL_AUTO && !variant ? generic : SNSDE_PATH_NONE);
+    // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor - but not where the
+    // plan made for the whole problem (global_rows) names a kernel this shard cannot run: that is no kernel at all
+    r.path = r.plan.ok ? snsde_mfma_path(r.plan)
+                       : (k == SNSDE_KERNEL_AUTO && !variant && !r.plan.shard_refused ? generic : SNSDE_PATH_NONE);
     // bf16 operands: the bf16 lean kernel or nothing (no f32 kernel stands in for it)
     if ((s->flags & SNSDE_FLAG_BF16_OPERANDS) && r.path != SNSDE_PATH_LEAN_BF16) r = ForwardRoute{};
     return r;
@@ -171,9 +179,11 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
 static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const SnsdeNet& net) {
     snsde_mfma::BackwardRoute r{};
     const int hint = snsde_flavor_hint(s), k = s->kernel;
+    if (!global_rows_ok(s)) return r;
     r.fp = make_plan(s, net, hint);
     r.rp = make_rev_plan(s, net, r.fp, hint);
     if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return r;     // an inference-only forward: no adjoint of any kind
+    if (r.fp.shard_refused) return r;                      // (no forward kernel either: route_forward)
     if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return r;     // no forward kernel either (validate_solve)
     const bool variant = snsde_solve_variant(s);      // tutorial-style fields: the 4-row-tile MFMA adjoint or nothing
     if (r.rp.ok && k != SNSDE_KERNEL_GENERIC && !(variant && k == SNSDE_KERNEL_MFMA_M16)) r.mode = 1;
@@ -362,6 +372,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
     int rc = validate_model(&s->model);
     if (rc) return rc;
     if (s->batch <= 0 || s->knots < 2) return SNSDE_ERR_DIMS;
+    if (!global_rows_ok(s)) return SNSDE_ERR_DIMS;
     if (!s->params || !s->coeffs || !s->workspace) return SNSDE_ERR_NULL;
     if (!eval) {
         if (s->n_steps <= 0 || s->n_out < 2) return SNSDE_ERR_DIMS;
@@ -463,6 +474,7 @@ int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_p
     if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;
     int slots = snsde_act_slots(&s->model);
     if (slots < 0) return slots;
+    if (!global_rows_ok(s)) return SNSDE_ERR_DIMS;
     const int nn = snsde_noise_net_layers(s->model.noise_option);
     int planes = 1;
     if (s->method == SNSDE_SRK && nn > 0) {

@@ -59,6 +59,21 @@ inline bool snsde_table_noise(int no) { return (no >= 1 && no <= 6) || no == 11 
 // y noise: raw = phi(y): sqrt y, y^3, sigmoid y, relu y
 inline bool snsde_y_noise(int no) { return no >= 7 && no <= 10; }
 
+// Rows to plan with: the rows of the whole problem where the caller names them (snsde_solve::global_rows: this call is one batch
+// shard of it), else the local batch.  Every choice between kernels whose results are NOT bit-identical to each other reads it, so
+// that a shard runs the kernel the unsharded problem runs on one device:
+//   planned from snsde_plan_rows (numerics)  - 16-row / 4-row tiles: the r4 / r16 test of make_plan, its 256-slot form (diffusion
+//                                              nets at H = 128) and its occupancy form;
+//                                            - the wave-pair forward (w4_takes: up to 6144 rows under Euler);
+//                                            - the fused wave-pair adjoint (make_rev_plan: up to 6144 rows).
+//   planned from the local batch (layout)    - grids, nwg, ragged tails, tile counts of the reduction kernels, workspace sizes,
+//                                              the 32-bit save-offset guards, "a tile is four rows" (batch < 4).
+//   local, and harmless                      - kernels pinned bit-identical to the one they stand in for: the lean kernel against
+//                                              its compile-time specialisation, H = 256 two-tile against streamed, H = 128
+//                                              two-tile against lean (none of them looks at the batch).
+// bf16 operands plan 4-row tiles at every batch size and a `kernel` other than auto names the tiles itself: neither reads it.
+inline int64_t snsde_plan_rows(const snsde_solve* s) { return s->global_rows > 0 ? s->global_rows : (int64_t)s->batch; }
+
 // launchers (snsde_generic.hip)
 int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, size_t* floats);
 int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int eval_mode,
@@ -82,6 +97,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfm
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net);
+bool snsde_w4_config_supported(const snsde_solve* s, const SnsdeNet& net);    // ... whatever the local batch (what a plan for the whole problem asks)
 int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
 bool snsde_w4_rev_supported(const snsde_solve* s, const SnsdeNet& net);       // adjoint of the Euler solve on the same wave pairs
 // gpart != null: the weight gradients are accumulated inside the adjoint (per-tile blocks in gpart, snsde_w4_grad_floats floats) and

@@ -253,12 +253,18 @@ __global__ void snsde_srk_expand_kernel(const float* __restrict__ step_tab, cons
 
 }  // namespace
 
-// Wave-owns-rows forward (snsde_w4.hip): forced by hint 2; under `auto` up to 6144 rows
-static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
+// Wave-owns-rows forward (snsde_w4.hip): forced by hint 2; under `auto` up to 6144 rows of the problem (snsde_plan_rows)
+// w4_planned: the plan for the whole problem is the wave pairs; w4_takes: ... and they can run this launch (a four-row tile)
+static bool w4_planned(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     // measured at the K4 shape (tools/time_w4.py, profiles/r05_time_w4.txt): 2048 rows 109 us against 156 (4-row tiles) / 216 (16-row
     // tiles), 6144 rows 275 against 316 (16-row tiles); from 8192 rows the 16-row tiles win (a third wave per SIMD does not fit)
     // SRK through a net has no 16-row flavour: the wave pair at every batch size (2048 rows 352 us against 456, 4096 rows 540 / 900)
-    return (flavor_hint == 2 || (flavor_hint == -1 && (s->batch <= 6144 || s->method == SNSDE_SRK))) && snsde_w4_supported(s, net);
+    const int64_t prows = snsde_plan_rows(s);
+    return (flavor_hint == 2 || (flavor_hint == -1 && prows >= 4 && (prows <= 6144 || s->method == SNSDE_SRK))) &&
+           snsde_w4_config_supported(s, net);
+}
+static bool w4_takes(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
+    return w4_planned(s, net, flavor_hint) && snsde_w4_supported(s, net);
 }
 
 // The forward's plan: does the MFMA fast path take this descriptor (ok), its workspace layout, and the kernel that runs it
@@ -281,6 +287,12 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     // (not only in the launchers) so that `auto` falls through to the generic kernels and snsde_backward_supported reports what the
     // launchers accept
     if ((uint64_t)16 * (uint64_t)(s->batch > 0 ? s->batch : 0) * (uint64_t)H >= (1ull << 32)) return p;
+    // a shard of a problem planned onto the wave pairs that cannot run them (fewer than four rows): no plan and no stand-in kernel
+    if (s->global_rows > 0 && hint_in == -1 && !bf16 && w4_planned(s, net, hint_in) && !snsde_w4_supported(s, net)) {
+        p.shard_refused = true;
+        return p;
+    }
+    const int64_t prows = snsde_plan_rows(s);      // the tile flavour is numerics: planned for the whole problem (snsde_internal.h)
     const bool srk = s->method == SNSDE_SRK;
     const bool variant = snsde_solve_variant(s);
     const int nn = snsde_noise_net_layers(no);
@@ -298,7 +310,7 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     bool m4n = noise_net && (s->method != SNSDE_EULER || snsde_model_variant(m));      // (field variants with a net: these kernels, every method)
     if (noise_net && !m4n && io != 0 && flavor_hint != 0 && m.num_hidden_layers <= 4 &&
         m4n_instantiated(H, kuxn, m.num_hidden_layers - 1, nn, SNSDE_EULER)) {
-        const long r4 = ((s->batch + 3) / 4 + 255) / 256, r16 = ((s->batch + 15) / 16 + 255) / 256;
+        const int64_t r4 = ((prows + 3) / 4 + 255) / 256, r16 = ((prows + 15) / 16 + 255) / 256;
         const bool m4_tiles = flavor_hint == 1 || 10 * r4 <= 22 * r16;
         if (kuxn == 5 || (H == 128 && m4_tiles)) m4n = true;
     }
@@ -322,10 +334,10 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
     {
         const int slots = 256 * (p.NW <= 4 ? 8 / (p.NW < 2 ? 2 : p.NW) : 1);
         const int slots16 = srk ? 256 : slots;      // (the SRK variant's 16-row workgroups do not co-reside: H = 64 at 6144 rows ran two rounds)
-        const long r4 = ((s->batch + 3) / 4 + slots - 1) / slots, r16 = ((s->batch + 15) / 16 + slots16 - 1) / slots16;
+        const int64_t r4 = ((prows + 3) / 4 + slots - 1) / slots, r16 = ((prows + 15) / 16 + slots16 - 1) / slots16;
         // (round 4, profiles/r04_sweep_flavour.txt: the ratio of an M16 round to an M4 round is 3.5 at H = 256 - streamed weights - and
         //  1.8 at H = 64, where two co-resident 4-row workgroups slow each other down; 2.2 elsewhere)
-        const long ratio10 = H == 256 ? 35 : ((H == 64 && !srk) ? 18 : 22);      // (measured under Euler; the SRK variant keeps 2.2)
+        const int64_t ratio10 = H == 256 ? 35 : ((H == 64 && !srk) ? 18 : 22);      // (measured under Euler; the SRK variant keeps 2.2)
         p.FL = flavor_hint >= 0 ? flavor_hint : (10 * r4 > ratio10 * r16 ? 0 : 1);
     }
     p.SRK = srk ? 1 : 0;
@@ -556,10 +568,11 @@ RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         p.total_floats = (int)(o + 16);
     }
     // the kernel.  Wave pairs with the weight gradients inside (snsde_w4_kernel.h) where `w4` or `auto` ran the forward on them: Euler
-    // or SRK (SRID2) with a diffusion net, every a_n or dL/dy0 only; forced by hint 2, under `auto` up to 6144 rows (w4_takes)
+    // or SRK (SRID2) with a diffusion net, every a_n or dL/dy0 only; forced by hint 2, under `auto` up to 6144 rows of the problem
+    // (w4_planned; snsde_plan_rows: the shards of a larger problem take the adjoint the whole problem takes)
     // (p.NW >= 4: the per-tile theta partials - four floats per 4-row tile - live in the plan's dth block of nwg x NW floats)
     const bool w4_method = srk ? (p.M4N == 1 && p.NW >= 4) : !p.M4N;
-    if ((flavor_hint == 2 || (flavor_hint == -1 && s->batch <= 6144)) && p.FL == 1 && w4_method && fp.NN > 0 && s->kl_column1 == 0 &&
+    if ((flavor_hint == 2 || (flavor_hint == -1 && snsde_plan_rows(s) <= 6144)) && p.FL == 1 && w4_method && fp.NN > 0 && s->kl_column1 == 0 &&
         snsde_w4_rev_supported(s, net))
         p.kernel = RevKernel::w4_fused;
     else if (p.M4N) p.kernel = p.M4N == 1 ? RevKernel::m4n_srk : RevKernel::m4n_milstein;

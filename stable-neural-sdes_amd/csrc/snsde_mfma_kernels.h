@@ -1810,6 +1810,8 @@ enum class FwdKernel { w4, m4n, lean, lean_two_tile_h128, lean_two_tile_h256, le
 
 struct MfmaPlan {
     bool ok;
+    bool shard_refused;    // !ok because the kernel planned for the whole problem (snsde_solve::global_rows) cannot run this shard:
+                           // the route is then "no kernel" (SNSDE_ERR_UNSUPPORTED), never the generic family in its place
     FwdKernel kernel;
     int H, KUX, NHID, IO, FL, TPW, NW, FOLD, NN, SRK;
     int LEAN, KUXT;    // lean M4 kernel (snsde_m4_kernel.h) and its 16-wide k-blocks of [X(t) | sin t, cos t]

@@ -4,7 +4,8 @@
 
 namespace snsde_w4 {
 
-static bool shape_ok(const snsde_solve* s, const SnsdeNet& net) {
+// the configurations the wave pairs take, whatever the batch
+static bool config_ok(const snsde_solve* s, const SnsdeNet& net) {
     const snsde_model& m = s->model;
     const int io = m.input_option, no = m.noise_option;
     if (m.hidden_channels != 64 || m.hidden_hidden_channels != 64) return false;
@@ -13,9 +14,16 @@ static bool shape_ok(const snsde_solve* s, const SnsdeNet& net) {
     if (s->method != SNSDE_EULER && s->method != SNSDE_SRK) return false;
     if (m.activation != 0 || m.drift_output != 0 || m.diffusion_output != 0 || m.time_feature != 0 || s->noise_table) return false;
     if (m.num_hidden_layers < 1 || m.num_hidden_layers > 2) return false;      // (two hidden layers: 258 weight registers, spills)
-    if (s->kl_column1 != 0 || s->batch < 4) return false;      // (a tile is four rows; ragged tails overlap the previous tile)
-    if ((uint64_t)16 * (uint64_t)s->batch * 64u >= (1ull << 32)) return false;   // 32-bit save offsets (uoff)
+    if (s->kl_column1 != 0) return false;
     if (net.ny0.K != 66 || net.in.K != (io >= 3 ? 66 : 64)) return false;
+    return true;
+}
+
+// ... and the launches they take: the LOCAL batch (snsde_plan_rows, snsde_internal.h: layout, not numerics)
+static bool shape_ok(const snsde_solve* s, const SnsdeNet& net) {
+    if (!config_ok(s, net)) return false;
+    if (s->batch < 4) return false;      // (a tile is four rows; ragged tails overlap the previous tile)
+    if ((uint64_t)16 * (uint64_t)s->batch * 64u >= (1ull << 32)) return false;   // 32-bit save offsets (uoff)
     return true;
 }
 
@@ -80,6 +88,7 @@ static int srk_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* d
 }  // namespace snsde_w4
 
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net) { return snsde_w4::shape_ok(s, net); }
+bool snsde_w4_config_supported(const snsde_solve* s, const SnsdeNet& net) { return snsde_w4::config_ok(s, net); }
 
 int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream) {
     using namespace snsde_w4;

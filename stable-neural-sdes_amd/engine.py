@@ -158,16 +158,47 @@ def precision_flags(precision):
     return _lib.FLAG_BF16_OPERANDS if precision == 'bf16' else 0
 
 
-def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32'):
-    """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query)."""
+def resolve_global_rows(global_rows, batch, row_offset=0):
+    """The `global_rows` of a descriptor (include/snsde.h) from what a caller passed: None / 0 = this call is the whole problem;
+    'world' = world_size x the local batch under an initialised process group (equal shards), else the local batch; an integer =
+    the rows of the whole problem, at least row_offset + batch (ValueError otherwise)."""
+    if global_rows is None or (not isinstance(global_rows, str) and int(global_rows) == 0):
+        return 0
+    if isinstance(global_rows, str):
+        if global_rows != 'world':
+            raise ValueError(f"global_rows must be an integer or 'world', got {global_rows!r}")
+        import torch.distributed as dist
+        world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        return world * int(batch)
+    g = int(global_rows)
+    if g < int(row_offset) + int(batch) or int(row_offset) < 0:
+        raise ValueError(f"global_rows={g} is smaller than row_offset + batch = {int(row_offset)} + {int(batch)}: it is the row count "
+                         "of the WHOLE problem this solve is a batch shard of")
+    return g
+
+
+def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
+                 row_offset=0):
+    """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
+    whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
+    s.row_offset, s.global_rows = int(row_offset), int(global_rows)
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
     s.flags = precision_flags(precision)
     s.noise_table = C.c_void_p(16) if table else None
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
+
+
+def shard_refused(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, global_rows=0, row_offset=0):
+    """True when the kernel planned for the whole problem (global_rows) cannot run this shard - a wave-pair plan and fewer than four
+    rows - although the whole problem has a kernel: such a solve is an error, never another kernel or the tensor-op loop."""
+    if not global_rows or forward_path(model, batch, knots, n_steps, method, kernel, table, global_rows=global_rows,
+                                       row_offset=row_offset) != 'none':
+        return False
+    return forward_path(model, min(int(global_rows), 2 ** 31 - 1), knots, n_steps, method, kernel, table) != 'none'
 
 
 def check_bf16(model, batch, knots, n_steps, method='euler', kernel='auto'):
@@ -394,7 +425,8 @@ def backward_recompute(call, grad_ys, chunk, stream=None):
         # the chunk reads the parent's increments in place (no second copy: the adjoint takes `dW` where there is no `dW_out`), and
         # its adjoint + weight-gradient pass are one C call
         c = SolveCall(model, flat, coeffs, sub, call.traj[n0], dW=call.dW_out[n0:n1], method=method, kernel='auto',
-                      save_traj=True, save_dW=False, save_act=True, exact_order=bool(call.base_flags & _lib.FLAG_EXACT_ORDER))
+                      save_traj=True, save_dW=False, save_act=True, exact_order=bool(call.base_flags & _lib.FLAG_EXACT_ORDER),
+                      global_rows=int(call.desc.global_rows))
         c.launch(stream)
         adj, part = backward_with_gradients(c, g, stream=stream, adj0_only=adj0_suffices(c))
         total = part if total is None else total.add_(part)
@@ -463,7 +495,7 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False):
+                 lean_general=False, global_rows=0):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -513,6 +545,8 @@ class SolveCall:
         # depends on the supplied increments, the noise table, the accumulator column and the per-row output selection)
         s.dW, s.row_out, s.noise_table = _ptr(dW), _ptr(row_out), _ptr(noise_table)
         s.row_offset = int(row_offset)
+        # rows of the whole problem this solve is a batch shard of (0: it is the whole problem): what the library plans its kernels from
+        s.global_rows = resolve_global_rows(global_rows, B, row_offset)
         if kl_column is not None:     # (column, a, b): path-integral accumulator column with the linear prior drift a y + b (snsde.h)
             s.kl_column1, s.kl_prior_a, s.kl_prior_b = int(kl_column[0]) + 1, float(kl_column[1]), float(kl_column[2])
         # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised
@@ -520,7 +554,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision)
+                        precision, int(s.global_rows))
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -608,12 +642,12 @@ _MODE_CACHE = _BoundedCache()
 _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per configuration (SolveCall.cfg_key)
 
 
-def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None):
+def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
-    supplies a noise_table."""
+    supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none)."""
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
-           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column)
+           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows))
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -625,6 +659,7 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
         if kl_column is not None:
             s.kl_column1 = int(kl_column) + 1
+        s.global_rows = int(global_rows)      # (the query needs no row_offset: the caller has checked global_rows against it)
         hit = int(_lib.lib().snsde_backward_supported(C.byref(s)))
         _MODE_CACHE[key] = hit
     return hit

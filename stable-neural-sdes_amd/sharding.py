@@ -15,6 +15,14 @@ def shard_rows(n_rows, world_size, rank):
     return lo, hi
 
 
+def shard_plan_options(n_rows, world_size, rank):
+    """The `sdeint` options of `rank`'s shard of an `n_rows`-row problem: its Philox `row_offset` (shard_rows) and `global_rows`,
+    the row count the library plans its kernels from - with both, the shards reproduce the unsharded solve's states, trajectory
+    and per-row adjoints bit for bit."""
+    lo, _ = shard_rows(n_rows, world_size, rank)
+    return {'row_offset': lo, 'global_rows': int(n_rows)}
+
+
 def max_over_ranks(value, device=None):
     """MAX all-reduce of a python float (no-op without an initialised process group)."""
     import torch.distributed as dist

@@ -147,6 +147,8 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     backend = options.get('backend', 'auto')
     if backend not in ('auto', 'hip', 'torch'):
         raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
+    if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
+        engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset') or 0)      # ValueError if malformed
 
     # names={'drift': 'f', 'diffusion': 'g'} is the default mapping: still the fused path
     default_names = names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
@@ -272,6 +274,10 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         import torch.distributed as dist
         if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
             options = dict(options, row_offset=dist.get_rank() * int(y0.shape[0]))
+    # options={'global_rows': N | 'world'}: the rows of the whole problem this batch is a shard of - the library then plans its
+    # kernels as for N rows on one device, and the shards reproduce the unsharded solve bit for bit (opt-in; default: the local batch)
+    global_rows = engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset', 0))
+    options = dict(options, global_rows=global_rows)
     row_out = options.get('row_out')
     if row_out is not None:     # per-row output selection fused into the solve: the result is (B, H)
         row_out = row_out.to(device=dev, dtype=torch.int32).contiguous()
@@ -283,6 +289,12 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         if options.get('save_traj', False):
             raise ValueError("precision='bf16' is inference only: save_traj is a training output")
         engine.check_bf16(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method, options.get('kernel', 'auto'))
+    if engine.shard_refused(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method, options.get('kernel', 'auto'),
+                            global_rows=global_rows, row_offset=int(options.get('row_offset', 0))):
+        # the kernel planned for the whole problem cannot run this shard (a wave-pair plan, fewer than four rows): an error with or
+        # without `strict` - another kernel or the tensor-op loop would not reproduce the unsharded solve
+        raise engine._lib.SnsdeError(-4, f"global_rows={global_rows}: the kernel planned for the whole problem cannot run this "
+                                         f"{y0c.shape[0]}-row shard")
     if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute'):
         pad = engine.padding_plan(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method)
         if pad is not None:       # a hidden size without MFMA instantiation: solve the zero-padded model (exact)
@@ -294,7 +306,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                 return out
     if needs_grad:
         mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)))
+                                    bool(options.get('exact_order', False)), global_rows=global_rows)
         if mode == 0 and not options.get('strict', False):
             # no fused adjoint for this configuration (Milstein with sqrt(y); shapes beyond the generic adjoint's LDS budget):
             # differentiate through the unfused tensor-op loop on the same device rather than fail the
@@ -312,7 +324,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                             save_traj=bool(options.get('save_traj', False)),
                             exact_order=bool(options.get('exact_order', False)), dU=dU, row_out=row_out,
                             z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
-                            precision=precision)
+                            precision=precision, global_rows=global_rows)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
@@ -372,24 +384,29 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
         import torch.distributed as dist
         multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
         row_offset = dist.get_rank() * int(y0.shape[0]) if multi else 0
+    # (these fields run on 4-row tiles at every batch size: the option is checked and handed down, it moves no choice today)
+    global_rows = engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], row_offset)
     row_out = options.get('row_out')
     if row_out is not None:
         row_out = row_out.to(device=dev, dtype=torch.int32).contiguous()
     if needs_grad:
         # training: the composition and the module's own g stay in the autograd graph; the solve between them is the fused
         # forward + adjoint + weight-gradient pass (flat-block and table gradients flow back through those graphs)
-        if engine.backward_mode(field.model, int(y0.shape[0]), coeffs.shape[1] + 1, grid, method, table=field.tabulated) != 1:
+        if engine.backward_mode(field.model, int(y0.shape[0]), coeffs.shape[1] + 1, grid, method, table=field.tabulated,
+                                global_rows=global_rows) != 1:
             return None
         flat = field.flat(dev, grad=True)
         tab = field.noise_table(tab_times, dev, grad=True) if field.tabulated else None
-        return _ComposedSolve.apply(field.model, coeffs, grid, dW, method, seed, int(row_offset), row_out, y0, flat, tab, dU)
+        return _ComposedSolve.apply(field.model, coeffs, grid, dW, method, seed, int(row_offset), row_out, y0, flat, tab, dU, None,
+                                    global_rows)
     # options={'trust_versions': True}: the cached composed block / table are keyed on the parameters' addresses and version
     # counters alone (no content fingerprint = no device->host read per solve); in-place edits through `.data` are then the
     # caller's to avoid
     field.trust_versions = bool(options.get('trust_versions', False))
     flat, tab = field.inference_inputs(tab_times, dev)
     call = engine.SolveCall(field.model, flat, coeffs, grid, y0.detach().to(torch.float32).contiguous(), dW=dW, dU=dU,
-                            method=method, seed=seed, row_offset=int(row_offset), row_out=row_out, noise_table=tab)
+                            method=method, seed=seed, row_offset=int(row_offset), row_out=row_out, noise_table=tab,
+                            global_rows=global_rows)
     try:
         return call.launch().to(y0.dtype)
     except engine._lib.SnsdeError as exc:
@@ -561,17 +578,18 @@ def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, seed, option
     model, layout, _ = rec
     model_p, layout_p, _, P = pad
     H, dev = model.hidden_channels, y0.device
-    if needs_grad and engine.backward_mode(model_p, int(y0.shape[0]), coeffs.shape[1] + 1, grid, method) != 1:
+    global_rows = int(options.get('global_rows', 0))      # (resolved by _sdeint_hip)
+    if needs_grad and engine.backward_mode(model_p, int(y0.shape[0]), coeffs.shape[1] + 1, grid, method, global_rows=global_rows) != 1:
         return None
     flat = engine.padded_flat(sde, layout, layout_p, H, P, dev, needs_grad)
     widen = lambda t: None if t is None else torch.nn.functional.pad(t, (0, P - H)).contiguous()
     row_offset = int(options.get('row_offset', 0))
     if needs_grad:
         ys = _ComposedSolve.apply(model_p, coeffs, grid, widen(dW), method, seed, row_offset, row_out,
-                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU))
+                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, global_rows)
     else:
         call = engine.SolveCall(model_p, flat, coeffs, grid, widen(y0.detach().to(torch.float32)), dW=widen(dW), method=method,
-                                seed=seed, row_offset=row_offset, dU=widen(dU), row_out=row_out)
+                                seed=seed, row_offset=row_offset, dU=widen(dU), row_out=row_out, global_rows=global_rows)
         ys = call.launch().to(y0.dtype)
     return ys[..., :H]
 
@@ -582,12 +600,12 @@ class _ComposedSolve(torch.autograd.Function):
     gradients this node returns (dL/dy0, dL/d block, dL/d table) on to the module."""
 
     @staticmethod
-    def forward(ctx, model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU=None, kl_column=None):
+    def forward(ctx, model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU=None, kl_column=None, global_rows=0):
         y0c = y0.detach().to(torch.float32).contiguous()
         call = engine.SolveCall(model, flat.detach().contiguous(), coeffs, grid, y0c, dW=dW, method=method, seed=seed,
                                 row_offset=row_offset, row_out=row_out, dU=dU,
                                 noise_table=None if tab is None else tab.detach().contiguous(),
-                                save_traj=True, save_dW=True, save_act=True, kl_column=kl_column)
+                                save_traj=True, save_dW=True, save_act=True, kl_column=kl_column, global_rows=global_rows)
         ys = call.launch()
         ctx.call, ctx.y0_dtype, ctx.has_tab = call, y0.dtype, tab is not None
         return ys.to(y0.dtype) if y0.dtype != ys.dtype else ys.detach()
@@ -598,7 +616,7 @@ class _ComposedSolve(torch.autograd.Function):
         out = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(), adj0_only=engine.adj0_suffices(call),
                                              want_table_grad=ctx.has_tab)
         adj, gflat, gtab = out if ctx.has_tab else (out + (None,))
-        return (None,) * 8 + (adj[0].to(ctx.y0_dtype), gflat, gtab, None, None)
+        return (None,) * 8 + (adj[0].to(ctx.y0_dtype), gflat, gtab, None, None, None)
 
 
 class _FusedSolve(torch.autograd.Function):
@@ -626,9 +644,9 @@ class _FusedSolve(torch.autograd.Function):
             return engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=seed,
                                     row_offset=int(options.get('row_offset', 0)), kernel=kernel, save_traj=True,
                                     save_dW=keep_dw, save_act=save_act, exact_order=bool(options.get('exact_order', False)),
-                                    row_out=options.get('row_out'), dU=dU)
+                                    row_out=options.get('row_out'), dU=dU, global_rows=options.get('global_rows', 0))
         mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)))
+                                    bool(options.get('exact_order', False)), global_rows=int(options.get('global_rows', 0)))
         if mode == 0:
             raise NotImplementedError(
                 "the fused backward covers 'euler', 'srk' and 'milstein' for every noise_option (Milstein: all but 7, "

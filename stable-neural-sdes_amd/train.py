@@ -341,13 +341,17 @@ def make_model(name, input_channels, output_channels, hidden_channels, hidden_hi
 
 def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloader, device, make_model, num_classes,
          max_epochs, lr, kwargs, step_mode, pos_weight=torch.tensor(1), results_dir=None, log=print, regularise='l2',
-         graph_steps=None):
+         graph_steps=None, shard_invariant=False):
     """common_sde.main (common_sde.py:248-298): build, train, evaluate; `num_classes=None` trains a regression model with
     the mean-squared error (the forecasting benchmark).  Results are written only when `name` and `results_dir` are set.
     graph_steps: replay the training step from a CUDA/HIP graph (GraphedStep) - the step of these models is bound by the host
     (whole-model neurallnsde step: 1.43 ms eager, 0.88 ms replayed, 0.61 ms for its solve).  None (default) = wherever it is eligible:
-    one process, CUDA device; False = eager steps; True = required where eligible (still eager under DDP / on the CPU)."""
+    one process, CUDA device; False = eager steps; True = required where eligible (still eager under DDP / on the CPU).
+    shard_invariant (default off): every solve passes options={'global_rows': 'world'} - under a process group the kernels are
+    planned for world_size x the local batch, so each rank's rows evolve as they would in the unsharded batch on one device."""
     device = torch.device(device)
+    if shard_invariant:
+        kwargs = dict(kwargs, options=dict(kwargs.get('options') or {}, global_rows='world'))
     times = times.to(device)
     on_gpu = device.type == 'cuda'
     baseline_memory = None
