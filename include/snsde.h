@@ -235,6 +235,19 @@ typedef struct snsde_solve {
      * save-offset guards stay per shard.  A shard the global plan's kernel cannot run (fewer than 4 rows under a wave-pair plan)
      * is SNSDE_ERR_UNSUPPORTED: never another kernel. */
     int64_t        global_rows;
+    /* Monte-Carlo sample paths: S = samples > 1 Brownian paths per input row in one solve (0 or 1: one path per row, today's
+     * behaviour).  `batch` is then the number of PATHS of this call; path p (local row p) integrates against input row p / S:
+     * coeffs is (batch / S, L-1, 4C), while y0, ys, dW, dU and row_out stay per path, (batch, ...).  The Philox counter stays
+     * (row_offset + p, step, col/4, 0), so the solve equals, bit for bit, the same descriptor with samples = 0 and every row
+     * of coeffs repeated S times - without the S copies in memory.  batch, row_offset (and global_rows where set) must be
+     * multiples of S, S >= 0: SNSDE_ERR_DIMS otherwise.  Inference only: act_save, stage_save, traj, dW_out, dU_out or
+     * z0_weight (the host materialises y0) is SNSDE_ERR_UNSUPPORTED, as are snsde_eval_fg and every backward entry point
+     * (snsde_backward_supported == 0).  Kernels: the lean 4-row-tile kernel (f32, specialised, bf16), the general MFMA kernel
+     * (4- and 16-row tiles; Euler, Milstein, SRK) and the generic family.  A plan that arrives at another kernel is no plan:
+     * snsde_forward_path == SNSDE_PATH_NONE and the launch is SNSDE_ERR_UNSUPPORTED, never another kernel.
+     * snsde_workspace_bytes does not depend on it. */
+    int32_t        samples;
+    int32_t        reserved3;  /* must be 0                                                          */
 } snsde_solve;
 
 SNSDE_API size_t snsde_workspace_bytes(const snsde_solve* s);
@@ -414,6 +427,15 @@ typedef struct snsde_affine_job {
 SNSDE_API int snsde_affine_compose(const snsde_affine_job* jobs, int32_t n_jobs, float* dst, void* hip_stream);
 SNSDE_API int snsde_affine_compose_backward(const snsde_affine_job* jobs, int32_t n_jobs, const float* grad_dst, float* grad_src,
                                             void* hip_stream);
+
+/* ---- statistics over sample paths ------------------------------------------------------------
+ * ys viewed as (groups, samples, width) - the T leading planes of a (T, B S, H) result of a solve with `samples` = S fold
+ * into groups = T B - reduced over the sample axis: mean (groups, width) and, where var != NULL, the unbiased variance
+ * (groups, width; / (S - 1), samples < 2 is then SNSDE_ERR_DIMS).  Enqueue-only, no workspace, capturable.  Deterministic:
+ * one lane per output element walks s = 0 .. S-1 in order, twice (the sum, then the squared deviations from the mean).
+ * All pointers device, fp32, contiguous. */
+SNSDE_API int snsde_sample_stats(const float* ys, int64_t groups, int32_t samples, int32_t width, float* mean, float* var,
+                                 void* hip_stream);
 
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /

@@ -53,7 +53,9 @@ class Solve(_Sized):
                 ('z0_weight', C.c_void_p), ('z0_bias', C.c_void_p),
                 ('workspace', C.c_void_p), ('workspace_bytes', C.c_size_t),
                 ('kl_column1', C.c_int32), ('kl_prior_a', C.c_float), ('kl_prior_b', C.c_float), ('reserved2', C.c_int32),
-                ('global_rows', C.c_int64)]      # rows of the whole problem this call is a shard of (0: this call is the whole problem)
+                ('global_rows', C.c_int64),      # rows of the whole problem this call is a shard of (0: this call is the whole problem)
+                ('samples', C.c_int32),          # Brownian paths per input row (0 / 1: one); batch counts paths, coeffs is (batch / samples, ..)
+                ('reserved3', C.c_int32)]
 
 
 class Backward(_Sized):
@@ -85,7 +87,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_backward_workspace_bytes', 'snsde_solve_backward', 'snsde_spline_workspace_bytes',
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
            'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
-           'snsde_affine_compose', 'snsde_affine_compose_backward')
+           'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats')
 
 
 MAX_AFFINE_JOBS = 12
@@ -147,6 +149,7 @@ def lib():
     L.snsde_backward_workspace_bytes.argtypes = [C.POINTER(Backward)]
     L.snsde_backward_workspace_bytes.restype = C.c_size_t
     L.snsde_solve_backward.argtypes = [C.POINTER(Backward), C.c_void_p]
+    L.snsde_sample_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

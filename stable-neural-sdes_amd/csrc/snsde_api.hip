@@ -144,6 +144,17 @@ static bool global_rows_ok(const snsde_solve* s) {
     return s->global_rows == 0 || (s->global_rows > 0 && s->row_offset >= 0 && s->global_rows - s->row_offset >= (int64_t)s->batch);
 }
 
+// samples (snsde.h): S paths per input row - whole groups of S paths per call, shard and problem
+static bool samples_ok(const snsde_solve* s) {
+    if (s->samples < 0 || s->reserved3 != 0) return false;
+    const int64_t S = snsde_samples(s);
+    return S == 1 || (s->batch % S == 0 && s->row_offset % S == 0 && s->global_rows % S == 0);
+}
+// ... an inference-only solve: no training-mode planes, and the initial state is the caller's (one row per path)
+static bool samples_inference_only(const snsde_solve* s) {
+    return snsde_samples(s) == 1 || !(s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out || s->z0_weight);
+}
+
 int snsde_flavor_hint(const snsde_solve* s) {
     if (snsde_solve_variant(s)) return 1;      // tutorial-style fields: 4-row tiles only
     return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
@@ -159,14 +170,16 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     const bool variant = snsde_solve_variant(s);
     const int generic = s->method == SNSDE_SRK ? SNSDE_PATH_GENERIC_SRK : SNSDE_PATH_GENERIC;
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
+    if (!samples_ok(s) || !samples_inference_only(s)) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
     if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS)) r.path = generic; return r; }
     if (!global_rows_ok(s)) return r;
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
     // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor - but not where the
-    // plan made for the whole problem (global_rows) names a kernel this shard cannot run: that is no kernel at all
+    // plan made for the whole problem (global_rows) names a kernel this shard cannot run, nor where the plan arrives at a kernel
+    // that does not address coeffs by sample group (samples): that is no kernel at all
     r.path = r.plan.ok ? snsde_mfma_path(r.plan)
-                       : (k == SNSDE_KERNEL_AUTO && !variant && !r.plan.shard_refused ? generic : SNSDE_PATH_NONE);
+                       : (k == SNSDE_KERNEL_AUTO && !variant && !r.plan.shard_refused && !r.plan.samples_refused ? generic : SNSDE_PATH_NONE);
     // bf16 operands: the bf16 lean kernel or nothing (no f32 kernel stands in for it)
     if ((s->flags & SNSDE_FLAG_BF16_OPERANDS) && r.path != SNSDE_PATH_LEAN_BF16) r = ForwardRoute{};
     return r;
@@ -180,6 +193,7 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
     snsde_mfma::BackwardRoute r{};
     const int hint = snsde_flavor_hint(s), k = s->kernel;
     if (!global_rows_ok(s)) return r;
+    if (snsde_samples(s) > 1 || !samples_ok(s)) return r;  // sample paths: an inference-only forward, no adjoint and nothing to plan
     r.fp = make_plan(s, net, hint);
     r.rp = make_rev_plan(s, net, r.fp, hint);
     if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return r;     // an inference-only forward: no adjoint of any kind
@@ -372,7 +386,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
     int rc = validate_model(&s->model);
     if (rc) return rc;
     if (s->batch <= 0 || s->knots < 2) return SNSDE_ERR_DIMS;
-    if (!global_rows_ok(s)) return SNSDE_ERR_DIMS;
+    if (!global_rows_ok(s) || !samples_ok(s)) return SNSDE_ERR_DIMS;
     if (!s->params || !s->coeffs || !s->workspace) return SNSDE_ERR_NULL;
     if (!eval) {
         if (s->n_steps <= 0 || s->n_out < 2) return SNSDE_ERR_DIMS;
@@ -387,6 +401,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
         if (s->noise_table && no != 12 && no != 13) return SNSDE_ERR_OPTION;   // a supplied table is the time-only factor
         if ((s->z0_weight != nullptr) != (s->z0_bias != nullptr)) return SNSDE_ERR_NULL;
         if (s->kl_column1 < 0 || s->kl_column1 > s->model.hidden_channels || s->reserved2 != 0) return SNSDE_ERR_DIMS;
+        if (!samples_inference_only(s)) return SNSDE_ERR_UNSUPPORTED;
     }
     return SNSDE_OK;
 }
@@ -398,6 +413,7 @@ size_t snsde_workspace_bytes(const snsde_solve* s) {
     size_t f = 0;
     snsde_solve tmp = *s;
     if (tmp.n_steps < 1) tmp.n_steps = 1;
+    tmp.samples = 0;      // (the workspace holds weights and tables: nothing per sample, and no plan is refused for the query)
     snsde_generic_workspace_floats(&tmp, net, &f);
     const size_t fm = snsde_mfma_workspace_floats(&tmp, net);
     if (fm > f) f = fm;
@@ -447,6 +463,7 @@ int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, f
     if (rc) return rc;
     if (!step_row || !y || !f_out || !g_out) return SNSDE_ERR_NULL;
     if (snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
+    if (snsde_samples(s) > 1) return SNSDE_ERR_UNSUPPORTED;      // (the probe is per input row: y and coeffs row for row)
     snsde_solve tmp = *s;
     tmp.n_steps = 1;
     tmp.n_out = 2;
@@ -516,6 +533,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
     if (b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
+    if (snsde_samples(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;                  // (sample paths: inference only)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;

@@ -74,7 +74,13 @@ struct GenericArgs {
     float* eval_f;
     float* eval_g;
     int32_t ldy, ldw, ldx;  // LDS row strides (floats, multiples of 4)
+    int32_t samples;        // paths per input row, >= 1 (snsde_solve::samples); the forward kernels read it, the adjoints do not
 };
+
+// coeffs row of a path: row / samples (sample paths share their input row's control path)
+__device__ __forceinline__ int snsde_coeff_row(int row, int samples) {
+    return samples > 1 ? (int)((uint32_t)row / (uint32_t)samples) : row;
+}
 
 // out[r][n] = act(bias[n] + sum_k in[r][k] * wt[k][n]) for the GR rows of the tile.
 template <int RPT>
@@ -199,7 +205,7 @@ __global__ void __launch_bounds__(GT) snsde_generic_kernel(GenericArgs a) {
                 const int r = i / C, c = i - r * C, row = row0 + r;
                 float v = 0.0f;
                 if (row < B) {
-                    const float* cp = a.coeffs + ((size_t)row * (d.L - 1) + idx) * (4 * C) + c;
+                    const float* cp = a.coeffs + ((size_t)snsde_coeff_row(row, a.samples) * (d.L - 1) + idx) * (4 * C) + c;
                     v = snsde_spline_eval(cp[0], cp[C], cp[2 * C], cp[3 * C], frac);
                 }
                 xbuf[r * ldx + c] = v;
@@ -387,7 +393,7 @@ __global__ void __launch_bounds__(GW) snsde_generic_srk_kernel(SrkArgs sa) {
                 const int r = i / C, c = i - r * C, row = row0 + r;
                 float v = 0.0f;
                 if (row < B) {
-                    const float* cp = a.coeffs + ((size_t)row * (d.L - 1) + idx) * (4 * C) + c;
+                    const float* cp = a.coeffs + ((size_t)snsde_coeff_row(row, a.samples) * (d.L - 1) + idx) * (4 * C) + c;
                     v = snsde_spline_eval(cp[0], cp[C], cp[2 * C], cp[3 * C], frac);
                 }
                 xbuf[r * ldx + c] = v;
@@ -660,7 +666,7 @@ __global__ void __launch_bounds__(GW) snsde_generic_milnet_kernel(GenericArgs a)
                 const int r = i / C, c = i - r * C, row = row0 + r;
                 float v = 0.0f;
                 if (row < B) {
-                    const float* cp = a.coeffs + ((size_t)row * (d.L - 1) + idx) * (4 * C) + c;
+                    const float* cp = a.coeffs + ((size_t)snsde_coeff_row(row, a.samples) * (d.L - 1) + idx) * (4 * C) + c;
                     v = snsde_spline_eval(cp[0], cp[C], cp[2 * C], cp[3 * C], frac);
                 }
                 xbuf[r * ldx + c] = v;
@@ -1527,6 +1533,7 @@ int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t 
     a.row_out = eval_mode ? nullptr : s->row_out;
     a.row_offset = s->row_offset;
     a.seed = s->seed; a.seed_dev = s->seed_dev;
+    a.samples = snsde_samples(s);
     a.eval_mode = eval_mode;
     a.eval_f = eval_f;
     a.eval_g = eval_g;
@@ -1614,6 +1621,7 @@ int snsde_generic_backward_launch(const snsde_backward* b, const SnsdeNet& net, 
     a.params = s->params; a.ws = bws; a.coeffs = s->coeffs;
     a.step_tab = s->step_tab; a.out_step = s->out_step; a.out_w = s->out_w; a.y0 = s->y0; a.dW = nullptr;
     a.ys = nullptr; a.traj = nullptr; a.dW_out = nullptr; a.row_out = s->row_out; a.row_offset = 0; a.seed = 0; a.seed_dev = nullptr; a.eval_mode = 0;
+    a.samples = 1;
     a.eval_f = nullptr; a.eval_g = nullptr;
     const int H = m.hidden_channels, HH = m.hidden_hidden_channels;
     a.ldy = round4(H + 2);
@@ -1674,6 +1682,7 @@ int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stre
     a.params = s->params; a.ws = ws; a.coeffs = s->coeffs; a.step_tab = s->step_tab; a.out_step = s->out_step;
     a.out_w = s->out_w; a.y0 = s->y0; a.dW = s->dW; a.ys = s->ys; a.traj = s->traj; a.dW_out = s->dW_out;
     a.row_out = s->row_out; a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.eval_mode = 0; a.eval_f = nullptr; a.eval_g = nullptr;
+    a.samples = snsde_samples(s);
     const int H = m.hidden_channels, HH = m.hidden_hidden_channels;
     a.ldy = round4(H + 2);
     const int wmax = 2 * H > HH ? 2 * H : HH;

@@ -74,6 +74,10 @@ inline bool snsde_y_noise(int no) { return no >= 7 && no <= 10; }
 // bf16 operands plan 4-row tiles at every batch size and a `kernel` other than auto names the tiles itself: neither reads it.
 inline int64_t snsde_plan_rows(const snsde_solve* s) { return s->global_rows > 0 ? s->global_rows : (int64_t)s->batch; }
 
+// Brownian paths per input row (snsde_solve::samples, 0 = 1): path p reads coeffs row p / S.  The forward kernels that take it do
+// the division once per lane before the step loop (the MFMA kernels) or per spline item (the generic family).
+inline int32_t snsde_samples(const snsde_solve* s) { return s->samples > 1 ? s->samples : 1; }
+
 // launchers (snsde_generic.hip)
 int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, size_t* floats);
 int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int eval_mode,

@@ -514,6 +514,11 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     // CfgSpec: lane 16 k + e evaluates entry e of this wave for step n + 1 + k of a batch (k = q), into ring slot (1 + k) & 3
     // (xslot: that slot's float offset; store_xt takes the slot's base, xdst[] is the offset inside a slot)
     [[maybe_unused]] const int xslot = SP ? ((1 + q) & 3) * (4 * LDX) : 0;
+    // sample paths (MfmaArgs::samples = S): path p reads coeffs row p / S.  srow0 = row0 / S is the tile's first coeffs row; tile
+    // row gr reads row (row0 + gr) / S = srow0 + (srem0 + gr) / S, and srem0 < S, gr <= 3: at most three subtractions, no division
+    // per lane.  S = 1: srow0 = row0, srem0 = 0, the offset is gr itself.
+    const uint32_t S = (uint32_t)a.samples;
+    const uint32_t srow0 = (uint32_t)row0 / S, srem0 = (uint32_t)row0 - srow0 * S;
 #pragma unroll
     for (int i = 0; i < CF::XI; ++i) {
         const int li_ = SP ? (lane & 15) : lane + 64 * i, it = wave * xquota + li_;
@@ -524,10 +529,13 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         xdst[i] = ok ? rr * LDX + col : (SP ? (lane & 3) * LDX + 16 * KUXT + (lane >> 2) : -1);
         xkind[i] = col < xc ? 0 : (col == xc ? 1 : 2);
         const int gr = row0 + rr < B ? rr : B - 1 - row0, ch = col < xc ? col : 0;
-        cvo[i] = (uint32_t)((gr * cstride + ch) * sizeof(float));
+        uint32_t sr = srem0 + (uint32_t)gr, gs = 0;      // gs = (row0 + gr) / S - row0 / S
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const bool over = sr >= S; sr -= over ? S : 0u; gs += over ? 1u : 0u; }
+        cvo[i] = (uint32_t)((gs * cstride + ch) * sizeof(float));
     }
     const bool has_x = SP || (KUXT > 0 && xc > 0);
-    const float* ctile = a.coeffs + (size_t)row0 * cstride;
+    const float* ctile = a.coeffs + (size_t)srow0 * cstride;
     const uint32_t cstep = (uint32_t)(C * sizeof(float));
     const uint32_t cidx = (uint32_t)(4 * C * sizeof(float));       // bytes per spline interval
     auto load_coeffs = [&](int idx) {      // idx may be a (lane-uniform) VGPR value: the interval offset is per-lane arithmetic,

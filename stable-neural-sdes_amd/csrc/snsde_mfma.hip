@@ -479,6 +479,12 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
         (io == 2 || io == 4 || io == 6) && m.input_channels > 0 && (no == 3 || no == 6 || no == 11 || no == 13 || no == 17) &&
         s->method == SNSDE_EULER && !s->dW && s->kl_column1 == 0)
         p.LEAN_SPEC = io == 6 ? 2 : 1;
+    // sample paths (snsde_solve::samples): the kernels that map path p to coeffs row p / S in their prologue, or no plan
+    if (snsde_samples(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4 &&
+        p.kernel != FwdKernel::general_m16) {
+        p.samples_refused = true;
+        return p;
+    }
     p.ok = true;
     return p;
 }
@@ -683,7 +689,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         a.act = s->model.activation; a.f_out = s->model.drift_output; a.g_out = s->model.diffusion_output;
         a.raw_time = s->model.time_feature; a.gt_ext = s->noise_table;       // (N, 4, H): the table at the four stage times
     }
-    a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev;
+    a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.samples = snsde_samples(s);
     a.acc_col = s->kl_column1 - 1; a.acc_a = s->kl_prior_a; a.acc_b = s->kl_prior_b;
     a.B = s->batch; a.L = s->knots; a.C = s->model.input_channels; a.N = s->n_steps; a.T = s->n_out;
     a.method = s->method; a.no = s->model.noise_option;

@@ -98,6 +98,8 @@ struct MfmaArgs {
     const float* gt_ext;                    // caller-supplied time-only diffusion table (N, H) or null
     int32_t acc_col;                        // path-integral accumulator column (snsde_solve.kl_column1 - 1), -1: none
     float acc_a, acc_b;                     // its linear prior drift a y + b
+    int32_t samples;                        // paths per input row, >= 1 (snsde_solve::samples): path p reads coeffs row p / samples;
+                                            // read by the lean and the general kernel only (make_plan refuses the others)
 };
 
 __host__ __device__ constexpr int ld_for(int K, int pad) { return ((K - pad + 63) / 64) * 64 + pad; }
@@ -483,7 +485,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     }
 
     // spline items of this thread: (xr, xc) = row-in-tile, channel
-    int xr[CF::XI], xc[CF::XI];
+    // (xs: the coeffs row of the item - the path's row, ragged tail clamped, over the paths per input row)
+    int xr[CF::XI], xc[CF::XI], xs[CF::XI];
     bool xok[CF::XI];
     float ca[CF::XI], cb[CF::XI], cc[CF::XI], cd[CF::XI];
 #pragma unroll
@@ -492,12 +495,14 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
         xr[i] = it / C; xc[i] = it - xr[i] * C;
         xok[i] = CF::USEX && it < M * C;
         if (!xok[i]) { xr[i] = 0; xc[i] = 0; }
+        const int rp = row0 + xr[i] < B ? row0 + xr[i] : B - 1;
+        xs[i] = a.samples > 1 ? (int)((uint32_t)rp / (uint32_t)a.samples) : rp;
     }
     auto load_coeffs = [&](int idx) {
 #pragma unroll
         for (int i = 0; i < CF::XI; ++i) {
             if (xok[i]) {
-                const int rr = row0 + xr[i] < B ? row0 + xr[i] : B - 1;
+                const int rr = xs[i];
                 const float* cp = a.coeffs + ((size_t)rr * (a.L - 1) + idx) * (4 * C) + xc[i];
                 ca[i] = cp[0]; cb[i] = cp[C]; cc[i] = cp[2 * C]; cd[i] = cp[3 * C];
             }
@@ -1812,6 +1817,8 @@ struct MfmaPlan {
     bool ok;
     bool shard_refused;    // !ok because the kernel planned for the whole problem (snsde_solve::global_rows) cannot run this shard:
                            // the route is then "no kernel" (SNSDE_ERR_UNSUPPORTED), never the generic family in its place
+    bool samples_refused;  // !ok because the plan arrived at a kernel that does not map paths to input rows (snsde_solve::samples):
+                           // "no kernel" as well
     FwdKernel kernel;
     int H, KUX, NHID, IO, FL, TPW, NW, FOLD, NN, SRK;
     int LEAN, KUXT;    // lean M4 kernel (snsde_m4_kernel.h) and its 16-wide k-blocks of [X(t) | sin t, cos t]

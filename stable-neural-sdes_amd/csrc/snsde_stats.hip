@@ -1,0 +1,83 @@
+// Mean and unbiased variance over the sample axis of a sampled solve's result (include/snsde.h: snsde_sample_stats).
+// ys is (groups, samples, width); one lane owns one output element (V = 1) or four adjacent ones (V = 4: 16-byte loads and stores,
+// width % 4 == 0 and 16-byte aligned pointers) and walks its samples in order, twice: the sum, then the squared deviations from
+// the mean.  Adjacent lanes own adjacent columns, so every load of a wave is one contiguous piece of a row.  No atomics, no
+// cross-lane traffic and no dependence on the grid: the same bits on every launch.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "snsde.h"
+
+namespace {
+
+constexpr int ST = 256;      // threads per block
+
+template <int V> struct Vec;
+template <> struct Vec<1> { using T = float; };
+template <> struct Vec<4> { using T = float4; };
+
+template <int V> __device__ __forceinline__ void load(const float* p, float (&x)[V]) {
+    const typename Vec<V>::T v = *reinterpret_cast<const typename Vec<V>::T*>(p);
+    if constexpr (V == 4) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
+    else x[0] = v;
+}
+template <int V> __device__ __forceinline__ void store(float* p, const float (&x)[V]) {
+    if constexpr (V == 4) *reinterpret_cast<float4*>(p) = make_float4(x[0], x[1], x[2], x[3]);
+    else *p = x[0];
+}
+
+template <int V>
+__global__ void __launch_bounds__(ST) snsde_sample_stats_kernel(const float* __restrict__ ys, int64_t groups, int32_t S, int32_t W,
+                                                                float* __restrict__ mean, float* __restrict__ var) {
+    const int64_t wv = W / V, total = groups * wv;      // items: (group, V adjacent columns)
+    const float fs = (float)S, fs1 = (float)(S > 1 ? S - 1 : 1);      // (divisions, correctly rounded: one rounding each)
+    for (int64_t e = (int64_t)blockIdx.x * ST + threadIdx.x; e < total; e += (int64_t)gridDim.x * ST) {
+        const int64_t g = e / wv, w = (e - g * wv) * V;
+        const float* src = ys + (g * S) * (int64_t)W + w;
+        float sum[V], m[V];
+#pragma unroll
+        for (int i = 0; i < V; ++i) sum[i] = 0.0f;
+        for (int s = 0; s < S; ++s) {
+            float x[V];
+            load<V>(src + (int64_t)s * W, x);
+#pragma unroll
+            for (int i = 0; i < V; ++i) sum[i] += x[i];
+        }
+#pragma unroll
+        for (int i = 0; i < V; ++i) m[i] = sum[i] / fs;
+        store<V>(mean + g * W + w, m);
+        if (var) {
+            float ss[V];
+#pragma unroll
+            for (int i = 0; i < V; ++i) ss[i] = 0.0f;
+            for (int s = 0; s < S; ++s) {
+                float x[V];
+                load<V>(src + (int64_t)s * W, x);
+#pragma unroll
+                for (int i = 0; i < V; ++i) { const float d = x[i] - m[i]; ss[i] = fmaf(d, d, ss[i]); }
+            }
+#pragma unroll
+            for (int i = 0; i < V; ++i) ss[i] /= fs1;
+            store<V>(var + g * W + w, ss);
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int snsde_sample_stats(const float* ys, int64_t groups, int32_t samples, int32_t width, float* mean, float* var,
+                                  void* hip_stream) {
+    if (!ys || !mean) return SNSDE_ERR_NULL;
+    if (groups <= 0 || samples <= 0 || width <= 0) return SNSDE_ERR_DIMS;
+    if (var && samples < 2) return SNSDE_ERR_DIMS;      // (the unbiased variance divides by samples - 1)
+    if (groups > INT64_MAX / samples / width) return SNSDE_ERR_DIMS;
+    const bool vec = width % 4 == 0 &&
+                     ((reinterpret_cast<uintptr_t>(ys) | reinterpret_cast<uintptr_t>(mean) | reinterpret_cast<uintptr_t>(var)) & 15) == 0;
+    const int64_t items = groups * (width / (vec ? 4 : 1));
+    int64_t blocks = (items + ST - 1) / ST;
+    if (blocks > 8192) blocks = 8192;      // (the kernel strides over the rest)
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (vec) hipLaunchKernelGGL(snsde_sample_stats_kernel<4>, dim3((unsigned)blocks), dim3(ST), 0, st, ys, groups, samples, width, mean, var);
+    else hipLaunchKernelGGL(snsde_sample_stats_kernel<1>, dim3((unsigned)blocks), dim3(ST), 0, st, ys, groups, samples, width, mean, var);
+    return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
+}

@@ -177,17 +177,26 @@ def resolve_global_rows(global_rows, batch, row_offset=0):
     return g
 
 
+def check_samples(samples):
+    """The `samples` option (Brownian paths per input row): an int >= 1, ValueError otherwise (bool is not an int here)."""
+    if isinstance(samples, bool) or not isinstance(samples, int) or samples < 1:
+        raise ValueError(f"samples must be an integer >= 1 (Brownian paths per input row), got {samples!r}")
+    return samples
+
+
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
-                 row_offset=0):
+                 row_offset=0, samples=0, lean_general=False, exact_order=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
-    whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none."""
+    whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
+    samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
+    at does not map paths to input rows."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
-    s.row_offset, s.global_rows = int(row_offset), int(global_rows)
+    s.row_offset, s.global_rows, s.samples = int(row_offset), int(global_rows), int(samples)
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
-    s.flags = precision_flags(precision)
+    s.flags = precision_flags(precision) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
     s.noise_table = C.c_void_p(16) if table else None
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
@@ -495,13 +504,19 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0):
+                 lean_general=False, global_rows=0, samples=0):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
         dev = y0.device
+        # samples = S > 1 (inference): y0, dW, dU, row_out and the result are per PATH (B rows), coeffs per input row (B / S rows)
+        S = int(samples) if samples else 1
+        if S < 1 or B % S:
+            raise ValueError(f'samples={samples!r}: the {B} rows of y0 are paths, a whole number of groups of `samples` per input row')
+        if S > 1 and (save_traj or save_dW or save_act or z0_linear is not None):
+            raise ValueError('samples > 1 is inference only: no saved trajectory, increments or activations, and y0 is the caller\'s')
         _check_f32('y0', y0, (B, model.hidden_channels))
-        _check_f32('coeffs', coeffs, (B, L - 1, 4 * C_))
+        _check_f32('coeffs', coeffs, (B // S, L - 1, 4 * C_))
         _check_f32('params', flat_params)
         if dW is not None:
             _check_f32('dW', dW, (grid.N, B, H))
@@ -547,6 +562,7 @@ class SolveCall:
         s.row_offset = int(row_offset)
         # rows of the whole problem this solve is a batch shard of (0: it is the whole problem): what the library plans its kernels from
         s.global_rows = resolve_global_rows(global_rows, B, row_offset)
+        s.samples = S if S > 1 else 0
         if kl_column is not None:     # (column, a, b): path-integral accumulator column with the linear prior drift a y + b (snsde.h)
             s.kl_column1, s.kl_prior_a, s.kl_prior_b = int(kl_column[0]) + 1, float(kl_column[1]), float(kl_column[2])
         # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised
@@ -554,7 +570,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows))
+                        precision, int(s.global_rows), S)
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -852,6 +868,30 @@ def readout_head(x, layers, stream=None):
     stream = torch.cuda.current_stream(x.device) if stream is None else stream
     _lib.check(_lib.lib().snsde_readout_head(C.byref(h), C.c_void_p(stream.cuda_stream)), 'snsde_readout_head')
     return out.reshape(*lead, lin2.out_features)
+
+
+def sample_stats(ys, samples, var=True):
+    """Mean and unbiased variance over the sample axis of a sampled solve's result (sdeint options={'samples': S}): ys is
+    (..., B S, H) with path index b S + s; returns (mean, var), each (..., B, H) (var None when var=False).  CUDA float32 input:
+    one launch of snsde_sample_stats (one lane per output element walks its S samples in order, twice: deterministic); other
+    tensors: the same two passes in torch."""
+    S = check_samples(samples)
+    if ys.dim() < 2 or ys.shape[-2] % S:
+        raise ValueError(f'ys has shape {tuple(ys.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
+    if var and S < 2:
+        raise ValueError('the unbiased variance needs samples >= 2')
+    W = ys.shape[-1]
+    out_shape = tuple(ys.shape[:-2]) + (ys.shape[-2] // S, W)
+    if not (ys.is_cuda and ys.dtype == torch.float32) or ys.numel() == 0:
+        v = ys.reshape(out_shape[:-1] + (S, W))
+        mean = v.sum(dim=-2) / S
+        return mean, ((v - mean.unsqueeze(-2)).square().sum(dim=-2) / (S - 1) if var else None)
+    ys = ys.contiguous()
+    mean = torch.empty(out_shape, device=ys.device, dtype=torch.float32)
+    vout = torch.empty(out_shape, device=ys.device, dtype=torch.float32) if var else None
+    _lib.check(_lib.lib().snsde_sample_stats(_ptr(ys), ys.numel() // (S * W), S, W, _ptr(mean), _ptr(vout),
+                                             C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_sample_stats')
+    return mean, vout
 
 
 def spline_coeffs(times, X, kind='natural'):

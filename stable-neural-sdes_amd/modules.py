@@ -285,6 +285,8 @@ class NeuralSDE(_SDEHead):
             return self._readout(self._solve_sde_path(times, times, z0, kwargs))
         ts, row_slot = self.output_times(times, final_index)
         z_t = self._solve_sde_path(times, ts, z0, kwargs)
+        if row_slot.numel() != z_t.shape[1]:      # options={'samples': S}: S paths per row, path-major
+            row_slot = row_slot.repeat_interleave(z_t.shape[1] // row_slot.numel())
         idx = row_slot.reshape(1, -1, 1).expand(1, z_t.shape[1], z_t.shape[2])
         z = z_t.gather(0, idx).squeeze(0)
         return self._readout(z)

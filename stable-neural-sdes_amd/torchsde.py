@@ -147,6 +147,10 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     backend = options.get('backend', 'auto')
     if backend not in ('auto', 'hip', 'torch'):
         raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
+    # options={'samples': S}: S Brownian paths per input row (inference; _sdeint_samples).  Checked for every backend; 1 = no option
+    samples = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
+    if samples > 1:
+        return _sdeint_samples(sde, y0, ts, bm, method, float(dt), options, names, samples)
     if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
         engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset') or 0)      # ValueError if malformed
 
@@ -184,6 +188,77 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if not default_names and rec is None and backend == 'auto' and y0.is_cuda:
         return _sdeint_latent(sde, y0, ts, bm, method, float(dt), options, names)    # LatentSDE-shaped modules (falls back itself)
     return _sdeint_torch(sde, y0, ts, bm, method, float(dt), options, names)
+
+
+def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S):
+    """options={'samples': S}, S > 1: S Brownian paths per input row in one solve, for a predictive mean / variance / ensemble
+    (engine.sample_stats).  The control path stays (B, L-1, 4C); y0 (B, H) - or already (B S, H) - and a row_out of length B are
+    expanded path-major (path b S + s), the result is (T, B S, H) ((B S, H) with row_out) and path p draws the Philox stream of
+    global row row_offset + p.  Inference only.  Where a kernel maps paths to input rows (engine.forward_path(..., samples=S)) the
+    coefficients are read in place; everywhere else (other kernel families, the composed / latent / tensor-op routes, CPU) they
+    are replicated with repeat_interleave and the ordinary solve runs with the same seed and offsets: the same result either way."""
+    params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
+    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)):
+        raise ValueError(f"samples={S} is inference only: y0 or a parameter requires grad (use torch.no_grad() or "
+                         "requires_grad_(False))")
+    if options.get('save_traj', False) or options.get('recompute'):
+        raise ValueError(f"samples={S} is inference only: save_traj / recompute are training options")
+    backend = options.get('backend', 'auto')
+    if 'z0_linear' in options:
+        y0 = _materialise_z0(sde, y0, ts, options)      # (per input row, before the expansion)
+    coeffs = getattr(sde, 'coeffs', None)
+    control = torch.is_tensor(coeffs) and coeffs.dim() == 3 and hasattr(sde, 'set_X')
+    B = int(coeffs.shape[0]) if control else int(y0.shape[0])
+    if y0.shape[0] == B:
+        y0 = y0.repeat_interleave(S, dim=0)
+    elif y0.shape[0] != B * S:
+        raise ValueError(f"samples={S}: y0 has {y0.shape[0]} rows, expected {B} (one per input row) or {B * S} (one per path)")
+    row_out = options.get('row_out')
+    if row_out is not None:
+        if row_out.numel() == B:
+            row_out = row_out.repeat_interleave(S)
+        elif row_out.numel() != B * S:
+            raise ValueError(f"samples={S}: row_out has {row_out.numel()} entries, expected {B} or {B * S}")
+        options['row_out'] = row_out
+    if options.get('row_offset') is None:
+        import torch.distributed as dist
+        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
+        options['row_offset'] = dist.get_rank() * B * S if multi else 0
+    row_offset = int(options['row_offset'])
+    if row_offset % S:
+        raise ValueError(f"samples={S}: row_offset={row_offset} must be a multiple of samples (whole groups of paths per shard)")
+    if backend != 'torch':
+        options['global_rows'] = engine.resolve_global_rows(options.get('global_rows'), B * S, row_offset)
+        if options['global_rows'] % S:
+            raise ValueError(f"samples={S}: global_rows={options['global_rows']} must be a multiple of samples")
+    default_names = names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
+                                      and not (set(names) - {'drift', 'diffusion'}))
+    rec = engine.recognise(sde) if default_names and control else None
+    if rec is not None and y0.is_cuda and backend != 'torch':
+        model = rec[0]
+        grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sde.times), y0.device)
+        kernel, precision, L = options.get('kernel', 'auto'), options.get('precision', 'fp32'), int(coeffs.shape[1]) + 1
+        engine.precision_flags(precision)
+        # (a hidden size the fused route zero-pads runs padded in the replicated solve: take that route, for the same result)
+        padded = precision == 'fp32' and kernel == 'auto' and engine.padding_plan(model, B * S, L, grid.N, method) is not None
+        if not padded and engine.forward_path(model, B * S, L, grid.N, method, kernel, precision=precision,
+                                              global_rows=int(options['global_rows']), row_offset=row_offset, samples=S,
+                                              exact_order=bool(options.get('exact_order', False))) != 'none':
+            try:
+                return _sdeint_hip(sde, rec, y0, ts, bm, method, dt, dict(options, samples=S))
+            except engine._lib.SnsdeError as exc:
+                # the query named a kernel and the launch still found none: the replicated solve, unless the caller's Brownian
+                # object has been queried already (a stateful one would not repeat its increments) or the caller is strict
+                if exc.code not in (-4, -6) or bm is not None or options.get('strict', False):
+                    raise
+    saved = (coeffs, sde.times) if control else None
+    if control:
+        sde.set_X(coeffs.repeat_interleave(S, dim=0), sde.times)
+    try:
+        return sdeint(sde, y0, ts, bm=bm, method=method, dt=dt, options=options, names=names)
+    finally:
+        if control:
+            sde.set_X(*saved)
 
 
 def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoint_adaptive=False, adjoint_rtol=1e-5,
@@ -246,7 +321,8 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in pidx.params))
     dev = y0.device
     coeffs = sde.coeffs
-    if coeffs.dim() != 3 or coeffs.shape[0] != y0.shape[0]:
+    samples = int(options.get('samples', 1))      # (> 1: from _sdeint_samples only - inference, a kernel that takes it, no padding)
+    if coeffs.dim() != 3 or coeffs.shape[0] * samples != y0.shape[0]:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     y0c = y0.detach().to(torch.float32).contiguous()
@@ -295,7 +371,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         # without `strict` - another kernel or the tensor-op loop would not reproduce the unsharded solve
         raise engine._lib.SnsdeError(-4, f"global_rows={global_rows}: the kernel planned for the whole problem cannot run this "
                                          f"{y0c.shape[0]}-row shard")
-    if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute'):
+    if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute') and samples == 1:
         pad = engine.padding_plan(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method)
         if pad is not None:       # a hidden size without MFMA instantiation: solve the zero-padded model (exact)
             if z0_lin is not None:
@@ -324,10 +400,12 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                             save_traj=bool(options.get('save_traj', False)),
                             exact_order=bool(options.get('exact_order', False)), dU=dU, row_out=row_out,
                             z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
-                            precision=precision, global_rows=global_rows)
+                            precision=precision, global_rows=global_rows, samples=samples)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
+        if samples > 1:              # (the path query accepted this solve: a refusal now is an error, not another route)
+            raise
         if precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
             raise ValueError(f"precision='bf16': the solve was refused ({exc})") from exc
         # a valid request no kernel covers (Milstein with noise_option 7, sqrt(y)): same behaviour as the gradient path, the
