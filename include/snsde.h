@@ -334,6 +334,29 @@ SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_para
 SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
                                             void* hip_stream);
 
+/* Gradient of the fused solve with respect to the control path, dL/d coeffs (mode 1 = MFMA path only), from what the adjoint left
+ * in HBM.  X(t) enters the drift's first layer only, and linearly: with delta_p (B, H) = dL/d(pre-activation of the drift's first
+ * rectified layer) at drift pass p (delta_save slot num_hidden_layers, the plane the weight-gradient pass reads for the folded
+ * first layer; passes = N, SRK: the three drift stages of every step), evaluated on spline interval k_p at offset r_p (step_tab
+ * columns 5 / 4; SRK: the srk_tab slot of the pass's drift stage), and
+ *     M (H, C) = emb.weight[:, H:] . initial_network.weight  (input_option 2 / 4 / 6),  initial_network.weight  (input_option 0)
+ * the call writes
+ *     grad_coeffs[b, k, j C + c] = sum_{p : k_p = k} phi_j(r_p) (delta_p M)[b, c],   phi = (1, r, r^2 / 2, r^3 / 3)
+ * for the blocks (a, b, two_c, three_d) - the derivatives of a + (b + (two_c / 2 + three_d r / 3) r) r.  The diffusion never
+ * reads X.  Intervals no pass falls into receive exactly 0; grad_coeffs (B, L-1, 4C) is overwritten.
+ * `b` is the descriptor snsde_solve_backward (or snsde_backward_with_gradients) ran with; delta_save is filled.  Enqueue-only and
+ * capturable: no allocation, no synchronisation.  Deterministic: no floating-point atomics, every (b, k, j, c) is summed by one
+ * owner in ascending pass order, so two runs are bit-equal; a row's result depends on that row's planes alone, so batch shards
+ * (row_offset / global_rows) reproduce the rows of the whole bit for bit.
+ * input_option 1 / 3 / 5 (the drift does not read X): grad_coeffs is zero-filled, SNSDE_OK.  SNSDE_ERR_UNSUPPORTED: a solve
+ * whose adjoint leaves no delta planes (snsde_save_layout: delta_slots == 0, the H = 64 wave-pair adjoints), mode 2 or 0,
+ * delta_save == NULL, fwd.samples > 1, fwd.kl_column1 != 0, the field variants and a supplied noise_table.  SNSDE_ERR_NULL /
+ * SNSDE_ERR_WORKSPACE as elsewhere; every check happens before the first launch.  The dependence of y0 on coeffs through a fused
+ * z0_weight is not part of this gradient (the host materialises y0 with tensor ops when coeffs require a gradient). */
+SNSDE_API size_t snsde_coeff_gradients_workspace_bytes(const snsde_backward* b);
+SNSDE_API int    snsde_coeff_gradients(const snsde_backward* b, float* grad_coeffs /* (B, L-1, 4C), overwritten */,
+                                       void* workspace, size_t workspace_bytes, void* hip_stream);
+
 /* ---- cubic spline evaluation (A10) -----------------------------------------------------------
  * out[b, c] = a + (b + (0.5*two_c + three_d*frac/3)*frac)*frac   on interval `index`
  * (derivative != 0: b + (two_c + three_d*frac)*frac), operation order as

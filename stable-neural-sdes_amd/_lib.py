@@ -87,7 +87,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_backward_workspace_bytes', 'snsde_solve_backward', 'snsde_spline_workspace_bytes',
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
            'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
-           'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats')
+           'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_coeff_gradients_workspace_bytes',
+           'snsde_coeff_gradients')
 
 
 MAX_AFFINE_JOBS = 12
@@ -139,6 +140,9 @@ def lib():
     L.snsde_param_gradients_workspace_bytes.argtypes = [C.POINTER(Backward)]
     L.snsde_param_gradients_workspace_bytes.restype = C.c_size_t
     L.snsde_param_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snsde_coeff_gradients_workspace_bytes.argtypes = [C.POINTER(Backward)]
+    L.snsde_coeff_gradients_workspace_bytes.restype = C.c_size_t
+    L.snsde_coeff_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snsde_backward_with_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snsde_backward_supported.argtypes = [C.POINTER(Solve)]
     L.snsde_forward_path.argtypes = [C.POINTER(Solve)]

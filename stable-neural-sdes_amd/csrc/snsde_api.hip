@@ -615,6 +615,46 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     return snsde_wgrad_launch(b, net, r, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(pg_workspace), st);
 }
 
+// The checks of snsde_coeff_gradients that need no pointer: the configurations it covers (mode 1 with delta planes, the reference's
+// Diffusion_model fields, one path per row, no accumulator column).  *delta_slots: the planes per pass of delta_save
+static int route_coeff_gradients(const snsde_solve* s, int32_t* delta_slots) {
+    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;
+    if (snsde_samples(s) > 1 || s->kl_column1 != 0 || snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
+    SnsdeNet net;
+    int rc = snsde_build_net(s->model, s->n_steps, &net);
+    if (rc) return rc;
+    if (route_backward(s, net).mode != 1) return SNSDE_ERR_UNSUPPORTED;
+    rc = snsde_save_layout(s, nullptr, nullptr, delta_slots);
+    if (rc) return rc;
+    return *delta_slots > 0 ? SNSDE_OK : SNSDE_ERR_UNSUPPORTED;      // (0: the wave-pair adjoint leaves no delta planes)
+}
+
+size_t snsde_coeff_gradients_workspace_bytes(const snsde_backward* b) {
+    if (!b || b->struct_size != sizeof(snsde_backward) || b->fwd.struct_size != sizeof(snsde_solve)) return 0;
+    if (validate_model(&b->fwd.model) || b->fwd.batch <= 0 || b->fwd.knots < 2 || b->fwd.n_steps <= 0) return 0;
+    int32_t dslots = 0;
+    if (route_coeff_gradients(&b->fwd, &dslots)) return 0;
+    return snsde_cgrad_workspace_floats(b->fwd) * sizeof(float);
+}
+
+int snsde_coeff_gradients(const snsde_backward* b, float* grad_coeffs, void* workspace, size_t workspace_bytes, void* hip_stream) {
+    if (!b || !grad_coeffs || !workspace) return SNSDE_ERR_NULL;
+    if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
+    int rc = validate_solve(&b->fwd, false);
+    if (rc) return rc;
+    int32_t dslots = 0;
+    rc = route_coeff_gradients(&b->fwd, &dslots);
+    if (rc) return rc;
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (!snsde_cgrad_reads_x(b->fwd.model)) return snsde_cgrad_zero_launch(b->fwd, grad_coeffs, st);      // the drift does not read X: exactly zero
+    if (!b->delta_save) return SNSDE_ERR_UNSUPPORTED;
+    if (workspace_bytes < snsde_cgrad_workspace_floats(b->fwd) * sizeof(float)) return SNSDE_ERR_WORKSPACE;
+    SnsdeNet net;
+    rc = snsde_build_net(b->fwd.model, b->fwd.n_steps, &net);
+    if (rc) return rc;
+    return snsde_cgrad_launch(b, net, dslots, grad_coeffs, static_cast<float*>(workspace), st);
+}
+
 int snsde_spline_evaluate(const float* coeffs, int32_t batch, int32_t knots, int32_t channels, int32_t index,
                           float frac, int32_t derivative, float* out, void* hip_stream) {
     if (!coeffs || !out) return SNSDE_ERR_NULL;

@@ -114,6 +114,11 @@ int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, fl
 size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net);
 int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, float* grad_params,
                        int32_t n_params, float* ws, hipStream_t stream);
+// launchers (snsde_cgrad.hip): dL/d coeffs from the adjoint's delta planes (snsde_coeff_gradients)
+bool snsde_cgrad_reads_x(const snsde_model& m);                        // the drift reads X(t): input_option 0 / 2 / 4 / 6
+size_t snsde_cgrad_workspace_floats(const snsde_solve& s);
+int snsde_cgrad_zero_launch(const snsde_solve& s, float* grad_coeffs, hipStream_t stream);
+int snsde_cgrad_launch(const snsde_backward* b, const SnsdeNet& net, int delta_slots, float* grad_coeffs, float* ws, hipStream_t stream);
 int snsde_z0_launch(const snsde_solve* s, hipStream_t stream);   // y0 = z0_weight . X(ts[0]) + z0_bias (stand-alone launch)
 int snsde_spline_launch(const float* coeffs, int32_t B, int32_t L, int32_t C, int32_t index, float frac,
                         int32_t derivative, float* out, hipStream_t stream);

@@ -742,9 +742,10 @@ def param_gradients(call, adj, delta, stream=None, want_table_grad=False):
     return (grad, tab_grad) if want_table_grad else grad
 
 
-def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_table_grad=False):
+def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_table_grad=False, return_delta=False):
     """solve_backward + param_gradients as ONE C call (snsde_backward_with_gradients; mode 1 solves): same results, one
-    host -> library transition.  Returns (adj, flat gradient[, dL/d noise_table])."""
+    host -> library transition.  Returns (adj, flat gradient[, dL/d noise_table]); return_delta appends the delta planes the
+    adjoint left (None where the solve has none) - what coeff_gradients reads."""
     if call.traj is None or call.act_save is None:
         raise ValueError('backward needs a solve run with save_traj and save_act')
     _check_f32('grad_ys', grad_ys, tuple(call.ys.shape))
@@ -783,7 +784,32 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
     call.keep_bwd = (ws, grad_ys)
     call.keep_pg = (pws, adj, delta, tab_grad)
     call.bwd_desc = b
-    return (adj, grad, tab_grad) if want_table_grad else (adj, grad)
+    out = (adj, grad, tab_grad) if want_table_grad else (adj, grad)
+    return out + (delta,) if return_delta else out
+
+
+def coeff_gradients(call, adj, delta, stream=None):
+    """dL/d coeffs (B, L-1, 4C) of a finished mode-1 solve + adjoint (solve_backward with save_delta, or backward_with_gradients
+    with return_delta): snsde_coeff_gradients on the delta planes, enqueue-only.  `adj` is the adjoint call's result (kept
+    alive with the planes).  SnsdeError -4 for a solve without delta planes (call.delta_slots == 0) and every other
+    configuration the entry point does not cover (include/snsde.h)."""
+    b = getattr(call, 'bwd_desc', None)
+    if b is None:
+        raise ValueError('coeff_gradients needs the adjoint of this solve first (solve_backward / backward_with_gradients)')
+    b.delta_save = _ptr(delta)
+    coeffs = call.keep[1]
+    L = _lib.lib()
+    key = ('cgrad',) + call.cfg_key
+    nbytes = _SIZE_CACHE.get(key)
+    if nbytes is None:
+        nbytes = _SIZE_CACHE[key] = int(L.snsde_coeff_gradients_workspace_bytes(C.byref(b)))
+    ws = torch.empty(max(nbytes, 256), device=coeffs.device, dtype=torch.uint8)
+    grad = torch.empty_like(coeffs)
+    stream = torch.cuda.current_stream(coeffs.device) if stream is None else stream
+    _lib.check(L.snsde_coeff_gradients(C.byref(b), _ptr(grad), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)),
+               'snsde_coeff_gradients')
+    call.keep_cg = (ws, adj, delta)
+    return grad
 
 
 def eval_fg(model, flat_params, coeffs, times_host, t, y, kernel='auto'):

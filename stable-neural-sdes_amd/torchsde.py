@@ -100,6 +100,30 @@ _CAPTURE_SEEDS = {}
 _UNFUSED_WARNED = set()
 
 
+def _coeffs_need_grad(sde):
+    """The control path's packed coefficients take part in this differentiation."""
+    coeffs = getattr(sde, 'coeffs', None)
+    return torch.is_grad_enabled() and torch.is_tensor(coeffs) and coeffs.requires_grad
+
+
+class _NoCoeffGradient(Exception):
+    """Raised before the launch by a fused solve that cannot return dL/d coeffs (its adjoint leaves no delta planes)."""
+
+
+def _unfused_coeff_grad(sde, what, options):
+    """The fallback rule for dL/d coeffs: a configuration whose fused backward does not produce it takes the tensor-op loop on
+    the same device (one warning per configuration); options={'strict': True} raises instead.  Never a silent None."""
+    if options.get('strict', False):
+        raise NotImplementedError(f"sdeint: no fused gradient with respect to the control path's coefficients for {what}; "
+                                  "drop options['strict'] (or pass options={'backend': 'torch'}) to differentiate through the "
+                                  "tensor-op loop")
+    key = ('coeffs', what)
+    if key not in _UNFUSED_WARNED:
+        _UNFUSED_WARNED.add(key)
+        warnings.warn(f"sdeint: no fused gradient with respect to the control path's coefficients for {what}; "
+                      "differentiating through the unfused tensor-op loop (slow).")
+
+
 def _dev_key(device):
     device = torch.device(device)
     return device.index if device.index is not None else torch.cuda.current_device()
@@ -165,8 +189,8 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
         if backend == 'torch':
             raise ValueError("precision='bf16' is a HIP kernel option; backend='torch' has no bf16 solve")
         params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
-        if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)):
-            raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad (use torch.no_grad(), "
+        if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde)):
+            raise ValueError("precision='bf16' is inference only: y0, the control path or a parameter requires grad (use torch.no_grad(), "
                              "requires_grad_(False) or precision='fp32')")
         if rec is None:
             raise ValueError("precision='bf16' needs an sde honouring the Diffusion_model contract (the fused HIP solve)")
@@ -198,8 +222,8 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S):
     coefficients are read in place; everywhere else (other kernel families, the composed / latent / tensor-op routes, CPU) they
     are replicated with repeat_interleave and the ordinary solve runs with the same seed and offsets: the same result either way."""
     params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params)):
-        raise ValueError(f"samples={S} is inference only: y0 or a parameter requires grad (use torch.no_grad() or "
+    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde)):
+        raise ValueError(f"samples={S} is inference only: y0, the control path or a parameter requires grad (use torch.no_grad() or "
                          "requires_grad_(False))")
     if options.get('save_traj', False) or options.get('recompute'):
         raise ValueError(f"samples={S} is inference only: save_traj / recompute are training options")
@@ -318,9 +342,10 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         else:
             y0 = _materialise_z0(sde, y0, ts, options)
     pidx = engine.param_index(sde, layout)
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in pidx.params))
+    coeff_grad = _coeffs_need_grad(sde)      # dL/d coeffs wanted: the adjoint's delta planes give it (engine.coeff_gradients)
+    needs_grad = (torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in pidx.params))) or coeff_grad
     dev = y0.device
-    coeffs = sde.coeffs
+    coeffs = coeffs_src = sde.coeffs
     samples = int(options.get('samples', 1))      # (> 1: from _sdeint_samples only - inference, a kernel that takes it, no padding)
     if coeffs.dim() != 3 or coeffs.shape[0] * samples != y0.shape[0]:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
@@ -373,6 +398,9 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                                          f"{y0c.shape[0]}-row shard")
     if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute') and samples == 1:
         pad = engine.padding_plan(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method)
+        if pad is not None and coeff_grad:      # (the padded solve's autograd node has no coefficient gradient: the fallback rule)
+            _unfused_coeff_grad(sde, f"hidden_channels={model.hidden_channels} (a zero-padded solve)", options)
+            return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
         if pad is not None:       # a hidden size without MFMA instantiation: solve the zero-padded model (exact)
             if z0_lin is not None:
                 y0 = _materialise_z0(sde, y0, ts, {'z0_linear': z0_lin})
@@ -393,7 +421,20 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                 warnings.warn(f"sdeint: no fused backward for input_option={key[0]}, noise_option={key[1]}, method={method!r}; "
                               "differentiating through the unfused tensor-op loop (slow).")
             return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
-        return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, y0, *pidx.params)
+        if not coeff_grad:
+            return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, None, y0, *pidx.params)
+        what = None
+        if mode == 1 and method != 'srk' and int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0) > 0:
+            what = "options['recompute']"
+        else:
+            try:
+                return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, coeffs_src, y0,
+                                         *pidx.params)
+            except _NoCoeffGradient:
+                what = (f"input_option={sde.input_option}, noise_option={sde.noise_option}, method={method!r}, "
+                        f"hidden_channels={model.hidden_channels} at {y0c.shape[0]} rows (an adjoint that sums the weight gradients itself)")
+        _unfused_coeff_grad(sde, what, options)
+        return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
     flat = engine.flatten_params(sde, layout, numel, dev)
     call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=seed,
                             row_offset=int(options.get('row_offset', 0)), kernel=options.get('kernel', 'auto'),
@@ -431,6 +472,9 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
     field = fields.compose(sde)
     coeffs = getattr(sde, 'coeffs', None)
     if field is None or not torch.is_tensor(coeffs) or coeffs.dim() != 3 or coeffs.shape[0] != y0.shape[0]:
+        return None
+    if _coeffs_need_grad(sde):      # (composed fields return no coefficient gradient: the fallback rule)
+        _unfused_coeff_grad(sde, "a composed (tutorial-style) field", options)
         return None
     dev = y0.device
     capturing = torch.cuda.is_current_stream_capturing()
@@ -706,7 +750,9 @@ class _FusedSolve(torch.autograd.Function):
     unrolled loop (benchmark_classification/common_sde.py:158-160)."""
 
     @staticmethod
-    def forward(ctx, sde, rec, coeffs, grid, times_host, increments, method, seed, options, y0, *params):
+    def forward(ctx, sde, rec, coeffs, grid, times_host, increments, method, seed, options, coeffs_src, y0, *params):
+        # coeffs_src: the caller's coefficient tensor when dL/d coeffs is wanted (a differentiable input; the kernels read
+        # `coeffs`, its detached float32 copy), else None - such a solve launches and allocates nothing beyond the parameter pass
         model, layout, numel = rec
         dW, dU = increments
         flat = engine.flatten_params(sde, layout, numel, y0.device)
@@ -740,6 +786,9 @@ class _FusedSolve(torch.autograd.Function):
                 ctx.recompute = 0            # (and the parent's states / increments kept beside the chunk's: MORE memory, K5 N = 49)
         # mode 2: the generic adjoint prepares its own weights, so the forward takes whatever kernel is fastest
         call = make(options.get('kernel', 'auto'), mode == 1 and not ctx.recompute)
+        ctx.coeffs_dtype = None if coeffs_src is None else coeffs_src.dtype
+        if coeffs_src is not None and mode == 1 and getattr(call, 'delta_slots', 1) == 0:
+            raise _NoCoeffGradient()      # (before the launch: _sdeint_hip applies the fallback rule)
         ctx.mode, ctx.method = mode, method
         ctx.param_pass = options.get('param_pass', 'hip')
         ctx.layout = (layout, numel)
@@ -753,31 +802,44 @@ class _FusedSolve(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_ys):
         call, sde, grid = ctx.call, ctx.sde, ctx.grid
+        want_c = ctx.coeffs_dtype is not None and ctx.needs_input_grad[9]      # dL/d coeffs: only where autograd asks for it
+        gcoeffs = None
         if ctx.mode == 1 and ctx.recompute:
             g0, flat = engine.backward_recompute(call, grad_ys.to(torch.float32).contiguous(), ctx.recompute)
             grads = engine.param_index(sde, ctx.layout[0]).grads_from_flat(flat)
-            return (None,) * 9 + (g0.to(ctx.y0_dtype),) + tuple(grads)
+            return (None,) * 10 + (g0.to(ctx.y0_dtype),) + tuple(grads)
         if ctx.mode == 1:     # MFMA adjoint kernel + native weight-gradient pass on the saved activations / deltas
             if ctx.param_pass == 'torch':     # library-GEMM cross-check of the native pass
                 adj, delta = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous(), save_delta=True, adj0_only=False)
-                grads = _parameter_gradients_gemm(sde, call, grid, adj, delta, method=ctx.method)
+                grads = _parameter_gradients_gemm(sde, call, grid, adj, delta, method=ctx.method, want_coeffs=want_c)
+                if want_c:
+                    grads, gcoeffs = grads
             else:
                 if ctx.param_pass == 'split':     # the two C calls one after the other (what the fused call must reproduce bit for bit)
                     adj, delta = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous(), save_delta=True,
                                                        adj0_only=engine.adj0_suffices(call))
                     flat = engine.param_gradients(call, adj, delta)
+                elif want_c:
+                    adj, flat, delta = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(),
+                                                                      adj0_only=engine.adj0_suffices(call), return_delta=True)
                 else:
                     adj, flat = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(),
                                                                adj0_only=engine.adj0_suffices(call))
                 grads = engine.param_index(sde, ctx.layout[0]).grads_from_flat(flat)
+                if want_c:      # the native pass over the same delta planes (snsde_coeff_gradients)
+                    gcoeffs = engine.coeff_gradients(call, adj, delta)
         else:                 # generic adjoint kernels (any dims; Euler / Milstein / SRK) + batched autograd parameter pass
             adj = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous())
-            grads = _parameter_gradients(sde, call, grid, adj, method=ctx.method)
-        return (None,) * 9 + (adj[0].to(ctx.y0_dtype),) + tuple(grads)
+            grads = _parameter_gradients(sde, call, grid, adj, method=ctx.method, want_coeffs=want_c)
+            if want_c:
+                grads, gcoeffs = grads
+        if gcoeffs is not None and gcoeffs.dtype != ctx.coeffs_dtype:
+            gcoeffs = gcoeffs.to(ctx.coeffs_dtype)
+        return (None,) * 9 + (gcoeffs, adj[0].to(ctx.y0_dtype)) + tuple(grads)
 
 
 @torch.no_grad()
-def _parameter_gradients_gemm(sde, call, grid, adj, delta, method='euler'):
+def _parameter_gradients_gemm(sde, call, grid, adj, delta, method='euler', want_coeffs=False):
     """Parameter gradients from the tensors the two kernels left in HBM, as plain library GEMMs:
         d layer.weight = sum_{step,row} delta_layer^T . layer_input,   d layer.bias = sum delta_layer
     (delta from the adjoint kernel, layer inputs from the forward's act_save / trajectory), plus the elementwise
@@ -868,10 +930,25 @@ def _parameter_gradients_gemm(sde, call, grid, adj, delta, method='euler'):
             grads['noise_t.' + name] = gval
     else:   # no == 0: theta receives no gradient (g == 0)
         grads['theta'] = torch.zeros_like(P['theta'])
-    return [grads[k] if grads[k] is not None else torch.zeros_like(P[k]) for k in P]
+    out = [grads[k] if grads[k] is not None else torch.zeros_like(P[k]) for k in P]
+    if not want_coeffs:
+        return out
+    # dL/d coeffs from the same delta plane (the cross-check of snsde_coeff_gradients): v = dL/dX(t_n) through initial_network,
+    # spread over the four coefficient blocks of step n's interval with the weights (1, r, r^2 / 2, r^3 / 3)
+    coeffs = call.keep[1]
+    gc = torch.zeros_like(coeffs)
+    if io in (0, 2, 4, 6):
+        Cn = coeffs.shape[-1] // 4
+        v = torch.matmul(d_x if io != 0 else d0, P['initial_network.weight'])                 # (N, B, C)
+        idx = torch.from_numpy(grid.step_tab[:, 5].copy().view('int32').astype('int64')).to(dev)
+        r = torch.from_numpy(grid.step_tab[:, 4].copy()).to(dev)
+        phi = torch.stack([torch.ones_like(r), r, 0.5 * r * r, r * r * r / 3], dim=-1)          # (N, 4)
+        contrib = (phi.view(N, 1, 4, 1) * v.unsqueeze(2)).reshape(N, B, 4 * Cn)
+        gc.index_add_(1, idx, contrib.permute(1, 0, 2).contiguous())
+    return out, gc
 
 
-def _parameter_gradients(sde, call, grid, adj, max_rows=1 << 19, method='euler'):
+def _parameter_gradients(sde, call, grid, adj, max_rows=1 << 19, method='euler', want_coeffs=False):
     """sum over steps n and rows of  a_{n+1} . d(f(t_n, y_n) h_n + g(t_n, y_n) dW_n)/d theta  with y_n, a_{n+1}, dW_n
     constants: one batched forward of the vector field over (step, row) pairs + autograd (library GEMMs)."""
     from . import modules
@@ -888,6 +965,10 @@ def _parameter_gradients(sde, call, grid, adj, max_rows=1 << 19, method='euler')
     Cn = coeffs.shape[-1] // 4
     uses_x = io in (0, 2, 4, 6)
     total = [torch.zeros_like(p) for p in params]
+    if want_coeffs:      # the coefficients as one more leaf of the batched evaluation: dL/d coeffs comes out of the same autograd pass
+        coeffs = coeffs.detach().requires_grad_(True)
+        params = params + [coeffs]
+        total.append(torch.zeros_like(coeffs))
     steps_per_chunk = max(1, max_rows // B)
     with torch.enable_grad():
         for lo in range(0, N, steps_per_chunk):
@@ -936,6 +1017,8 @@ def _parameter_gradients(sde, call, grid, adj, max_rows=1 << 19, method='euler')
             for acc, gpart in zip(total, gs):
                 if gpart is not None:
                     acc.add_(gpart)
+    if want_coeffs:
+        return total[:-1], total[-1]
     return total
 
 
@@ -1081,7 +1164,7 @@ def _sdeint_torch(sde, y0, ts, bm, method, dt, options, names):
     else:
         dW_all = torch.stack([bm(t0s[n], t1s[n]).to(device=y0.device, dtype=y0.dtype) for n in range(grid.N)])
         dU_all = None
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(
+    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or _coeffs_need_grad(sde) or any(
         p.requires_grad for p in getattr(sde, 'parameters', lambda: [])()))
     if (y0.is_cuda and not needs_grad and method in ('euler', 'srk') and options.get('graph', True)
             and not torch.cuda.is_current_stream_capturing()):
@@ -1103,7 +1186,7 @@ def _sdeint_torch(sde, y0, ts, bm, method, dt, options, names):
             v = I * I - h
             # g * dg/dy * v for diagonal noise; when differentiating, the cotangent keeps its dependence on y so that
             # autograd through this loop is the exact gradient of the discrete scheme (what the fused adjoint computes)
-            diff = torch.is_grad_enabled() and (y.requires_grad or any(
+            diff = torch.is_grad_enabled() and (y.requires_grad or _coeffs_need_grad(sde) or any(
                 p.requires_grad for p in getattr(sde, 'parameters', lambda: [])()))
             with torch.enable_grad():
                 yy = y if y.requires_grad else y.detach().requires_grad_(True)
