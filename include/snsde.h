@@ -374,6 +374,20 @@ SNSDE_API int snsde_natural_cubic_coeffs(const float* times, const float* X, int
 SNSDE_API int snsde_hermite_coeffs(const float* times, const float* X, int32_t batch, int32_t knots, int32_t channels,
                          float* coeffs, void* hip_stream);
 
+/* Adjoints of the two constructions: grad_X (B, L, C) = J^T grad_coeffs, J the (linear) map X -> coeffs.  The knot compaction,
+ * the tridiagonal matrix, the end imputation and the fill weights depend on `times` and on WHICH entries of X are NaN only, so X is
+ * read for its mask and nothing of the forward is needed.  Every entry of grad_X is written: missing entries and series without an
+ * observation get exactly 0.  One lane per series, a fixed operation order, no atomics: bit-equal from run to run and independent
+ * of the batch a row sits in.  Enqueue-only on hip_stream.  SNSDE_ERR_NULL / SNSDE_ERR_DIMS / SNSDE_ERR_WORKSPACE as the
+ * constructions; every check happens before the launch.  The Hermite adjoint needs no workspace. */
+SNSDE_API size_t snsde_spline_backward_workspace_bytes(int32_t batch, int32_t knots, int32_t channels);
+SNSDE_API int snsde_natural_cubic_coeffs_backward(const float* times, const float* X, const float* grad_coeffs,
+                                        int32_t batch, int32_t knots, int32_t channels,
+                                        float* grad_X, void* workspace, size_t workspace_bytes, void* hip_stream);
+SNSDE_API int snsde_hermite_coeffs_backward(const float* times, const float* X, const float* grad_coeffs,
+                                  int32_t batch, int32_t knots, int32_t channels,
+                                  float* grad_X, void* hip_stream);
+
 /* vector-field probe: one evaluation of f(t,y) and g(t,y) (neuralsde.py:295-307) through the same
  * device code the solver uses.  `step_row` = one step_tab row (device, SNSDE_STEP_STRIDE floats)
  * describing t; y, f_out, g_out are device (B, H).  Uses s->model/batch/knots/params/coeffs/

@@ -88,7 +88,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
            'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_coeff_gradients_workspace_bytes',
-           'snsde_coeff_gradients')
+           'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
+           'snsde_hermite_coeffs_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -135,6 +136,12 @@ def lib():
     L.snsde_natural_cubic_coeffs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                              C.c_size_t, C.c_void_p]
     L.snsde_hermite_coeffs.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.snsde_spline_backward_workspace_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.snsde_spline_backward_workspace_bytes.restype = C.c_size_t
+    L.snsde_natural_cubic_coeffs_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                      C.c_void_p, C.c_size_t, C.c_void_p]
+    L.snsde_hermite_coeffs_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                                C.c_void_p]
     L.snsde_act_slots.argtypes = [C.POINTER(Model)]
     L.snsde_save_layout.argtypes = [C.POINTER(Solve), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
     L.snsde_param_gradients_workspace_bytes.argtypes = [C.POINTER(Backward)]

@@ -920,8 +920,21 @@ def sample_stats(ys, samples, var=True):
     return mean, vout
 
 
+def spline_grad_native():
+    """False under SNSDE_SPLINE_GRAD=torch: the spline constructors then differentiate their tensor-op statement with autograd
+    (the in-repo cross-check of the HIP adjoint, and the route that supports double backward).  Read at every call."""
+    return os.environ.get('SNSDE_SPLINE_GRAD', '') != 'torch'
+
+
 def spline_coeffs(times, X, kind='natural'):
-    """Packed spline coefficients (B, L-1, 4C) on the GPU; times (L,), X (B, L, C) CUDA float32 with NaN = missing."""
+    """Packed spline coefficients (B, L-1, 4C) on the GPU; times (L,), X (B, L, C) CUDA float32 with NaN = missing.
+    An X that requires grad gets the same kernel inside one autograd node whose backward is `spline_coeffs_backward`."""
+    if X.requires_grad and torch.is_grad_enabled():
+        return _SplineCoeffs.apply(times, X, kind)
+    return _spline_coeffs(times, X, kind)
+
+
+def _spline_coeffs(times, X, kind):
     _check_f32('X', X)
     _check_f32('times', times)
     B, L, Cn = X.shape
@@ -936,6 +949,47 @@ def spline_coeffs(times, X, kind='natural'):
     else:
         _lib.check(lib.snsde_hermite_coeffs(_ptr(times), _ptr(X), B, L, Cn, _ptr(out), stream), 'snsde_hermite_coeffs')
     return out
+
+
+def spline_coeffs_backward(times, X, grad_coeffs, kind='natural'):
+    """grad_X (B, L, C) = J^T grad_coeffs for the construction `spline_coeffs(times, X, kind)`: one launch of the adjoint kernel
+    (snsde_natural_cubic_coeffs_backward / snsde_hermite_coeffs_backward).  X is read for its NaN mask only; missing entries get
+    exactly 0.  Enqueue-only: the natural adjoint's workspace comes from the caching allocator on the launch stream, which hands
+    the block to nobody else before the kernel has run, so there is no host synchronisation here."""
+    _check_f32('X', X)
+    _check_f32('times', times)
+    B, L, Cn = X.shape
+    _check_f32('grad_coeffs', grad_coeffs, (B, L - 1, 4 * Cn))
+    if tuple(times.shape) != (L,):
+        raise ValueError(f'times has shape {tuple(times.shape)}, expected {(L,)}')
+    grad_X = torch.empty((B, L, Cn), device=X.device, dtype=torch.float32)
+    stream = C.c_void_p(torch.cuda.current_stream(X.device).cuda_stream)
+    lib = _lib.lib()
+    if kind == 'natural':
+        ws = torch.empty(lib.snsde_spline_backward_workspace_bytes(B, L, Cn), device=X.device, dtype=torch.uint8)
+        _lib.check(lib.snsde_natural_cubic_coeffs_backward(_ptr(times), _ptr(X), _ptr(grad_coeffs), B, L, Cn, _ptr(grad_X),
+                                                           _ptr(ws), ws.numel(), stream), 'snsde_natural_cubic_coeffs_backward')
+    else:
+        _lib.check(lib.snsde_hermite_coeffs_backward(_ptr(times), _ptr(X), _ptr(grad_coeffs), B, L, Cn, _ptr(grad_X), stream),
+                   'snsde_hermite_coeffs_backward')
+    return grad_X
+
+
+class _SplineCoeffs(torch.autograd.Function):
+    """X -> packed coefficients with the HIP adjoint as its backward.  The forward is the kernel the no-grad call runs (same
+    bits); the map is linear in the observed values, so the backward needs `times` and the NaN mask of X and nothing else."""
+
+    @staticmethod
+    def forward(ctx, times, X, kind):
+        ctx.save_for_backward(times, X)
+        ctx.kind = kind
+        return _spline_coeffs(times, X, kind)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_coeffs):
+        times, X = ctx.saved_tensors
+        return None, spline_coeffs_backward(times, X, grad_coeffs.contiguous(), ctx.kind), None
 
 
 def spline_evaluate(coeffs, index, frac, derivative=False):
