@@ -93,7 +93,10 @@ enum {
     SNSDE_FLAG_BF16_OPERANDS = 16,
     /* Run the lean 4-row-tile kernel's general instantiation even where a compile-time specialised one covers the launch
      * (snsde_lean_variant).  Same results bit for bit; exists for A/B measurements and the bit-identity test. */
-    SNSDE_FLAG_LEAN_GENERAL = 32
+    SNSDE_FLAG_LEAN_GENERAL = 32,
+    /* Opt-in: a solve of `samples` = S > 1 paths per input row may be differentiated (snsde_solve.samples, last paragraph).  No
+     * effect when samples <= 1.  Together with SNSDE_FLAG_BF16_OPERANDS (an inference-only forward): SNSDE_ERR_UNSUPPORTED. */
+    SNSDE_FLAG_SAMPLE_GRAD = 64
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -245,7 +248,19 @@ typedef struct snsde_solve {
      * (snsde_backward_supported == 0).  Kernels: the lean 4-row-tile kernel (f32, specialised, bf16), the general MFMA kernel
      * (4- and 16-row tiles; Euler, Milstein, SRK) and the generic family.  A plan that arrives at another kernel is no plan:
      * snsde_forward_path == SNSDE_PATH_NONE and the launch is SNSDE_ERR_UNSUPPORTED, never another kernel.
-     * snsde_workspace_bytes does not depend on it. */
+     * snsde_workspace_bytes does not depend on it.
+     * Training through the sample paths is opt-in, SNSDE_FLAG_SAMPLE_GRAD; without the flag everything above holds.  With it,
+     * act_save, stage_save, traj, dW_out and dU_out are accepted by the lean kernel (general and specialised) and the general MFMA
+     * kernel (4- and 16-row tiles; Euler, Milstein, SRK; elementwise diffusions, H <= 128) - the plans snsde_backward_supported
+     * answers 1 for; with these planes any other plan is SNSDE_PATH_NONE / SNSDE_ERR_UNSUPPORTED.  Every saved plane is per path, (.., batch, ..), exactly as in the solve
+     * with replicated coefficients, so training memory grows S times and only the coefficient side stays at batch / S rows.
+     * z0_weight and snsde_eval_fg stay refused.  snsde_backward_supported plans such a descriptor: 1 where the MFMA adjoint with
+     * delta planes (snsde_save_layout: delta_slots > 0) takes it; the generic adjoints (mode 2), the wave-pair kernels, the
+     * diffusion-net kernels, H = 256, the H = 128 two-tile kernel, the field variants and kl_column1 != 0 are 0, and such a plan
+     * is no plan: never another kernel.  snsde_solve_backward, snsde_param_gradients, snsde_backward_with_gradients,
+     * snsde_coeff_gradients, their workspace queries and snsde_save_layout then take the descriptor; the adjoints, delta planes and
+     * parameter gradients equal those of the replicated solve bit for bit, and grad_coeffs is (batch / S, L-1, 4C): the sum over
+     * the S paths of an input row, formed in place (snsde_coeff_gradients). */
     int32_t        samples;
     int32_t        reserved3;  /* must be 0                                                          */
 } snsde_solve;
@@ -350,9 +365,14 @@ SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad
  * (row_offset / global_rows) reproduce the rows of the whole bit for bit.
  * input_option 1 / 3 / 5 (the drift does not read X): grad_coeffs is zero-filled, SNSDE_OK.  SNSDE_ERR_UNSUPPORTED: a solve
  * whose adjoint leaves no delta planes (snsde_save_layout: delta_slots == 0, the H = 64 wave-pair adjoints), mode 2 or 0,
- * delta_save == NULL, fwd.samples > 1, fwd.kl_column1 != 0, the field variants and a supplied noise_table.  SNSDE_ERR_NULL /
+ * delta_save == NULL, fwd.samples > 1 without SNSDE_FLAG_SAMPLE_GRAD, fwd.kl_column1 != 0, the field variants and a supplied noise_table.  SNSDE_ERR_NULL /
  * SNSDE_ERR_WORKSPACE as elsewhere; every check happens before the first launch.  The dependence of y0 on coeffs through a fused
- * z0_weight is not part of this gradient (the host materialises y0 with tensor ops when coeffs require a gradient). */
+ * z0_weight is not part of this gradient (the host materialises y0 with tensor ops when coeffs require a gradient).
+ * fwd.samples = S > 1 under SNSDE_FLAG_SAMPLE_GRAD: delta_save holds `batch` paths and grad_coeffs is (batch / S, L-1, 4C),
+ *     grad_coeffs[b, k, j C + c] = sum_{p : k_p = k} sum_{s < S} phi_j(r_p) (delta_p M)[b S + s, c]
+ * - one owner per element that walks the passes in ascending order and, inside a pass, the paths s = 0 .. S-1 in order.  A path
+ * whose delta planes are zero adds exact zeros; a row's result depends on the planes of its own S paths alone, so a shard of whole
+ * groups reproduces its rows of the whole bit for bit.  The workspace holds v for `batch` paths. */
 SNSDE_API size_t snsde_coeff_gradients_workspace_bytes(const snsde_backward* b);
 SNSDE_API int    snsde_coeff_gradients(const snsde_backward* b, float* grad_coeffs /* (B, L-1, 4C), overwritten */,
                                        void* workspace, size_t workspace_bytes, void* hip_stream);
@@ -473,6 +493,14 @@ SNSDE_API int snsde_affine_compose_backward(const snsde_affine_job* jobs, int32_
  * All pointers device, fp32, contiguous. */
 SNSDE_API int snsde_sample_stats(const float* ys, int64_t groups, int32_t samples, int32_t width, float* mean, float* var,
                                  void* hip_stream);
+
+/* Adjoint of snsde_sample_stats: with grad_mean and (optionally, NULL = none) grad_var, each (groups, width), the ys the
+ * statistics were formed from and their mean,
+ *     grad_ys[g, s, w] = grad_mean[g, w] / S + grad_var[g, w] * 2 (ys[g, s, w] - mean[g, w]) / (S - 1)
+ * (grad_var != NULL with samples < 2 is SNSDE_ERR_DIMS; `mean` is read only with grad_var).  One lane per (g, w) - or four adjacent
+ * w - walks s in order; every element of grad_ys is written.  Enqueue-only, no workspace, capturable, deterministic. */
+SNSDE_API int snsde_sample_stats_backward(const float* grad_mean, const float* grad_var, const float* ys, const float* mean,
+                                          int64_t groups, int32_t samples, int32_t width, float* grad_ys, void* hip_stream);
 
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /

@@ -19,6 +19,7 @@ FLAG_STREAM_ALL = 4
 FLAG_TWO_TILE = 8
 FLAG_BF16_OPERANDS = 16     # inference only: bf16 MFMA operands on the lean 4-row-tile kernel (include/snsde.h)
 FLAG_LEAN_GENERAL = 32      # the lean kernel's general instantiation where a specialised one covers the launch (A/B, bit-identity test)
+FLAG_SAMPLE_GRAD = 64       # opt-in: a solve of samples = S > 1 paths per input row may be differentiated (include/snsde.h)
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 BWD_ADJ0_ONLY = 1
 PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4', 'lean-bf16')
@@ -89,7 +90,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
-           'snsde_hermite_coeffs_backward')
+           'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -161,6 +162,8 @@ def lib():
     L.snsde_backward_workspace_bytes.restype = C.c_size_t
     L.snsde_solve_backward.argtypes = [C.POINTER(Backward), C.c_void_p]
     L.snsde_sample_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.snsde_sample_stats_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                              C.c_void_p]
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

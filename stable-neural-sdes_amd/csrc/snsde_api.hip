@@ -150,9 +150,23 @@ static bool samples_ok(const snsde_solve* s) {
     const int64_t S = snsde_samples(s);
     return S == 1 || (s->batch % S == 0 && s->row_offset % S == 0 && s->global_rows % S == 0);
 }
-// ... an inference-only solve: no training-mode planes, and the initial state is the caller's (one row per path)
+// SNSDE_FLAG_SAMPLE_GRAD (snsde.h): the opt-in to training through the sample paths; nothing without samples > 1
+static bool sample_grad(const snsde_solve* s) { return snsde_samples(s) > 1 && (s->flags & SNSDE_FLAG_SAMPLE_GRAD) != 0; }
+static bool samples_training(const snsde_solve* s) {
+    return snsde_samples(s) > 1 && (s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out);
+}
+// ... an inference-only solve: no training-mode planes unless the flag opts in (never together with bf16 operands), and the
+// initial state is the caller's (one row per path) either way
 static bool samples_inference_only(const snsde_solve* s) {
-    return snsde_samples(s) == 1 || !(s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out || s->z0_weight);
+    if (sample_grad(s) && (s->flags & SNSDE_FLAG_BF16_OPERANDS)) return false;
+    return !(samples_training(s) && !sample_grad(s)) && !(snsde_samples(s) > 1 && s->z0_weight);
+}
+
+// ... and the forward plans whose training planes the sampled adjoint route takes (route_backward): the lean kernel and the general
+// MFMA kernel, elementwise diffusions, H <= 128 - the planes of any other plan would have no backward to read them
+static bool sampled_training_plan(const snsde_mfma::MfmaPlan& p) {
+    return p.ok && p.H != 256 && p.NN == 0 && (p.kernel == snsde_mfma::FwdKernel::lean || p.kernel == snsde_mfma::FwdKernel::general_m4 ||
+                                               p.kernel == snsde_mfma::FwdKernel::general_m16);
 }
 
 int snsde_flavor_hint(const snsde_solve* s) {
@@ -172,9 +186,13 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
     if (!samples_ok(s) || !samples_inference_only(s)) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
-    if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS)) r.path = generic; return r; }
+    // training planes of a sampled solve (SNSDE_FLAG_SAMPLE_GRAD): the MFMA kernels the sampled adjoint route covers, or nothing
+    const bool strain = samples_training(s);
+    if (strain && (variant || s->kl_column1 != 0)) return r;
+    if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS) && !strain) r.path = generic; return r; }
     if (!global_rows_ok(s)) return r;
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
+    if (strain && !sampled_training_plan(r.plan)) return ForwardRoute{};
     // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor - but not where the
     // plan made for the whole problem (global_rows) names a kernel this shard cannot run, nor where the plan arrives at a kernel
     // that does not address coeffs by sample group (samples): that is no kernel at all
@@ -193,9 +211,23 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
     snsde_mfma::BackwardRoute r{};
     const int hint = snsde_flavor_hint(s), k = s->kernel;
     if (!global_rows_ok(s)) return r;
-    if (snsde_samples(s) > 1 || !samples_ok(s)) return r;  // sample paths: an inference-only forward, no adjoint and nothing to plan
+    const bool sampled = snsde_samples(s) > 1;
+    // sample paths: an inference-only forward, no adjoint and nothing to plan - unless SNSDE_FLAG_SAMPLE_GRAD opts in
+    if ((sampled && (!sample_grad(s) || (s->flags & SNSDE_FLAG_BF16_OPERANDS))) || !samples_ok(s)) return r;
     r.fp = make_plan(s, net, hint);
     r.rp = make_rev_plan(s, net, r.fp, hint);
+    if (sampled) {
+        // the sampled adjoint route: a forward kernel that maps path p to coeffs row p / S (make_plan refuses the others) and the
+        // general MFMA adjoint, which reads no coefficients and leaves delta planes - the weight-gradient pass and
+        // snsde_coeff_gradients map paths to input rows themselves.  Anything else is no plan (never another kernel, no mode 2)
+        const bool fwd_ok = sampled_training_plan(r.fp);
+        const bool rev_ok = r.rp.ok && (r.rp.kernel == snsde_mfma::RevKernel::general || r.rp.kernel == snsde_mfma::RevKernel::general_srk);
+        if (!fwd_ok || !rev_ok || s->kl_column1 != 0 || snsde_solve_variant(s) || k == SNSDE_KERNEL_GENERIC ||
+            (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7))
+            return snsde_mfma::BackwardRoute{};
+        r.mode = 1;
+        return r;
+    }
     if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return r;     // an inference-only forward: no adjoint of any kind
     if (r.fp.shard_refused) return r;                      // (no forward kernel either: route_forward)
     if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return r;     // no forward kernel either (validate_solve)
@@ -533,7 +565,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
     if (b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
-    if (snsde_samples(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;                  // (sample paths: inference only)
+    if (snsde_samples(&b->fwd) > 1 && !sample_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (sample paths: inference only without the opt-in)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;
@@ -616,10 +648,10 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
 }
 
 // The checks of snsde_coeff_gradients that need no pointer: the configurations it covers (mode 1 with delta planes, the reference's
-// Diffusion_model fields, one path per row, no accumulator column).  *delta_slots: the planes per pass of delta_save
+// Diffusion_model fields, no accumulator column; sample paths where route_backward plans them).  *delta_slots: the planes per pass of delta_save
 static int route_coeff_gradients(const snsde_solve* s, int32_t* delta_slots) {
     if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;
-    if (snsde_samples(s) > 1 || s->kl_column1 != 0 || snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
+    if (s->kl_column1 != 0 || snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
     SnsdeNet net;
     int rc = snsde_build_net(s->model, s->n_steps, &net);
     if (rc) return rc;

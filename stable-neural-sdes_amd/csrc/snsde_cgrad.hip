@@ -19,6 +19,14 @@
 //                                stored before: a store and a reload do not change the value, so every (b, k, j, c) is one
 //                                owner's sum in ascending pass order).
 // A row's result depends on that row's delta planes and the tables only: bit-equal run to run and under any batch sharding.
+// Sample paths (snsde_solve::samples = S > 1 under SNSDE_FLAG_SAMPLE_GRAD): delta and v stay per path (B = paths), grad_coeffs is
+// per input row (B / S rows) and snsde_cgrad_walk_groups_kernel takes launch 3: it sums over the S paths of a row where it walks
+// the passes - passes ascending and, inside a pass, the row's paths s = 0 .. S-1: one owner per element, one fmaf chain.  A path
+// with zero planes adds exact zeros, so with the cotangent on one path of a group the sums are those of that path's own walk, bit
+// for bit.  The S values of (pass, input row) are S C adjacent floats of v: a workgroup owns RB input rows, ALL its lanes fetch the
+// rows' RB S C contiguous floats of up to eight passes into LDS (coalesced, eight loads in flight per lane: the memory
+// parallelism of the one-path walk), then the first RB C lanes run the chains out of LDS.  Where one pass of one row does not fit
+// the LDS (S C > 16320 floats) the round holds one pass and a chunk of its paths, in the same order.
 // The intermediate v costs P B C floats of traffic twice beside the P B H floats of delta (a third more at the K2 shape); in
 // exchange both kernels are fully parallel instead of one workgroup per row tile walking its passes one after the other.
 #include "snsde_internal.h"
@@ -39,6 +47,9 @@ struct CArgs {
     float* grad;                   // (B, L - 1, 4 C)
     int64_t R;                     // P B
     int32_t B, H, C, Lm1, P, NG, slot, srk, CC, LDH;
+    int32_t S;                     // paths per input row (>= 1): v and delta have B rows per pass, grad B / S rows
+    int32_t RB, SEG, WBS, SCH;     // walk_groups: input rows per workgroup, floats of a pass in an LDS round (RB SCH C), passes per
+                                   // round (<= 8), paths per round (S; fewer - then RB = WBS = 1 - where S C floats exceed the LDS)
     int32_t emb_w, init_w, fold;   // float offsets of emb.weight / initial_network.weight in params
 };
 
@@ -160,6 +171,70 @@ __global__ __launch_bounds__(64) void snsde_cgrad_walk_kernel(CArgs a) {
     }
 }
 
+constexpr int WNT = 256;      // threads of a walk_groups workgroup
+constexpr int WBMAX = 8;      // passes per LDS round
+
+__global__ __launch_bounds__(WNT) void snsde_cgrad_walk_groups_kernel(CArgs a) {
+    extern __shared__ __align__(16) float lds[];        // (WBS, SEG)
+    const int C = a.C, S = a.S, SEG = a.SEG, wb = a.WBS, SCH = a.SCH;
+    const int64_t rows = a.B / S;
+    const int64_t b0 = (int64_t)blockIdx.x * a.RB;
+    const int rbn = rows - b0 < a.RB ? (int)(rows - b0) : a.RB;      // input rows of this workgroup (>= 1 by the grid)
+    const int64_t BC = (int64_t)a.B * C;
+    const float* v = a.v + (size_t)b0 * S * C;
+    const bool owner = (int)threadIdx.x < rbn * C;
+    const int rb = owner ? (int)threadIdx.x / C : 0, c = owner ? (int)threadIdx.x - rb * C : 0;
+    float* out = a.grad + (size_t)(b0 + rb) * a.Lm1 * 4 * C + c;
+    const float* mine = lds + rb * S * C + c;          // (a chunked round has RB = 1: rb = 0)
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int cur = -1;
+    for (int p0 = 0; p0 < a.P; p0 += wb) {
+        const int np = a.P - p0 < wb ? a.P - p0 : wb;
+        for (int sb = 0; sb < S; sb += SCH) {          // one trip (SCH = S) unless S C floats exceed the LDS: paths sb .. sb + sc - 1
+            const int sc = S - sb < SCH ? S - sb : SCH;
+            const int seg = SCH == S ? rbn * S * C : sc * C;      // the round's floats of one pass of v: contiguous
+            const float* vs = v + (size_t)sb * C;
+            __syncthreads();                   // (the previous round's readers)
+            for (int i = threadIdx.x; i < seg; i += WNT) {
+                float t[WBMAX];
+#pragma unroll
+                for (int j = 0; j < WBMAX; ++j) t[j] = j < np ? vs[(size_t)(p0 + j) * BC + i] : 0.0f;
+#pragma unroll
+                for (int j = 0; j < WBMAX; ++j) if (j < np) lds[j * SEG + i] = t[j];
+            }
+            __syncthreads();
+            if (owner) {
+                for (int j = 0; j < np; ++j) {
+                    float r; int k;
+                    pass_interval(a, p0 + j, &r, &k);
+                    if (k != cur) {            // (a later chunk of the same pass: k == cur)
+                        if (cur >= 0) {
+                            float* o = out + (size_t)cur * 4 * C;
+                            o[0] = s0; o[C] = s1; o[2 * C] = s2; o[3 * C] = s3;
+                        }
+                        cur = k;
+                        const float* o = out + (size_t)cur * 4 * C;
+                        s0 = o[0]; s1 = o[C]; s2 = o[2 * C]; s3 = o[3 * C];
+                    }
+                    const float f2 = 0.5f * r * r, f3 = r * r * r / 3.0f;
+                    const float* x_ = mine + j * SEG;
+                    for (int s = 0; s < sc; ++s) {
+                        const float x = x_[s * C];
+                        s0 += x;
+                        s1 = fmaf(r, x, s1);
+                        s2 = fmaf(f2, x, s2);
+                        s3 = fmaf(f3, x, s3);
+                    }
+                }
+            }
+        }
+    }
+    if (owner && cur >= 0) {
+        float* o = out + (size_t)cur * 4 * C;
+        o[0] = s0; o[C] = s1; o[2 * C] = s2; o[3 * C] = s3;
+    }
+}
+
 // channels per chunk of the vjp kernel so that M's chunk and one row tile share 64 KiB of LDS (0: H too large)
 int chunk_channels(int H, int C) {
     const int room = LDS_FLOATS - TR * (H + 4);
@@ -183,7 +258,7 @@ size_t snsde_cgrad_workspace_floats(const snsde_solve& s) {
 }
 
 int snsde_cgrad_zero_launch(const snsde_solve& s, float* grad_coeffs, hipStream_t stream) {
-    const size_t bytes = (size_t)s.batch * (s.knots - 1) * 4 * s.model.input_channels * sizeof(float);
+    const size_t bytes = (size_t)(s.batch / snsde_samples(&s)) * (s.knots - 1) * 4 * s.model.input_channels * sizeof(float);      // (input rows)
     return hipMemsetAsync(grad_coeffs, 0, bytes, stream) == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
@@ -202,6 +277,9 @@ int snsde_cgrad_launch(const snsde_backward* b, const SnsdeNet& net, int delta_s
     a.srk = s.method == SNSDE_SRK ? 1 : 0;
     a.P = s.n_steps * (a.srk ? 3 : 1);
     a.B = s.batch; a.H = H; a.C = C; a.Lm1 = s.knots - 1; a.NG = delta_slots; a.slot = nhid + 1;
+    a.S = snsde_samples(&s);
+    if (a.B % a.S != 0) return SNSDE_ERR_DIMS;
+    if (a.S > 1 && C > WNT) return SNSDE_ERR_UNSUPPORTED;      // (walk_groups: a lane per channel of a row; the MFMA paths stop at C = 80)
     a.R = (int64_t)a.P * a.B;
     a.CC = CC; a.LDH = H + 4;
     a.emb_w = emb ? net.emb.src_w : 0; a.init_w = net.init.src_w; a.fold = emb ? 1 : 0;
@@ -212,7 +290,21 @@ int snsde_cgrad_launch(const snsde_backward* b, const SnsdeNet& net, int delta_s
     const int gx = (int)(ntiles < 1024 ? ntiles : 1024);
     const size_t lds_bytes = ((size_t)H * CC + (size_t)TR * a.LDH) * sizeof(float);
     hipLaunchKernelGGL(snsde_cgrad_vjp_kernel, dim3(gx, (C + CC - 1) / CC), dim3(NT), lds_bytes, stream, a);
-    const int64_t BC = (int64_t)a.B * C;
-    hipLaunchKernelGGL(snsde_cgrad_walk_kernel, dim3((unsigned)((BC + 63) / 64)), dim3(64), 0, stream, a);
+    const int64_t BC = (int64_t)(a.B / a.S) * C;      // one lane per (input row, channel)
+    if (a.S > 1) {
+        const int64_t SC = (int64_t)a.S * C;          // floats of v per (pass, input row)
+        if (SC <= LDS_FLOATS) {
+            a.SCH = a.S;
+            a.RB = SC >= WNT ? 1 : (int)(WNT / SC);
+            a.SEG = a.RB * (int)SC;
+            a.WBS = LDS_FLOATS / a.SEG < WBMAX ? LDS_FLOATS / a.SEG : WBMAX;
+        } else {                                      // one pass of one row per round, in chunks of SCH paths
+            a.SCH = LDS_FLOATS / C; a.RB = 1; a.SEG = a.SCH * C; a.WBS = 1;
+        }
+        const int64_t rows = a.B / a.S;
+        hipLaunchKernelGGL(snsde_cgrad_walk_groups_kernel, dim3((unsigned)((rows + a.RB - 1) / a.RB)), dim3(WNT),
+                           (size_t)a.WBS * a.SEG * sizeof(float), stream, a);
+    }
+    else hipLaunchKernelGGL(snsde_cgrad_walk_kernel, dim3((unsigned)((BC + 63) / 64)), dim3(64), 0, stream, a);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }

@@ -1,4 +1,5 @@
-// Mean and unbiased variance over the sample axis of a sampled solve's result (include/snsde.h: snsde_sample_stats).
+// Mean and unbiased variance over the sample axis of a sampled solve's result, and their adjoint (include/snsde.h: snsde_sample_stats,
+// snsde_sample_stats_backward).
 // ys is (groups, samples, width); one lane owns one output element (V = 1) or four adjacent ones (V = 4: 16-byte loads and stores,
 // width % 4 == 0 and 16-byte aligned pointers) and walks its samples in order, twice: the sum, then the squared deviations from
 // the mean.  Adjacent lanes own adjacent columns, so every load of a wave is one contiguous piece of a row.  No atomics, no
@@ -63,7 +64,63 @@ __global__ void __launch_bounds__(ST) snsde_sample_stats_kernel(const float* __r
     }
 }
 
+// grad_ys[g, s, w] = grad_mean / S + grad_var 2 (ys - mean) / (S - 1): the same ownership as the forward, one walk over s
+template <int V>
+__global__ void __launch_bounds__(ST) snsde_sample_stats_backward_kernel(const float* __restrict__ gmean, const float* __restrict__ gvar,
+                                                                         const float* __restrict__ ys, const float* __restrict__ mean,
+                                                                         int64_t groups, int32_t S, int32_t W, float* __restrict__ gys) {
+    const int64_t wv = W / V, total = groups * wv;
+    const float fs = (float)S, fs1 = (float)(S > 1 ? S - 1 : 1);
+    for (int64_t e = (int64_t)blockIdx.x * ST + threadIdx.x; e < total; e += (int64_t)gridDim.x * ST) {
+        const int64_t g = e / wv, w = (e - g * wv) * V;
+        const int64_t row = (g * S) * (int64_t)W + w;
+        float a[V], c[V], m[V];
+        load<V>(gmean + g * W + w, a);
+#pragma unroll
+        for (int i = 0; i < V; ++i) { a[i] /= fs; c[i] = 0.0f; m[i] = 0.0f; }
+        if (gvar) {
+            load<V>(gvar + g * W + w, c);
+            load<V>(mean + g * W + w, m);
+#pragma unroll
+            for (int i = 0; i < V; ++i) c[i] = (2.0f * c[i]) / fs1;
+        }
+        for (int s = 0; s < S; ++s) {
+            float o[V];
+            if (gvar) {
+                float x[V];
+                load<V>(ys + row + (int64_t)s * W, x);
+#pragma unroll
+                for (int i = 0; i < V; ++i) o[i] = fmaf(c[i], x[i] - m[i], a[i]);
+            } else {
+#pragma unroll
+                for (int i = 0; i < V; ++i) o[i] = a[i];
+            }
+            store<V>(gys + row + (int64_t)s * W, o);
+        }
+    }
+}
+
 }  // namespace
+
+extern "C" int snsde_sample_stats_backward(const float* grad_mean, const float* grad_var, const float* ys, const float* mean,
+                                           int64_t groups, int32_t samples, int32_t width, float* grad_ys, void* hip_stream) {
+    if (!grad_mean || !grad_ys || (grad_var && (!ys || !mean))) return SNSDE_ERR_NULL;
+    if (groups <= 0 || samples <= 0 || width <= 0) return SNSDE_ERR_DIMS;
+    if (grad_var && samples < 2) return SNSDE_ERR_DIMS;
+    if (groups > INT64_MAX / samples / width) return SNSDE_ERR_DIMS;
+    uintptr_t al = reinterpret_cast<uintptr_t>(grad_mean) | reinterpret_cast<uintptr_t>(grad_ys);
+    if (grad_var) al |= reinterpret_cast<uintptr_t>(grad_var) | reinterpret_cast<uintptr_t>(ys) | reinterpret_cast<uintptr_t>(mean);
+    const bool vec = width % 4 == 0 && (al & 15) == 0;
+    const int64_t items = groups * (width / (vec ? 4 : 1));
+    int64_t blocks = (items + ST - 1) / ST;
+    if (blocks > 8192) blocks = 8192;      // (the kernel strides over the rest)
+    hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    if (vec) hipLaunchKernelGGL(snsde_sample_stats_backward_kernel<4>, dim3((unsigned)blocks), dim3(ST), 0, st, grad_mean, grad_var, ys, mean,
+                                groups, samples, width, grad_ys);
+    else hipLaunchKernelGGL(snsde_sample_stats_backward_kernel<1>, dim3((unsigned)blocks), dim3(ST), 0, st, grad_mean, grad_var, ys, mean,
+                            groups, samples, width, grad_ys);
+    return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
+}
 
 extern "C" int snsde_sample_stats(const float* ys, int64_t groups, int32_t samples, int32_t width, float* mean, float* var,
                                   void* hip_stream) {

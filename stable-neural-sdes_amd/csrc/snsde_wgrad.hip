@@ -62,8 +62,9 @@ struct WTile {
 };
 
 struct XInfo { const float* coeffs; const float* step_tab; int32_t B, C, Lm1, t_col0, t_cols, x_col0, x_cols, raw_time;
-               int32_t n_col0; };   // SRK + diffusion net: columns n_col0 + {0, 1} = sin / cos of the pass's own diffusion stage time,
+               int32_t n_col0;      // SRK + diffusion net: columns n_col0 + {0, 1} = sin / cos of the pass's own diffusion stage time,
                                     // n_col0 + {4, 5} = those of the step's fourth evaluation (rows of passes 3n + 2), else -1
+               int32_t samples; };  // paths per input row, >= 1 (snsde_solve::samples): batch row b reads coeffs row b / samples
 
 struct DArgs {
     const float* ds_part; const float* dth_part;
@@ -119,7 +120,9 @@ __device__ __forceinline__ float4 xaux_raw(const XInfo& a, const XStep& x, int b
     if (j >= a.t_col0 && j < a.t_col0 + a.t_cols) r.x = j == a.t_col0 ? x.t0 : x.t1;
     else if (j >= a.x_col0 && j < a.x_col0 + a.x_cols) {
         const int c = j - a.x_col0;
-        const float* cr = a.coeffs + ((size_t)b * a.Lm1 + x.idx) * 4 * a.C;
+        // (sample paths: the row's input row; a uniform branch, so one path per row pays no division - the loads still issue here)
+        const int br = a.samples > 1 ? (int)((uint32_t)b / (uint32_t)a.samples) : b;
+        const float* cr = a.coeffs + ((size_t)br * a.Lm1 + x.idx) * 4 * a.C;
         r = make_float4(cr[c], cr[a.C + c], cr[2 * a.C + c], cr[3 * a.C + c]);
     }
     return r;
@@ -897,7 +900,7 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     a.R = wp->n_pass * s.batch; a.ntiles = wp->ntiles; a.NP = wp->NP;
     for (int i = 0; i < wp->ntiles; ++i) a.tile[i] = wp->tile[i];
     a.x = XInfo{s.coeffs, pass_tab, s.batch, C, s.knots - 1, wp->t_col0, wp->xt, wp->x_col0, wp->x_cols,
-                s.model.time_feature == SNSDE_TIME_RAW ? 1 : 0, wp->n_col0};
+                s.model.time_feature == SNSDE_TIME_RAW ? 1 : 0, wp->n_col0, snsde_samples(&s)};
     AArgs aa = wp->aa;
     const float* gt = s.noise_table ? s.noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s.workspace) + fp.gt_off : nullptr);
     float* ds = ws + wp->ds_off;

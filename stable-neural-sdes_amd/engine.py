@@ -184,12 +184,20 @@ def check_samples(samples):
     return samples
 
 
+def check_sample_grad(sample_grad):
+    """The `sample_grad` option (training through sample paths, SNSDE_FLAG_SAMPLE_GRAD): a bool, ValueError otherwise."""
+    if not isinstance(sample_grad, bool):
+        raise ValueError(f"sample_grad must be a bool (differentiate a solve of `samples` paths per input row), got {sample_grad!r}")
+    return sample_grad
+
+
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
-                 row_offset=0, samples=0, lean_general=False, exact_order=False):
+                 row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
-    at does not map paths to input rows."""
+    at does not map paths to input rows.  sample_grad: SNSDE_FLAG_SAMPLE_GRAD; training: the solve writes its training planes
+    (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers)."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
@@ -197,6 +205,9 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
     s.flags = precision_flags(precision) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
+    s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
+    if training:      # (only their presence matters to the query)
+        s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
@@ -504,16 +515,17 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0, samples=0):
+                 lean_general=False, global_rows=0, samples=0, sample_grad=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
         dev = y0.device
-        # samples = S > 1 (inference): y0, dW, dU, row_out and the result are per PATH (B rows), coeffs per input row (B / S rows)
+        # samples = S > 1: y0, dW, dU, row_out, the result and (sample_grad: training) every saved plane are per PATH (B rows), coeffs
+        # per input row (B / S rows)
         S = int(samples) if samples else 1
         if S < 1 or B % S:
             raise ValueError(f'samples={samples!r}: the {B} rows of y0 are paths, a whole number of groups of `samples` per input row')
-        if S > 1 and (save_traj or save_dW or save_act or z0_linear is not None):
+        if S > 1 and (((save_traj or save_dW or save_act) and not sample_grad) or z0_linear is not None):
             raise ValueError('samples > 1 is inference only: no saved trajectory, increments or activations, and y0 is the caller\'s')
         _check_f32('y0', y0, (B, model.hidden_channels))
         _check_f32('coeffs', coeffs, (B // S, L - 1, 4 * C_))
@@ -548,6 +560,8 @@ class SolveCall:
         self.base_flags |= precision_flags(precision)      # bf16: inference only (the library refuses training outputs and every backward)
         if lean_general:    # (SNSDE_FLAG_LEAN_GENERAL: the lean kernel's general instantiation; same results bit for bit)
             self.base_flags |= _lib.FLAG_LEAN_GENERAL
+        if sample_grad and S > 1:      # (SNSDE_FLAG_SAMPLE_GRAD: no effect on one path per row)
+            self.base_flags |= _lib.FLAG_SAMPLE_GRAD
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -570,7 +584,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S)
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1)
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -658,12 +672,16 @@ _MODE_CACHE = _BoundedCache()
 _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per configuration (SolveCall.cfg_key)
 
 
-def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0):
+def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
+                  samples=0, sample_grad=False):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
-    supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none)."""
+    supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none); samples: paths
+    per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD)."""
+    samples = int(samples) if samples and int(samples) > 1 else 0
+    sample_grad = bool(sample_grad) and samples > 1
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
-           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows))
+           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad)
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -671,7 +689,8 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.batch, s.knots, s.n_steps, s.n_out = batch, knots, grid.N, grid.T
         s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
         s.kernel = _lib.KERNELS[kernel]
-        s.flags = _lib.FLAG_EXACT_ORDER if exact_order else 0
+        s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0)
+        s.samples = samples
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
         if kl_column is not None:
             s.kl_column1 = int(kl_column) + 1
@@ -789,7 +808,7 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
 
 
 def coeff_gradients(call, adj, delta, stream=None):
-    """dL/d coeffs (B, L-1, 4C) of a finished mode-1 solve + adjoint (solve_backward with save_delta, or backward_with_gradients
+    """dL/d coeffs (B, L-1, 4C; a sampled solve: one row per INPUT row, the sum over its paths) of a finished mode-1 solve + adjoint (solve_backward with save_delta, or backward_with_gradients
     with return_delta): snsde_coeff_gradients on the delta planes, enqueue-only.  `adj` is the adjoint call's result (kept
     alive with the planes).  SnsdeError -4 for a solve without delta planes (call.delta_slots == 0) and every other
     configuration the entry point does not cover (include/snsde.h)."""
@@ -899,8 +918,9 @@ def readout_head(x, layers, stream=None):
 def sample_stats(ys, samples, var=True):
     """Mean and unbiased variance over the sample axis of a sampled solve's result (sdeint options={'samples': S}): ys is
     (..., B S, H) with path index b S + s; returns (mean, var), each (..., B, H) (var None when var=False).  CUDA float32 input:
-    one launch of snsde_sample_stats (one lane per output element walks its S samples in order, twice: deterministic); other
-    tensors: the same two passes in torch."""
+    one launch of snsde_sample_stats (one lane per output element walks its S samples in order, twice: deterministic) - inside an
+    autograd node whose backward is snsde_sample_stats_backward when the input requires grad; other tensors: the same two passes
+    in torch, which autograd differentiates."""
     S = check_samples(samples)
     if ys.dim() < 2 or ys.shape[-2] % S:
         raise ValueError(f'ys has shape {tuple(ys.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
@@ -908,6 +928,9 @@ def sample_stats(ys, samples, var=True):
         raise ValueError('the unbiased variance needs samples >= 2')
     W = ys.shape[-1]
     out_shape = tuple(ys.shape[:-2]) + (ys.shape[-2] // S, W)
+    if ys.is_cuda and ys.dtype == torch.float32 and ys.numel() > 0 and ys.requires_grad and torch.is_grad_enabled():
+        mean, vout = _SampleStats.apply(ys, S, bool(var))      # (the kernels below inside one autograd node)
+        return mean, (vout if var else None)
     if not (ys.is_cuda and ys.dtype == torch.float32) or ys.numel() == 0:
         v = ys.reshape(out_shape[:-1] + (S, W))
         mean = v.sum(dim=-2) / S
@@ -918,6 +941,47 @@ def sample_stats(ys, samples, var=True):
     _lib.check(_lib.lib().snsde_sample_stats(_ptr(ys), ys.numel() // (S * W), S, W, _ptr(mean), _ptr(vout),
                                              C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_sample_stats')
     return mean, vout
+
+
+def sample_stats_backward(grad_mean, grad_var, ys, mean, samples):
+    """dL/d ys of `sample_stats` from dL/d mean and dL/d var (None: no variance term): one launch of snsde_sample_stats_backward.
+    ys (..., B S, H), mean / grad_mean / grad_var (..., B, H): contiguous float32 CUDA tensors."""
+    S, W = int(samples), ys.shape[-1]
+    _check_f32('ys', ys)
+    _check_f32('grad_mean', grad_mean, tuple(ys.shape[:-2]) + (ys.shape[-2] // S, W))
+    if grad_var is not None:
+        _check_f32('grad_var', grad_var, tuple(grad_mean.shape))
+        _check_f32('mean', mean, tuple(grad_mean.shape))
+    out = torch.empty_like(ys)
+    _lib.check(_lib.lib().snsde_sample_stats_backward(_ptr(grad_mean), _ptr(grad_var), _ptr(ys), _ptr(mean if grad_var is not None else None),
+                                                      ys.numel() // (S * W), S, W, _ptr(out),
+                                                      C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_stats_backward')
+    return out
+
+
+class _SampleStats(torch.autograd.Function):
+    """sample_stats of a CUDA float32 tensor that requires grad: the forward kernel, and snsde_sample_stats_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ys, S, var):
+        ysc = ys.detach().contiguous()
+        with torch.no_grad():
+            mean, vout = sample_stats(ysc, S, var)
+        ctx.S, ctx.var = S, var
+        ctx.save_for_backward(ysc, mean)
+        if not var:
+            vout = mean.new_empty(0)
+            ctx.mark_non_differentiable(vout)
+        return mean, vout
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mean, grad_var):
+        ys, mean = ctx.saved_tensors
+        gm = torch.zeros_like(mean) if grad_mean is None else grad_mean.to(torch.float32).contiguous()
+        gv = grad_var.to(torch.float32).contiguous() if ctx.var and grad_var is not None else None
+        return sample_stats_backward(gm, gv, ys, mean, ctx.S), None, None
 
 
 def spline_grad_native():

@@ -217,7 +217,9 @@ class _SDEHead(nn.Module):
     def _initial_state(self, times, z0, kwargs):
         """(z0, kwargs).  Inference on the fused path: z0 is an uninitialised placeholder and options['z0_linear'] hands the
         solve `initial_network`, which evaluates initial_network(X(times[0])) inside its prepare launch (no spline-evaluate
-        and addmm launches of its own); everything else: `_prepare_initial_state` (neuralsde.py:63-69)."""
+        and addmm launches of its own); everything else: `_prepare_initial_state` (neuralsde.py:63-69).  Under grad - training
+        through sample paths included (options={'samples': S, 'sample_grad': True}) - z0 is materialised here with tensor ops, one
+        row per INPUT row; sdeint expands it to one row per path, so autograd sums its gradient over the paths."""
         func = self.func
         if (z0 is None and self.initial and not torch.is_grad_enabled() and getattr(func, 'coeffs', None) is not None
                 and func.coeffs.is_cuda and self.initial_network.weight.is_cuda

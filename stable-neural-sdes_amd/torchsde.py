@@ -172,9 +172,11 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if backend not in ('auto', 'hip', 'torch'):
         raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
     # options={'samples': S}: S Brownian paths per input row (inference; _sdeint_samples).  Checked for every backend; 1 = no option
+    # options={'sample_grad': True}: such a solve may be differentiated (opt-in: its training planes are per path).  No effect on 1
     samples = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
+    sample_grad = engine.check_sample_grad(options.pop('sample_grad')) if 'sample_grad' in options else False
     if samples > 1:
-        return _sdeint_samples(sde, y0, ts, bm, method, float(dt), options, names, samples)
+        return _sdeint_samples(sde, y0, ts, bm, method, float(dt), options, names, samples, sample_grad)
     if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
         engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset') or 0)      # ValueError if malformed
 
@@ -214,17 +216,31 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     return _sdeint_torch(sde, y0, ts, bm, method, float(dt), options, names)
 
 
-def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S):
+def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=False):
     """options={'samples': S}, S > 1: S Brownian paths per input row in one solve, for a predictive mean / variance / ensemble
     (engine.sample_stats).  The control path stays (B, L-1, 4C); y0 (B, H) - or already (B S, H) - and a row_out of length B are
     expanded path-major (path b S + s), the result is (T, B S, H) ((B S, H) with row_out) and path p draws the Philox stream of
-    global row row_offset + p.  Inference only.  Where a kernel maps paths to input rows (engine.forward_path(..., samples=S)) the
-    coefficients are read in place; everywhere else (other kernel families, the composed / latent / tensor-op routes, CPU) they
-    are replicated with repeat_interleave and the ordinary solve runs with the same seed and offsets: the same result either way."""
+    global row row_offset + p.  Inference only unless options={'sample_grad': True}.  Where a kernel maps paths to input rows
+    (engine.forward_path(..., samples=S)) the coefficients are read in place; everywhere else (other kernel families, the composed /
+    latent / tensor-op routes, CPU) they are replicated with repeat_interleave and the ordinary solve runs with the same seed and
+    offsets: the same result either way.
+    sample_grad: the solve is differentiable - gradients arrive at the caller's y0 (a (B, H) one: summed over the paths by the
+    expansion's own backward), parameters and (B, L-1, 4C) coefficients.  Where the library plans the sampled adjoint
+    (engine.backward_mode(..., samples=S, sample_grad=True) == 1) the fused node runs on the coefficients in place and
+    dL/d coeffs comes out of snsde_coeff_gradients already summed over the paths; everywhere else the coefficients are
+    replicated and the ordinary differentiable solve runs (autograd sums over the paths) - the fused solve again, no warning.
+    param_pass='torch' (the library-GEMM cross-check of the native pass) has no sampled form: ValueError."""
     params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
-    if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde)):
+    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde))
+    if needs_grad and not sample_grad:
         raise ValueError(f"samples={S} is inference only: y0, the control path or a parameter requires grad (use torch.no_grad() or "
-                         "requires_grad_(False))")
+                         "requires_grad_(False), or opt in to training through the sample paths with options={'sample_grad': True})")
+    if sample_grad:
+        for name, bad in (('recompute', bool(options.get('recompute'))), ('save_traj', bool(options.get('save_traj', False))),
+                          ("precision='bf16'", options.get('precision', 'fp32') == 'bf16'),
+                          ("param_pass='torch'", options.get('param_pass', 'hip') == 'torch')):
+            if bad:
+                raise ValueError(f"sample_grad=True (training through samples={S} paths per input row) does not take {name}")
     if options.get('save_traj', False) or options.get('recompute'):
         raise ValueError(f"samples={S} is inference only: save_traj / recompute are training options")
     backend = options.get('backend', 'auto')
@@ -265,15 +281,23 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S):
         engine.precision_flags(precision)
         # (a hidden size the fused route zero-pads runs padded in the replicated solve: take that route, for the same result)
         padded = precision == 'fp32' and kernel == 'auto' and engine.padding_plan(model, B * S, L, grid.N, method) is not None
-        if not padded and engine.forward_path(model, B * S, L, grid.N, method, kernel, precision=precision,
-                                              global_rows=int(options['global_rows']), row_offset=row_offset, samples=S,
-                                              exact_order=bool(options.get('exact_order', False))) != 'none':
+        # (SNSDE_RECOMPUTE_STEPS, the process-wide equivalent of options['recompute'] that the ordinary solve honours: recompute mode
+        #  re-runs the forward chunk by chunk on one coefficient row per path, so such a process trains on the replicated route)
+        env_recompute = int(os.environ.get('SNSDE_RECOMPUTE_STEPS', 0) or 0) > 0
+        if needs_grad:      # the sampled adjoint route (mode 1 with delta planes), or the replicated differentiable solve below
+            fused = not padded and not env_recompute and engine.backward_mode(model, B * S, L, grid, method, kernel, bool(options.get('exact_order', False)),
+                                                        global_rows=int(options['global_rows']), samples=S, sample_grad=True) == 1
+        else:
+            fused = not padded and engine.forward_path(model, B * S, L, grid.N, method, kernel, precision=precision,
+                                                       global_rows=int(options['global_rows']), row_offset=row_offset, samples=S,
+                                                       exact_order=bool(options.get('exact_order', False))) != 'none'
+        if fused:
             try:
-                return _sdeint_hip(sde, rec, y0, ts, bm, method, dt, dict(options, samples=S))
+                return _sdeint_hip(sde, rec, y0, ts, bm, method, dt, dict(options, samples=S, sample_grad=needs_grad))
             except engine._lib.SnsdeError as exc:
                 # the query named a kernel and the launch still found none: the replicated solve, unless the caller's Brownian
                 # object has been queried already (a stateful one would not repeat its increments) or the caller is strict
-                if exc.code not in (-4, -6) or bm is not None or options.get('strict', False):
+                if exc.code not in (-4, -6) or bm is not None or options.get('strict', False) or needs_grad:
                     raise
     saved = (coeffs, sde.times) if control else None
     if control:
@@ -346,7 +370,8 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     needs_grad = (torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in pidx.params))) or coeff_grad
     dev = y0.device
     coeffs = coeffs_src = sde.coeffs
-    samples = int(options.get('samples', 1))      # (> 1: from _sdeint_samples only - inference, a kernel that takes it, no padding)
+    # (samples > 1: from _sdeint_samples only - a kernel that takes it, no padding; sample_grad: a training solve the library plans)
+    samples, sample_grad = int(options.get('samples', 1)), bool(options.get('sample_grad', False))
     if coeffs.dim() != 3 or coeffs.shape[0] * samples != y0.shape[0]:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -410,7 +435,9 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                 return out
     if needs_grad:
         mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)), global_rows=global_rows)
+                                    bool(options.get('exact_order', False)), global_rows=global_rows, samples=samples, sample_grad=sample_grad)
+        if samples > 1 and mode != 1:      # (_sdeint_samples asked the same query: the sampled node is mode 1 or not built at all)
+            raise engine._lib.SnsdeError(-4, f"samples={samples}: no fused adjoint plans this sampled solve")
         if mode == 0 and not options.get('strict', False):
             # no fused adjoint for this configuration (Milstein with sqrt(y); shapes beyond the generic adjoint's LDS budget):
             # differentiate through the unfused tensor-op loop on the same device rather than fail the
@@ -424,7 +451,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         if not coeff_grad:
             return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, None, y0, *pidx.params)
         what = None
-        if mode == 1 and method != 'srk' and int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0) > 0:
+        if mode == 1 and method != 'srk' and samples == 1 and int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0) > 0:
             what = "options['recompute']"
         else:
             try:
@@ -768,9 +795,13 @@ class _FusedSolve(torch.autograd.Function):
             return engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=seed,
                                     row_offset=int(options.get('row_offset', 0)), kernel=kernel, save_traj=True,
                                     save_dW=keep_dw, save_act=save_act, exact_order=bool(options.get('exact_order', False)),
-                                    row_out=options.get('row_out'), dU=dU, global_rows=options.get('global_rows', 0))
+                                    row_out=options.get('row_out'), dU=dU, global_rows=options.get('global_rows', 0),
+                                    samples=samples, sample_grad=samples > 1,
+                                    lean_general=samples > 1 and bool(options.get('lean_general', False)))      # (the sampled route's A/B switch)
+        samples = int(options.get('samples', 1)) if options.get('sample_grad', False) else 1      # (sampled training: _sdeint_samples)
         mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)), global_rows=int(options.get('global_rows', 0)))
+                                    bool(options.get('exact_order', False)), global_rows=int(options.get('global_rows', 0)),
+                                    samples=samples, sample_grad=samples > 1)
         if mode == 0:
             raise NotImplementedError(
                 "the fused backward covers 'euler', 'srk' and 'milstein' for every noise_option (Milstein: all but 7, "
@@ -780,7 +811,7 @@ class _FusedSolve(torch.autograd.Function):
         # recompute mode (options={'recompute': steps per chunk} or SNSDE_RECOMPUTE_STEPS): keep states and increments only,
         # re-run the forward kernel chunk by chunk inside backward (engine.backward_recompute)
         ctx.recompute = 0
-        if mode == 1 and method != 'srk':
+        if mode == 1 and method != 'srk' and samples == 1:      # (a sampled node never recomputes: _sdeint_samples routes around it)
             ctx.recompute = max(int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0), 0)
             if ctx.recompute >= grid.N:      # one chunk = the whole solve: the saved-activation mode with a second forward on top
                 ctx.recompute = 0            # (and the parent's states / increments kept beside the chunk's: MORE memory, K5 N = 49)
