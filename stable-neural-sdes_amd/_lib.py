@@ -72,11 +72,19 @@ class Head(_Sized):
                 ('bn_weight', C.c_void_p), ('bn_bias', C.c_void_p), ('w2', C.c_void_p), ('b2', C.c_void_p), ('out', C.c_void_p)]
 
 
+SNSDE_ERR_UNSUPPORTED, SNSDE_ERR_LDS = -4, -6      # (include/snsde.h: the two codes of a valid request that no kernel covers)
+
+
 class SnsdeError(RuntimeError):
     def __init__(self, code, what=''):
         self.code = code
         msg = lib().snsde_strerror(code).decode()
         super().__init__(f'libsnsde: {msg} (code {code}){": " + what if what else ""}')
+
+    @property
+    def no_kernel(self):
+        """A valid request without a kernel in this build or within the LDS budget: what a front end may answer with another route."""
+        return self.code in (SNSDE_ERR_UNSUPPORTED, SNSDE_ERR_LDS)
 
 
 _lib = None

@@ -481,6 +481,11 @@ def srk_stage_times(grid):
     return grid._d_srk_times
 
 
+def noise_table_times(grid, method):
+    """Device tensor of the times a time-only diffusion factor is tabulated at: the step times; SRK: every step's four stage times."""
+    return srk_stage_times(grid) if method == 'srk' else grid.d_t0
+
+
 def step_grid(ts_host, dt, times_host, device):
     key = (np.asarray(ts_host, dtype=np.float32).tobytes(), float(dt),
            np.asarray(times_host, dtype=np.float32).tobytes(), str(device))

@@ -4,18 +4,32 @@ torch-ists/.../nsde_model.py:63-74):
 
     sdeint(sde=func, y0=z0, ts=ts, dt=dt, method='euler', options={'dt': dt})  ->  (T, B, H)
 
-Dispatch
-  * ``sde`` honours the Diffusion_model contract (engine.recognise) and ``y0`` is a CUDA tensor:
-    ONE fused HIP solve (libsnsde.so).  No fallback: if the library is missing this raises.
-  * anything else (arbitrary ``sde.f/g`` such as the tutorial's vector fields, or CPU tensors = the
-    reference's CPU plumbing configuration): the same fixed-step scheme written with tensor ops,
-    calling ``sde.f`` / ``sde.g`` once per step.
+Dispatch, in the order ``sdeint`` asks (the first route that takes the call solves it)
+  1. sampled (_sdeint_samples): options={'samples': S > 1}, every backend.  It expands y0 / row_out to S paths per input row
+     and either hands the fused route the coefficients in place (a kernel that maps paths to rows) or replicates them and
+     calls ``sdeint`` again without the option.
+  2. fused (_sdeint_hip): ``sde`` honours the Diffusion_model contract (engine.recognise) under the default drift /
+     diffusion names and ``y0`` is a CUDA tensor (backend 'auto'), or backend='hip'.  ONE fused HIP solve (libsnsde.so);
+     with gradients the fused adjoint (_FusedSolve).  If the library is missing this raises.  A valid request that no kernel
+     covers, or a gradient no fused adjoint returns, takes the tensor-op loop on the same device (one warning per
+     configuration) unless options={'strict': True}; a refused shard, a bf16 refusal and a sampled solve that the query
+     accepted are errors either way.
+  3. padded (_sdeint_padded), from inside the fused route: fp32, kernel 'auto', no save_traj / recompute / samples and a hidden
+     size without an MFMA instantiation (engine.padding_plan): the zero-padded model on the MFMA kernels, exactly.
+  4. composed (_sdeint_composed): default names, not a Diffusion_model, backend 'auto', CUDA: a tutorial-style field that
+     fields.compose maps onto the lean kernel and verifies.  None (not such a field, not covered) passes the call on.
+  5. latent (_sdeint_latent): other names (torch-ists' f_aug / g_aug), backend 'auto', CUDA: the latent dynamics on the fused
+     kernels, the KL accumulator in the solve or as one batched quadrature.  Falls back to the loop itself.
+  6. tensor-op loop (_sdeint_torch): everything else (backend='torch', CPU tensors = the reference's CPU plumbing
+     configuration, arbitrary ``sde.f/g``): the same fixed-step scheme written with tensor ops, calling ``sde.f`` / ``sde.g``
+     once per step.
 
 Fixed-step semantics (restated from torchsde 0.2.5; its source is not in the
 reference tree): time accumulates in float32 by repeated ``curr_t + dt`` clamped to ``ts[-1]``;
 outputs are linearly interpolated between the two solver states bracketing each ``ts[k]``;
 Euler ``y + f*h + g*dW``; Milstein adds ``0.5 * g * dg/dy * (dW^2 - h)`` (Ito, diagonal noise).
 """
+import collections
 import os
 import warnings
 
@@ -150,6 +164,53 @@ def prepare_graph_capture(device):
     return _CAPTURE_SEEDS[key]
 
 
+def _philox_key(options, device):
+    """The Philox key of a solve whose kernels draw the increments: options['seed'] (an int; a device tensor as it is), else a
+    device-resident key that a recording advances itself (fresh noise per replay), else a fresh host draw."""
+    seed = options.get('seed')
+    if seed is None:      # (only a CUDA device records: the capture query needs one)
+        capturing = torch.device(device).type == 'cuda' and torch.cuda.is_current_stream_capturing()
+        return _capture_seed(device) if capturing else _fresh_seed()
+    return seed if torch.is_tensor(seed) else int(seed)
+
+
+def _row_offset(options, rows):
+    """The global row of this call's first row (Philox counters use the global row): options['row_offset'], where None is "not
+    given"; else, one process per GPU (DDP), rank * rows - ranks that seed identically must not integrate against identical
+    Brownian paths, and shard r of equal-sized shards starts at row r * rows; else 0.  Always an int."""
+    given = options.get('row_offset')
+    if given is not None:
+        return int(given)
+    import torch.distributed as dist
+    if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+        return dist.get_rank() * int(rows)
+    return 0
+
+
+def _device_row_out(options, device):
+    """options['row_out'] (per-row output selection fused into the solve: the result is (B, H)) as the kernels read it."""
+    row_out = options.get('row_out')
+    return None if row_out is None else row_out.to(device=device, dtype=torch.int32).contiguous()
+
+
+def _recompute_steps(options):
+    """Steps per chunk of recompute mode: options['recompute'], else the process-wide environment variable; 0 = off."""
+    return max(int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0), 0)
+
+
+def _default_names(names):
+    """names={'drift': 'f', 'diffusion': 'g'} is the default mapping: such a call may still take a fused route."""
+    return names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
+                             and not (set(names) - {'drift', 'diffusion'}))
+
+
+def _differentiated(sde, y0, params=None):
+    """This solve is differentiated: grad is enabled and y0, a parameter or the control path's coefficients require it.
+    params: the module's parameters where the caller has them listed already (engine.param_index spares the walk)."""
+    params = getattr(sde, 'parameters', tuple)() if params is None else params      # (a generator: nothing is walked yet)
+    return torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde))
+
+
 def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5, atol=1e-4, dt_min=1e-5,
            options=None, names=None, logqp=False, extra=False, extra_solver_state=None, **unused_kwargs):
     if unused_kwargs:
@@ -180,9 +241,7 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
         engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset') or 0)      # ValueError if malformed
 
-    # names={'drift': 'f', 'diffusion': 'g'} is the default mapping: still the fused path
-    default_names = names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
-                                      and not (set(names) - {'drift', 'diffusion'}))
+    default_names = _default_names(names)
     rec = engine.recognise(sde) if default_names else None
     # options={'precision': 'bf16'}: inference on the bf16-operand kernel (engine.check_bf16), or a ValueError - never fp32 instead
     precision = options.get('precision', 'fp32')
@@ -190,8 +249,7 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if precision == 'bf16':
         if backend == 'torch':
             raise ValueError("precision='bf16' is a HIP kernel option; backend='torch' has no bf16 solve")
-        params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
-        if torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde)):
+        if _differentiated(sde, y0):
             raise ValueError("precision='bf16' is inference only: y0, the control path or a parameter requires grad (use torch.no_grad(), "
                              "requires_grad_(False) or precision='fp32')")
         if rec is None:
@@ -200,7 +258,7 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
             raise ValueError("precision='bf16' needs CUDA (ROCm) tensors")
     want_hip = backend == 'hip' or (backend == 'auto' and rec is not None and y0.is_cuda)
     if 'z0_linear' in options and not (want_hip and rec is not None and y0.is_cuda):
-        y0 = _materialise_z0(sde, y0, ts, options)      # only the fused solve evaluates the initial state itself
+        y0 = _materialise_z0(sde, y0, ts, options.pop('z0_linear'))      # only the fused solve evaluates the initial state itself
     if want_hip:
         if rec is None:
             raise ValueError("options['backend']='hip' needs an sde honouring the Diffusion_model contract")
@@ -230,8 +288,7 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
     dL/d coeffs comes out of snsde_coeff_gradients already summed over the paths; everywhere else the coefficients are
     replicated and the ordinary differentiable solve runs (autograd sums over the paths) - the fused solve again, no warning.
     param_pass='torch' (the library-GEMM cross-check of the native pass) has no sampled form: ValueError."""
-    params = list(sde.parameters()) if isinstance(sde, torch.nn.Module) else []
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde))
+    needs_grad = _differentiated(sde, y0)
     if needs_grad and not sample_grad:
         raise ValueError(f"samples={S} is inference only: y0, the control path or a parameter requires grad (use torch.no_grad() or "
                          "requires_grad_(False), or opt in to training through the sample paths with options={'sample_grad': True})")
@@ -245,7 +302,7 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
         raise ValueError(f"samples={S} is inference only: save_traj / recompute are training options")
     backend = options.get('backend', 'auto')
     if 'z0_linear' in options:
-        y0 = _materialise_z0(sde, y0, ts, options)      # (per input row, before the expansion)
+        y0 = _materialise_z0(sde, y0, ts, options.pop('z0_linear'))      # (per input row, before the expansion)
     coeffs = getattr(sde, 'coeffs', None)
     control = torch.is_tensor(coeffs) and coeffs.dim() == 3 and hasattr(sde, 'set_X')
     B = int(coeffs.shape[0]) if control else int(y0.shape[0])
@@ -260,20 +317,14 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
         elif row_out.numel() != B * S:
             raise ValueError(f"samples={S}: row_out has {row_out.numel()} entries, expected {B} or {B * S}")
         options['row_out'] = row_out
-    if options.get('row_offset') is None:
-        import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        options['row_offset'] = dist.get_rank() * B * S if multi else 0
-    row_offset = int(options['row_offset'])
+    row_offset = options['row_offset'] = _row_offset(options, B * S)      # (counted in paths)
     if row_offset % S:
         raise ValueError(f"samples={S}: row_offset={row_offset} must be a multiple of samples (whole groups of paths per shard)")
     if backend != 'torch':
         options['global_rows'] = engine.resolve_global_rows(options.get('global_rows'), B * S, row_offset)
         if options['global_rows'] % S:
             raise ValueError(f"samples={S}: global_rows={options['global_rows']} must be a multiple of samples")
-    default_names = names is None or (names.get('drift', 'f') == 'f' and names.get('diffusion', 'g') == 'g'
-                                      and not (set(names) - {'drift', 'diffusion'}))
-    rec = engine.recognise(sde) if default_names and control else None
+    rec = engine.recognise(sde) if _default_names(names) and control else None
     if rec is not None and y0.is_cuda and backend != 'torch':
         model = rec[0]
         grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sde.times), y0.device)
@@ -281,11 +332,10 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
         engine.precision_flags(precision)
         # (a hidden size the fused route zero-pads runs padded in the replicated solve: take that route, for the same result)
         padded = precision == 'fp32' and kernel == 'auto' and engine.padding_plan(model, B * S, L, grid.N, method) is not None
-        # (SNSDE_RECOMPUTE_STEPS, the process-wide equivalent of options['recompute'] that the ordinary solve honours: recompute mode
-        #  re-runs the forward chunk by chunk on one coefficient row per path, so such a process trains on the replicated route)
-        env_recompute = int(os.environ.get('SNSDE_RECOMPUTE_STEPS', 0) or 0) > 0
+        # (options['recompute'] was refused above; its process-wide equivalent, which the ordinary solve honours, is left: recompute
+        #  mode re-runs the forward chunk by chunk on one coefficient row per path, so such a process trains on the replicated route)
         if needs_grad:      # the sampled adjoint route (mode 1 with delta planes), or the replicated differentiable solve below
-            fused = not padded and not env_recompute and engine.backward_mode(model, B * S, L, grid, method, kernel, bool(options.get('exact_order', False)),
+            fused = not padded and not _recompute_steps(options) and engine.backward_mode(model, B * S, L, grid, method, kernel, bool(options.get('exact_order', False)),
                                                         global_rows=int(options['global_rows']), samples=S, sample_grad=True) == 1
         else:
             fused = not padded and engine.forward_path(model, B * S, L, grid.N, method, kernel, precision=precision,
@@ -297,7 +347,7 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
             except engine._lib.SnsdeError as exc:
                 # the query named a kernel and the launch still found none: the replicated solve, unless the caller's Brownian
                 # object has been queried already (a stateful one would not repeat its increments) or the caller is strict
-                if exc.code not in (-4, -6) or bm is not None or options.get('strict', False) or needs_grad:
+                if not exc.no_kernel or bm is not None or options.get('strict', False) or needs_grad:
                     raise
     saved = (coeffs, sde.times) if control else None
     if control:
@@ -329,11 +379,10 @@ def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoi
     return sdeint(sde, y0, ts, bm=bm, method=method, names=names, **kwargs)
 
 
-def _materialise_z0(sde, y0, ts, options):
-    """options['z0_linear'] = the wrapper's `initial_network`: y0 is a placeholder and the solve starts from
+def _materialise_z0(sde, y0, ts, lin):
+    """lin = options['z0_linear'] = the wrapper's `initial_network`: y0 is a placeholder and the solve starts from
     initial_network(X(ts[0])) (NeuralSDE._prepare_initial_state, neuralsde.py:63-69).  Evaluated here with tensor ops for
     every path but the no-grad fused solve, which computes it inside its prepare launch."""
-    lin = options.pop('z0_linear')
     return lin(sde.X.evaluate(ts[0])).to(y0.dtype)
 
 
@@ -355,90 +404,86 @@ class _DrawnIncrements:
         return (self.dW[i], self.dU[i]) if return_U else self.dW[i]
 
 
+# What a fused solve reads from `options`, resolved once by _sdeint_hip: _FusedSolve.forward and _sdeint_padded take this record
+# and the backward mode decided beside it, never the dict
+_FusedOptions = collections.namedtuple('_FusedOptions', (
+    'kernel', 'precision', 'exact_order', 'save_traj', 'strict', 'param_pass', 'recompute', 'samples', 'sample_grad', 'lean_general',
+    'row_offset', 'global_rows', 'row_out', 'seed'))
+
+
 def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     model, layout, numel = rec
+    dev = y0.device
     z0_lin = None
     if 'z0_linear' in options:
-        options = dict(options)
-        if (_z0_fusable(options['z0_linear'], sde, y0) and bm is None and options.get('kernel', 'auto') == 'auto'
+        z0_lin = options['z0_linear']
+        if not (_z0_fusable(z0_lin, sde, y0) and bm is None and options.get('kernel', 'auto') == 'auto'
                 and not options.get('save_traj', False)):
-            z0_lin = options.pop('z0_linear')
-        else:
-            y0 = _materialise_z0(sde, y0, ts, options)
+            y0, z0_lin = _materialise_z0(sde, y0, ts, z0_lin), None
     pidx = engine.param_index(sde, layout)
     coeff_grad = _coeffs_need_grad(sde)      # dL/d coeffs wanted: the adjoint's delta planes give it (engine.coeff_gradients)
-    needs_grad = (torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in pidx.params))) or coeff_grad
-    dev = y0.device
+    needs_grad = _differentiated(sde, y0, pidx.params)
     coeffs = coeffs_src = sde.coeffs
     # (samples > 1: from _sdeint_samples only - a kernel that takes it, no padding; sample_grad: a training solve the library plans)
-    samples, sample_grad = int(options.get('samples', 1)), bool(options.get('sample_grad', False))
+    samples = int(options.get('samples', 1))
     if coeffs.dim() != 3 or coeffs.shape[0] * samples != y0.shape[0]:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     y0c = y0.detach().to(torch.float32).contiguous()
+    B, L = y0c.shape[0], coeffs.shape[1] + 1
     times_host = _HostTimes.get(sde.times)
-    ts_host = _HostTimes.get(ts)
-    grid = engine.step_grid(ts_host, dt, times_host, dev)
-    dW = dU = None
-    if bm is not None:
-        t0 = torch.from_numpy(grid.t0)
-        t1 = torch.from_numpy(grid.t1)
-        if method == 'srk':   # torchsde: I_k, I_k0 = bm(t0, t1, return_U=True)
-            pairs = [bm(t0[n], t1[n], return_U=True) for n in range(grid.N)]
-            dW = torch.stack([p[0].to(device=dev, dtype=torch.float32) for p in pairs]).contiguous()
-            dU = torch.stack([p[1].to(device=dev, dtype=torch.float32) for p in pairs]).contiguous()
-        else:
-            dW = torch.stack([bm(t0[n], t1[n]).to(device=dev, dtype=torch.float32) for n in range(grid.N)]).contiguous()
-    seed = options.get('seed')
-    if seed is None:
-        seed = _capture_seed(dev) if torch.cuda.is_current_stream_capturing() else _fresh_seed()
-    elif not torch.is_tensor(seed):
-        seed = int(seed)
-    if 'row_offset' not in options:
-        # one process per GPU (DDP): ranks that seed identically must not integrate against identical Brownian paths.
-        # Philox counters use the global row, so shard r of equal-sized shards starts at row r * local_batch.
-        import torch.distributed as dist
-        if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-            options = dict(options, row_offset=dist.get_rank() * int(y0.shape[0]))
+    grid = engine.step_grid(_HostTimes.get(ts), dt, times_host, dev)
+    # (without `bm` the kernels draw Philox increments: nothing to draw here)
+    dW, dU = _draw_increments(bm, grid, y0, method, dtype=torch.float32, philox=True, host_times=True)
+
+    def loop():      # the tensor-op loop on the same device, on the increments already drawn (and on y0 as it is by then)
+        return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
+    row_offset = _row_offset(options, B)
     # options={'global_rows': N | 'world'}: the rows of the whole problem this batch is a shard of - the library then plans its
     # kernels as for N rows on one device, and the shards reproduce the unsharded solve bit for bit (opt-in; default: the local batch)
-    global_rows = engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], options.get('row_offset', 0))
-    options = dict(options, global_rows=global_rows)
-    row_out = options.get('row_out')
-    if row_out is not None:     # per-row output selection fused into the solve: the result is (B, H)
-        row_out = row_out.to(device=dev, dtype=torch.int32).contiguous()
-        options = dict(options, row_out=row_out)
-    precision = options.get('precision', 'fp32')
-    if precision == 'bf16':
-        if needs_grad or (z0_lin is not None and torch.is_grad_enabled() and any(p.requires_grad for p in z0_lin.parameters())):
+    opt = _FusedOptions(
+        seed=_philox_key(options, dev), kernel=options.get('kernel', 'auto'), precision=options.get('precision', 'fp32'),
+        exact_order=bool(options.get('exact_order', False)), save_traj=bool(options.get('save_traj', False)),
+        strict=bool(options.get('strict', False)), param_pass=options.get('param_pass', 'hip'), recompute=_recompute_steps(options),
+        samples=samples, sample_grad=bool(options.get('sample_grad', False)), lean_general=bool(options.get('lean_general', False)),
+        row_offset=row_offset, global_rows=engine.resolve_global_rows(options.get('global_rows'), B, row_offset),
+        row_out=_device_row_out(options, dev))
+    if opt.precision == 'bf16':
+        if needs_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
             raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad")
-        if options.get('save_traj', False):
+        if opt.save_traj:
             raise ValueError("precision='bf16' is inference only: save_traj is a training output")
-        engine.check_bf16(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method, options.get('kernel', 'auto'))
-    if engine.shard_refused(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method, options.get('kernel', 'auto'),
-                            global_rows=global_rows, row_offset=int(options.get('row_offset', 0))):
+        engine.check_bf16(model, B, L, grid.N, method, opt.kernel)
+    if engine.shard_refused(model, B, L, grid.N, method, opt.kernel, global_rows=opt.global_rows, row_offset=opt.row_offset):
         # the kernel planned for the whole problem cannot run this shard (a wave-pair plan, fewer than four rows): an error with or
         # without `strict` - another kernel or the tensor-op loop would not reproduce the unsharded solve
-        raise engine._lib.SnsdeError(-4, f"global_rows={global_rows}: the kernel planned for the whole problem cannot run this "
-                                         f"{y0c.shape[0]}-row shard")
-    if precision == 'fp32' and options.get('kernel', 'auto') == 'auto' and not options.get('save_traj', False) and not options.get('recompute') and samples == 1:
-        pad = engine.padding_plan(model, y0c.shape[0], coeffs.shape[1] + 1, grid.N, method)
+        raise engine._lib.SnsdeError(engine._lib.SNSDE_ERR_UNSUPPORTED,
+                                     f"global_rows={opt.global_rows}: the kernel planned for the whole problem cannot run this "
+                                     f"{B}-row shard")
+    # (options['recompute'] alone, not _recompute_steps: its process-wide equivalent moves no model off the padded solve, which
+    #  never recomputes)
+    if opt.precision == 'fp32' and opt.kernel == 'auto' and not opt.save_traj and not options.get('recompute') and samples == 1:
+        pad = engine.padding_plan(model, B, L, grid.N, method)
         if pad is not None and coeff_grad:      # (the padded solve's autograd node has no coefficient gradient: the fallback rule)
             _unfused_coeff_grad(sde, f"hidden_channels={model.hidden_channels} (a zero-padded solve)", options)
-            return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
-        if pad is not None:       # a hidden size without MFMA instantiation: solve the zero-padded model (exact)
+            return loop()
+        # a hidden size without MFMA instantiation: solve the zero-padded model (exact) - in training, where its adjoint is the MFMA one
+        if pad is not None and (not needs_grad or engine.backward_mode(pad[0], B, L, grid, method, global_rows=opt.global_rows) == 1):
             if z0_lin is not None:
-                y0 = _materialise_z0(sde, y0, ts, {'z0_linear': z0_lin})
-                y0c, z0_lin = y0.detach().to(torch.float32).contiguous(), None
-            out = _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, seed, options, row_out, needs_grad)
-            if out is not None:
-                return out
+                y0, z0_lin = _materialise_z0(sde, y0, ts, z0_lin), None
+            return _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad)
     if needs_grad:
-        mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)), global_rows=global_rows, samples=samples, sample_grad=sample_grad)
+        mode = engine.backward_mode(model, B, L, grid, method, opt.kernel, opt.exact_order, global_rows=opt.global_rows,
+                                    samples=samples, sample_grad=opt.sample_grad)
         if samples > 1 and mode != 1:      # (_sdeint_samples asked the same query: the sampled node is mode 1 or not built at all)
-            raise engine._lib.SnsdeError(-4, f"samples={samples}: no fused adjoint plans this sampled solve")
-        if mode == 0 and not options.get('strict', False):
+            raise engine._lib.SnsdeError(engine._lib.SNSDE_ERR_UNSUPPORTED, f"samples={samples}: no fused adjoint plans this sampled solve")
+        if mode == 0 and opt.strict:
+            raise NotImplementedError(
+                "the fused backward covers 'euler', 'srk' and 'milstein' for every noise_option (Milstein: all but 7, "
+                "sqrt(y), whose derivative is not finite at the clipped values), within the LDS budget of the generic "
+                "adjoint kernels; pass options={'backend': 'torch'} to differentiate this configuration through the "
+                "tensor-op loop")
+        if mode == 0:
             # no fused adjoint for this configuration (Milstein with sqrt(y); shapes beyond the generic adjoint's LDS budget):
             # differentiate through the unfused tensor-op loop on the same device rather than fail the
             # reference's training loop; options={'strict': True} raises instead
@@ -447,45 +492,40 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
                 _UNFUSED_WARNED.add(key)
                 warnings.warn(f"sdeint: no fused backward for input_option={key[0]}, noise_option={key[1]}, method={method!r}; "
                               "differentiating through the unfused tensor-op loop (slow).")
-            return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
-        if not coeff_grad:
-            return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, None, y0, *pidx.params)
-        what = None
-        if mode == 1 and method != 'srk' and samples == 1 and int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0) > 0:
+            return loop()
+        if coeff_grad and mode == 1 and method != 'srk' and samples == 1 and opt.recompute > 0:
             what = "options['recompute']"
         else:
-            try:
-                return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, seed, options, coeffs_src, y0,
-                                         *pidx.params)
+            try:      # (_NoCoeffGradient: only where dL/d coeffs is wanted)
+                return _FusedSolve.apply(sde, rec, coeffs, grid, times_host, (dW, dU), method, opt, mode,
+                                         coeffs_src if coeff_grad else None, y0, *pidx.params)
             except _NoCoeffGradient:
                 what = (f"input_option={sde.input_option}, noise_option={sde.noise_option}, method={method!r}, "
-                        f"hidden_channels={model.hidden_channels} at {y0c.shape[0]} rows (an adjoint that sums the weight gradients itself)")
+                        f"hidden_channels={model.hidden_channels} at {B} rows (an adjoint that sums the weight gradients itself)")
         _unfused_coeff_grad(sde, what, options)
-        return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
+        return loop()
     flat = engine.flatten_params(sde, layout, numel, dev)
-    call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=seed,
-                            row_offset=int(options.get('row_offset', 0)), kernel=options.get('kernel', 'auto'),
-                            save_traj=bool(options.get('save_traj', False)),
-                            exact_order=bool(options.get('exact_order', False)), dU=dU, row_out=row_out,
+    call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=opt.seed, row_offset=opt.row_offset,
+                            kernel=opt.kernel, save_traj=opt.save_traj, exact_order=opt.exact_order, dU=dU, row_out=opt.row_out,
                             z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
-                            precision=precision, global_rows=global_rows, samples=samples)
+                            precision=opt.precision, global_rows=opt.global_rows, samples=samples)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
         if samples > 1:              # (the path query accepted this solve: a refusal now is an error, not another route)
             raise
-        if precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
+        if opt.precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
             raise ValueError(f"precision='bf16': the solve was refused ({exc})") from exc
         # a valid request no kernel covers (Milstein with noise_option 7, sqrt(y)): same behaviour as the gradient path, the
         # unfused tensor-op loop, unless strict
-        # (-6, SNSDE_ERR_LDS: a hidden size whose per-tile buffers exceed the LDS budget of the only kernel family that covers
+        # (SNSDE_ERR_LDS: a hidden size whose per-tile buffers exceed the LDS budget of the only kernel family that covers
         # the request — the generic Milstein kernel for the diffusion nets above H ~ 460 — is the same situation)
-        if exc.code not in (-4, -6) or options.get('strict', False):
+        if not exc.no_kernel or opt.strict:
             raise
         if z0_lin is not None:
-            y0 = _materialise_z0(sde, y0, ts, {'z0_linear': z0_lin})
-        return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
-    if options.get('save_traj', False):
+            y0 = _materialise_z0(sde, y0, ts, z0_lin)
+        return loop()
+    if opt.save_traj:
         sde.last_trajectory = call.traj
     return ys.to(y0.dtype)
 
@@ -495,7 +535,7 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
     4-row-tile kernel with the variant switches.  None = not such a field / not covered: the caller takes the generic
     stepper."""
     from . import fields
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in sde.parameters()))
+    needs_grad = _differentiated(sde, y0)      # (a solve whose coefficients require grad returns below)
     field = fields.compose(sde)
     coeffs = getattr(sde, 'coeffs', None)
     if field is None or not torch.is_tensor(coeffs) or coeffs.dim() != 3 or coeffs.shape[0] != y0.shape[0]:
@@ -504,40 +544,22 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
         _unfused_coeff_grad(sde, "a composed (tutorial-style) field", options)
         return None
     dev = y0.device
-    capturing = torch.cuda.is_current_stream_capturing()
-    if capturing and (bm is not None or field.verified.get(str(dev)) is not True):
+    if torch.cuda.is_current_stream_capturing() and (bm is not None or field.verified.get(str(dev)) is not True):
         return None      # graph capture: solves (training ones too) of a mapping that was verified before the capture (a warm-up solve)
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     times_host = _HostTimes.get(sde.times)
     if not fields.verify(field, coeffs, times_host, dev):
         return None
     grid = engine.step_grid(_HostTimes.get(ts), dt, times_host, dev)
-    dW = dU = None
-    if bm is not None and not field.parts.get('ode', False):      # (the ODE field has no diffusion: nothing to draw)
-        t0, t1 = torch.from_numpy(grid.t0), torch.from_numpy(grid.t1)
-        if method == 'srk':
-            pairs = [bm(t0[n], t1[n], return_U=True) for n in range(grid.N)]
-            dW = torch.stack([p[0].to(device=dev, dtype=torch.float32) for p in pairs]).contiguous()
-            dU = torch.stack([p[1].to(device=dev, dtype=torch.float32) for p in pairs]).contiguous()
-        else:
-            dW = torch.stack([bm(t0[n], t1[n]).to(device=dev, dtype=torch.float32) for n in range(grid.N)]).contiguous()
-    # the times the time-only diffusion factor is tabulated at: the step times; SRK: the four stage times of every step
-    tab_times = grid.d_t0 if method != 'srk' else engine.srk_stage_times(grid)
-    seed = options.get('seed')
-    if seed is None:     # recorded solves read a device-resident key that the recording itself advances: fresh noise per replay
-        seed = _capture_seed(dev) if capturing else _fresh_seed()
-    elif not torch.is_tensor(seed):
-        seed = int(seed)
-    row_offset = options.get('row_offset')
-    if row_offset is None:
-        import torch.distributed as dist
-        multi = dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1
-        row_offset = dist.get_rank() * int(y0.shape[0]) if multi else 0
+    # (the ODE field has no diffusion: nothing to draw; without `bm` the kernels draw Philox increments)
+    dW, dU = _draw_increments(None if field.parts.get('ode', False) else bm, grid, y0, method, dtype=torch.float32, philox=True,
+                              host_times=True)
+    tab_times = engine.noise_table_times(grid, method)
+    seed = _philox_key(options, dev)
+    row_offset = _row_offset(options, y0.shape[0])
     # (these fields run on 4-row tiles at every batch size: the option is checked and handed down, it moves no choice today)
     global_rows = engine.resolve_global_rows(options.get('global_rows'), y0.shape[0], row_offset)
-    row_out = options.get('row_out')
-    if row_out is not None:
-        row_out = row_out.to(device=dev, dtype=torch.int32).contiguous()
+    row_out = _device_row_out(options, dev)
     if needs_grad:
         # training: the composition and the module's own g stay in the autograd graph; the solve between them is the fused
         # forward + adjoint + weight-gradient pass (flat-block and table gradients flow back through those graphs)
@@ -546,7 +568,7 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
             return None
         flat = field.flat(dev, grad=True)
         tab = field.noise_table(tab_times, dev, grad=True) if field.tabulated else None
-        return _ComposedSolve.apply(field.model, coeffs, grid, dW, method, seed, int(row_offset), row_out, y0, flat, tab, dU, None,
+        return _ComposedSolve.apply(field.model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU, None,
                                     global_rows)
     # options={'trust_versions': True}: the cached composed block / table are keyed on the parameters' addresses and version
     # counters alone (no content fingerprint = no device->host read per solve); in-place edits through `.data` are then the
@@ -554,38 +576,42 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
     field.trust_versions = bool(options.get('trust_versions', False))
     flat, tab = field.inference_inputs(tab_times, dev)
     call = engine.SolveCall(field.model, flat, coeffs, grid, y0.detach().to(torch.float32).contiguous(), dW=dW, dU=dU,
-                            method=method, seed=seed, row_offset=int(row_offset), row_out=row_out, noise_table=tab,
+                            method=method, seed=seed, row_offset=row_offset, row_out=row_out, noise_table=tab,
                             global_rows=global_rows)
     try:
         return call.launch().to(y0.dtype)
     except engine._lib.SnsdeError as exc:
-        if exc.code not in (-4, -6):
+        if not exc.no_kernel:
             raise
         return None
 
 
-def _draw_increments(bm, grid, y0, method, options):
-    """Every increment of a solve up front, (N, B, H) I_k (and I_k0 for SRK): from the caller's Brownian object, in step
-    order, or from a torch generator (options['seed'])."""
-    dev = y0.device
-    t0s, t1s = torch.from_numpy(grid.t0).to(dev), torch.from_numpy(grid.t1).to(dev)
-    hs = (t1s - t0s).to(y0.dtype)
+def _draw_increments(bm, grid, y0, method, seed=None, dtype=None, philox=False, scalar=False, host_times=False):
+    """Every increment of a solve up front, (N, B, H) I_k (and I_k0 for SRK, which asks `bm` with return_U=True as torchsde does),
+    on y0's device in `dtype` (default: y0's).  The only code that queries a caller's Brownian object: once per step, in step
+    order, at the grid's times - host tensors with host_times, else on y0's device.  Without `bm`: (None, None) under `philox`
+    (the kernels draw the increments), else a torch generator seeded with `seed` (an int; otherwise a fresh seed); `scalar`:
+    that draw is (N, B, 1), torchsde's scalar noise."""
+    if bm is None and philox:
+        return None, None
+    dev, dtype = y0.device, y0.dtype if dtype is None else dtype
+    t0s, t1s = torch.from_numpy(grid.t0), torch.from_numpy(grid.t1)
+    if not host_times or bm is None:
+        t0s, t1s = t0s.to(dev), t1s.to(dev)
     if bm is None:
         gen = torch.Generator(device=dev)
-        seed = options.get('seed')
         gen.manual_seed(int(seed) if seed is not None and not torch.is_tensor(seed) else _fresh_seed())
-        hcol = hs.reshape(-1, *([1] * y0.dim()))
-        dW = torch.randn((grid.N,) + tuple(y0.shape), dtype=y0.dtype, device=dev, generator=gen) * hcol.sqrt()
+        hcol = (t1s - t0s).to(dtype).reshape(-1, *([1] * y0.dim()))
+        wshape = (grid.N, y0.shape[0], 1) if scalar else (grid.N,) + tuple(y0.shape)
+        dW = torch.randn(wshape, dtype=dtype, device=dev, generator=gen) * hcol.sqrt()
         dU = None
         if method == 'srk':      # I_k0 = h (I_k / 2 + sqrt(h / 12) xi): the space-time Levy integral
-            xi = torch.randn((grid.N,) + tuple(y0.shape), dtype=y0.dtype, device=dev, generator=gen)
+            xi = torch.randn((grid.N,) + tuple(y0.shape), dtype=dtype, device=dev, generator=gen)
             dU = hcol * (0.5 * dW + (hcol / 12).sqrt() * xi)
         return dW, dU
-    if method == 'srk':
-        pairs = [bm(t0s[n], t1s[n], return_U=True) for n in range(grid.N)]
-        return (torch.stack([p[0].to(device=dev, dtype=y0.dtype) for p in pairs]),
-                torch.stack([p[1].to(device=dev, dtype=y0.dtype) for p in pairs]))
-    return torch.stack([bm(t0s[n], t1s[n]).to(device=dev, dtype=y0.dtype) for n in range(grid.N)]), None
+    drawn = [bm(t0s[n], t1s[n], **({'return_U': True} if method == 'srk' else {})) for n in range(grid.N)]
+    stack = lambda parts: torch.stack([p.to(device=dev, dtype=dtype) for p in parts])
+    return (stack([d[0] for d in drawn]), stack([d[1] for d in drawn])) if method == 'srk' else (stack(drawn), None)
 
 
 def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
@@ -618,17 +644,16 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
     in_solve = (acc is not None and P > Hl and os.environ.get('SNSDE_LATENT_SPLIT') != '1' and
                 not (torch.is_grad_enabled() and any(t.requires_grad for t in field.parts.get('prior_leaves', ()))))
     philox = in_solve and bm is None and options.get('seed') is None
-    drawn_box = []
+    drawn = []
 
     def increments():
-        if not drawn_box:
-            dW_, dU_ = _draw_increments(bm, grid, y0, method, options)
-            drawn_box.append((dW_, dU_, _DrawnIncrements(dW_, dU_)))
-        return drawn_box[0]
-    dW, dU = (None, None) if philox else increments()[:2]
+        if not drawn:
+            drawn.append(_draw_increments(bm, grid, y0, method, seed=options.get('seed')))
+        return drawn[0]
+    dW, dU = (None, None) if philox else increments()
 
     def fallback():
-        return _sdeint_torch(sde, y0, ts, increments()[2], method, dt, options, names)
+        return _sdeint_torch(sde, y0, ts, _DrawnIncrements(*increments()), method, dt, options, names)
     view = field.sde
     cache = field.__dict__.setdefault('_dummy_control', {})
     key = (B, str(dev))
@@ -642,7 +667,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
             return fallback()
     except RuntimeError:
         return fallback()
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in sde.parameters()))
+    needs_grad = _differentiated(sde, y0)      # (a latent module has no control path: y0 and the parameters)
     widen = lambda t: None if t is None else torch.nn.functional.pad(t[..., :Hl].to(torch.float32), (0, P - Hl)).contiguous()
     # (1) the accumulator INSIDE the solve (snsde.h: kl_column1): column Hl of the padded state integrates the KL rate with the
     #     scheme's own drift weights, the adjoint kernels carry its cotangent back into the drift net - one solve over the
@@ -651,7 +676,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
     if in_solve:
         kl = (Hl, acc[0], acc[1])
         key = _fresh_seed() if philox else 0
-        tt = grid.d_t0 if method != 'srk' else engine.srk_stage_times(grid)
+        tt = engine.noise_table_times(grid, method)
         y0a = torch.nn.functional.pad(y0[:, :Hl + 1], (0, P - Hl - 1))
         try:
             if needs_grad:
@@ -666,12 +691,12 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
                                         dU=widen(dU), method=method, seed=key, noise_table=tab, kl_column=kl)
                 return call.launch()[:, :, :Hl + 1].to(y0.dtype)
         except engine._lib.SnsdeError as exc:
-            if exc.code not in (-4, -6):      # (no kernel for this shape: the split solve below)
+            if not exc.no_kernel:      # (no kernel for this shape: the split solve below)
                 raise
     # (2) the split solve: latent dynamics fused, the accumulator as one batched quadrature over every state
-    dW, dU = increments()[:2]
+    dW, dU = increments()
     full = engine.every_step_grid(grid)
-    tab_times = full.d_t0 if method != 'srk' else engine.srk_stage_times(full)
+    tab_times = engine.noise_table_times(full, method)
     y0p = torch.nn.functional.pad(y0[:, :Hl], (0, P - Hl))
     if needs_grad:
         if engine.backward_mode(field.model, B, 2, full, method, table=True) != 1:
@@ -685,7 +710,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
         try:
             Y = _ComposedSolve.apply(field.model, coeffs, full, widen(dW), method, 0, 0, None, y0p, flat, tab, widen(dU))
         except engine._lib.SnsdeError as exc:
-            if exc.code not in (-4, -6):      # no kernel / LDS budget: the tensor-op loop on the increments already drawn
+            if not exc.no_kernel:      # no kernel / LDS budget: the tensor-op loop on the increments already drawn
                 raise
             return fallback()
     else:
@@ -695,7 +720,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
         try:
             Y = call.launch()
         except engine._lib.SnsdeError as exc:
-            if exc.code not in (-4, -6):
+            if not exc.no_kernel:
                 raise
             return fallback()
     N = grid.N
@@ -722,23 +747,21 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
     return torch.cat([y0.unsqueeze(0).to(aug.dtype), outs], dim=0)
 
 
-def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, seed, options, row_out, needs_grad):
-    """Solve the zero-padded model (engine.padding_plan) on the MFMA kernels and drop the padded state components."""
+def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad):
+    """Solve the zero-padded model (engine.padding_plan) on the MFMA kernels and drop the padded state components.  opt: the
+    _FusedOptions of _sdeint_hip, which has also checked that a training solve of the padded model has the MFMA adjoint."""
     model, layout, _ = rec
     model_p, layout_p, _, P = pad
     H, dev = model.hidden_channels, y0.device
-    global_rows = int(options.get('global_rows', 0))      # (resolved by _sdeint_hip)
-    if needs_grad and engine.backward_mode(model_p, int(y0.shape[0]), coeffs.shape[1] + 1, grid, method, global_rows=global_rows) != 1:
-        return None
     flat = engine.padded_flat(sde, layout, layout_p, H, P, dev, needs_grad)
     widen = lambda t: None if t is None else torch.nn.functional.pad(t, (0, P - H)).contiguous()
-    row_offset = int(options.get('row_offset', 0))
     if needs_grad:
-        ys = _ComposedSolve.apply(model_p, coeffs, grid, widen(dW), method, seed, row_offset, row_out,
-                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, global_rows)
+        ys = _ComposedSolve.apply(model_p, coeffs, grid, widen(dW), method, opt.seed, opt.row_offset, opt.row_out,
+                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, opt.global_rows)
     else:
         call = engine.SolveCall(model_p, flat, coeffs, grid, widen(y0.detach().to(torch.float32)), dW=widen(dW), method=method,
-                                seed=seed, row_offset=row_offset, dU=widen(dU), row_out=row_out, global_rows=global_rows)
+                                seed=opt.seed, row_offset=opt.row_offset, dU=widen(dU), row_out=opt.row_out,
+                                global_rows=opt.global_rows)
         ys = call.launch().to(y0.dtype)
     return ys[..., :H]
 
@@ -776,52 +799,43 @@ class _FusedSolve(torch.autograd.Function):
     all (step, row) pairs whose autograd yields them.  This replaces autograd through the ~25 x N nodes of the
     unrolled loop (benchmark_classification/common_sde.py:158-160)."""
 
+    # forward's leading inputs that take no gradient (sde .. mode); coeffs_src, y0 and the parameters follow in this order
+    NO_GRAD_INPUTS = 9
+
     @staticmethod
-    def forward(ctx, sde, rec, coeffs, grid, times_host, increments, method, seed, options, coeffs_src, y0, *params):
+    def forward(ctx, sde, rec, coeffs, grid, times_host, increments, method, opt, mode, coeffs_src, y0, *params):
+        # opt, mode: the _FusedOptions and engine.backward_mode (1 or 2) that _sdeint_hip resolved - nothing is decided again here
         # coeffs_src: the caller's coefficient tensor when dL/d coeffs is wanted (a differentiable input; the kernels read
         # `coeffs`, its detached float32 copy), else None - such a solve launches and allocates nothing beyond the parameter pass
         model, layout, numel = rec
         dW, dU = increments
         flat = engine.flatten_params(sde, layout, numel, y0.device)
         y0c = y0.detach().to(torch.float32).contiguous()
-
-        def make(kernel, save_act):
-            # the increments are kept only where the backward cannot get them otherwise: the MFMA Euler / Milstein adjoint reads
-            # supplied ones in place and REGENERATES Philox ones (host key) - one (N, B, H) store and load less per step
-            nets = model.noise_option in (14, 15, 18, 19)
-            keep_dw = not (save_act and method in ('euler', 'milstein') and not (nets and method == 'milstein')
-                           and not torch.is_tensor(seed) and options.get('param_pass', 'hip') in ('hip', 'split')
-                           and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
-            return engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=seed,
-                                    row_offset=int(options.get('row_offset', 0)), kernel=kernel, save_traj=True,
-                                    save_dW=keep_dw, save_act=save_act, exact_order=bool(options.get('exact_order', False)),
-                                    row_out=options.get('row_out'), dU=dU, global_rows=options.get('global_rows', 0),
-                                    samples=samples, sample_grad=samples > 1,
-                                    lean_general=samples > 1 and bool(options.get('lean_general', False)))      # (the sampled route's A/B switch)
-        samples = int(options.get('samples', 1)) if options.get('sample_grad', False) else 1      # (sampled training: _sdeint_samples)
-        mode = engine.backward_mode(model, y0c.shape[0], coeffs.shape[1] + 1, grid, method, options.get('kernel', 'auto'),
-                                    bool(options.get('exact_order', False)), global_rows=int(options.get('global_rows', 0)),
-                                    samples=samples, sample_grad=samples > 1)
-        if mode == 0:
-            raise NotImplementedError(
-                "the fused backward covers 'euler', 'srk' and 'milstein' for every noise_option (Milstein: all but 7, "
-                "sqrt(y), whose derivative is not finite at the clipped values), within the LDS budget of the generic "
-                "adjoint kernels; pass options={'backend': 'torch'} to differentiate this configuration through the "
-                "tensor-op loop")
-        # recompute mode (options={'recompute': steps per chunk} or SNSDE_RECOMPUTE_STEPS): keep states and increments only,
+        samples = opt.samples if opt.sample_grad else 1      # (sampled training: _sdeint_samples)
+        # recompute mode (_recompute_steps: options={'recompute': steps per chunk} or the environment): keep states and increments only,
         # re-run the forward kernel chunk by chunk inside backward (engine.backward_recompute)
         ctx.recompute = 0
         if mode == 1 and method != 'srk' and samples == 1:      # (a sampled node never recomputes: _sdeint_samples routes around it)
-            ctx.recompute = max(int(options.get('recompute', os.environ.get('SNSDE_RECOMPUTE_STEPS', 0)) or 0), 0)
+            ctx.recompute = opt.recompute
             if ctx.recompute >= grid.N:      # one chunk = the whole solve: the saved-activation mode with a second forward on top
                 ctx.recompute = 0            # (and the parent's states / increments kept beside the chunk's: MORE memory, K5 N = 49)
         # mode 2: the generic adjoint prepares its own weights, so the forward takes whatever kernel is fastest
-        call = make(options.get('kernel', 'auto'), mode == 1 and not ctx.recompute)
+        save_act = mode == 1 and not ctx.recompute
+        # the increments are kept only where the backward cannot get them otherwise: the MFMA Euler / Milstein adjoint reads
+        # supplied ones in place and REGENERATES Philox ones (host key) - one (N, B, H) store and load less per step
+        nets = model.noise_option in (14, 15, 18, 19)
+        keep_dw = not (save_act and method in ('euler', 'milstein') and not (nets and method == 'milstein')
+                       and not torch.is_tensor(opt.seed) and opt.param_pass in ('hip', 'split')
+                       and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
+        call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=opt.seed, row_offset=opt.row_offset,
+                                kernel=opt.kernel, save_traj=True, save_dW=keep_dw, save_act=save_act, exact_order=opt.exact_order,
+                                row_out=opt.row_out, dU=dU, global_rows=opt.global_rows, samples=samples, sample_grad=samples > 1,
+                                lean_general=samples > 1 and opt.lean_general)      # (the sampled route's A/B switch)
         ctx.coeffs_dtype = None if coeffs_src is None else coeffs_src.dtype
         if coeffs_src is not None and mode == 1 and getattr(call, 'delta_slots', 1) == 0:
             raise _NoCoeffGradient()      # (before the launch: _sdeint_hip applies the fallback rule)
         ctx.mode, ctx.method = mode, method
-        ctx.param_pass = options.get('param_pass', 'hip')
+        ctx.param_pass = opt.param_pass
         ctx.layout = (layout, numel)
         ys = call.launch()
         ctx.call, ctx.sde, ctx.grid, ctx.times_host = call, sde, grid, times_host
@@ -833,40 +847,47 @@ class _FusedSolve(torch.autograd.Function):
     @staticmethod
     def backward(ctx, grad_ys):
         call, sde, grid = ctx.call, ctx.sde, ctx.grid
-        want_c = ctx.coeffs_dtype is not None and ctx.needs_input_grad[9]      # dL/d coeffs: only where autograd asks for it
-        gcoeffs = None
+        lead = (None,) * _FusedSolve.NO_GRAD_INPUTS
+        want_c = ctx.coeffs_dtype is not None and ctx.needs_input_grad[len(lead)]      # dL/d coeffs: only where autograd asks for it
+        gcoeffs, grad_ys = None, grad_ys.to(torch.float32).contiguous()
         if ctx.mode == 1 and ctx.recompute:
-            g0, flat = engine.backward_recompute(call, grad_ys.to(torch.float32).contiguous(), ctx.recompute)
+            g0, flat = engine.backward_recompute(call, grad_ys, ctx.recompute)
             grads = engine.param_index(sde, ctx.layout[0]).grads_from_flat(flat)
-            return (None,) * 10 + (g0.to(ctx.y0_dtype),) + tuple(grads)
+            return lead + (None, g0.to(ctx.y0_dtype)) + tuple(grads)
         if ctx.mode == 1:     # MFMA adjoint kernel + native weight-gradient pass on the saved activations / deltas
             if ctx.param_pass == 'torch':     # library-GEMM cross-check of the native pass
-                adj, delta = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous(), save_delta=True, adj0_only=False)
+                adj, delta = engine.solve_backward(call, grad_ys, save_delta=True, adj0_only=False)
                 grads = _parameter_gradients_gemm(sde, call, grid, adj, delta, method=ctx.method, want_coeffs=want_c)
                 if want_c:
                     grads, gcoeffs = grads
             else:
                 if ctx.param_pass == 'split':     # the two C calls one after the other (what the fused call must reproduce bit for bit)
-                    adj, delta = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous(), save_delta=True,
-                                                       adj0_only=engine.adj0_suffices(call))
+                    adj, delta = engine.solve_backward(call, grad_ys, save_delta=True, adj0_only=engine.adj0_suffices(call))
                     flat = engine.param_gradients(call, adj, delta)
                 elif want_c:
-                    adj, flat, delta = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(),
-                                                                      adj0_only=engine.adj0_suffices(call), return_delta=True)
+                    adj, flat, delta = engine.backward_with_gradients(call, grad_ys, adj0_only=engine.adj0_suffices(call), return_delta=True)
                 else:
-                    adj, flat = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(),
-                                                               adj0_only=engine.adj0_suffices(call))
+                    adj, flat = engine.backward_with_gradients(call, grad_ys, adj0_only=engine.adj0_suffices(call))
                 grads = engine.param_index(sde, ctx.layout[0]).grads_from_flat(flat)
                 if want_c:      # the native pass over the same delta planes (snsde_coeff_gradients)
                     gcoeffs = engine.coeff_gradients(call, adj, delta)
         else:                 # generic adjoint kernels (any dims; Euler / Milstein / SRK) + batched autograd parameter pass
-            adj = engine.solve_backward(call, grad_ys.to(torch.float32).contiguous())
+            adj = engine.solve_backward(call, grad_ys)
             grads = _parameter_gradients(sde, call, grid, adj, method=ctx.method, want_coeffs=want_c)
             if want_c:
                 grads, gcoeffs = grads
         if gcoeffs is not None and gcoeffs.dtype != ctx.coeffs_dtype:
             gcoeffs = gcoeffs.to(ctx.coeffs_dtype)
-        return (None,) * 9 + (gcoeffs, adj[0].to(ctx.y0_dtype)) + tuple(grads)
+        return lead + (gcoeffs, adj[0].to(ctx.y0_dtype)) + tuple(grads)
+
+
+def _spline_piece(coeffs, idx, frac):
+    """X(t) of n (step, interval) pairs for every row, (n, B, C): coeffs (B, L - 1, 4C) packed (a, b, 2c, 3d), idx (n,) the
+    interval of each time and frac (n, 1, 1) its offset into it.  The operation order is the kernels' (cross-checked bit for bit)."""
+    Cn = coeffs.shape[-1] // 4
+    rows = coeffs[:, idx, :].permute(1, 0, 2)
+    a_, b_, c2, d3 = (rows[..., k * Cn:(k + 1) * Cn] for k in range(4))
+    return a_ + (b_ + (0.5 * c2 + d3 * frac / 3) * frac) * frac
 
 
 @torch.no_grad()
@@ -909,14 +930,10 @@ def _parameter_gradients_gemm(sde, call, grid, adj, delta, method='euler', want_
         yin = torch.cat([tau, Y], dim=-1)
     else:
         yin = Y
+    idx = torch.from_numpy(grid.step_tab[:, 5].copy().view('int32').astype('int64')).to(dev)      # each step's spline interval
+    frac = torch.from_numpy(grid.step_tab[:, 4].copy()).to(dev).view(N, 1, 1)                      # ... and its offset into it
     if io in (2, 4, 6):
-        idx = torch.from_numpy(grid.step_tab[:, 5].copy().view('int32').astype('int64')).to(dev)
-        frac = torch.from_numpy(grid.step_tab[:, 4].copy()).to(dev).view(N, 1, 1)
-        coeffs = call.keep[1]
-        Cn = coeffs.shape[-1] // 4
-        rows = coeffs[:, idx, :].permute(1, 0, 2)
-        a_, b_, c2, d3 = (rows[..., k * Cn:(k + 1) * Cn] for k in range(4))
-        Xraw = a_ + (b_ + (0.5 * c2 + d3 * frac / 3) * frac) * frac                     # (N, B, C)
+        Xraw = _spline_piece(call.keep[1], idx, frac)                                   # (N, B, C)
         yy = torch.baddbmm(P['linear_in.bias'], yin, P['linear_in.weight'].t().expand(N, -1, -1))
         Xt = torch.baddbmm(P['initial_network.bias'], Xraw, P['initial_network.weight'].t().expand(N, -1, -1))
         grads['emb.weight'] = torch.cat([wgrad(d0, yy), wgrad(d0, Xt)], dim=1)
@@ -971,8 +988,7 @@ def _parameter_gradients_gemm(sde, call, grid, adj, delta, method='euler', want_
     if io in (0, 2, 4, 6):
         Cn = coeffs.shape[-1] // 4
         v = torch.matmul(d_x if io != 0 else d0, P['initial_network.weight'])                 # (N, B, C)
-        idx = torch.from_numpy(grid.step_tab[:, 5].copy().view('int32').astype('int64')).to(dev)
-        r = torch.from_numpy(grid.step_tab[:, 4].copy()).to(dev)
+        r = frac.view(N)
         phi = torch.stack([torch.ones_like(r), r, 0.5 * r * r, r * r * r / 3], dim=-1)          # (N, 4)
         contrib = (phi.view(N, 1, 4, 1) * v.unsqueeze(2)).reshape(N, B, 4 * Cn)
         gc.index_add_(1, idx, contrib.permute(1, 0, 2).contiguous())
@@ -1013,20 +1029,12 @@ def _parameter_gradients(sde, call, grid, adj, max_rows=1 << 19, method='euler',
             tau = torch.cat([col.sin(), col.cos()], dim=-1)
             Xraw = None
             if uses_x:
-                rows = coeffs[:, idx[lo:hi], :].permute(1, 0, 2)                      # (n, B, 4C)
-                fr = frac[lo:hi].view(n, 1, 1)
-                a_, b_, c2, d3 = (rows[..., k * Cn:(k + 1) * Cn] for k in range(4))
-                Xraw = (a_ + (b_ + (0.5 * c2 + d3 * fr / 3) * fr) * fr).reshape(n * B, Cn)
+                Xraw = _spline_piece(coeffs, idx[lo:hi], frac[lo:hi].view(n, 1, 1)).reshape(n * B, Cn)
+            f = None if method == 'srk' else modules.drift_rows(P, io, tau, Y, Xraw)
             if method == 'srk':
                 surrogate = (A * _srk_rows(P, io, no, grid, lo, hi, B, Y, DW, call.dU_out[lo:hi].reshape(n * B, H), coeffs,
                                            hcol)).sum()
-                gs = torch.autograd.grad(surrogate, params, allow_unused=True)
-                for acc, gpart in zip(total, gs):
-                    if gpart is not None:
-                        acc.add_(gpart)
-                continue
-            f = modules.drift_rows(P, io, tau, Y, Xraw)
-            if method == 'milstein' and no in (14, 15, 18, 19):
+            elif method == 'milstein' and no in (14, 15, 18, 19):
                 # diffusion net: torchsde's Milstein term is the VJP of g with cotangent g (dW^2 - h) (dense dg/dy)
                 Yg = Y.detach().requires_grad_(True)
                 g = modules.diffusion_rows(P, no, col, tau, Yg)
@@ -1068,10 +1076,7 @@ def _srk_rows(P, io, no, grid, lo, hi, B, Y, I_k, I_k0, coeffs, hcol):
         Xraw = None
         if uses_x:
             idx = tab[:, slot, 4].contiguous().view(torch.int32).to(torch.int64)
-            fr = tab[:, slot, 3].to(Y.dtype).view(n, 1, 1)
-            rows = coeffs[:, idx, :].permute(1, 0, 2)
-            a_, b_, c2, d3 = (rows[..., k * Cn:(k + 1) * Cn] for k in range(4))
-            Xraw = (a_ + (b_ + (0.5 * c2 + d3 * fr / 3) * fr) * fr).reshape(n * B, Cn)
+            Xraw = _spline_piece(coeffs, idx, tab[:, slot, 3].to(Y.dtype).view(n, 1, 1)).reshape(n * B, Cn)
         return t, tau, Xraw
 
     slots_f = (0, 3, 2, 0)      # C0 = 0, 1, 1/2, 0  -> stage-table slots (0, 1/4, 1/2, 1)
@@ -1173,30 +1178,10 @@ def _sdeint_torch(sde, y0, ts, bm, method, dt, options, names):
     ts_host = _HostTimes.get(ts)
     grid = engine.StepGrid(ts_host, dt, np.array([0.0, 1.0], dtype=np.float32), None)
     t0s = torch.from_numpy(grid.t0).to(y0.device)
-    t1s = torch.from_numpy(grid.t1).to(y0.device)
     w = torch.from_numpy(grid.out_w).to(device=y0.device, dtype=y0.dtype)
-    hs = (t1s - t0s).to(y0.dtype)
-    # every increment of the solve up front: (N, B, H) I_k (and I_k0 for SRK)
-    if bm is None:
-        gen = torch.Generator(device=y0.device)
-        seed = options.get('seed')
-        gen.manual_seed(int(seed) if seed is not None and not torch.is_tensor(seed) else _fresh_seed())
-        hcol = hs.reshape(-1, *([1] * y0.dim()))
-        wshape = (grid.N, y0.shape[0], 1) if noise_type == 'scalar' else (grid.N,) + tuple(y0.shape)
-        dW_all = torch.randn(wshape, dtype=y0.dtype, device=y0.device, generator=gen) * hcol.sqrt()
-        dU_all = None
-        if method == 'srk':      # I_k0 = h (I_k / 2 + sqrt(h / 12) xi): the space-time Levy integral
-            xi = torch.randn((grid.N,) + tuple(y0.shape), dtype=y0.dtype, device=y0.device, generator=gen)
-            dU_all = hcol * (0.5 * dW_all + (hcol / 12).sqrt() * xi)
-    elif method == 'srk':
-        pairs = [bm(t0s[n], t1s[n], return_U=True) for n in range(grid.N)]
-        dW_all = torch.stack([p[0].to(device=y0.device, dtype=y0.dtype) for p in pairs])
-        dU_all = torch.stack([p[1].to(device=y0.device, dtype=y0.dtype) for p in pairs])
-    else:
-        dW_all = torch.stack([bm(t0s[n], t1s[n]).to(device=y0.device, dtype=y0.dtype) for n in range(grid.N)])
-        dU_all = None
-    needs_grad = torch.is_grad_enabled() and (y0.requires_grad or _coeffs_need_grad(sde) or any(
-        p.requires_grad for p in getattr(sde, 'parameters', lambda: [])()))
+    hs = (torch.from_numpy(grid.t1).to(y0.device) - t0s).to(y0.dtype)
+    dW_all, dU_all = _draw_increments(bm, grid, y0, method, seed=options.get('seed'), scalar=noise_type == 'scalar')
+    needs_grad = _differentiated(sde, y0)
     if (y0.is_cuda and not needs_grad and method in ('euler', 'srk') and options.get('graph', True)
             and not torch.cuda.is_current_stream_capturing()):
         ys = _graphed_steps(f, g, y0, grid, t0s, hs, w, dW_all, dU_all, method)
@@ -1217,8 +1202,8 @@ def _sdeint_torch(sde, y0, ts, bm, method, dt, options, names):
             v = I * I - h
             # g * dg/dy * v for diagonal noise; when differentiating, the cotangent keeps its dependence on y so that
             # autograd through this loop is the exact gradient of the discrete scheme (what the fused adjoint computes)
-            diff = torch.is_grad_enabled() and (y.requires_grad or _coeffs_need_grad(sde) or any(
-                p.requires_grad for p in getattr(sde, 'parameters', lambda: [])()))
+            # (the state, not y0 alone: it also carries a graph from a tensor that f / g close over without declaring a parameter)
+            diff = needs_grad or (torch.is_grad_enabled() and y.requires_grad)
             with torch.enable_grad():
                 yy = y if y.requires_grad else y.detach().requires_grad_(True)
                 gv = g(t0, yy)
