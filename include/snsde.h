@@ -89,14 +89,29 @@ enum {
      * the hidden activations.  The state, accumulators, biases, tanh, the diffusion, Milstein's term, the increments, X(t), the
      * update and the output interpolation stay f32.  SNSDE_ERR_UNSUPPORTED (never an f32 kernel instead) for any other
      * configuration, with training outputs (act_save, stage_save, traj, dW_out, dU_out), and from every backward entry point
-     * (snsde_backward_supported returns 0). */
+     * (snsde_backward_supported returns 0) - unless SNSDE_FLAG_BF16_GRAD opts in to training. */
     SNSDE_FLAG_BF16_OPERANDS = 16,
     /* Run the lean 4-row-tile kernel's general instantiation even where a compile-time specialised one covers the launch
      * (snsde_lean_variant).  Same results bit for bit; exists for A/B measurements and the bit-identity test. */
     SNSDE_FLAG_LEAN_GENERAL = 32,
     /* Opt-in: a solve of `samples` = S > 1 paths per input row may be differentiated (snsde_solve.samples, last paragraph).  No
      * effect when samples <= 1.  Together with SNSDE_FLAG_BF16_OPERANDS (an inference-only forward): SNSDE_ERR_UNSUPPORTED. */
-    SNSDE_FLAG_SAMPLE_GRAD = 64
+    SNSDE_FLAG_SAMPLE_GRAD = 64,
+    /* Opt-in: training through the bf16-operand forward.  Meaningful only together with SNSDE_FLAG_BF16_OPERANDS (alone: no
+     * effect).  The forward then accepts act_save, traj and dW_out on SNSDE_PATH_LEAN_BF16 (training-mode instantiations of the same
+     * kernel: the states are the inference kernel's bit for bit, the planes hold the f32 values in front of the operand rounding),
+     * and the backward entry points return the gradient of the function that forward computed, with the rounding q treated as the
+     * identity in the backward pass (straight-through), in f32 arithmetic: for a layer z = q(W) q(x) + b
+     *     dL/dx = q(W)^T delta,   dL/dW = delta (x) q(x),   dL/db = sum delta
+     * - the adjoint multiplies the rounded weights (the folded products emb . linear_in of input_option 2 / 4 / 6 rounded after
+     * folding, as in the forward), the weight-gradient pass rounds its X operands (act_save slots, traj, the control-path columns and
+     * sin t, cos t after evaluation) while staging them; the gradient of a folded product reaches emb, linear_in and
+     * initial_network through the f32 fold.  Masks, tanh', the diffusion, Milstein's term and the Philox regeneration have no matrix
+     * operand and are the f32 path's.  snsde_backward_supported == 1 where the forward plan is the bf16 lean kernel (Euler /
+     * Milstein, elementwise diffusions, H = 64 / 128, the reference's fields, kl_column1 == 0) and no noise_table is supplied;
+     * 0 (never an f32 kernel, never mode 2) for everything else, samples > 1 included.  stage_save / dU_out stay refused, and
+     * snsde_coeff_gradients returns SNSDE_ERR_UNSUPPORTED under bf16 operands with or without this flag. */
+    SNSDE_FLAG_BF16_GRAD = 128
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -319,7 +334,8 @@ SNSDE_API int    snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int
                                                           /* adjoint of this solve accumulates the weight gradients itself (Euler /  */
                                                           /* SRK at H = 64 with a diffusion net: per-tile sums in the backward       */
                                                           /* workspace), delta_save is not written and may be NULL                   */
-SNSDE_API int    snsde_backward_supported(const snsde_solve* s);    /* 1 / 2 / 0, see above                          */
+SNSDE_API int    snsde_backward_supported(const snsde_solve* s);    /* 1 / 2 / 0, see above; bf16 operands: 0, or 1 under */
+                                                                    /* SNSDE_FLAG_BF16_GRAD where it covers the solve     */
 SNSDE_API size_t snsde_backward_workspace_bytes(const snsde_backward* b);
 /* INVARIANT between forward and backward (mode 1): `fwd.workspace` is untouched AND `fwd.params` holds the values the forward ran
  * with.  The adjoint re-packs its transposed weights from the CURRENT params, but takes the folded first-layer product
@@ -365,7 +381,8 @@ SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad
  * (row_offset / global_rows) reproduce the rows of the whole bit for bit.
  * input_option 1 / 3 / 5 (the drift does not read X): grad_coeffs is zero-filled, SNSDE_OK.  SNSDE_ERR_UNSUPPORTED: a solve
  * whose adjoint leaves no delta planes (snsde_save_layout: delta_slots == 0, the H = 64 wave-pair adjoints), mode 2 or 0,
- * delta_save == NULL, fwd.samples > 1 without SNSDE_FLAG_SAMPLE_GRAD, fwd.kl_column1 != 0, the field variants and a supplied noise_table.  SNSDE_ERR_NULL /
+ * delta_save == NULL, fwd.samples > 1 without SNSDE_FLAG_SAMPLE_GRAD, fwd.kl_column1 != 0, the field variants, a supplied noise_table and
+ * SNSDE_FLAG_BF16_OPERANDS (also under SNSDE_FLAG_BF16_GRAD: the rounded folded control-path weights are not formed here).  SNSDE_ERR_NULL /
  * SNSDE_ERR_WORKSPACE as elsewhere; every check happens before the first launch.  The dependence of y0 on coeffs through a fused
  * z0_weight is not part of this gradient (the host materialises y0 with tensor ops when coeffs require a gradient).
  * fwd.samples = S > 1 under SNSDE_FLAG_SAMPLE_GRAD: delta_save holds `batch` paths and grad_coeffs is (batch / S, L-1, 4C),

@@ -20,6 +20,7 @@ FLAG_TWO_TILE = 8
 FLAG_BF16_OPERANDS = 16     # inference only: bf16 MFMA operands on the lean 4-row-tile kernel (include/snsde.h)
 FLAG_LEAN_GENERAL = 32      # the lean kernel's general instantiation where a specialised one covers the launch (A/B, bit-identity test)
 FLAG_SAMPLE_GRAD = 64       # opt-in: a solve of samples = S > 1 paths per input row may be differentiated (include/snsde.h)
+FLAG_BF16_GRAD = 128        # opt-in: training through the bf16-operand forward (straight-through gradient; with FLAG_BF16_OPERANDS only)
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 BWD_ADJ0_ONLY = 1
 PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4', 'lean-bf16')

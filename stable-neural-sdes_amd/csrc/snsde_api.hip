@@ -152,6 +152,10 @@ static bool samples_ok(const snsde_solve* s) {
 }
 // SNSDE_FLAG_SAMPLE_GRAD (snsde.h): the opt-in to training through the sample paths; nothing without samples > 1
 static bool sample_grad(const snsde_solve* s) { return snsde_samples(s) > 1 && (s->flags & SNSDE_FLAG_SAMPLE_GRAD) != 0; }
+// SNSDE_FLAG_BF16_GRAD (snsde.h): the opt-in to training through the bf16-operand forward; nothing without bf16 operands
+static bool bf16_grad(const snsde_solve* s) {
+    return (s->flags & SNSDE_FLAG_BF16_OPERANDS) != 0 && (s->flags & SNSDE_FLAG_BF16_GRAD) != 0;
+}
 static bool samples_training(const snsde_solve* s) {
     return snsde_samples(s) > 1 && (s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out);
 }
@@ -228,7 +232,18 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
         r.mode = 1;
         return r;
     }
-    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return r;     // an inference-only forward: no adjoint of any kind
+    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) {
+        // an inference-only forward: no adjoint of any kind - unless SNSDE_FLAG_BF16_GRAD opts in.  Then mode 1 exactly where the
+        // forward plan is the bf16 lean kernel and the adjoint make_rev_plan gives that lean forward is the general one, which leaves
+        // delta planes (its pack rounds the transposed weights, the weight-gradient pass its X operands); a supplied noise_table
+        // and everything the forward plan refuses (SRK, nets, other H, field variants, kl_column1) is no plan: never an f32 kernel,
+        // never mode 2
+        if (bf16_grad(s) && r.fp.ok && r.fp.kernel == snsde_mfma::FwdKernel::lean_bf16 && r.rp.ok &&
+            r.rp.kernel == snsde_mfma::RevKernel::general && !s->noise_table && s->kl_column1 == 0 && !snsde_solve_variant(s) &&
+            k != SNSDE_KERNEL_GENERIC && k != SNSDE_KERNEL_MFMA_M16)
+            r.mode = 1;
+        return r;
+    }
     if (r.fp.shard_refused) return r;                      // (no forward kernel either: route_forward)
     if (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) return r;     // no forward kernel either (validate_solve)
     const bool variant = snsde_solve_variant(s);      // tutorial-style fields: the 4-row-tile MFMA adjoint or nothing
@@ -564,7 +579,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
-    if (b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
+    if ((b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) && !bf16_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
     if (snsde_samples(&b->fwd) > 1 && !sample_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (sample paths: inference only without the opt-in)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
@@ -650,7 +665,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
 // The checks of snsde_coeff_gradients that need no pointer: the configurations it covers (mode 1 with delta planes, the reference's
 // Diffusion_model fields, no accumulator column; sample paths where route_backward plans them).  *delta_slots: the planes per pass of delta_save
 static int route_coeff_gradients(const snsde_solve* s, int32_t* delta_slots) {
-    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;
+    if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;      // (also under SNSDE_FLAG_BF16_GRAD: M is not rounded here)
     if (s->kl_column1 != 0 || snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
     SnsdeNet net;
     int rc = snsde_build_net(s->model, s->n_steps, &net);

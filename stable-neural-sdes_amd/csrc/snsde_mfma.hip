@@ -40,8 +40,10 @@ __device__ __forceinline__ int packed_index(int flavor, int KU, int feat, int k)
 
 // fsrc: where the folded products live (fold_tmp offsets): the workspace being packed into, or - backward pack after a folded forward -
 // the FORWARD's workspace, whose prepare launch already formed emb[:, 0:H] . linear_in (no second fold launch in the backward)
+// q: the backward pack after a bf16-operand forward (SNSDE_FLAG_BF16_GRAD) - every weight goes through the forward's operand rounding
+// (lean_bf16x4: nearest even), the folded product after folding, and stays an f32 value: the adjoint multiplies what the forward did
 __device__ __forceinline__ void pack_layer(const float* __restrict__ params, float* __restrict__ ws, const float* __restrict__ fsrc,
-                                           const MfmaPackJob& job, const MfmaLayerPack& L, int bx, int nbx, bool direct) {
+                                           const MfmaPackJob& job, const MfmaLayerPack& L, int bx, int nbx, bool direct, bool q = false) {
     const int per_wave = job.TPW * L.KU * 256;
     const int total = job.NW * per_wave;
     const bool skip = direct && L.fold && !L.transpose;
@@ -65,13 +67,14 @@ __device__ __forceinline__ void pack_layer(const float* __restrict__ params, flo
         } else if (k >= L.hole0 && k < L.hole1) {
             continue;                                   // columns another piece owns (the redirected time columns)
         }
+        if (q) v = (float)(__bf16)v;
         ws[L.dst + i] = v;
     }
     if (L.t_on && !skip && !L.transpose) {              // leading time columns -> the [X(t) | sin t, cos t] block
         for (int i = bx * blockDim.x + threadIdx.x; i < L.N * L.tshift; i += nbx * blockDim.x) {
             const int feat = i / L.tshift, j = i - feat * L.tshift;
-            ws[L.t_dst + packed_index(job.flavor, L.t_KU, feat, L.t_col0 + j)] =
-                L.fold ? fsrc[L.fold_tmp + feat * L.K + j] : params[L.src_w + feat * L.K + j];
+            const float v = L.fold ? fsrc[L.fold_tmp + feat * L.K + j] : params[L.src_w + feat * L.K + j];
+            ws[L.t_dst + packed_index(job.flavor, L.t_KU, feat, L.t_col0 + j)] = q ? (float)(__bf16)v : v;
         }
     }
     // bias table [row][H]
@@ -91,14 +94,14 @@ __device__ __forceinline__ void pack_layer(const float* __restrict__ params, flo
 }
 
 // kernarg offsets of the by-value job structs (their `layer` arrays are indexed by blockIdx.y: snsde_kernarg_element)
-constexpr size_t PACK_JOB_OFF = 24;      // snsde_mfma_pack_kernel(params, ws, fold_src, job)
+constexpr size_t PACK_JOB_OFF = 24;      // snsde_mfma_pack_kernel(params, ws, fold_src, job, round_bf16)
 constexpr size_t PREP_JOB_OFF = (16 + sizeof(FoldJob) + alignof(MfmaPackJob) - 1) / alignof(MfmaPackJob) * alignof(MfmaPackJob);
 static_assert(alignof(FoldJob) == 8 && alignof(MfmaPackJob) == 4, "kernarg layout of snsde_prepare_kernel");
 
 __global__ void snsde_mfma_pack_kernel(const float* __restrict__ params, float* __restrict__ ws, const float* __restrict__ fold_src,
-                                       MfmaPackJob job) {
+                                       MfmaPackJob job, int round_bf16) {
     const MfmaLayerPack L = snsde_kernarg_element<MfmaLayerPack>(PACK_JOB_OFF + offsetof(MfmaPackJob, layer), blockIdx.y);
-    pack_layer(params, ws, fold_src ? fold_src : ws, job, L, blockIdx.x, gridDim.x, false);
+    pack_layer(params, ws, fold_src ? fold_src : ws, job, L, blockIdx.x, gridDim.x, false, round_bf16 != 0);
 }
 
 // position of weight (feature, k) inside a layer's packed fragment block (inverse of the pack loop's index map)
@@ -468,8 +471,10 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
                                       ? FwdKernel::lean_two_tile_h256 : FwdKernel::lean_streamed_h256;
     else p.kernel = two_tile && H == 128 && (s->flags & SNSDE_FLAG_TWO_TILE) && s->kl_column1 == 0 && m4t_instantiated(nhid, kuxt, save)
                         ? FwdKernel::lean_two_tile_h128 : FwdKernel::lean;
-    if (bf16) {      // inference on the reference's Diffusion_model fields, H = 64 / 128 (snsde_m4b_kernel.h)
-        const bool train = save || s->stage_save || s->dU_out;
+    if (bf16) {      // the reference's Diffusion_model fields, H = 64 / 128 (snsde_m4b_kernel.h); inference only, unless
+        // SNSDE_FLAG_BF16_GRAD opts in to the training planes the bf16 adjoint route reads (act_save, traj, dW_out; no supplied table)
+        const bool grad = (s->flags & SNSDE_FLAG_BF16_GRAD) != 0;
+        const bool train = (save && !(grad && !s->noise_table)) || s->stage_save || s->dU_out;
         if (p.kernel != FwdKernel::lean || !(H == 64 || H == 128) || variant || train || s->kl_column1 != 0 || srk) return p;
         p.kernel = FwdKernel::lean_bf16;
     }
@@ -768,7 +773,9 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
         if (fold_src && job.layer[i].fold) job.layer[i].fold_tmp = fwd_fold_tmp;
     }
     job.n_layers = p.n_layers; job.flavor = p.FL; job.TPW = 1; job.NW = p.NW; job.bias_off = 0; job.H = p.H;
-    hipLaunchKernelGGL(snsde_mfma_pack_kernel, dim3(16, p.n_layers), dim3(256), 0, stream, s->params, ws, fold_src, job);
+    // (mode 1 after a bf16-operand forward = SNSDE_FLAG_BF16_GRAD: the adjoint multiplies the ROUNDED weights, straight-through)
+    const int round_bf16 = fp.kernel == FwdKernel::lean_bf16 ? 1 : 0;
+    hipLaunchKernelGGL(snsde_mfma_pack_kernel, dim3(16, p.n_layers), dim3(256), 0, stream, s->params, ws, fold_src, job, round_bf16);
     RevArgs a{};
     a.params = s->params; a.ws = ws;
     a.gt = s->noise_table ? s->noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s->workspace) + fp.gt_off : nullptr);

@@ -128,6 +128,8 @@ __device__ __forceinline__ float4 xaux_raw(const XInfo& a, const XStep& x, int b
     return r;
 }
 __device__ __forceinline__ float xaux_eval(const float4& r, float frac) { return snsde_spline_eval(r.x, r.y, r.z, r.w, frac); }
+// an X operand as the bf16-operand forward multiplied it (snsde_m4_kernel.h: the (OpT) stores), kept as an f32 value
+__device__ __forceinline__ float wgrad_q(float v) { return (float)(__bf16)v; }
 
 // ---- epilogue descriptors (declared here: the reduce launch also carries the noise MLP's hidden-gradient blocks) ----
 struct GJob {     // C (M x N) = A . B^T (trans 0: A (M, K), B (N, K)) or A^T . B (trans 1: A (K, M), B (K, N); B null = ones)
@@ -203,7 +205,10 @@ __device__ __forceinline__ void dsum_block(const DArgs& a, int blk, int nblk, fl
 // (8 / G strips) x (G groups of NKT / G column sub-tiles) and every wave issues MFMAs (H = 64: G = 2, H <= 32: G = 4)
 // XFLY: the tile's X operand is the control-path columns, evaluated while staging (x_kind 2); a body of its own so that its extra
 // registers (step values, sixteen coefficient loads per row) do not push the plain tiles' staging into scratch
-template <int NKT, bool BIAS, int G, bool XFLY>
+// XQ: the forward ran with bf16 MFMA operands (SNSDE_FLAG_BF16_GRAD): the forward operands among the X operands (x_kind 0 / 1 / 2)
+// are rounded to bf16, nearest even, while they are staged - dL/dW = delta (x) q(x).  A compile-time switch of the KERNEL
+// (snsde_wgrad_kernel / snsde_wgrad_bf16_kernel): the fp32 training step keeps a kernel without the rounding or a test for it
+template <int NKT, bool BIAS, int G, bool XFLY, bool XQ>
 __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const XInfo& xi, float* lds) {
     static_assert(NKT % G == 0 && NKT / G >= 1, "column groups must divide the sub-tiles");
     constexpr int NKTG = NKT / G;
@@ -246,6 +251,7 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
     // (tid & 15) + 16 i, i < NKT - so the spline evaluations are spread over all 512 threads (NKT values = 4 NKT coefficient loads
     // each, all independent: the pass's step values sit in registers and are re-read only when the row enters another pass)
     const int xr0 = tid >> 4, xc0 = tid & 15;
+    [[maybe_unused]] const bool xq = XQ && t.x_kind <= 2;        // uniform per tile
     int xrow_r = r_begin + xr0, xrow_b = 0, xrow_n = 0;
     [[maybe_unused]] float4 xv[NKT];
     [[maybe_unused]] float xfr = 0.0f;             // the interval fraction of the staged row (xs moves on to the next chunk's pass)
@@ -305,14 +311,21 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
         for (int p = 0; p < PR; ++p) {
             const int rr = (tid >> 5) + 16 * p;
             *reinterpret_cast<float4*>(Dl + rr * LD + c4) = dreg[p];
-            if constexpr (!XFLY) *reinterpret_cast<float4*>(Xl + rr * LD + c4) = xreg[p];
+            if constexpr (!XFLY) {
+                float4 xs4 = xreg[p];
+                if constexpr (XQ) if (xq) xs4 = make_float4(wgrad_q(xs4.x), wgrad_q(xs4.y), wgrad_q(xs4.z), wgrad_q(xs4.w));
+                *reinterpret_cast<float4*>(Xl + rr * LD + c4) = xs4;
+            }
             if constexpr (BIAS) {
                 bsum.x += dreg[p].x; bsum.y += dreg[p].y; bsum.z += dreg[p].z; bsum.w += dreg[p].w;
             }
         }
         if constexpr (XFLY) {
 #pragma unroll
-            for (int i = 0; i < NKT; ++i) Xl[xr0 * LD + xc0 + 16 * i] = xaux_eval(xv[i], xfr);
+            for (int i = 0; i < NKT; ++i) {
+                const float v = xaux_eval(xv[i], xfr);
+                Xl[xr0 * LD + xc0 + 16 * i] = XQ ? wgrad_q(v) : v;      // (rounded after evaluation, as the forward's store of X(t))
+            }
         }
     };
 
@@ -387,15 +400,15 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
     }
 }
 
-template <int NKT, bool BIAS, bool XFLY>
+template <int NKT, bool BIAS, bool XFLY, bool XQ>
 __device__ __forceinline__ void wgrad_groups(const WArgs& a, const WTile& t, const XInfo& xi, float* lds, int g) {
-    if constexpr (NKT >= 4) { if (g == 4) { wgrad_body<NKT, BIAS, 4, XFLY>(a, t, xi, lds); return; } }
-    if constexpr (NKT >= 2) { if (g >= 2) { wgrad_body<NKT, BIAS, 2, XFLY>(a, t, xi, lds); return; } }
-    wgrad_body<NKT, BIAS, 1, XFLY>(a, t, xi, lds);
+    if constexpr (NKT >= 4) { if (g == 4) { wgrad_body<NKT, BIAS, 4, XFLY, XQ>(a, t, xi, lds); return; } }
+    if constexpr (NKT >= 2) { if (g >= 2) { wgrad_body<NKT, BIAS, 2, XFLY, XQ>(a, t, xi, lds); return; } }
+    wgrad_body<NKT, BIAS, 1, XFLY, XQ>(a, t, xi, lds);
 }
 
-__global__ void __launch_bounds__(NT, 4) snsde_wgrad_kernel(WArgs a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];   // [2 buffers][D | X][RC][LD]
+template <bool XQ>
+__device__ __forceinline__ void wgrad_main(const WArgs& a, float* lds) {
     // dispatch order = blockIdx.y ascending: the latency-bound riders go FIRST (they would otherwise start when the GEMM workgroups
     // drain and form a 25 - 50 us tail): y = 0 the diffusion-side reductions (when present), then the tiles in REVERSE plan order
     // (the control-path tiles, whose staging evaluates spline pieces, were planned last)
@@ -411,28 +424,39 @@ __global__ void __launch_bounds__(NT, 4) snsde_wgrad_kernel(WArgs a) {
     if (t.x_kind == 2) {     // control-path columns built while staging; the descriptor through scalar loads (see snsde_kernarg_element)
         const XInfo xi = snsde_kernarg_element<XInfo>(offsetof(WArgs, x), 0);
         switch (t.cls) {
-            case 0: wgrad_groups<8, true, true>(a, t, xi, lds, g); break;
-            case 1: wgrad_groups<8, false, true>(a, t, xi, lds, g); break;
-            case 2: wgrad_groups<4, true, true>(a, t, xi, lds, g); break;
-            case 3: wgrad_groups<4, false, true>(a, t, xi, lds, g); break;
-            case 4: wgrad_groups<2, true, true>(a, t, xi, lds, g); break;
-            case 5: wgrad_groups<2, false, true>(a, t, xi, lds, g); break;
-            case 6: wgrad_groups<1, true, true>(a, t, xi, lds, g); break;
-            default: wgrad_groups<1, false, true>(a, t, xi, lds, g); break;
+            case 0: wgrad_groups<8, true, true, XQ>(a, t, xi, lds, g); break;
+            case 1: wgrad_groups<8, false, true, XQ>(a, t, xi, lds, g); break;
+            case 2: wgrad_groups<4, true, true, XQ>(a, t, xi, lds, g); break;
+            case 3: wgrad_groups<4, false, true, XQ>(a, t, xi, lds, g); break;
+            case 4: wgrad_groups<2, true, true, XQ>(a, t, xi, lds, g); break;
+            case 5: wgrad_groups<2, false, true, XQ>(a, t, xi, lds, g); break;
+            case 6: wgrad_groups<1, true, true, XQ>(a, t, xi, lds, g); break;
+            default: wgrad_groups<1, false, true, XQ>(a, t, xi, lds, g); break;
         }
         return;
     }
     const XInfo xi{};
     switch (t.cls) {     // uniform per workgroup
-        case 0: wgrad_groups<8, true, false>(a, t, xi, lds, g); break;
-        case 1: wgrad_groups<8, false, false>(a, t, xi, lds, g); break;
-        case 2: wgrad_groups<4, true, false>(a, t, xi, lds, g); break;
-        case 3: wgrad_groups<4, false, false>(a, t, xi, lds, g); break;
-        case 4: wgrad_groups<2, true, false>(a, t, xi, lds, g); break;
-        case 5: wgrad_groups<2, false, false>(a, t, xi, lds, g); break;
-        case 6: wgrad_groups<1, true, false>(a, t, xi, lds, g); break;
-        default: wgrad_groups<1, false, false>(a, t, xi, lds, g); break;
+        case 0: wgrad_groups<8, true, false, XQ>(a, t, xi, lds, g); break;
+        case 1: wgrad_groups<8, false, false, XQ>(a, t, xi, lds, g); break;
+        case 2: wgrad_groups<4, true, false, XQ>(a, t, xi, lds, g); break;
+        case 3: wgrad_groups<4, false, false, XQ>(a, t, xi, lds, g); break;
+        case 4: wgrad_groups<2, true, false, XQ>(a, t, xi, lds, g); break;
+        case 5: wgrad_groups<2, false, false, XQ>(a, t, xi, lds, g); break;
+        case 6: wgrad_groups<1, true, false, XQ>(a, t, xi, lds, g); break;
+        default: wgrad_groups<1, false, false, XQ>(a, t, xi, lds, g); break;
     }
+}
+
+__global__ void __launch_bounds__(NT, 4) snsde_wgrad_kernel(WArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];   // [2 buffers][D | X][RC][LD]
+    wgrad_main<false>(a, lds);
+}
+
+// ... after a bf16-operand forward (SNSDE_FLAG_BF16_GRAD): the same tiles with the forward operands rounded while staged (XQ)
+__global__ void __launch_bounds__(NT, 4) snsde_wgrad_bf16_kernel(WArgs a) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    wgrad_main<true>(a, lds);
 }
 
 // noise_option 16/17, s_n = relu(W2 relu(W1 tau_n + b1) + b2):  a1, dz2 = ds * [s_n > 0], dz1 = [a1 > 0] W2^T dz2.
@@ -898,6 +922,7 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     a.NSAVE = wp->nact + (smooth ? s.model.num_hidden_layers + (snsde_noise_net_layers(no) == 2 ? (srk ? 2 : 1) : 0) : 0);      // (SRK: + the fourth evaluation's)
     a.adj = b->adj;
     a.R = wp->n_pass * s.batch; a.ntiles = wp->ntiles; a.NP = wp->NP;
+    const bool xq = fp.kernel == snsde_mfma::FwdKernel::lean_bf16;      // (mode 1 after a bf16-operand forward: SNSDE_FLAG_BF16_GRAD)
     for (int i = 0; i < wp->ntiles; ++i) a.tile[i] = wp->tile[i];
     a.x = XInfo{s.coeffs, pass_tab, s.batch, C, s.knots - 1, wp->t_col0, wp->xt, wp->x_col0, wp->x_cols,
                 s.model.time_feature == SNSDE_TIME_RAW ? 1 : 0, wp->n_col0, snsde_samples(&s)};
@@ -911,8 +936,9 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     aa.tau_stride = srk ? SNSDE_SRK_STRIDE : SNSDE_STEP_STRIDE;
     const bool two = (no == 16 || no == 17);
     const size_t lds_bytes = (size_t)2 * 2 * RC * LD * sizeof(float);
-    static SnsdeLdsAttr lds_attr;
-    if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_wgrad_kernel), lds_bytes, lds_attr)) return rc;
+    static SnsdeLdsAttr lds_attr[2];      // per instantiation
+    if (const int rc = snsde_lds_attr(xq ? reinterpret_cast<const void*>(snsde_wgrad_bf16_kernel) : reinterpret_cast<const void*>(snsde_wgrad_kernel),
+                                      lds_bytes, lds_attr[xq ? 1 : 0])) return rc;
     a.dsum_blocks = 0;
     if (wp->has_dth) {
         if ((wp->tnoise && !gt) || !b->workspace || rp.dth_off == 0) return SNSDE_ERR_UNSUPPORTED;
@@ -928,7 +954,9 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
         const int want = a.dsum_blocks < 64 ? a.dsum_blocks : 64;
         if (gx < want) gx = want;
     }
-    hipLaunchKernelGGL(snsde_wgrad_kernel, dim3(gx, wp->ntiles + (a.dsum_blocks > 0 ? 1 : 0)), dim3(NT), lds_bytes, stream, a);
+    const dim3 wgrid(gx, wp->ntiles + (a.dsum_blocks > 0 ? 1 : 0));
+    if (xq) hipLaunchKernelGGL(snsde_wgrad_bf16_kernel, wgrid, dim3(NT), lds_bytes, stream, a);
+    else hipLaunchKernelGGL(snsde_wgrad_kernel, wgrid, dim3(NT), lds_bytes, stream, a);
     NHArgs nh{};
     const bool mlp = (no == 12 || no == 13 || no == 16 || no == 17) && !s.noise_table;    // (a supplied table: noise_t takes no part)
     if (two && mlp) {

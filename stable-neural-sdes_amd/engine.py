@@ -151,11 +151,21 @@ _PAD_CACHE = {}
 PRECISIONS = ('fp32', 'bf16')
 
 
-def precision_flags(precision):
-    """SNSDE_FLAG_* bits of an operand precision ('fp32': none; 'bf16': SNSDE_FLAG_BF16_OPERANDS)."""
+def precision_flags(precision, bf16_grad=False):
+    """SNSDE_FLAG_* bits of an operand precision ('fp32': none; 'bf16': SNSDE_FLAG_BF16_OPERANDS, with bf16_grad also
+    SNSDE_FLAG_BF16_GRAD - the flag means nothing without bf16 operands)."""
     if precision not in PRECISIONS:
         raise ValueError(f"precision must be one of {PRECISIONS}, got {precision!r}")
-    return _lib.FLAG_BF16_OPERANDS if precision == 'bf16' else 0
+    if precision != 'bf16':
+        return 0
+    return _lib.FLAG_BF16_OPERANDS | (_lib.FLAG_BF16_GRAD if bf16_grad else 0)
+
+
+def check_bf16_grad(bf16_grad):
+    """The `bf16_grad` option (training through the bf16-operand forward, SNSDE_FLAG_BF16_GRAD): a bool, ValueError otherwise."""
+    if not isinstance(bf16_grad, bool):
+        raise ValueError(f"bf16_grad must be a bool (differentiate a precision='bf16' solve), got {bf16_grad!r}")
+    return bf16_grad
 
 
 def resolve_global_rows(global_rows, batch, row_offset=0):
@@ -192,19 +202,20 @@ def check_sample_grad(sample_grad):
 
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
-                 row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False):
+                 row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
     at does not map paths to input rows.  sample_grad: SNSDE_FLAG_SAMPLE_GRAD; training: the solve writes its training planes
-    (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers)."""
+    (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers; a bf16 solve under bf16_grad
+    only: SNSDE_FLAG_BF16_GRAD)."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
     s.row_offset, s.global_rows, s.samples = int(row_offset), int(global_rows), int(samples)
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
-    s.flags = precision_flags(precision) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
+    s.flags = precision_flags(precision, bf16_grad) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
     s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
@@ -520,7 +531,7 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0, samples=0, sample_grad=False):
+                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -562,7 +573,8 @@ class SolveCall:
         #  whether it needs delta planes at all - depends on them)
         s.kernel = _lib.KERNELS[kernel]
         self.base_flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_STREAM_ALL if stream_all else 0) | (_lib.FLAG_TWO_TILE if two_tile else 0)
-        self.base_flags |= precision_flags(precision)      # bf16: inference only (the library refuses training outputs and every backward)
+        # bf16: inference only (the library refuses training outputs and every backward) unless bf16_grad opts in (SNSDE_FLAG_BF16_GRAD)
+        self.base_flags |= precision_flags(precision, bf16_grad)
         if lean_general:    # (SNSDE_FLAG_LEAN_GENERAL: the lean kernel's general instantiation; same results bit for bit)
             self.base_flags |= _lib.FLAG_LEAN_GENERAL
         if sample_grad and S > 1:      # (SNSDE_FLAG_SAMPLE_GRAD: no effect on one path per row)
@@ -589,7 +601,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1)
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16')
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -678,15 +690,18 @@ _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per c
 
 
 def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
-                  samples=0, sample_grad=False):
+                  samples=0, sample_grad=False, precision='fp32', bf16_grad=False):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
     supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none); samples: paths
-    per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD)."""
+    per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD).  precision='bf16': 0, or under bf16_grad
+    (SNSDE_FLAG_BF16_GRAD) 1 where the bf16 lean kernel runs the forward and the general MFMA adjoint its backward."""
     samples = int(samples) if samples and int(samples) > 1 else 0
     sample_grad = bool(sample_grad) and samples > 1
+    pflags = precision_flags(precision, bf16_grad)
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
-           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad)
+           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad,
+           pflags)
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -694,7 +709,7 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.batch, s.knots, s.n_steps, s.n_out = batch, knots, grid.N, grid.T
         s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
         s.kernel = _lib.KERNELS[kernel]
-        s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0)
+        s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0) | pflags
         s.samples = samples
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
         if kl_column is not None:

@@ -219,7 +219,9 @@ class _SDEHead(nn.Module):
         solve `initial_network`, which evaluates initial_network(X(times[0])) inside its prepare launch (no spline-evaluate
         and addmm launches of its own); everything else: `_prepare_initial_state` (neuralsde.py:63-69).  Under grad - training
         through sample paths included (options={'samples': S, 'sample_grad': True}) - z0 is materialised here with tensor ops, one
-        row per INPUT row; sdeint expands it to one row per path, so autograd sums its gradient over the paths."""
+        row per INPUT row; sdeint expands it to one row per path, so autograd sums its gradient over the paths.  Training through
+        bf16 operands (options={'precision': 'bf16', 'bf16_grad': True}) likewise: the options pass through to sdeint untouched and
+        z0 = initial_network(X(t0)) is an fp32 tensor op outside the solve, as in fp32 training."""
         func = self.func
         if (z0 is None and self.initial and not torch.is_grad_enabled() and getattr(func, 'coeffs', None) is not None
                 and func.coeffs.is_cuda and self.initial_network.weight.is_cuda

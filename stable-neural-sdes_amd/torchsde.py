@@ -236,6 +236,11 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     # options={'sample_grad': True}: such a solve may be differentiated (opt-in: its training planes are per path).  No effect on 1
     samples = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
     sample_grad = engine.check_sample_grad(options.pop('sample_grad')) if 'sample_grad' in options else False
+    # options={'precision': 'bf16', 'bf16_grad': True}: the bf16-operand solve may be differentiated (opt-in, straight-through gradient;
+    # _bf16_grad_conflicts).  Checked for every backend, before anything is routed
+    bf16_grad = engine.check_bf16_grad(options['bf16_grad']) if 'bf16_grad' in options else False
+    if bf16_grad:
+        _bf16_grad_conflicts(sde, y0, options, backend, samples)
     if samples > 1:
         return _sdeint_samples(sde, y0, ts, bm, method, float(dt), options, names, samples, sample_grad)
     if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
@@ -249,9 +254,9 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if precision == 'bf16':
         if backend == 'torch':
             raise ValueError("precision='bf16' is a HIP kernel option; backend='torch' has no bf16 solve")
-        if _differentiated(sde, y0):
+        if _differentiated(sde, y0) and not bf16_grad:
             raise ValueError("precision='bf16' is inference only: y0, the control path or a parameter requires grad (use torch.no_grad(), "
-                             "requires_grad_(False) or precision='fp32')")
+                             "requires_grad_(False) or precision='fp32'; options={'bf16_grad': True} opts in to training through it)")
         if rec is None:
             raise ValueError("precision='bf16' needs an sde honouring the Diffusion_model contract (the fused HIP solve)")
         if not y0.is_cuda:
@@ -272,6 +277,20 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     if not default_names and rec is None and backend == 'auto' and y0.is_cuda:
         return _sdeint_latent(sde, y0, ts, bm, method, float(dt), options, names)    # LatentSDE-shaped modules (falls back itself)
     return _sdeint_torch(sde, y0, ts, bm, method, float(dt), options, names)
+
+
+def _bf16_grad_conflicts(sde, y0, options, backend, samples):
+    """options={'bf16_grad': True} (training through the bf16-operand forward, SNSDE_FLAG_BF16_GRAD): ValueError for everything the
+    option does not go with - it is the bf16 kernel and the fused adjoint behind it or nothing, never an fp32 stand-in."""
+    if options.get('precision', 'fp32') != 'bf16':
+        raise ValueError("bf16_grad=True differentiates a precision='bf16' solve: pass options={'precision': 'bf16', 'bf16_grad': True}")
+    for name, bad in (('samples > 1', samples > 1),
+                      ("recompute (options['recompute'] or SNSDE_RECOMPUTE_STEPS in the environment)", _recompute_steps(options) > 0),
+                      ("param_pass='torch'", options.get('param_pass', 'hip') == 'torch'), ("backend='torch'", backend == 'torch'),
+                      ('a control path that requires grad (dL/dcoeffs has no bf16 form yet)', _coeffs_need_grad(sde)),
+                      ('CPU tensors', not y0.is_cuda)):
+        if bad:
+            raise ValueError(f"bf16_grad=True (training through the bf16-operand solve) does not take {name}")
 
 
 def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=False):
@@ -408,7 +427,7 @@ class _DrawnIncrements:
 # and the backward mode decided beside it, never the dict
 _FusedOptions = collections.namedtuple('_FusedOptions', (
     'kernel', 'precision', 'exact_order', 'save_traj', 'strict', 'param_pass', 'recompute', 'samples', 'sample_grad', 'lean_general',
-    'row_offset', 'global_rows', 'row_out', 'seed'))
+    'row_offset', 'global_rows', 'row_out', 'seed', 'bf16_grad'))
 
 
 def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
@@ -447,13 +466,21 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         strict=bool(options.get('strict', False)), param_pass=options.get('param_pass', 'hip'), recompute=_recompute_steps(options),
         samples=samples, sample_grad=bool(options.get('sample_grad', False)), lean_general=bool(options.get('lean_general', False)),
         row_offset=row_offset, global_rows=engine.resolve_global_rows(options.get('global_rows'), B, row_offset),
-        row_out=_device_row_out(options, dev))
+        row_out=_device_row_out(options, dev), bf16_grad=bool(options.get('bf16_grad', False)) and options.get('precision', 'fp32') == 'bf16')
     if opt.precision == 'bf16':
-        if needs_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
+        if needs_grad and not opt.bf16_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
             raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad")
-        if opt.save_traj:
+        if opt.save_traj and not (needs_grad and opt.bf16_grad):
             raise ValueError("precision='bf16' is inference only: save_traj is a training output")
         engine.check_bf16(model, B, L, grid.N, method, opt.kernel)
+        # training (bf16_grad): the bf16 kernel with the fused MFMA adjoint behind it, or an error - whatever `strict` says, the
+        # tensor-op loop cannot round operands and no f32 kernel stands in
+        if needs_grad and engine.backward_mode(model, B, L, grid, method, opt.kernel, opt.exact_order, global_rows=opt.global_rows,
+                                               precision='bf16', bf16_grad=True) != 1:
+            raise ValueError(f"bf16_grad=True does not cover this configuration (hidden_channels={model.hidden_channels}, "
+                             f"num_hidden_layers={model.num_hidden_layers}, input_option={model.input_option}, "
+                             f"noise_option={model.noise_option}, method={method!r}, kernel={opt.kernel!r}): no fused adjoint plans "
+                             "this bf16-operand solve")
     if engine.shard_refused(model, B, L, grid.N, method, opt.kernel, global_rows=opt.global_rows, row_offset=opt.row_offset):
         # the kernel planned for the whole problem cannot run this shard (a wave-pair plan, fewer than four rows): an error with or
         # without `strict` - another kernel or the tensor-op loop would not reproduce the unsharded solve
@@ -474,7 +501,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
             return _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad)
     if needs_grad:
         mode = engine.backward_mode(model, B, L, grid, method, opt.kernel, opt.exact_order, global_rows=opt.global_rows,
-                                    samples=samples, sample_grad=opt.sample_grad)
+                                    samples=samples, sample_grad=opt.sample_grad, precision=opt.precision, bf16_grad=opt.bf16_grad)
         if samples > 1 and mode != 1:      # (_sdeint_samples asked the same query: the sampled node is mode 1 or not built at all)
             raise engine._lib.SnsdeError(engine._lib.SNSDE_ERR_UNSUPPORTED, f"samples={samples}: no fused adjoint plans this sampled solve")
         if mode == 0 and opt.strict:
@@ -830,7 +857,8 @@ class _FusedSolve(torch.autograd.Function):
         call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=opt.seed, row_offset=opt.row_offset,
                                 kernel=opt.kernel, save_traj=True, save_dW=keep_dw, save_act=save_act, exact_order=opt.exact_order,
                                 row_out=opt.row_out, dU=dU, global_rows=opt.global_rows, samples=samples, sample_grad=samples > 1,
-                                lean_general=samples > 1 and opt.lean_general)      # (the sampled route's A/B switch)
+                                lean_general=samples > 1 and opt.lean_general,      # (the sampled route's A/B switch)
+                                precision=opt.precision, bf16_grad=opt.bf16_grad)   # (bf16 reaches here under bf16_grad, mode 1, only)
         ctx.coeffs_dtype = None if coeffs_src is None else coeffs_src.dtype
         if coeffs_src is not None and mode == 1 and getattr(call, 'delta_slots', 1) == 0:
             raise _NoCoeffGradient()      # (before the launch: _sdeint_hip applies the fallback rule)
