@@ -451,6 +451,35 @@ SNSDE_API int snsde_forward_path(const snsde_solve* s);
  * results bit for bit.  SNSDE_LEAN_NONE when the forward runs on another kernel. */
 enum { SNSDE_LEAN_NONE = 0, SNSDE_LEAN_GENERAL = 1, SNSDE_LEAN_SPECIALISED = 2 };
 SNSDE_API int snsde_lean_variant(const snsde_solve* s);
+/* Host-only queries next to snsde_forward_path / snsde_backward_supported: the exact kernel the plan of this descriptor names, one
+ * value per kernel the launchers dispatch on (csrc/snsde_mfma_kernels.h: FwdKernel / RevKernel) - the families above fold several
+ * of them into one value.  Both read the route the launches dispatch on (route_forward / route_backward) and re-derive nothing, so
+ * they see what a launch sees: the training-mode pointers, the supplied increments and the flags of THIS descriptor.
+ * snsde_forward_kernel: nhid / kuxt (each may be NULL) receive the plan's hidden-layer count and its 16-wide k-blocks of
+ * [X(t) | sin t, cos t] on an MFMA route - the keys of the two-tile kernels' instantiation lists - and -1 otherwise.
+ * snsde_backward_kernel: SNSDE_REV_NONE exactly where snsde_backward_supported is 0, SNSDE_REV_GENERIC exactly where it is 2. */
+enum { SNSDE_FWD_NONE = 0,                /* no kernel (SNSDE_PATH_NONE)                                                    */
+       SNSDE_FWD_GENERIC = 1,             /* generic family, Euler / Milstein (SNSDE_PATH_GENERIC)                          */
+       SNSDE_FWD_GENERIC_SRK = 2,         /* generic family, SRK (SNSDE_PATH_GENERIC_SRK)                                   */
+       SNSDE_FWD_W4 = 3,                  /* wave pairs (csrc/snsde_w4_kernel.h)                                            */
+       SNSDE_FWD_M4N = 4,                 /* diffusion-net kernel on 4-row tiles (csrc/snsde_m4n_kernel.h)                  */
+       SNSDE_FWD_LEAN = 5,                /* lean kernel, one tile per workgroup (csrc/snsde_m4_kernel.h)                   */
+       SNSDE_FWD_LEAN_TWO_TILE_H128 = 6,  /* H = 128, two tiles per wave (csrc/snsde_m4t_kernel.h; SNSDE_FLAG_TWO_TILE)     */
+       SNSDE_FWD_LEAN_TWO_TILE_H256 = 7,  /* H = 256, two tiles per wave (csrc/snsde_m4s2_kernel.h)                         */
+       SNSDE_FWD_LEAN_STREAMED_H256 = 8,  /* H = 256, fully streamed weights (csrc/snsde_m4s_kernel.h)                      */
+       SNSDE_FWD_GENERAL_M4 = 9,          /* general MFMA kernel, 4-row tiles (its SRK variant included)                    */
+       SNSDE_FWD_GENERAL_M16 = 10,        /* general MFMA kernel, 16-row tiles (its SRK variant included)                   */
+       SNSDE_FWD_LEAN_BF16 = 11 };        /* lean kernel with bf16 MFMA operands (csrc/snsde_m4b_kernel.h)                  */
+SNSDE_API int snsde_forward_kernel(const snsde_solve* s, int32_t* nhid, int32_t* kuxt);
+enum { SNSDE_REV_NONE = 0,                /* no fused backward (mode 0)                                                     */
+       SNSDE_REV_GENERIC = 1,             /* generic adjoint kernels (mode 2)                                               */
+       SNSDE_REV_W4_FUSED = 2,            /* wave-pair adjoint with the weight gradients inside: delta_slots == 0           */
+       SNSDE_REV_M4N_SRK = 3,             /* SRK through a diffusion net (csrc/snsde_m4n_rev_kernel.h)                      */
+       SNSDE_REV_M4N_MILSTEIN = 4,        /* Milstein through a diffusion net (csrc/snsde_m4n_mil_rev_kernel.h)             */
+       SNSDE_REV_GENERAL_SRK = 5,         /* SRK adjoint of the general kernel                                              */
+       SNSDE_REV_TWO_TILE_H256 = 6,       /* H = 256, two tiles per wave (csrc/snsde_m4s2_rev_kernel.h)                     */
+       SNSDE_REV_GENERAL = 7 };           /* Euler / Milstein adjoint of the general kernel, 4- or 16-row tiles             */
+SNSDE_API int snsde_backward_kernel(const snsde_solve* s);
 
 /* Readout head of the wrappers in one launch (inference; replaces the 4-5 tensor ops of `self.linear(z)`,
  * benchmark_classification/models_sde/neuralsde.py:59-61,119; benchmark_forecasting/models_sde/neuralsde.py:186; torch_ists

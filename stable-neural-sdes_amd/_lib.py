@@ -22,6 +22,10 @@ FLAG_LEAN_GENERAL = 32      # the lean kernel's general instantiation where a sp
 FLAG_SAMPLE_GRAD = 64       # opt-in: a solve of samples = S > 1 paths per input row may be differentiated (include/snsde.h)
 FLAG_BF16_GRAD = 128        # opt-in: training through the bf16-operand forward (straight-through gradient; with FLAG_BF16_OPERANDS only)
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
+# snsde_forward_kernel / snsde_backward_kernel (SNSDE_FWD_* / SNSDE_REV_*): the names of csrc/snsde_mfma_kernels.h FwdKernel / RevKernel
+FWD_KERNELS = ('none', 'generic', 'generic_srk', 'w4', 'm4n', 'lean', 'lean_two_tile_h128', 'lean_two_tile_h256', 'lean_streamed_h256',
+               'general_m4', 'general_m16', 'lean_bf16')
+REV_KERNELS = ('none', 'generic', 'w4_fused', 'm4n_srk', 'm4n_milstein', 'general_srk', 'two_tile_h256', 'general')
 BWD_ADJ0_ONLY = 1
 PATHS = ('none', 'generic', 'mfma16', 'mfma4', 'lean', 'lean-streamed', 'generic-srk', 'mfma-srk', 'w4', 'lean-bf16')
 KERNELS = {'auto': KERNEL_AUTO, 'generic': KERNEL_GENERIC, 'mfma': KERNEL_MFMA, 'mfma16': 3, 'mfma4': 4, 'w4': 5}
@@ -96,7 +100,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_spline_evaluate', 'snsde_eval_fg', 'snsde_act_slots', 'snsde_backward_supported',
            'snsde_backward_workspace_bytes', 'snsde_solve_backward', 'snsde_spline_workspace_bytes',
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
-           'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_readout_head', 'snsde_save_layout',
+           'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_forward_kernel',
+           'snsde_backward_kernel', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward')
@@ -164,6 +169,8 @@ def lib():
     L.snsde_backward_supported.argtypes = [C.POINTER(Solve)]
     L.snsde_forward_path.argtypes = [C.POINTER(Solve)]
     L.snsde_lean_variant.argtypes = [C.POINTER(Solve)]
+    L.snsde_forward_kernel.argtypes = [C.POINTER(Solve), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.snsde_backward_kernel.argtypes = [C.POINTER(Solve)]
     L.snsde_readout_head.argtypes = [C.POINTER(Head), C.c_void_p]
     L.snsde_affine_compose.argtypes = [C.POINTER(AffineJob), C.c_int32, C.c_void_p, C.c_void_p]
     L.snsde_affine_compose_backward.argtypes = [C.POINTER(AffineJob), C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]

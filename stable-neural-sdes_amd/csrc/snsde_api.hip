@@ -504,6 +504,58 @@ int snsde_lean_variant(const snsde_solve* s) {
     return r.plan.LEAN_SPEC ? SNSDE_LEAN_SPECIALISED : SNSDE_LEAN_GENERAL;
 }
 
+// The kernel the forward route names (SNSDE_FWD_*): the plan's FwdKernel on an MFMA route, the generic family's two launchers otherwise
+static int forward_kernel_of(const ForwardRoute& r) {
+    using snsde_mfma::FwdKernel;
+    if (r.path == SNSDE_PATH_NONE) return SNSDE_FWD_NONE;
+    if (!r.plan.ok) return r.path == SNSDE_PATH_GENERIC_SRK ? SNSDE_FWD_GENERIC_SRK : SNSDE_FWD_GENERIC;
+    switch (r.plan.kernel) {
+        case FwdKernel::w4: return SNSDE_FWD_W4;
+        case FwdKernel::m4n: return SNSDE_FWD_M4N;
+        case FwdKernel::lean: return SNSDE_FWD_LEAN;
+        case FwdKernel::lean_two_tile_h128: return SNSDE_FWD_LEAN_TWO_TILE_H128;
+        case FwdKernel::lean_two_tile_h256: return SNSDE_FWD_LEAN_TWO_TILE_H256;
+        case FwdKernel::lean_streamed_h256: return SNSDE_FWD_LEAN_STREAMED_H256;
+        case FwdKernel::general_m4: return SNSDE_FWD_GENERAL_M4;
+        case FwdKernel::general_m16: return SNSDE_FWD_GENERAL_M16;
+        case FwdKernel::lean_bf16: return SNSDE_FWD_LEAN_BF16;
+    }
+    return SNSDE_FWD_NONE;
+}
+
+int snsde_forward_kernel(const snsde_solve* s, int32_t* nhid, int32_t* kuxt) {
+    if (nhid) *nhid = -1;
+    if (kuxt) *kuxt = -1;
+    if (snsde_forward_path(s) == SNSDE_PATH_NONE) return SNSDE_FWD_NONE;      // (its descriptor checks)
+    SnsdeNet net;
+    if (snsde_build_net(s->model, s->n_steps, &net)) return SNSDE_FWD_NONE;
+    const ForwardRoute r = route_forward(s, net);
+    if (r.path != SNSDE_PATH_NONE && r.plan.ok) {
+        if (nhid) *nhid = r.plan.NHID;
+        if (kuxt) *kuxt = r.plan.KUXT;
+    }
+    return forward_kernel_of(r);
+}
+
+int snsde_backward_kernel(const snsde_solve* s) {
+    using snsde_mfma::RevKernel;
+    if (snsde_backward_supported(s) == 0) return SNSDE_REV_NONE;      // (its descriptor checks)
+    SnsdeNet net;
+    if (snsde_build_net(s->model, s->n_steps, &net)) return SNSDE_REV_NONE;
+    const snsde_mfma::BackwardRoute r = route_backward(s, net);
+    if (r.mode == 2) return SNSDE_REV_GENERIC;
+    if (r.mode != 1) return SNSDE_REV_NONE;
+    switch (r.rp.kernel) {
+        case RevKernel::w4_fused: return SNSDE_REV_W4_FUSED;
+        case RevKernel::m4n_srk: return SNSDE_REV_M4N_SRK;
+        case RevKernel::m4n_milstein: return SNSDE_REV_M4N_MILSTEIN;
+        case RevKernel::general_srk: return SNSDE_REV_GENERAL_SRK;
+        case RevKernel::two_tile_h256: return SNSDE_REV_TWO_TILE_H256;
+        case RevKernel::general: return SNSDE_REV_GENERAL;
+    }
+    return SNSDE_REV_NONE;
+}
+
 int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, float* f_out, float* g_out,
                   void* hip_stream) {
     int rc = validate_solve(s, true);

@@ -668,6 +668,25 @@ def lean_variant(call):
     return _lib.LEAN_VARIANTS[_lib.lib().snsde_lean_variant(C.byref(call.desc))]
 
 
+def _desc(call_or_desc):
+    return call_or_desc.desc if hasattr(call_or_desc, 'desc') else call_or_desc
+
+
+def forward_kernel(call_or_desc, keys=False):
+    """Name of the exact kernel the forward of a SolveCall (or a _lib.Solve descriptor) launches (_lib.FWD_KERNELS: the
+    enumerators of csrc/snsde_mfma_kernels.h FwdKernel, 'generic', 'generic_srk' or 'none'); forward_path folds several of them into
+    one family.  keys=True: (name, NHID, KUXT) - the plan's keys of the two-tile kernels' instantiation lists, -1 off the MFMA routes."""
+    nhid, kuxt = C.c_int32(), C.c_int32()
+    name = _lib.FWD_KERNELS[_lib.lib().snsde_forward_kernel(C.byref(_desc(call_or_desc)), C.byref(nhid), C.byref(kuxt))]
+    return (name, nhid.value, kuxt.value) if keys else name
+
+
+def backward_kernel(call_or_desc):
+    """Name of the exact adjoint kernel of a SolveCall (or a _lib.Solve descriptor): _lib.REV_KERNELS - the enumerators of
+    csrc/snsde_mfma_kernels.h RevKernel where backward_supported is 1, 'generic' where it is 2, 'none' where it is 0."""
+    return _lib.REV_KERNELS[_lib.lib().snsde_backward_kernel(C.byref(_desc(call_or_desc)))]
+
+
 def backward_supported(call):
     """0 = no fused backward; 1 = MFMA adjoint kernel (needs save_act); 2 = generic adjoint kernel (forward must run
     on the generic kernel; needs traj + dW_out only)."""

@@ -184,3 +184,52 @@ def grad_close(got, ref, name, tol, tag=''):
             fh.write(f'{tag or "-"} - - - - - {name} {err:.3e} {mean_rel:.3e}\n')
     assert err < tol, (tag, name, err)
     assert mean_rel < tol, (tag, name, mean_rel)
+
+
+# ---------------------------------------------------------------------------------------------------
+# which kernel a test ran (tests/kernel_cases.py): read from the descriptor that was launched
+# ---------------------------------------------------------------------------------------------------
+def assert_kernels(call, fwd=None, rev=None):
+    """The forward / adjoint kernel the plan of THIS call's descriptor names (engine.forward_kernel / engine.backward_kernel)."""
+    from stable_neural_sdes_amd import engine
+    if fwd is not None:
+        assert engine.forward_kernel(call) == fwd, (engine.forward_kernel(call, keys=True), 'meant', fwd)
+    if rev is not None:
+        assert engine.backward_kernel(call) == rev, (engine.backward_kernel(call), 'meant', rev)
+
+
+class launched_kernels:
+    """Context manager around code that solves through a front end (sdeint): records the forward kernel of every SolveCall launched
+    inside it and the adjoint kernel of every call a backward ran on, each read from that call's own descriptor.
+    `fwd` / `rev`: the sets of names, in launch order without repeats."""
+
+    def __enter__(self):
+        from stable_neural_sdes_amd import engine
+        self.fwd, self.rev, self._engine = [], [], engine
+        self._saved = (engine.SolveCall.launch, engine.solve_backward, engine.backward_with_gradients)
+        launch, solve_backward, backward_with_gradients = self._saved
+        rec = self
+
+        def note(lst, name):
+            if name not in lst:
+                lst.append(name)
+
+        def launch_(call, *a, **k):
+            out = launch(call, *a, **k)
+            note(rec.fwd, engine.forward_kernel(call))
+            return out
+
+        def solve_backward_(call, *a, **k):
+            note(rec.rev, engine.backward_kernel(call))
+            return solve_backward(call, *a, **k)
+
+        def backward_with_gradients_(call, *a, **k):
+            note(rec.rev, engine.backward_kernel(call))
+            return backward_with_gradients(call, *a, **k)
+
+        engine.SolveCall.launch, engine.solve_backward, engine.backward_with_gradients = launch_, solve_backward_, backward_with_gradients_
+        return self
+
+    def __exit__(self, *exc):
+        self._engine.SolveCall.launch, self._engine.solve_backward, self._engine.backward_with_gradients = self._saved
+        return False

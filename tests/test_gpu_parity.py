@@ -12,7 +12,10 @@ import torch
 
 import stable_neural_sdes_amd as S
 from oracle import sde_oracle as O
-from tests.helpers import (assert_parity, draw_dW, group, load, make_problem, param_spec, params_of, unflatten)
+from tests import kernel_cases as K
+from tests.helpers import (assert_kernels, assert_parity, draw_dW, group, launched_kernels, load, make_problem, param_spec, params_of,
+                           unflatten)
+from tests.kernel_cases import EULER_NET_CASES, MIL_NET_BWD_CASES, SRK_BWD_CASES, SRK_CASES, SRK_NET_ROWS
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
@@ -347,7 +350,8 @@ def test_k2_full_size_parity_and_properties():
     pr = make_problem(1234, 4, 17, 2, B, H, C, L, nan_frac=0.3)
     ts, dt = [0, N], 1.0
     dW = draw_dW(2024, ts, dt, B, H)
-    ys, _ = hip_solve(pr, ts, dt, dW=dW)
+    ys, call = hip_solve(pr, ts, dt, dW=dW)
+    assert_kernels(call, fwd=K.K_SHAPES['K2'][8]['auto'])
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
     rep = assert_parity(ys, ref64, cpu32, what='K2')
@@ -465,22 +469,24 @@ def test_mfma_unsupported_configuration_is_refused_not_silently_rerouted():
     assert np.isfinite(ys).all()
 
 
-@pytest.mark.parametrize('H,method', [(32, 'euler'), (64, 'milstein'), (128, 'euler'), (256, 'milstein'), (256, 'euler')])
+@pytest.mark.parametrize('H,method', K.LONG_CASES)
 def test_long_solves_cross_the_step_table_chunks(H, method):
-    """More than 128 solver steps: the kernels re-stage their step-table rows in LDS chunk by chunk (forward: lean /
-    streamed kernels; backward: the adjoint kernel).  States vs the float64 oracle, gradients vs float64 autograd, with two
-    off-grid outputs among the 300 steps."""
+    """More than 128 solver steps: the kernels re-stage their step-table rows in LDS chunk by chunk (forward: the lean kernel, at
+    H = 256 the two-tile kernel; backward: the general adjoint, at H = 256 the two-tile adjoint - K.LONG_KERNELS, asserted on the
+    launched descriptors).  States vs the float64 oracle, gradients vs float64 autograd, with two off-grid outputs among the 300
+    steps."""
     io, no, NL, B, C, L = 4, 17, 2, 9, 5, 9
     pr = make_problem(700 + H, io, no, NL, B, H, C, L)
     ts = np.asarray([0.0, 3.1, 8.0], np.float32)
     dt = 8.0 / 300
     dW = draw_dW(700 + H, ts, dt, B, H)
     assert dW.shape[0] > 256
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, method=method, kernel='mfma4')
+    ys, call = hip_solve(pr, ts, dt, dW=dW, method=method, kernel='mfma4')
+    assert_kernels(call, fwd=K.LONG_KERNELS[H][0])
     ref64, _ = oracle_solve(pr, ts, dt, dW, method, np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, method, np.float32)
     assert_parity(ys, ref64, cpu32, what=f'long solve H={H}')
-    _check_backward(700 + H, io, no, NL, B, H, C, L, list(ts), dt, method, 'mfma4')
+    _check_backward(700 + H, io, no, NL, B, H, C, L, list(ts), dt, method, 'mfma4', expect=K.LONG_KERNELS[H])
 
 
 @pytest.mark.parametrize('H', [128, 256])       # 256: the streamed-weight kernel keeps its Philox normals in registers
@@ -511,7 +517,8 @@ def test_k2_full_size_mfma(kernel):
     pr = make_problem(1234, 4, 17, 2, B, H, C, L, nan_frac=0.3)
     ts, dt = [0, N], 1.0
     dW = draw_dW(2024, ts, dt, B, H)
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+    ys, call = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+    assert_kernels(call, fwd=K.K_SHAPES['K2'][8][kernel])
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
     print('K2 parity', kernel, assert_parity(ys, ref64, cpu32, what='K2 ' + kernel))
@@ -609,7 +616,8 @@ def test_k3_gsde_per_gpu_shard_full_size():
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
     for kernel in ('mfma4', 'mfma16', 'generic'):
-        ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+        ys, call = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+        assert_kernels(call, fwd=K.K_SHAPES['K3'][8][kernel])
         # 200 GSDE steps amplify fp32 round-off on isolated rows (CPU fp32 is equally far from fp64): relative criterion
         print('K3', kernel, assert_parity(ys, ref64, cpu32, what='K3 ' + kernel, amplifying=True))
 
@@ -625,7 +633,8 @@ def test_bench_sized_single_gpu_solves_vs_oracle():
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
     assert S.engine.forward_path(S.engine.model_struct(C, H, H, 2, 6, 17), B, L, L - 1) == 'mfma16'
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel='auto')
+    ys, call = hip_solve(pr, ts, dt, dW=dW, kernel='auto')
+    assert_kernels(call, fwd=K.K_SHAPES['K3 4096'][8]['auto'])
     print('K3 4096 rows', assert_parity(ys, ref64, cpu32, what='K3 4096 rows auto', amplifying=True))
     B, H, C, L = 1024, 256, 14, 50
     pr = make_problem(5006, 4, 17, 2, B, H, C, L, nan_frac=0.3)
@@ -634,7 +643,8 @@ def test_bench_sized_single_gpu_solves_vs_oracle():
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'milstein', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'milstein', np.float32)
     assert S.engine.forward_path(S.engine.model_struct(C, H, H, 2, 4, 17), B, L, L - 1, method='milstein') == 'lean-streamed'
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, method='milstein', kernel='auto')
+    ys, call = hip_solve(pr, ts, dt, dW=dW, method='milstein', kernel='auto')
+    assert_kernels(call, fwd=K.K_SHAPES['K5 1024'][8]['auto'])
     assert ys.shape == (50, B, H)
     print('K5 1024 rows', assert_parity(ys, ref64, cpu32, what='K5 1024 rows auto'))
 
@@ -657,7 +667,8 @@ def test_k4_sepsis_shaped_nsde_full_size():
     model = S.engine.model_struct(C, H, H, 2, 3, 18)
     assert S.engine.forward_path(model, B, L, len(times) - 1) == 'w4'      # `auto` = the wave-pair kernels (snsde_w4_euler_kernel) since round 5
     for kernel in ('auto', 'w4', 'mfma4', 'mfma16', 'generic'):
-        ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+        ys, call = hip_solve(pr, ts, dt, dW=dW, kernel=kernel)
+        assert_kernels(call, fwd=K.K_SHAPES['K4'][8][kernel])
         assert ys.shape[0] == len(ts)
         print('K4', kernel, assert_parity(ys, ref64, cpu32, what='K4 ' + kernel))
     # ... and under torch_ists' default method (nsde_model.py:63-74), SRI2W1 through the net at the full K4 size
@@ -669,19 +680,14 @@ def test_k4_sepsis_shaped_nsde_full_size():
     cpu32s, _ = O.solve_diffusion_model(pr['params'], 3, 18, pr['coeffs'], pr['times'], pr['y0'], ts, dt, dW, method='srk', dtype=np.float32, dU=dU)
     assert S.engine.forward_path(model, B, L, len(times) - 1, method='srk') == 'w4'
     for kernel in ('auto', 'mfma4'):
-        ys, _ = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel=kernel)
+        ys, call = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel=kernel)
+        assert_kernels(call, fwd=K.K_SHAPES['K4 srk'][8][kernel])
         print('K4 srk', kernel, assert_parity(ys, ref64s, cpu32s, what='K4 srk ' + kernel))
 
 
-@pytest.mark.parametrize('case', [(4, 17, 2, 14, 37, 'milstein'), (4, 17, 2, 14, 128, 'euler'), (6, 16, 2, 21, 9, 'euler'), (1, 13, 1, 3, 21, 'milstein'),
-                                  (3, 12, 2, 3, 5, 'euler'), (4, 9, 2, 40, 12, 'euler'), (2, 17, 3, 14, 8, 'euler')])
-@pytest.mark.parametrize('train', [False, True])
-def test_h256_two_tile_kernel_is_bit_identical_to_the_streamed_one(case, train):
-    """H = 256 on 4-row tiles (round 6): eight waves of two tiles with the first 4 k-blocks of every layer in registers
-    (snsde_m4s2_kernel.h) keep the k order and accumulator chains of the fully streamed sixteen-wave kernel (snsde_m4s_kernel.h, kept
-    behind SNSDE_FLAG_STREAM_ALL): every output, the trajectory and every saved plane agree bit for bit - Philox and supplied
-    increments, ragged tiles, interpolated outputs.  (NL = 3 and wide control blocks fall back to the streamed kernel where the
-    two-tile instantiation would spill: equal by construction there.)"""
+def _h256_forward_arms(case, train, planned):
+    """Both arms of one H = 256 forward case (SNSDE_FLAG_STREAM_ALL and the plan's own choice, which must be `planned`), Philox and
+    supplied increments: every output, the trajectory and every saved plane bit for bit."""
     io, no, NL, C, B, method = case
     pr = make_problem(6100 + B, io, no, NL, B, 256, C, 9)
     ts, dt = np.array([0., 2.5, 6., 8.], np.float32), 1.0
@@ -696,6 +702,7 @@ def test_h256_two_tile_kernel_is_bit_identical_to_the_streamed_one(case, train):
                                       dW=supplied, method=method, seed=11, kernel='mfma4', stream_all=all_, save_traj=train, save_dW=train,
                                       save_act=train)
             ys = call.launch().clone()
+            assert_kernels(call, fwd='lean_streamed_h256' if all_ else planned)
             outs.append((ys, call.traj, call.act_save, call.dW_out))
         assert torch.isfinite(outs[0][0]).all()
         for x, y in zip(*outs):
@@ -703,12 +710,33 @@ def test_h256_two_tile_kernel_is_bit_identical_to_the_streamed_one(case, train):
     if no == 17 and io == 4:      # ... and the K5 model against the oracle, through the two-tile kernel
         ref64, _ = oracle_solve(pr, ts, dt, dW, method, np.float64)
         cpu32, _ = oracle_solve(pr, ts, dt, dW, method, np.float32)
-        ys, _ = hip_solve(pr, ts, dt, dW=dW, method=method, kernel='mfma4')
+        ys, call = hip_solve(pr, ts, dt, dW=dW, method=method, kernel='mfma4')
+        assert_kernels(call, fwd='lean_two_tile_h256')      # (an inference launch: cases 0 and 1, the (1, 1) instantiation)
         assert_parity(ys, ref64, cpu32, what='H=256 two-tile')
 
 
+def _h256_ids(pairs):      # (the ids the (case, train) cross product had: train, then the case's index in K.H256_FWD_CASES)
+    return [f'{train}-case{ci}' for ci, train in pairs]
+
+
+@pytest.mark.parametrize('ci,train', K.H256_FWD_TWO_TILE, ids=_h256_ids(K.H256_FWD_TWO_TILE))
+def test_h256_two_tile_kernel_is_bit_identical_to_the_streamed_one(ci, train):
+    """H = 256 on 4-row tiles (round 6): eight waves of two tiles with the first 4 k-blocks of every layer in registers
+    (snsde_m4s2_kernel.h) keep the k order and accumulator chains of the fully streamed sixteen-wave kernel (snsde_m4s_kernel.h, kept
+    behind SNSDE_FLAG_STREAM_ALL): every output, the trajectory and every saved plane agree bit for bit - Philox and supplied
+    increments, ragged tiles, interpolated outputs.  The two arms are two kernels: each launch's descriptor names its own."""
+    _h256_forward_arms(K.H256_FWD_CASES[ci], train, 'lean_two_tile_h256')
+
+
+@pytest.mark.parametrize('ci,train', K.H256_FWD_DECLINES, ids=_h256_ids(K.H256_FWD_DECLINES))
+def test_h256_forward_declines_to_the_streamed_kernel(ci, train):
+    """Where SNSDE_M4S2_LIST has no instantiation (KUXT = 3, NHID = 2 with a control block, (1, 2) in training mode: they would
+    spill) the plan keeps the streamed kernel with or without SNSDE_FLAG_STREAM_ALL: both launches name it, and agree bit for bit."""
+    _h256_forward_arms(K.H256_FWD_CASES[ci], train, 'lean_streamed_h256')
+
+
 @pytest.mark.parametrize('train', [False, True])
-@pytest.mark.parametrize('case', [(4, 17, 21, 64, 'euler'), (4, 17, 21, 37, 'milstein'), (6, 16, 5, 9, 'euler'), (3, 13, 3, 21, 'milstein')])
+@pytest.mark.parametrize('case', K.H128_CASES)
 def test_h128_two_tile_kernel_is_bit_identical_to_the_lean_one(case, train):
     """SNSDE_FLAG_TWO_TILE (round 6 experiment): four waves of two tiles, one wave per SIMD, hidden / output weights pinned in
     AccVGPRs with asm-issued MFMAs - measured slower than the eight-wave lean kernel at K2 (214 vs 184 us), kept opt-in; its results are
@@ -726,25 +754,32 @@ def test_h128_two_tile_kernel_is_bit_identical_to_the_lean_one(case, train):
             call = S.engine.SolveCall(model, flat, torch.from_numpy(pr['coeffs']).to(DEV), grid, torch.from_numpy(pr['y0']).to(DEV), dW=supplied,
                                       method=method, seed=11, kernel='mfma4', two_tile=two, save_traj=train, save_dW=train, save_act=train)
             outs.append((call.launch().clone(), call.traj, call.act_save, call.dW_out))
+            assert_kernels(call, fwd='lean_two_tile_h128' if two else 'lean')
         assert torch.isfinite(outs[0][0]).all()
         for x, y in zip(*outs):
             assert (x is None and y is None) or torch.equal(x, y)
 
 
-@pytest.mark.parametrize('case', [(4, 17, 2, 14, 37, 'milstein', False), (4, 17, 2, 14, 128, 'euler', True), (6, 16, 2, 21, 9, 'euler', False),
-                                  (1, 13, 1, 3, 21, 'milstein', True), (3, 9, 2, 3, 5, 'euler', False), (5, 3, 1, 4, 12, 'milstein', False)])
+@pytest.mark.parametrize('case', K.H256_REV_CASES)
 def test_h256_two_tile_adjoint_is_bit_identical_to_the_streamed_one(case):
     """The H = 256 adjoint on two tiles per wave (snsde_m4s2_rev_kernel.h, round 6) against the sixteen-wave streamed adjoint
     (SNSDE_FLAG_STREAM_ALL): dL/dy0, every adjoint state, every delta plane and the flat parameter gradient (which also sums the
     per-tile theta / table partials) bit for bit - supplied and Philox increments, per-row outputs, gated drifts (io 5 / 6), y-only and
     table diffusions."""
     io, no, NL, C, B, method, row_out = case
-    pr = make_problem(6200 + B, io, no, NL, B, 256, C, 9)
+    h256_adjoint_arms(6200 + B, io, no, NL, C, B, method, row_out, K.H256_REV_FWD[K.H256_REV_CASES.index(case)])
+
+
+def h256_adjoint_arms(seed, io, no, NL, C, B, method, row_out, fwd):
+    """Both arms of one H = 256 adjoint case (SNSDE_FLAG_STREAM_ALL: the streamed forward and the general adjoint; without it `fwd`
+    and the two-tile adjoint - asserted on each launched descriptor), Philox and supplied increments: every adjoint state, every
+    delta plane and the flat parameter gradient bit for bit."""
+    pr = make_problem(seed, io, no, NL, B, 256, C, 9)
     ts, dt = np.array([0., 2.5, 6., 8.], np.float32), 1.0
     model = S.engine.model_struct(C, 256, 256, NL, io, no)
     flat = flat_params(pr['params'], io, no, NL, C, 256)
     grid = S.engine.step_grid(ts, dt, pr['times'], torch.device(DEV))
-    dW = torch.from_numpy(draw_dW(6200 + B, ts, dt, B, 256)).to(DEV)
+    dW = torch.from_numpy(draw_dW(seed, ts, dt, B, 256)).to(DEV)
     ro = torch.from_numpy(np.random.default_rng(5).integers(0, len(ts), size=B).astype(np.int32)).to(DEV) if row_out else None
     rng = np.random.default_rng(7)
     for supplied in (None, dW):
@@ -754,6 +789,7 @@ def test_h256_two_tile_adjoint_is_bit_identical_to_the_streamed_one(case):
                                       method=method, seed=11, kernel='mfma4', stream_all=all_, save_traj=True, save_dW=supplied is None, save_act=True,
                                       row_out=ro)
             ys = call.launch()
+            assert_kernels(call, fwd='lean_streamed_h256' if all_ else fwd, rev='general' if all_ else 'two_tile_h256')
             gy = torch.from_numpy(rng.standard_normal(tuple(ys.shape)).astype(np.float32)).to(DEV) if not outs else outs[0][-1]
             adj, delta = S.engine.solve_backward(call, gy, save_delta=True)
             grad = S.engine.param_gradients(call, adj, delta)
@@ -766,7 +802,7 @@ def test_h256_two_tile_adjoint_is_bit_identical_to_the_streamed_one(case):
 def test_h256_two_tile_kernels_over_more_steps_than_one_table_chunk():
     """160 steps (> the 128-row chunk of the step table both kernels stage in LDS: fill_rows re-stages mid-solve), ragged batch: forward
     (training mode) and adjoint + gradients of the two-tile kernels bit for bit against the sixteen-wave ones."""
-    io, no, NL, C, B, L = 4, 17, 2, 14, 23, 161
+    io, no, NL, C, B, L = K.H256_CHUNK_CASE
     pr = make_problem(6400, io, no, NL, B, 256, C, L, weight_scale=0.5)
     ts, dt = np.array([0., 77.5, 160.], np.float32), 1.0
     model = S.engine.model_struct(C, 256, 256, NL, io, no)
@@ -778,6 +814,7 @@ def test_h256_two_tile_kernels_over_more_steps_than_one_table_chunk():
         call = S.engine.SolveCall(model, flat, torch.from_numpy(pr['coeffs']).to(DEV), grid, torch.from_numpy(pr['y0']).to(DEV), method='milstein',
                                   seed=5, kernel='mfma4', stream_all=all_, save_traj=True, save_act=True)
         ys = call.launch().clone()
+        assert_kernels(call, fwd='lean_streamed_h256' if all_ else 'lean_two_tile_h256', rev='general' if all_ else 'two_tile_h256')
         gy = torch.ones_like(ys) if not outs else outs[0][-1]
         adj, grad = S.engine.backward_with_gradients(call, gy, adj0_only=True)
         outs.append((ys, call.traj.clone(), adj.clone(), grad.clone(), gy))
@@ -789,13 +826,15 @@ def test_h256_two_tile_kernels_over_more_steps_than_one_table_chunk():
 def test_h256_two_tile_kernels_fuzz_against_the_streamed_ones():
     """60 random configurations (input / noise options, depth, channels, ragged batches, output grids with interpolated outputs, Euler /
     Milstein, supplied / Philox increments, per-row outputs): forward in training mode, adjoint and parameter gradients of the two-tile
-    H = 256 kernels bit for bit against the sixteen-wave ones (tools/fuzz_h256.py; 300 cases were run when the kernels were written)."""
+    H = 256 kernels bit for bit against the sixteen-wave ones (tools/fuzz_h256.py; 300 cases were run when the kernels were written).
+    The tool redraws a configuration whose plan does not name both two-tile kernels: all 60 cases are real comparisons."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, 'tools', 'fuzz_h256.py'), '60', '7'], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert '60 cases, 0 mismatches' in r.stdout, r.stdout[-2000:]
+    assert 'two-tile forward 60 of 60, two-tile adjoint 60 of 60' in r.stdout, r.stdout[-2000:]
 
 
 def test_k5_milstein_h256_forecast_shaped():
@@ -807,7 +846,8 @@ def test_k5_milstein_h256_forecast_shaped():
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'milstein', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'milstein', np.float32)
     for kernel in ('mfma4', 'mfma16', 'generic'):
-        ys, _ = hip_solve(pr, ts, dt, dW=dW, method='milstein', kernel=kernel)
+        ys, call = hip_solve(pr, ts, dt, dW=dW, method='milstein', kernel=kernel)
+        assert_kernels(call, fwd=K.K_SHAPES['K5'][8][kernel])
         assert ys.shape == (50, B, H)
         print('K5', kernel, assert_parity(ys, ref64, cpu32, what='K5 ' + kernel))
 
@@ -903,38 +943,6 @@ def test_backward_matches_fp64_autograd_through_the_unrolled_loop(ci, kernel):
     _check_backward(500 + ci, io, no, NL, B, H, C, L, ts, dt, method, kernel)
 
 
-SRK_BWD_CASES = [
-    # io, no, NL, B, H, C, L, ts, dt     (MFMA SRK forward + MFMA SRK adjoint + native parameter pass)
-    (4, 17, 2, 11, 32, 5, 9, [0, 3.5, 8], 1.0),
-    (6, 17, 3, 9, 64, 3, 9, [0, 8], 0.5),
-    (2, 16, 1, 9, 16, 2, 12, None, 0.05),
-    (1, 0, 2, 7, 32, 3, 8, [0, 7], 1.0),
-    (3, 13, 2, 10, 64, 3, 8, [0, 2.5, 7], 1.0),
-    (5, 12, 4, 6, 128, 3, 7, [0, 6], 1.0),
-    (4, 17, 2, 21, 128, 21, 9, [0, 8], 1.0),
-    (2, 3, 2, 9, 32, 3, 8, [0, 7], 1.0),             # closed-form table noise under SRK
-    (6, 5, 1, 9, 64, 3, 8, [0, 3, 7], 0.5),
-    (3, 11, 2, 9, 16, 3, 8, [0, 7], 1.0),
-    (4, 1, 2, 9, 32, 5, 8, [0, 7], 1.0),
-    (4, 9, 2, 9, 32, 5, 8, [0, 7], 1.0),             # y-only closed forms under SRK
-    (1, 8, 2, 9, 16, 3, 8, [0, 3, 7], 0.5),
-    (6, 10, 1, 9, 64, 3, 8, [0, 7], 1.0),
-    (4, 17, 2, 9, 256, 14, 8, [0, 3, 7], 1.0),       # H = 256 (streamed weights): the torch_ists default method at the K5 width
-    (6, 16, 1, 6, 256, 5, 7, [0, 6], 0.5),
-    (4, 17, 2, 9, 64, 40, 8, [0, 3, 7], 1.0),        # wide control path (C > 32) under SRK
-    (6, 13, 3, 7, 128, 69, 7, [0, 6], 1.0),
-    (1, 18, 2, 9, 16, 3, 8, [0, 7], 0.5),            # SRK through a diffusion net: snsde_m4n_srk_reverse_kernel + weight-gradient
-    (3, 15, 3, 8, 16, 4, 8, [0, 7], 1.0),            # jobs over the pass subsets / state planes of the four evaluations
-    (1, 14, 1, 17, 32, 3, 9, [0, 2.5, 8], 0.5),
-    (3, 18, 2, 33, 64, 5, 12, [0, 2.5, 11], 0.5),
-    (5, 19, 2, 21, 64, 5, 9, [0, 8], 1.0),
-    (4, 19, 2, 21, 128, 21, 10, [0, 9], 1.0),
-    (2, 14, 2, 13, 32, 7, 9, [0, 3.5, 8], 0.5),
-    (6, 15, 3, 9, 64, 40, 8, [0, 7], 1.0),
-    (1, 18, 2, 37, 128, 5, 9, [0, 8], 1.0),
-    (3, 18, 3, 11, 128, 5, 9, [0, 8], 0.5),
-    (4, 18, 1, 11, 128, 69, 9, [0, 8], 1.0),
-]
 
 
 @pytest.mark.parametrize('kernel', ['mfma4', 'auto'])
@@ -944,21 +952,17 @@ def test_srk_backward_on_the_mfma_path(ci, kernel):
     if ts is not None:      # the fused MFMA adjoint, not the generic family
         grid = S.engine.step_grid(np.asarray(ts, np.float32), dt, np.arange(L, dtype=np.float32), torch.device(DEV))
         assert S.engine.backward_mode(S.engine.model_struct(C, H, H, NL, io, no), B, L, grid, 'srk', kernel) == 1
-    _check_backward(4000 + ci, io, no, NL, B, H, C, L, ts, dt, 'srk', kernel, strict=True)
+    # (K.srk_bwd_kernels: general_srk for the elementwise diffusions, m4n_srk through a net - under 'auto' the wave pair at H = 64)
+    _check_backward(4000 + ci, io, no, NL, B, H, C, L, ts, dt, 'srk', kernel, strict=True, expect=K.srk_bwd_kernels(ci, kernel))
 
 
-EULER_NET_CASES = [
-    # io, no, NL, B, H, C, L     (Euler through a diffusion net on snsde_m4n_kernel.h: wide control paths behind the embedding - the
-    (4, 18, 2, 19, 64, 69, 9),   #  sepsis channel count - and H = 128 on 4-row tiles)
-    (6, 15, 3, 9, 128, 40, 8),
-    (2, 14, 1, 13, 32, 33, 8),
-    (1, 18, 2, 21, 128, 5, 9),
-    (5, 19, 2, 11, 128, 3, 8),
-]
 
 
 @pytest.mark.parametrize('ci', range(len(EULER_NET_CASES)))
 def test_euler_through_a_diffusion_net_on_the_net_kernels(ci):
+    """Euler through a diffusion net on 4-row tiles: the net kernel (snsde_m4n_kernel.h) behind a wide control path and at H = 128,
+    the general kernel's 4-row tiles elsewhere (K.EULER_NET_FWD says which, per case; the adjoint is the general one on either side):
+    forward against the oracle and the generic kernels, gradients against fp64 autograd."""
     io, no, NL, B, H, C, L = EULER_NET_CASES[ci]
     pr = make_problem(800 + ci, io, no, NL, B, H, C, L)
     ts, dt = [0, 2.5, L - 1], 0.5
@@ -966,28 +970,16 @@ def test_euler_through_a_diffusion_net_on_the_net_kernels(ci):
     grid = S.engine.step_grid(np.asarray(ts, np.float32), dt, pr['times'], torch.device(DEV))
     assert S.engine.forward_path(model, B, L, grid.N) == 'mfma4' and S.engine.backward_mode(model, B, L, grid, 'euler') == 1
     dW = draw_dW(800 + ci, ts, dt, B, H)
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel='auto')
+    ys, call = hip_solve(pr, ts, dt, dW=dW, kernel='auto')
+    assert_kernels(call, fwd=K.EULER_NET_FWD[ci])
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
     assert_parity(ys, ref64, cpu32, what=f'euler net case {ci}')
     yg, _ = hip_solve(pr, ts, dt, dW=dW, kernel='generic')
     assert np.abs(ys - yg).max() <= 2e-4 * (np.abs(yg).max() + 1e-9)
-    _check_backward(4700 + ci, io, no, NL, B, H, C, L, ts, dt, 'euler', 'auto', strict=True)
+    _check_backward(4700 + ci, io, no, NL, B, H, C, L, ts, dt, 'euler', 'auto', strict=True, expect=(K.EULER_NET_FWD[ci], 'general'))
 
 
-MIL_NET_BWD_CASES = [
-    # io, no, NL, B, H, C, L, ts, dt     (Milstein through a diffusion net: snsde_m4n_mil_reverse_kernel - tangent + reverse pass
-    (1, 18, 2, 9, 16, 3, 8, [0, 7], 0.5),            #  through the net per step - and the second-order weight-gradient jobs)
-    (3, 15, 3, 8, 16, 4, 8, [0, 7], 1.0),
-    (1, 14, 1, 17, 32, 3, 9, [0, 2.5, 8], 0.5),
-    (3, 18, 2, 33, 64, 5, 12, [0, 2.5, 11], 0.5),
-    (5, 19, 2, 21, 64, 5, 9, [0, 8], 1.0),
-    (2, 14, 2, 13, 32, 7, 9, [0, 3.5, 8], 0.5),
-    (6, 15, 3, 9, 64, 40, 8, [0, 7], 1.0),
-    (6, 19, 4, 7, 32, 3, 8, [0, 7], 1.0),
-    (4, 14, 1, 11, 128, 21, 9, [0, 8], 1.0),         # H = 128, one-layer net: matrices parked in LDS
-    (4, 18, 2, 12, 64, 69, 9, [0, 4, 8], 1.0),       # the K4 channel count
-]
 
 
 @pytest.mark.parametrize('ci', range(len(MIL_NET_BWD_CASES)))
@@ -995,7 +987,7 @@ def test_milstein_backward_through_a_diffusion_net_on_the_mfma_path(ci):
     io, no, NL, B, H, C, L, ts, dt = MIL_NET_BWD_CASES[ci]
     grid = S.engine.step_grid(np.asarray(ts, np.float32), dt, np.arange(L, dtype=np.float32), torch.device(DEV))
     assert S.engine.backward_mode(S.engine.model_struct(C, H, H, NL, io, no), B, L, grid, 'milstein') == 1
-    _check_backward(4500 + ci, io, no, NL, B, H, C, L, ts, dt, 'milstein', 'auto', strict=True)
+    _check_backward(4500 + ci, io, no, NL, B, H, C, L, ts, dt, 'milstein', 'auto', strict=True, expect=K.MIL_NET_KERNELS)
 
 
 @pytest.mark.parametrize('io', [0, 1, 2, 3, 4, 5, 6])
@@ -1037,7 +1029,9 @@ GRAD_TOL_LOOSE = {2009: 5e-4, 4006: 5e-4, 4009: 5e-4, 906: 5e-4, 907: 5e-4,
                   3035: 5e-4}      # (round 6, srk (6,5) on the generic kernels under the SRI2W1 rows: theta's gradient cancels to 0.0027, measured 2.5e-4)
 
 
-def _check_backward(seed, io, no, NL, B, H, C, L, ts, dt, method, kernel, strict=False):
+def _check_backward(seed, io, no, NL, B, H, C, L, ts, dt, method, kernel, strict=False, expect=None):
+    """expect = (forward kernel, adjoint kernel): the only kernels the fused solve may launch and run its backward on, read from
+    the descriptors it launched (tests.helpers.launched_kernels)."""
     times = np.linspace(0, 1, L).astype(np.float32) if ts is None else None
     pr = make_problem(seed, io, no, NL, B, H, C, L, times=times)
     ts = pr['times'] if ts is None else np.asarray(ts, np.float32)
@@ -1067,10 +1061,13 @@ def _check_backward(seed, io, no, NL, B, H, C, L, ts, dt, method, kernel, strict
     (ys_ref * torch.from_numpy(wsum).double()).sum().backward()
 
     m, y0 = build(torch.float32, DEV)
-    ys = S.sdeint(m, y0, torch.from_numpy(ts).to(DEV),
-                  bm=_ReplayBM(torch.from_numpy(dW).to(DEV), None if dU is None else torch.from_numpy(dU).to(DEV)),
-                  method=method, dt=dt, options={'kernel': kernel, 'strict': strict})     # strict: no tensor-op fallback
-    (ys * torch.from_numpy(wsum).to(DEV)).sum().backward()
+    with launched_kernels() as ran:
+        ys = S.sdeint(m, y0, torch.from_numpy(ts).to(DEV),
+                      bm=_ReplayBM(torch.from_numpy(dW).to(DEV), None if dU is None else torch.from_numpy(dU).to(DEV)),
+                      method=method, dt=dt, options={'kernel': kernel, 'strict': strict})     # strict: no tensor-op fallback
+        (ys * torch.from_numpy(wsum).to(DEV)).sum().backward()
+    if expect is not None:
+        assert (ran.fwd, ran.rev) == ([expect[0]], [expect[1]]), (ran.fwd, ran.rev, 'meant', expect)
 
     def close(got, ref, name):
         ref = ref.numpy()
@@ -1491,45 +1488,6 @@ def test_neuralsde_training_step_on_cuda():
 
 
 # ---- SRK (SRID2) ---------------------------------------------------------------------------------------
-SRK_CASES = [
-    # io, no, NL, B, H, C, L, ts, dt
-    (6, 17, 2, 19, 32, 5, 9, [0, 2.5, 8], 0.5),      # torch_ists / tutorial GSDE-SRK flavour
-    (4, 17, 2, 37, 128, 21, 13, [0, 12], 1.0),
-    (2, 16, 1, 9, 16, 2, 12, None, None),            # ts = times = linspace(0,1,12): interpolated outputs
-    (1, 18, 2, 8, 24, 3, 8, [0, 7], 0.5),
-    (3, 15, 3, 8, 16, 4, 8, [0, 7], 1.0),
-    (0, 5, 2, 8, 12, 3, 8, [0, 7], 1.0),
-    (5, 8, 2, 8, 10, 3, 8, [0, 3.5, 7], 0.25),
-    (1, 0, 2, 5, 8, 3, 8, [0, 7], 1.0),
-    (1, 12, 1, 9, 64, 3, 8, [0, 2.5, 7], 1.0),       # MFMA SRK variant: every drift family, H = 16 .. 128, NL 1 .. 4
-    (3, 13, 3, 21, 32, 3, 9, [0, 8], 0.5),
-    (5, 17, 2, 13, 16, 3, 8, [0, 7], 1.0),
-    (4, 16, 4, 9, 64, 21, 9, [0, 4, 8], 1.0),
-    (2, 0, 2, 7, 128, 32, 8, [0, 7], 1.0),
-    (4, 6, 2, 9, 32, 5, 8, [0, 7], 1.0),
-    (1, 2, 2, 9, 64, 3, 8, [0, 3, 7], 0.5),
-    (2, 9, 2, 9, 32, 3, 8, [0, 7], 1.0),
-    (5, 7, 2, 9, 16, 3, 8, [0, 7], 0.5),
-    (4, 17, 2, 9, 256, 14, 9, [0, 3.5, 8], 1.0),     # H = 256 on the MFMA SRK variant (weights streamed)
-    (1, 13, 1, 5, 256, 3, 8, [0, 7], 0.5),
-    (0, 17, 2, 9, 64, 5, 8, [0, 7], 1.0),            # y-free drift and wide control paths on the MFMA SRK variant
-    (0, 4, 1, 6, 128, 21, 8, [0, 3, 7], 0.5),
-    (4, 17, 2, 9, 64, 40, 9, [0, 8], 1.0),
-    (6, 16, 3, 7, 128, 69, 8, [0, 7], 1.0),
-    (2, 12, 1, 9, 32, 33, 8, [0, 2.5, 7], 0.5),
-    (1, 18, 2, 9, 16, 3, 8, [0, 7], 0.5),            # diffusion nets on the MFMA net kernels (snsde_m4n_kernel.h): H = 16 .. 128,
-    (1, 14, 1, 17, 32, 3, 9, [0, 2.5, 8], 0.5),      # one- and two-layer nets, raw = net and net * y, every drift family
-    (3, 18, 2, 33, 64, 5, 12, [0, 2.5, 11], 0.5),
-    (5, 19, 2, 21, 64, 5, 9, [0, 8], 1.0),
-    (4, 19, 2, 21, 128, 21, 10, [0, 9], 1.0),
-    (2, 14, 2, 13, 32, 7, 9, [0, 3.5, 8], 0.5),
-    (6, 15, 3, 9, 64, 40, 8, [0, 7], 1.0),
-    (1, 18, 2, 37, 128, 5, 9, [0, 8], 1.0),          # H = 128: net matrices parked in the waves' LDS slices
-    (3, 18, 3, 11, 128, 5, 9, [0, 8], 0.5),
-    (4, 18, 1, 11, 128, 69, 9, [0, 8], 1.0),         # wide control path (C = 69) with a net
-    (6, 19, 4, 7, 32, 3, 8, [0, 7], 1.0),
-]
-SRK_NET_ROWS = [i for i, c in enumerate(SRK_CASES) if c[1] in (14, 15, 18, 19) and c[4] in (16, 32, 64, 128)]
 
 
 def _draw_dU(seed, dW, ts, dt):
@@ -1572,8 +1530,11 @@ def test_srk_diffusion_nets_take_the_mfma_net_kernels(ci):
     assert S.engine.backward_mode(model, B, L, grid, 'srk') == 1
     dW = draw_dW(700 + ci, ts, dt, B, H)
     dU = _draw_dU(700 + ci, dW, ts, dt)
-    y_auto, _ = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='auto')
-    y_m4, _ = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='mfma4')
+    y_auto, call = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='auto')
+    assert_kernels(call, fwd='w4' if ci in K.SRK_NET_AUTO_W4 else 'm4n')
+    assert (path == 'w4') == (ci in K.SRK_NET_AUTO_W4)
+    y_m4, call = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='mfma4')
+    assert_kernels(call, fwd='m4n')
     if path == 'mfma-srk':
         assert np.array_equal(y_auto, y_m4)
     else:

@@ -7,21 +7,14 @@ import pytest
 import torch
 
 import stable_neural_sdes_amd as S
-from tests.helpers import assert_parity, draw_dW, make_problem
+from tests import kernel_cases as K
+from tests.helpers import assert_kernels, assert_parity, draw_dW, launched_kernels, make_problem
+from tests.kernel_cases import W4_BWD as BWD, W4_CASES, W4_SRK_BWD as SRK_BWD, W4_SRK_CASES as SRK_W4
 from tests.test_gpu_parity import _check_backward, hip_solve, oracle_solve
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda:0'
 
-W4_CASES = [
-    # io, no, NL, B, C, L, ts, dt
-    (3, 18, 2, 37, 5, 9, [0, 3.5, 8], 1.0),          # BASELINE config 4's model; ragged last tile, an interpolated output
-    (1, 14, 1, 9, 3, 8, [0, 7], 0.5),                # one-layer drift, one-layer net, no time features in the drift
-    (5, 19, 2, 21, 3, 9, [0, 8], 1.0),               # geometric drift, raw = net * y
-    (3, 15, 1, 13, 4, 8, [0, 2.5, 7], 1.0),
-    (1, 18, 2, 64, 3, 12, None, None),               # every knot an output, linspace grid
-    (5, 14, 2, 8, 3, 8, [0, 7], 1.0),
-]
 
 
 @pytest.mark.parametrize('ci', range(len(W4_CASES)))
@@ -39,14 +32,18 @@ def test_w4_forward_vs_oracle_and_the_tile_kernels(ci):
     dW = draw_dW(8800 + ci, ts, dt, B, H)
     ref64, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float64)
     cpu32, _ = oracle_solve(pr, ts, dt, dW, 'euler', np.float32)
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, kernel='w4', save_traj=True)
+    ys, call = hip_solve(pr, ts, dt, dW=dW, kernel='w4', save_traj=True)
+    assert_kernels(call, fwd=K.W4_KERNELS['euler']['w4'][0])
     assert ys.shape == ref64.shape
     assert_parity(ys, ref64, cpu32, what=f'w4 case {ci}')
-    y4, _ = hip_solve(pr, ts, dt, dW=dW, kernel='mfma4')
+    y4, call = hip_solve(pr, ts, dt, dW=dW, kernel='mfma4')
+    assert_kernels(call, fwd=K.W4_KERNELS['euler']['mfma4'][0])
     assert np.abs(ys - y4).max() <= 2e-5 * (np.abs(y4).max() + 1.0)
     # in-kernel Philox: the same stream as every other kernel family (global row, step block, column)
-    yp, _ = hip_solve(pr, ts, dt, seed=77, row_offset=5, kernel='w4')
-    yg, _ = hip_solve(pr, ts, dt, seed=77, row_offset=5, kernel='generic')
+    yp, call = hip_solve(pr, ts, dt, seed=77, row_offset=5, kernel='w4')
+    assert_kernels(call, fwd='w4')
+    yg, call = hip_solve(pr, ts, dt, seed=77, row_offset=5, kernel='generic')
+    assert_kernels(call, fwd=K.W4_KERNELS['euler']['generic'][0])
     assert np.isfinite(yp).all() and np.abs(yp - yg).max() <= 2e-4 * (np.abs(yg).max() + 1.0)
     # row shards keep the global stream bit for bit
     half = B // 2
@@ -70,6 +67,7 @@ def test_w4_per_row_outputs_and_trajectory():
     call = S.engine.SolveCall(model, flat, torch.from_numpy(pr['coeffs']).to(DEV), grid, torch.from_numpy(pr['y0']).to(DEV),
                               dW=torch.from_numpy(dW).to(DEV), kernel='w4', row_out=row_out, save_traj=True, save_dW=True)
     ys = call.launch()
+    assert_kernels(call, fwd='w4')
     torch.cuda.synchronize()
     want = ref64[row_out.cpu().numpy(), np.arange(B)]
     assert_parity(ys.cpu().numpy(), want, what='w4 row_out')
@@ -77,14 +75,6 @@ def test_w4_per_row_outputs_and_trajectory():
     np.testing.assert_array_equal(call.dW_out.cpu().numpy(), dW)
 
 
-BWD = [
-    # io, no, NL, B, C, L, ts, dt
-    (3, 18, 2, 21, 5, 9, [0, 3.5, 8], 1.0),
-    (1, 14, 1, 9, 3, 8, [0, 7], 0.5),
-    (5, 19, 2, 13, 3, 9, [0, 8], 1.0),
-    (3, 15, 2, 11, 4, 8, [0, 2.5, 7], 1.0),
-    (1, 18, 1, 10, 3, 8, [0, 7], 1.0),
-]
 
 
 @pytest.mark.parametrize('ci', range(len(BWD)))
@@ -96,22 +86,14 @@ def test_w4_training_saves_drive_the_fused_adjoint(ci):
     grid = S.engine.step_grid(np.asarray(ts, np.float32), dt, np.arange(L, dtype=np.float32), torch.device(DEV))
     model = S.engine.model_struct(C, 64, 64, NL, io, no)
     assert S.engine.forward_path(model, B, L, grid.N) == 'w4' and S.engine.backward_mode(model, B, L, grid, 'euler') == 1
-    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'w4', strict=True)
-    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'auto', strict=True)
-    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'mfma4', strict=True)
+    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'w4', strict=True, expect=K.W4_KERNELS['euler']['w4'])
+    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'auto', strict=True, expect=K.W4_KERNELS['euler']['auto'])
+    _check_backward(8950 + ci, io, no, NL, B, 64, C, L, ts, dt, 'euler', 'mfma4', strict=True, expect=K.W4_KERNELS['euler']['mfma4'])
 
 
 # ---- SRK (SRID2) on the wave pair -------------------------------------------------------------------------------------------------
 from oracle import sde_oracle as O      # noqa: E402
 
-SRK_W4 = [
-    # io, no, NL, B, C, L, ts, dt
-    (3, 18, 2, 37, 5, 9, [0, 3.5, 8], 1.0),          # the README's neuralsde_3_18 under torch_ists' default method
-    (1, 18, 2, 9, 3, 8, [0, 7], 0.5),
-    (5, 19, 2, 21, 3, 9, [0, 8], 1.0),
-    (3, 15, 1, 13, 4, 8, [0, 2.5, 7], 1.0),
-    (1, 14, 2, 16, 3, 12, None, None),
-]
 
 
 def _levy(seed, dW, ts, dt):
@@ -137,12 +119,16 @@ def test_w4_srk_forward_vs_oracle_and_the_tile_kernels(ci):
     dU = _levy(9300 + ci, dW, ts, dt)
     ref64, _ = O.solve_diffusion_model(pr['params'], io, no, pr['coeffs'], pr['times'], pr['y0'], ts, dt, dW, method='srk', dtype=np.float64, dU=dU)
     cpu32, _ = O.solve_diffusion_model(pr['params'], io, no, pr['coeffs'], pr['times'], pr['y0'], ts, dt, dW, method='srk', dtype=np.float32, dU=dU)
-    ys, _ = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='w4')
+    ys, call = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='w4')
+    assert_kernels(call, fwd=K.W4_KERNELS['srk']['w4'][0])
     assert_parity(ys, ref64, cpu32, what=f'w4 srk case {ci}')
-    y4, _ = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='mfma4')
+    y4, call = hip_solve(pr, ts, dt, dW=dW, dU=dU, method='srk', kernel='mfma4')
+    assert_kernels(call, fwd=K.W4_KERNELS['srk']['mfma4'][0])
     assert np.abs(ys - y4).max() <= 5e-5 * (np.abs(y4).max() + 1.0)
-    yp, _ = hip_solve(pr, ts, dt, seed=78, row_offset=3, method='srk', kernel='w4')
-    yg, _ = hip_solve(pr, ts, dt, seed=78, row_offset=3, method='srk', kernel='generic')
+    yp, call = hip_solve(pr, ts, dt, seed=78, row_offset=3, method='srk', kernel='w4')
+    assert_kernels(call, fwd='w4')
+    yg, call = hip_solve(pr, ts, dt, seed=78, row_offset=3, method='srk', kernel='generic')
+    assert_kernels(call, fwd=K.W4_KERNELS['srk']['generic'][0])
     assert np.isfinite(yp).all() and np.abs(yp - yg).max() <= 5e-4 * (np.abs(yg).max() + 1.0)
     half = B // 2
     ya, _ = hip_solve(pr, ts, dt, seed=78, method='srk', kernel='w4')
@@ -151,13 +137,6 @@ def test_w4_srk_forward_vs_oracle_and_the_tile_kernels(ci):
     np.testing.assert_array_equal(np.concatenate([yb0, yb1], axis=1), ya)
 
 
-SRK_BWD = [
-    (3, 18, 2, 21, 5, 9, [0, 3.5, 8], 1.0),
-    (1, 14, 1, 9, 3, 8, [0, 7], 0.5),
-    (5, 19, 2, 13, 3, 9, [0, 8], 1.0),
-    (3, 15, 2, 11, 4, 8, [0, 2.5, 7], 1.0),
-    (1, 18, 1, 10, 3, 8, [0, 7], 1.0),
-]
 
 
 @pytest.mark.parametrize('ci', range(len(SRK_BWD)))
@@ -169,9 +148,9 @@ def test_w4_srk_training_saves_drive_the_fused_srk_adjoint(ci):
     """Forward SRID2 on the wave pair in training mode; backward: under 'w4' / 'auto' the wave-group SRK adjoint with the weight
     gradients inside (snsde_w4_srk_reverse_kernel: stage states from stage_save, no delta planes), under 'mfma4' the tile adjoint +
     weight-gradient pass on the same saves - all against fp64 autograd through the tensor loop."""
-    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'w4', strict=True)
-    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'auto', strict=True)
-    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'mfma4', strict=True)
+    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'w4', strict=True, expect=K.W4_KERNELS['srk']['w4'])
+    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'auto', strict=True, expect=K.W4_KERNELS['srk']['auto'])
+    _check_backward(9350 + ci, io, no, NL, B, 64, C, L, ts, dt, 'srk', 'mfma4', strict=True, expect=K.W4_KERNELS['srk']['mfma4'])
 
 
 @pytest.mark.parametrize('case', [(3, 18, 2, 37, False), (5, 19, 2, 22, True), (1, 14, 1, 9, False), (3, 15, 2, 130, True), (5, 18, 1, 64, False)])
@@ -195,6 +174,7 @@ def test_w4_srk_adjoint_equals_the_tile_adjoint(case):
         call = S.engine.SolveCall(model, flat, torch.from_numpy(pr['coeffs']).to(DEV), grid, torch.from_numpy(pr['y0']).to(DEV), seed=5,
                                   method='srk', kernel=kernel, save_traj=True, save_dW=True, save_act=True)
         assert (call.delta_slots == 0) == fused, (kernel, call.delta_slots)
+        assert_kernels(call, *K.W4_KERNELS['srk'][kernel])
     out = {}
     for kernel in ('auto', 'mfma4'):
         m = S.Diffusion_model(C, H, H, NL, input_option=io, noise_option=no)
@@ -205,9 +185,11 @@ def test_w4_srk_adjoint_equals_the_tile_adjoint(case):
         opts = {'seed': 99, 'kernel': kernel, 'strict': True}
         if ro is not None:
             opts['row_out'] = ro
-        ys = S.sdeint(m, y0, ts, dt=0.5, method='srk', options=opts)
-        w = torch.from_numpy(np.random.default_rng(3).standard_normal(tuple(ys.shape)).astype(np.float32)).to(DEV)
-        (ys * w).sum().backward()
+        with launched_kernels() as ran:
+            ys = S.sdeint(m, y0, ts, dt=0.5, method='srk', options=opts)
+            w = torch.from_numpy(np.random.default_rng(3).standard_normal(tuple(ys.shape)).astype(np.float32)).to(DEV)
+            (ys * w).sum().backward()
+        assert (ran.fwd, ran.rev) == tuple([k] for k in K.W4_KERNELS['srk'][kernel]), (kernel, ran.fwd, ran.rev)
         out[kernel] = (ys.detach(), y0.grad.clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None})
     ya, ga, pa = out['auto']
     yb, gb, pb = out['mfma4']
@@ -228,7 +210,7 @@ def test_w4_adjoints_on_the_shortest_solves_and_smallest_batches(method, case):
     grid = S.engine.step_grid(np.asarray(ts, np.float32), 1.0, np.arange(L, dtype=np.float32), torch.device(DEV))
     model = S.engine.model_struct(C, 64, 64, NL, io, no)
     assert S.engine.forward_path(model, B, L, grid.N, method=method) == 'w4' and grid.N == int(ts[-1])
-    _check_backward(9800 + 10 * B + len(ts), io, no, NL, B, 64, C, L, ts, 1.0, method, 'auto', strict=True)
+    _check_backward(9800 + 10 * B + len(ts), io, no, NL, B, 64, C, L, ts, 1.0, method, 'auto', strict=True, expect=K.W4_KERNELS[method]['auto'])
 
 
 @pytest.mark.parametrize('row_out', [False, True])
@@ -250,9 +232,11 @@ def test_w4_adjoint_with_in_kernel_philox_and_row_outputs_equals_the_tile_adjoin
         opts = {'seed': 99, 'kernel': kernel, 'strict': True}
         if ro is not None:
             opts['row_out'] = ro
-        ys = S.sdeint(m, y0, ts, dt=0.5, method='euler', options=opts)
-        w = torch.from_numpy(np.random.default_rng(3).standard_normal(tuple(ys.shape)).astype(np.float32)).to(DEV)
-        (ys * w).sum().backward()
+        with launched_kernels() as ran:
+            ys = S.sdeint(m, y0, ts, dt=0.5, method='euler', options=opts)
+            w = torch.from_numpy(np.random.default_rng(3).standard_normal(tuple(ys.shape)).astype(np.float32)).to(DEV)
+            (ys * w).sum().backward()
+        assert (ran.fwd, ran.rev) == tuple([k] for k in K.W4_KERNELS['euler'][kernel]), (kernel, ran.fwd, ran.rev)
         out[kernel] = (ys.detach(), y0.grad.clone(), {n: p.grad.clone() for n, p in m.named_parameters() if p.grad is not None})
     ya, ga, pa = out['auto']
     yb, gb, pb = out['mfma4']
@@ -279,6 +263,7 @@ def test_fused_weight_gradients_need_no_delta_planes_and_fall_back_with_them():
     for kernel in ('auto', 'w4', 'mfma4'):
         call = S.engine.SolveCall(model, flat, *args, seed=11, kernel=kernel, save_traj=True, save_dW=True, save_act=True)
         call.launch()
+        assert_kernels(call, *K.W4_KERNELS['euler'][kernel])
         assert (call.delta_slots == 0) == (kernel != 'mfma4'), (kernel, call.delta_slots)
         adj, delta = S.engine.solve_backward(call, g, save_delta=True, adj0_only=True)
         assert (delta is None) == (kernel != 'mfma4')
@@ -290,6 +275,7 @@ def test_fused_weight_gradients_need_no_delta_planes_and_fall_back_with_them():
     seed_dev = torch.tensor([11], dtype=torch.int64, device=DEV)
     call = S.engine.SolveCall(model, flat, *args, seed=seed_dev, save_traj=True, save_dW=True, save_act=True)
     call.launch()
+    assert_kernels(call, 'w4', 'w4_fused')
     assert call.delta_slots == 0
     grads['device key'] = S.engine.backward_with_gradients(call, g)[1]
     ref = grads['mfma4']
