@@ -186,13 +186,33 @@ typedef struct snsde_solve {
     int32_t  method;       /* SNSDE_EULER | SNSDE_MILSTEIN | SNSDE_SRK                           */
     int32_t  kernel;       /* SNSDE_KERNEL_*                                                     */
     int32_t  flags;        /* SNSDE_FLAG_*                                                       */
-    int32_t  reserved;     /* must be 0                                                          */
+    int32_t  members;      /* M: models of one architecture solved by this call (0 or 1: one model, today's behaviour).   */
+                           /* M > 1, a model ensemble (inference only): `batch` counts ALL rows, member-major - row         */
+                           /* r = m Bm + b with Bm = batch / M rows per member; `params` is (M, snsde_param_numel)          */
+                           /* contiguous, member m reads block m; `coeffs` stays (Bm, L-1, 4C) and is shared - row r reads  */
+                           /* coefficient row r - m Bm; y0, ys, dW, dU and row_out stay per row, the Philox counter stays   */
+                           /* (row_offset + r, ..).  Member m's rows equal, bit for bit, the ordinary solve of member m     */
+                           /* alone run as a shard of the whole: members = 0, batch = Bm, params = block m, row_offset +    */
+                           /* m Bm, global_rows = this call's global_rows (or, where that is 0, this call's batch).         */
+                           /* SNSDE_ERR_DIMS: members < 0, batch % M != 0, Bm % 4 != 0 (a 4-row tile never straddles two    */
+                           /* members, and no member has a ragged tail).  SNSDE_ERR_UNSUPPORTED (snsde_backward_supported   */
+                           /* == 0): samples > 1, z0_weight, noise_table, kl_column1 != 0, act_save / stage_save / traj /   */
+                           /* dW_out / dU_out, every backward entry point, snsde_eval_fg.  Kernels: the lean 4-row-tile     */
+                           /* kernel (general, specialised, bf16; Euler / Milstein) and the general MFMA kernel on 4-row    */
+                           /* tiles (Euler, Milstein, SRK); the member is a prologue property of these kernels (their       */
+                           /* launch's second grid axis), not a kernel of its own.  A plan that arrives at any other kernel */
+                           /* (16-row tiles, wave pairs, the diffusion-net kernels, H = 256, the two-tile kernels) is no    */
+                           /* plan: snsde_forward_path == SNSDE_PATH_NONE, the launch is SNSDE_ERR_UNSUPPORTED, and `auto`  */
+                           /* does not fall to the generic family.  The workspace holds one prepared block per member:      */
+                           /* snsde_workspace_bytes = M x (the plan's floats rounded up to a multiple of four, plus the     */
+                           /* 64-float tail of every workspace), so every block starts 16-byte aligned; one prepare launch  */
+                           /* fills all of them and SNSDE_FLAG_REUSE_PREPARED skips it as for one model.                    */
     int64_t  row_offset;   /* global index of local row 0 (batch shards keep the global Philox   */
                            /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
                            /* sees the local batch unless `global_rows` (below) is set           */
     uint64_t seed;         /* Philox key                                                         */
-    const float*   params;    /* device, snsde_param_numel floats                                */
-    const float*   coeffs;    /* device (B, L-1, 4C) = cat[a, b, two_c, three_d]                  */
+    const float*   params;    /* device, snsde_param_numel floats (members = M > 1: M such blocks) */
+    const float*   coeffs;    /* device (B, L-1, 4C) = cat[a, b, two_c, three_d] (members: (B / M, ..)) */
     const float*   step_tab;  /* device (N, SNSDE_STEP_STRIDE)                                   */
     const int32_t* out_step;  /* device (T-1)                                                    */
     const float*   out_w;     /* device (T-1, 2)                                                 */
@@ -282,6 +302,12 @@ typedef struct snsde_solve {
 
 SNSDE_API size_t snsde_workspace_bytes(const snsde_solve* s);
 SNSDE_API int    snsde_solve_forward(const snsde_solve* s, void* hip_stream);
+/* The initial state of a solve with z0_weight / z0_bias as a launch of its own: y0 (B, H, an OUTPUT as there) = z0_weight .
+ * X(ts[0]) + z0_bias, through the device code the forward's prepare launch runs - the same bits.  For callers that need the state
+ * a fused z0_weight solve would start from where the solve itself cannot form it (a model ensemble takes the caller's y0 and
+ * refuses z0_weight: each member's rows are filled by one such call).  Reads model.hidden_channels / input_channels, batch, knots,
+ * coeffs (batch, L-1, 4C), step_tab (row 0), z0_weight, z0_bias and y0 only.  Enqueue-only, no workspace, capturable. */
+SNSDE_API int    snsde_initial_state(const snsde_solve* s, void* hip_stream);
 
 /* ---- backward of the solve (discretise-then-optimise adjoint of the fixed-step scheme) ------
  * Replaces autograd THROUGH the unrolled solver loop (`loss.backward()` in

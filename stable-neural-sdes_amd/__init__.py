@@ -3,10 +3,10 @@ yongkyung-oh/Stable-Neural-SDEs).  See DESIGN.md / INTEGRATION.md."""
 import sys as _sys
 
 from . import _lib, build, controldiffeq, engine, fields, modules, sharding, torchcde, torchsde, train  # noqa: F401
-from .modules import (Diffusion_model, IstsNeuralSDE, NeuralSDE, NeuralSDE_forecasting,  # noqa: F401
+from .modules import (Diffusion_model, Ensemble, IstsNeuralSDE, NeuralSDE, NeuralSDE_forecasting,  # noqa: F401
                       make_sde_model, prepare_sde_solver_kwargs)
 from .engine import sample_stats  # noqa: F401
-from .torchsde import sdeint  # noqa: F401
+from .torchsde import sdeint, sdeint_ensemble  # noqa: F401
 
 __version__ = '0.1.0'
 

@@ -50,7 +50,7 @@ class _Sized(C.Structure):
 class Solve(_Sized):
     _fields_ = [('struct_size', C.c_uint32), ('model', Model), ('batch', C.c_int32), ('knots', C.c_int32), ('n_steps', C.c_int32),
                 ('n_out', C.c_int32), ('method', C.c_int32), ('kernel', C.c_int32), ('flags', C.c_int32),
-                ('reserved', C.c_int32),
+                ('members', C.c_int32),          # models solved by this call (0 / 1: one); batch counts all rows member-major, params is (members, numel)
                 ('row_offset', C.c_int64), ('seed', C.c_uint64),
                 ('params', C.c_void_p), ('coeffs', C.c_void_p), ('step_tab', C.c_void_p),
                 ('out_step', C.c_void_p), ('out_w', C.c_void_p), ('y0', C.c_void_p), ('dW', C.c_void_p),
@@ -102,7 +102,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_natural_cubic_coeffs', 'snsde_hermite_coeffs', 'snsde_param_gradients_workspace_bytes',
            'snsde_param_gradients', 'snsde_backward_with_gradients', 'snsde_forward_path', 'snsde_lean_variant', 'snsde_forward_kernel',
            'snsde_backward_kernel', 'snsde_readout_head', 'snsde_save_layout',
-           'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_coeff_gradients_workspace_bytes',
+           'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_initial_state', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward')
 
@@ -143,6 +143,7 @@ def lib():
     L.snsde_workspace_bytes.argtypes = [C.POINTER(Solve)]
     L.snsde_workspace_bytes.restype = C.c_size_t
     L.snsde_solve_forward.argtypes = [C.POINTER(Solve), C.c_void_p]
+    L.snsde_initial_state.argtypes = [C.POINTER(Solve), C.c_void_p]
     L.snsde_spline_evaluate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.c_int32, C.c_void_p, C.c_void_p]
     L.snsde_eval_fg.argtypes = [C.POINTER(Solve), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]

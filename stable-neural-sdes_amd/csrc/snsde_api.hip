@@ -173,6 +173,19 @@ static bool sampled_training_plan(const snsde_mfma::MfmaPlan& p) {
                                                p.kernel == snsde_mfma::FwdKernel::general_m16);
 }
 
+// members (snsde.h): M models in one call - whole members, each a whole number of 4-row tiles
+static bool members_ok(const snsde_solve* s) {
+    if (s->members < 0) return false;
+    const int32_t M = snsde_members(s);
+    return M == 1 || (s->batch % M == 0 && (s->batch / M) % 4 == 0);
+}
+// ... an inference-only solve of the members' own fields from the caller's initial states: not combined with sample paths, a fused
+// initial network, a supplied diffusion table (one table, M models), the accumulator column or any training-mode plane
+static bool members_refused(const snsde_solve* s) {
+    return snsde_members(s) > 1 && (snsde_samples(s) > 1 || s->z0_weight || s->noise_table || s->kl_column1 != 0 || s->act_save ||
+                                    s->stage_save || s->traj || s->dW_out || s->dU_out);
+}
+
 int snsde_flavor_hint(const snsde_solve* s) {
     if (snsde_solve_variant(s)) return 1;      // tutorial-style fields: 4-row tiles only
     return s->kernel == SNSDE_KERNEL_MFMA_M16 ? 0 : (s->kernel == SNSDE_KERNEL_MFMA_M4 ? 1 : (s->kernel == SNSDE_KERNEL_MFMA_W4 ? 2 : -1));
@@ -189,6 +202,9 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     const int generic = s->method == SNSDE_SRK ? SNSDE_PATH_GENERIC_SRK : SNSDE_PATH_GENERIC;
     if (k < SNSDE_KERNEL_AUTO || k > SNSDE_KERNEL_MFMA_W4) return r;
     if (!samples_ok(s) || !samples_inference_only(s)) return r;
+    // model ensembles: the MFMA kernels that map a tile to its member, or nothing - the generic family is neither a request nor a fallback
+    const bool ensemble = snsde_members(s) > 1;
+    if (!members_ok(s) || members_refused(s) || (ensemble && k == SNSDE_KERNEL_GENERIC)) return r;
     if (variant && (k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16)) return r;   // tutorial-style fields: 4-row tiles or nothing
     // training planes of a sampled solve (SNSDE_FLAG_SAMPLE_GRAD): the MFMA kernels the sampled adjoint route covers, or nothing
     const bool strain = samples_training(s);
@@ -201,7 +217,8 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     // plan made for the whole problem (global_rows) names a kernel this shard cannot run, nor where the plan arrives at a kernel
     // that does not address coeffs by sample group (samples): that is no kernel at all
     r.path = r.plan.ok ? snsde_mfma_path(r.plan)
-                       : (k == SNSDE_KERNEL_AUTO && !variant && !r.plan.shard_refused && !r.plan.samples_refused ? generic : SNSDE_PATH_NONE);
+                       : (k == SNSDE_KERNEL_AUTO && !variant && !r.plan.shard_refused && !r.plan.samples_refused && !ensemble ? generic
+                                                                                                                             : SNSDE_PATH_NONE);
     // bf16 operands: the bf16 lean kernel or nothing (no f32 kernel stands in for it)
     if ((s->flags & SNSDE_FLAG_BF16_OPERANDS) && r.path != SNSDE_PATH_LEAN_BF16) r = ForwardRoute{};
     return r;
@@ -215,6 +232,7 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
     snsde_mfma::BackwardRoute r{};
     const int hint = snsde_flavor_hint(s), k = s->kernel;
     if (!global_rows_ok(s)) return r;
+    if (snsde_members(s) > 1 || !members_ok(s)) return r;      // model ensembles: an inference-only forward, no adjoint and nothing to plan
     const bool sampled = snsde_samples(s) > 1;
     // sample paths: an inference-only forward, no adjoint and nothing to plan - unless SNSDE_FLAG_SAMPLE_GRAD opts in
     if ((sampled && (!sample_grad(s) || (s->flags & SNSDE_FLAG_BF16_OPERANDS))) || !samples_ok(s)) return r;
@@ -433,7 +451,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
     int rc = validate_model(&s->model);
     if (rc) return rc;
     if (s->batch <= 0 || s->knots < 2) return SNSDE_ERR_DIMS;
-    if (!global_rows_ok(s) || !samples_ok(s)) return SNSDE_ERR_DIMS;
+    if (!global_rows_ok(s) || !samples_ok(s) || !members_ok(s)) return SNSDE_ERR_DIMS;
     if (!s->params || !s->coeffs || !s->workspace) return SNSDE_ERR_NULL;
     if (!eval) {
         if (s->n_steps <= 0 || s->n_out < 2) return SNSDE_ERR_DIMS;
@@ -449,6 +467,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
         if ((s->z0_weight != nullptr) != (s->z0_bias != nullptr)) return SNSDE_ERR_NULL;
         if (s->kl_column1 < 0 || s->kl_column1 > s->model.hidden_channels || s->reserved2 != 0) return SNSDE_ERR_DIMS;
         if (!samples_inference_only(s)) return SNSDE_ERR_UNSUPPORTED;
+        if (members_refused(s)) return SNSDE_ERR_UNSUPPORTED;
     }
     return SNSDE_OK;
 }
@@ -461,6 +480,10 @@ size_t snsde_workspace_bytes(const snsde_solve* s) {
     snsde_solve tmp = *s;
     if (tmp.n_steps < 1) tmp.n_steps = 1;
     tmp.samples = 0;      // (the workspace holds weights and tables: nothing per sample, and no plan is refused for the query)
+    tmp.members = 0;
+    // model ensembles: one prepared block per member (snsde_member_ws_stride); where no MFMA kernel plans the model there is no
+    // ensemble launch either, and the query answers as for one model
+    if (const size_t stride = snsde_members(s) > 1 ? snsde_member_ws_stride(&tmp, net) : 0) return (size_t)snsde_members(s) * stride * sizeof(float);
     snsde_generic_workspace_floats(&tmp, net, &f);
     const size_t fm = snsde_mfma_workspace_floats(&tmp, net);
     if (fm > f) f = fm;
@@ -482,6 +505,15 @@ int snsde_solve_forward(const snsde_solve* s, void* hip_stream) {
     if (s->z0_weight && (rc = snsde_z0_launch(s, st)) != SNSDE_OK) return rc;
     if (r.path == SNSDE_PATH_GENERIC_SRK) return snsde_srk_launch(s, net, st);
     return snsde_generic_launch(s, net, st, 0, nullptr, nullptr, nullptr, nullptr);
+}
+
+int snsde_initial_state(const snsde_solve* s, void* hip_stream) {
+    if (!s) return SNSDE_ERR_NULL;
+    if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;
+    if (s->batch <= 0 || s->knots < 2 || s->model.hidden_channels <= 0 || s->model.input_channels <= 0) return SNSDE_ERR_DIMS;
+    if ((int64_t)s->batch * s->model.hidden_channels > INT32_MAX) return SNSDE_ERR_DIMS;      // (the launch counts elements in 32 bits)
+    if (!s->coeffs) return SNSDE_ERR_NULL;
+    return snsde_z0_launch(s, static_cast<hipStream_t>(hip_stream));      // (SNSDE_ERR_NULL without z0_weight, z0_bias, y0 or step_tab)
 }
 
 // Host-only query: the kernel family snsde_solve_forward would launch for this descriptor (needs model, batch, knots,
@@ -563,6 +595,7 @@ int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, f
     if (!step_row || !y || !f_out || !g_out) return SNSDE_ERR_NULL;
     if (snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
     if (snsde_samples(s) > 1) return SNSDE_ERR_UNSUPPORTED;      // (the probe is per input row: y and coeffs row for row)
+    if (snsde_members(s) > 1) return SNSDE_ERR_UNSUPPORTED;      // (... and of one model)
     snsde_solve tmp = *s;
     tmp.n_steps = 1;
     tmp.n_out = 2;
@@ -633,6 +666,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     if (rc) return rc;
     if ((b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) && !bf16_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
     if (snsde_samples(&b->fwd) > 1 && !sample_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (sample paths: inference only without the opt-in)
+    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;                                // (model ensembles: inference only)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;
@@ -681,6 +715,7 @@ int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* wor
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
+    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only)
     if (!b->adj || !b->fwd.traj || !b->fwd.act_save || !b->fwd.workspace)
         return SNSDE_ERR_NULL;
     SnsdeNet net;
@@ -699,6 +734,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
+    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj || !b->fwd.act_save || !b->fwd.workspace)
         return SNSDE_ERR_NULL;
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;

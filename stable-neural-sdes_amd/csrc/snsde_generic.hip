@@ -44,9 +44,12 @@ __global__ void snsde_pack_kernel(const float* __restrict__ params, float* __res
 // (relu applied for 16/17).
 __global__ void snsde_time_table_kernel(const float* __restrict__ params, const float* __restrict__ step_tab,
                                         float* __restrict__ gt, SnsdeLayer nt0, SnsdeLayer nt1, int H, int no,
-                                        int row_stride, int sin_col, int off_sigma = -1, int off_sigma_diag = -1) {
+                                        int row_stride, int sin_col, int off_sigma = -1, int off_sigma_diag = -1,
+                                        size_t param_stride = 0, size_t gt_stride = 0) {
     extern __shared__ float hbuf[];
     const int n = blockIdx.x;   // one block per table row (a solver step, or an SRK stage time)
+    params += blockIdx.y * param_stride;      // blockIdx.y: the member of a model ensemble (one model: gridDim.y == 1)
+    gt += blockIdx.y * gt_stride;
     const float* st = step_tab + (size_t)n * row_stride;
     snsde_time_table_row(params, st[0], st[sin_col], st[sin_col + 1], gt + (size_t)n * H, nt0, nt1, H, no, hbuf, off_sigma,
                          off_sigma_diag);
@@ -1476,10 +1479,11 @@ inline int round4(int x) { return (x + 3) & ~3; }
 }  // namespace
 
 int snsde_time_table_srk_launch(const float* params, const float* srk_tab, float* gt, const SnsdeNet& net, int H, int no,
-                                int n_rows, hipStream_t stream) {
-    // time-only diffusion at the stage times of every step: gt[(n*4 + slot)][H], rows of the SRK stage table
-    hipLaunchKernelGGL(snsde_time_table_kernel, dim3(n_rows), dim3(128), H * sizeof(float), stream, params, srk_tab,
-                       gt, net.nt0, net.nt1, H, no, SNSDE_SRK_STRIDE, 1, net.off_sigma, net.off_sigma_diag);
+                                int n_rows, hipStream_t stream, int members, size_t param_stride, size_t gt_stride) {
+    // time-only diffusion at the stage times of every step: gt[(n*4 + slot)][H], rows of the SRK stage table; one table per member
+    // of a model ensemble (params + m param_stride -> gt + m gt_stride) in the same launch
+    hipLaunchKernelGGL(snsde_time_table_kernel, dim3(n_rows, members), dim3(128), H * sizeof(float), stream, params, srk_tab,
+                       gt, net.nt0, net.nt1, H, no, SNSDE_SRK_STRIDE, 1, net.off_sigma, net.off_sigma_diag, param_stride, gt_stride);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 

@@ -78,6 +78,11 @@ inline int64_t snsde_plan_rows(const snsde_solve* s) { return s->global_rows > 0
 // the division once per lane before the step loop (the MFMA kernels) or per spline item (the generic family).
 inline int32_t snsde_samples(const snsde_solve* s) { return s->samples > 1 ? s->samples : 1; }
 
+// Models solved by one call (snsde_solve::members, 0 = 1): row r belongs to member r / (batch / M) and reads that member's block of
+// `params` and of the prepared workspace, and coefficient row r - m (batch / M).  The forward kernels that take it (the lean kernel
+// and the general MFMA kernel on 4-row tiles) are launched on a (tiles per member, M) grid: the member is blockIdx.y.
+inline int32_t snsde_members(const snsde_solve* s) { return s->members > 1 ? s->members : 1; }
+
 // launchers (snsde_generic.hip)
 int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, size_t* floats);
 int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int eval_mode,
@@ -86,7 +91,7 @@ bool snsde_generic_backward_supported(const snsde_solve* s);
 int snsde_generic_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream);
 int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
 int snsde_time_table_srk_launch(const float* params, const float* srk_tab, float* gt, const SnsdeNet& net, int H, int no,
-                                int n_rows, hipStream_t stream);
+                                int n_rows, hipStream_t stream, int members = 1, size_t param_stride = 0, size_t gt_stride = 0);
 // tile-flavour hint of s->kernel (-1: chosen from the batch, 0: 16-row tiles, 1: 4-row tiles, 2: wave pairs), the same for the
 // forward's route and every backward query (snsde_api.hip)
 int snsde_flavor_hint(const snsde_solve* s);
@@ -97,6 +102,9 @@ snsde_mfma::MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int fl
 snsde_mfma::RevPlan make_rev_plan(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& fp, int flavor_hint);
 int snsde_mfma_path(const snsde_mfma::MfmaPlan& p);
 size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
+// floats from one member's prepared block to the next (snsde_solve::members > 1): the plan's floats rounded up to a multiple of four
+// (every f32x4 load of a block stays 16-byte aligned) plus the 64-float tail of every workspace; 0: no MFMA plan
+size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net);
 int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream);
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)

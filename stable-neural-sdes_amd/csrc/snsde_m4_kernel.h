@@ -437,7 +437,12 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 3, s = (lane >> 2) & 3, q = lane >> 4;
     const int fo = wave * 16 + 4 * q + s;                 // the state / activation element this lane owns (row r)
-    const int row0 = blockIdx.x * 4;
+    // model ensembles: blockIdx.y is the member (MfmaArgs::members; one model: 0) - its first row, its parameter and workspace blocks
+    const uint32_t mem = blockIdx.y;
+    const int mrow0 = (int)mem * a.member_rows;
+    const int row0 = mrow0 + blockIdx.x * 4;
+    const float* const params = a.params + (size_t)mem * a.param_stride;
+    const float* const ws = a.ws + (size_t)mem * a.ws_stride;
     const int B = a.B, C = a.C, N = a.N;
     const int row = row0 + r;
     const bool row_ok = row < B;
@@ -456,16 +461,16 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     int li = 0;
     LeanWt<BF, (KUXT > 0 ? KUXT : 1)> wxt;
     LeanWt<BF, KUH> wy, wh[NHID > 0 ? NHID : 1], wo;
-    if constexpr (KUXT > 0) lean_load_w<KUXT>(wxt, a.ws + a.w_off[li++], wave, lane);
-    if constexpr (YIN) lean_load_w<KUH>(wy, a.ws + a.w_off[li++], wave, lane);
+    if constexpr (KUXT > 0) lean_load_w<KUXT>(wxt, ws + a.w_off[li++], wave, lane);
+    if constexpr (YIN) lean_load_w<KUH>(wy, ws + a.w_off[li++], wave, lane);
 #pragma unroll
-    for (int l = 0; l < NHID; ++l) lean_load_w<KUH>(wh[l], a.ws + a.w_off[li++], wave, lane);
-    lean_load_w<KUH>(wo, a.ws + a.w_off[li++], wave, lane);
+    for (int l = 0; l < NHID; ++l) lean_load_w<KUH>(wh[l], ws + a.w_off[li++], wave, lane);
+    lean_load_w<KUH>(wo, ws + a.w_off[li++], wave, lane);
     f32x4 bfr[CF::NLAYER];                                 // accumulator init: the bias in the k-slot 0 lanes, 0 elsewhere
 #pragma unroll
     for (int l = 0; l < CF::NLAYER; ++l)
 #pragma unroll
-        for (int i = 0; i < 4; ++i) bfr[l][i] = (s == 0) ? a.ws[a.bias_off + l * H + wave * 16 + 4 * q + i] : 0.0f;
+        for (int i = 0; i < 4; ++i) bfr[l][i] = (s == 0) ? ws[a.bias_off + l * H + wave * 16 + 4 * q + i] : 0.0f;
 
     // ---- LDS init; the step table is re-cut into the two quads per step this kernel reads -------------------------
     for (int i = tid; i < 4 * (LDY + XS * LDX + 2 * LDA); i += NT) lds[i] = 0.0f;
@@ -481,10 +486,10 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     fill_rows(0);
     __syncthreads();
 
-    const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
+    const float sig_theta = snsde_sigmoid(params[a.off_theta]);
     const int no = a.no;
     const bool tab = SP || a.gt_off >= 0;
-    const float* gt = a.gt_ext ? a.gt_ext : a.ws + (tab ? a.gt_off : 0);
+    const float* gt = a.gt_ext ? a.gt_ext : ws + (tab ? a.gt_off : 0);
     const bool mul_y = SP || (no == 13 || no == 17 || no == 3 || no == 6 || no == 11);
     const bool yfun = !SP && (no >= 7 && no <= 10);
     const bool mil = !SP && a.method == SNSDE_MILSTEIN;
@@ -517,8 +522,10 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     // sample paths (MfmaArgs::samples = S): path p reads coeffs row p / S.  srow0 = row0 / S is the tile's first coeffs row; tile
     // row gr reads row (row0 + gr) / S = srow0 + (srem0 + gr) / S, and srem0 < S, gr <= 3: at most three subtractions, no division
     // per lane.  S = 1: srow0 = row0, srem0 = 0, the offset is gr itself.
+    // model ensembles: the tile's coefficient rows count from its member's first row (crow0; one model: row0 itself)
     const uint32_t S = (uint32_t)a.samples;
-    const uint32_t srow0 = (uint32_t)row0 / S, srem0 = (uint32_t)row0 - srow0 * S;
+    const uint32_t crow0 = (uint32_t)(row0 - mrow0);
+    const uint32_t srow0 = crow0 / S, srem0 = crow0 - srow0 * S;
 #pragma unroll
     for (int i = 0; i < CF::XI; ++i) {
         const int li_ = SP ? (lane & 15) : lane + 64 * i, it = wave * xquota + li_;
@@ -864,8 +871,9 @@ int launch_lean(const MfmaArgs& a, hipStream_t stream) {
     const size_t lds_bytes = (size_t)CF::LDS_FLOATS * sizeof(float) + LT_LDS_EXTRA;
     static SnsdeLdsAttr lds_attr;   // per instantiation and device
     if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_m4_kernel<CF>), lds_bytes, lds_attr)) return rc;
-    const int grid = (a.B + 3) / 4;
-    hipLaunchKernelGGL(snsde_m4_kernel<CF>, dim3(grid), dim3(CF::NT), lds_bytes, stream, a);
+    const int members = a.members > 1 ? a.members : 1;      // (model ensembles: tiles of a member x members; one model: a grid of one row)
+    const int grid = ((members > 1 ? a.member_rows : a.B) + 3) / 4;
+    hipLaunchKernelGGL(snsde_m4_kernel<CF>, dim3(grid, members), dim3(CF::NT), lds_bytes, stream, a);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 

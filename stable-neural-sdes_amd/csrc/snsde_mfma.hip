@@ -221,8 +221,14 @@ __global__ void snsde_fold_kernel(const float* __restrict__ params, float* __res
 
 // Forward prepare in ONE launch: blockIdx.y 0/1 = folded products (written to the temp the backward reads AND to their
 // packed fragments), 2 = time-only diffusion table, 3 + l = packing of layer l (16 blocks each).
-__global__ void snsde_prepare_kernel(const float* __restrict__ params, float* __restrict__ ws, FoldJob fj, MfmaPackJob job) {
+// blockIdx.z = the member of a model ensemble (snsde_solve::members; one model: gridDim.z == 1): it prepares params + z param_stride
+// into ws + z ws_stride, every offset inside a block as for one model.  (The strides follow the job structs: the kernarg offsets
+// of their `layer` arrays, PREP_JOB_OFF, are what snsde_kernarg_element reads.)
+__global__ void snsde_prepare_kernel(const float* __restrict__ params, float* __restrict__ ws, FoldJob fj, MfmaPackJob job,
+                                     uint32_t param_stride, uint32_t ws_stride) {
     extern __shared__ float erow[];
+    params += (size_t)blockIdx.z * param_stride;
+    ws += (size_t)blockIdx.z * ws_stride;
     if (blockIdx.y < 3) {
         const MfmaLayerPack L = snsde_kernarg_element<MfmaLayerPack>(PREP_JOB_OFF + offsetof(MfmaPackJob, layer), blockIdx.y < 2 ? blockIdx.y : 0);
         fold_block(params, ws, fj, fj.fold_on ? &job : nullptr, &L, erow);
@@ -484,6 +490,12 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
         (io == 2 || io == 4 || io == 6) && m.input_channels > 0 && (no == 3 || no == 6 || no == 11 || no == 13 || no == 17) &&
         s->method == SNSDE_EULER && !s->dW && s->kl_column1 == 0)
         p.LEAN_SPEC = io == 6 ? 2 : 1;
+    // model ensembles (snsde_solve::members): the kernels that map a tile to its member in their prologue - the lean kernel and the
+    // general kernel, 4-row tiles (a tile never straddles two members) - or no plan
+    if (snsde_members(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4) {
+        p.members_refused = true;
+        return p;
+    }
     // sample paths (snsde_solve::samples): the kernels that map path p to coeffs row p / S in their prologue, or no plan
     if (snsde_samples(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4 &&
         p.kernel != FwdKernel::general_m16) {
@@ -625,9 +637,25 @@ size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net) {
     return need;
 }
 
+size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net) {
+    snsde_solve tmp = *s;      // the block of one model: sized as snsde_workspace_bytes sizes it, whichever tile flavour a launch selects
+    if (tmp.n_steps < 1) tmp.n_steps = 1;
+    tmp.samples = 0; tmp.members = 0;
+    const size_t f = snsde_mfma_workspace_floats(&tmp, net);
+    return f ? ((f + 3) & ~(size_t)3) + 64 : 0;
+}
+
 int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& p, hipStream_t stream) {
     if (!p.ok) return SNSDE_ERR_UNSUPPORTED;
     float* ws = static_cast<float*>(s->workspace);
+    // model ensembles: one prepared block per member, M parameter blocks (one model: one block, strides unused)
+    const int members = snsde_members(s);
+    const size_t ws_stride = members > 1 ? snsde_member_ws_stride(s, net) : 0;
+    const int64_t param_stride = members > 1 ? snsde_param_numel(&s->model) : 0;
+    if (members > 65535) return SNSDE_ERR_UNSUPPORTED;      // (the member is the kernels' second grid axis)
+    if (members > 1 && (ws_stride == 0 || ws_stride >= (1ull << 32) || param_stride <= 0 || param_stride >= (1ll << 32) ||
+                        (size_t)p.total_floats > ws_stride))
+        return SNSDE_ERR_UNSUPPORTED;
     const bool w4 = p.kernel == FwdKernel::w4;
     if (w4 && !s->act_save) {
         // inference on the wave-owns-rows kernel: it reads the nn.Linear layout of `params` itself - no packing, no tables
@@ -665,16 +693,18 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
                 if (gz > 2048) gz = 2048;
                 if (gz > gx) gx = gz;
             }
-            hipLaunchKernelGGL(snsde_prepare_kernel, dim3(gx, 3 + p.n_layers + (s->z0_weight ? 1 : 0)), dim3(256),
-                               2 * p.H * sizeof(float), stream, s->params, ws, fj, job);
+            hipLaunchKernelGGL(snsde_prepare_kernel, dim3(gx, 3 + p.n_layers + (s->z0_weight ? 1 : 0), members), dim3(256),
+                               2 * p.H * sizeof(float), stream, s->params, ws, fj, job, (uint32_t)param_stride, (uint32_t)ws_stride);
         }
         if (p.SRK) {
             if (!s->srk_tab) return SNSDE_ERR_NULL;
+            // (the pass table does not depend on the parameters: written once, into block 0, which every member's tiles read)
             hipLaunchKernelGGL(snsde_srk_expand_kernel, dim3((3 * s->n_steps + 127) / 128), dim3(128), 0, stream, s->step_tab,
                                s->srk_tab, ws + p.srk_tab_off, s->n_steps, s->model.time_feature == SNSDE_TIME_RAW ? 1 : 0);
             if (p.gt_off >= 0 && !s->noise_table) {
                 const int rc = snsde_time_table_srk_launch(s->params, s->srk_tab, ws + p.gt_off, net, p.H,
-                                                           s->model.noise_option, s->n_steps * 4, stream);
+                                                           s->model.noise_option, s->n_steps * 4, stream, members,
+                                                           (size_t)param_stride, ws_stride);
                 if (rc) return rc;
             }
         }
@@ -695,6 +725,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         a.raw_time = s->model.time_feature; a.gt_ext = s->noise_table;       // (N, 4, H): the table at the four stage times
     }
     a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.samples = snsde_samples(s);
+    a.members = members; a.member_rows = members > 1 ? s->batch / members : 0; a.param_stride = (uint32_t)param_stride; a.ws_stride = (uint32_t)ws_stride;
     a.acc_col = s->kl_column1 - 1; a.acc_a = s->kl_prior_a; a.acc_b = s->kl_prior_b;
     a.B = s->batch; a.L = s->knots; a.C = s->model.input_channels; a.N = s->n_steps; a.T = s->n_out;
     a.method = s->method; a.no = s->model.noise_option;

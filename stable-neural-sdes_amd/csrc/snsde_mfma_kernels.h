@@ -100,6 +100,13 @@ struct MfmaArgs {
     float acc_a, acc_b;                     // its linear prior drift a y + b
     int32_t samples;                        // paths per input row, >= 1 (snsde_solve::samples): path p reads coeffs row p / samples;
                                             // read by the lean and the general kernel only (make_plan refuses the others)
+    // model ensembles (snsde_solve::members = M > 1): the member is the launch's second grid axis, m = blockIdx.y (one model: a
+    // grid of one row, m = 0 and the strides are 0) - tile blockIdx.x of member m covers rows m member_rows + 4 blockIdx.x .., reads
+    // params + m param_stride, ws + m ws_stride and coefficient rows counted from the member's first row.  No division and no branch:
+    // a `row0 / member_rows` behind a uniform test put a dependent kernarg load in front of every other load of the prologue.  Read by
+    // the lean kernel and the general kernel only (make_plan refuses the others for M > 1), once per workgroup before the step loop
+    int32_t members, member_rows;           // member_rows: rows per member (batch / M; one model: unused, m = 0)
+    uint32_t param_stride, ws_stride;       // floats
 };
 
 __host__ __device__ constexpr int ld_for(int K, int pad) { return ((K - pad + 63) / 64) * 64 + pad; }
@@ -423,7 +430,12 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     const int r = FL ? (lane & 3) : (lane & 15);          // batch row within the tile
     const int s = FL ? ((lane >> 2) & 3) : (lane >> 4);   // k-slot
     const int fsub = FL ? 4 * (lane >> 4) : 4 * s;        // first feature (within a 16-feature tile) of the D fragment
-    const int row0 = blockIdx.x * M;
+    // model ensembles: blockIdx.y is the member (MfmaArgs::members; one model: 0) - its first row, its parameter and workspace blocks
+    const uint32_t mem = blockIdx.y;
+    const int mrow0 = (int)mem * a.member_rows;
+    const int row0 = mrow0 + blockIdx.x * M;
+    const float* const params = a.params + (size_t)mem * a.param_stride;
+    const float* const ws = a.ws + (size_t)mem * a.ws_stride;
     float* zstash = zstash_all + wave * CF::ZSTASH;
     const int B = a.B, C = a.C;
     const int row = row0 + r;
@@ -440,23 +452,23 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     Wt<CF::STREAM, KUH, TPW> wo;
     Wt<CF::STREAM, (CF::NN > 0) ? CF::KUN : 1, TPW> wn0;
     Wt<CF::STREAM, (CF::NN > 1) ? KUH : 1, TPW> wn1;
-    if constexpr (CF::USEX) wx.load(a.ws + a.w_off[li++], wave, lane);
-    if constexpr (!CF::IO0) wy.load(a.ws + a.w_off[li++], wave, lane);
-    if constexpr (CF::EMB && !CF::FOLD) we.load(a.ws + a.w_off[li++], wave, lane);
+    if constexpr (CF::USEX) wx.load(ws + a.w_off[li++], wave, lane);
+    if constexpr (!CF::IO0) wy.load(ws + a.w_off[li++], wave, lane);
+    if constexpr (CF::EMB && !CF::FOLD) we.load(ws + a.w_off[li++], wave, lane);
 #pragma unroll
-    for (int l = 0; l < NHID; ++l) wh[l].load(a.ws + a.w_off[li++], wave, lane);
-    wo.load(a.ws + a.w_off[li++], wave, lane);
-    if constexpr (CF::NN > 0) wn0.load(a.ws + a.w_off[li++], wave, lane);
-    if constexpr (CF::NN > 1) wn1.load(a.ws + a.w_off[li++], wave, lane);
+    for (int l = 0; l < NHID; ++l) wh[l].load(ws + a.w_off[li++], wave, lane);
+    wo.load(ws + a.w_off[li++], wave, lane);
+    if constexpr (CF::NN > 0) wn0.load(ws + a.w_off[li++], wave, lane);
+    if constexpr (CF::NN > 1) wn1.load(ws + a.w_off[li++], wave, lane);
 
     // ---- LDS init ------------------------------------------------------------------------------
     for (int i = tid; i < M * (LDY + LDX + LDC + 3 * LDA); i += NT) lds[i] = 0.0f;
-    for (int i = tid; i < CF::NLAYER * H; i += NT) bias[i] = a.ws[a.bias_off + i];
+    for (int i = tid; i < CF::NLAYER * H; i += NT) bias[i] = ws[a.bias_off + i];
     __syncthreads();
 
-    const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
+    const float sig_theta = snsde_sigmoid(params[a.off_theta]);
     const int no = a.no;
-    const float* gt = a.gt_ext ? a.gt_ext : a.ws + a.gt_off;     // (a caller-supplied time-only table: field variants)
+    const float* gt = a.gt_ext ? a.gt_ext : ws + a.gt_off;     // (a caller-supplied time-only table: field variants)
 
     // owned state: tile t covers features 32*wave.. ; element e of this lane = feature f0(t) + fsub + (FL ? s : e)
     float yv[TPW][EPT];
@@ -495,7 +507,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
         xr[i] = it / C; xc[i] = it - xr[i] * C;
         xok[i] = CF::USEX && it < M * C;
         if (!xok[i]) { xr[i] = 0; xc[i] = 0; }
-        const int rp = row0 + xr[i] < B ? row0 + xr[i] : B - 1;
+        const int rp = (row0 + xr[i] < B ? row0 + xr[i] : B - 1) - mrow0;
         xs[i] = a.samples > 1 ? (int)((uint32_t)rp / (uint32_t)a.samples) : rp;
     }
     auto load_coeffs = [&](int idx) {
@@ -545,7 +557,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     // M4: the layer's bias is added after the k-slot reduction, from a register (one value per lane and layer)
     float bias_own[CF::NLAYER];
 #pragma unroll
-    for (int l = 0; l < CF::NLAYER; ++l) bias_own[l] = FL ? a.ws[a.bias_off + l * H + wave * 16 + fsub + s] : 0.0f;
+    for (int l = 0; l < CF::NLAYER; ++l) bias_own[l] = FL ? ws[a.bias_off + l * H + wave * 16 + fsub + s] : 0.0f;
     auto finish = [&](int lyr, f32x4 v) { return m4_reduce_scatter(v) + bias_own[lyr]; };   // M4: this lane's output
     auto store_frag = [&](float* buf, int ld, int col0, f32x4 v, bool relu, int save_slot, int lyr) {
         if constexpr (FL) {
@@ -1020,8 +1032,9 @@ int launch_cfg(const MfmaArgs& a, hipStream_t stream) {
     const size_t lds_bytes = (size_t)(a.dW ? CF::LDS_BASE : CF::LDS_FLOATS) * sizeof(float);
     static SnsdeLdsAttr lds_attr;   // per instantiation and device
     if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_mfma_kernel<CF>), lds_bytes, lds_attr)) return rc;
-    const int grid = (a.B + CF::M - 1) / CF::M;
-    hipLaunchKernelGGL(snsde_mfma_kernel<CF>, dim3(grid), dim3(CF::NT), lds_bytes, stream, a);
+    const int members = a.members > 1 ? a.members : 1;      // (model ensembles: tiles of a member x members; one model: a grid of one row)
+    const int grid = ((members > 1 ? a.member_rows : a.B) + CF::M - 1) / CF::M;
+    hipLaunchKernelGGL(snsde_mfma_kernel<CF>, dim3(grid, members), dim3(CF::NT), lds_bytes, stream, a);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
@@ -1819,6 +1832,7 @@ struct MfmaPlan {
                            // the route is then "no kernel" (SNSDE_ERR_UNSUPPORTED), never the generic family in its place
     bool samples_refused;  // !ok because the plan arrived at a kernel that does not map paths to input rows (snsde_solve::samples):
                            // "no kernel" as well
+    bool members_refused;  // !ok because the plan arrived at a kernel that does not map rows to members (snsde_solve::members): the same
     FwdKernel kernel;
     int H, KUX, NHID, IO, FL, TPW, NW, FOLD, NN, SRK;
     int LEAN, KUXT;    // lean M4 kernel (snsde_m4_kernel.h) and its 16-wide k-blocks of [X(t) | sin t, cos t]

@@ -201,18 +201,16 @@ def check_sample_grad(sample_grad):
     return sample_grad
 
 
-def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
-                 row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False):
-    """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
-    whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
-    samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
-    at does not map paths to input rows.  sample_grad: SNSDE_FLAG_SAMPLE_GRAD; training: the solve writes its training planes
-    (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers; a bf16 solve under bf16_grad
-    only: SNSDE_FLAG_BF16_GRAD)."""
+def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
+                     row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
+                     members=0):
+    """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
+    device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
     s = _lib.Solve()
     s.model = model
     s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
     s.row_offset, s.global_rows, s.samples = int(row_offset), int(global_rows), int(samples)
+    s.members = int(members)
     s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
     s.kernel = _lib.KERNELS[kernel]
     s.flags = precision_flags(precision, bf16_grad) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
@@ -220,6 +218,21 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
+    return s
+
+
+def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
+                 row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
+                 members=0):
+    """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
+    whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
+    samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
+    at does not map paths to input rows.  sample_grad: SNSDE_FLAG_SAMPLE_GRAD; training: the solve writes its training planes
+    (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers; a bf16 solve under bf16_grad
+    only: SNSDE_FLAG_BF16_GRAD).  members: models of one architecture in the call (include/snsde.h; `batch` then counts the rows
+    of all members); 'none' where the plan arrives at a kernel that does not map rows to members."""
+    s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
+                         exact_order, sample_grad, training, bf16_grad, members)
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
 
@@ -531,7 +544,7 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False):
+                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -543,9 +556,19 @@ class SolveCall:
             raise ValueError(f'samples={samples!r}: the {B} rows of y0 are paths, a whole number of groups of `samples` per input row')
         if S > 1 and (((save_traj or save_dW or save_act) and not sample_grad) or z0_linear is not None):
             raise ValueError('samples > 1 is inference only: no saved trajectory, increments or activations, and y0 is the caller\'s')
+        # members = M > 1 (a model ensemble, inference): flat_params is (M, numel), y0 / dW / dU / row_out and the result hold the rows
+        # of all members, member-major (B = M Bm rows), coeffs is the members' shared control path (Bm rows)
+        M = int(members) if members else 1
+        if M < 1 or B % M or (M > 1 and (B // M) % 4):
+            raise ValueError(f'members={members!r}: the {B} rows of y0 are those of all members, each a whole number of 4-row tiles')
+        if M > 1 and (S > 1 or save_traj or save_dW or save_act or z0_linear is not None or noise_table is not None or kl_column is not None):
+            raise ValueError('members > 1 is inference only: no samples, saved planes, fused initial network, supplied noise table or '
+                             'accumulator column')
         _check_f32('y0', y0, (B, model.hidden_channels))
-        _check_f32('coeffs', coeffs, (B // S, L - 1, 4 * C_))
+        _check_f32('coeffs', coeffs, (B // S // M, L - 1, 4 * C_))
         _check_f32('params', flat_params)
+        if M > 1 and tuple(flat_params.shape) != (M, _lib.param_layout(model)[1]):
+            raise ValueError(f'params has shape {tuple(flat_params.shape)}, expected (members, numel) = {(M, _lib.param_layout(model)[1])}')
         if dW is not None:
             _check_f32('dW', dW, (grid.N, B, H))
         self.model, self.grid = model, grid
@@ -594,6 +617,7 @@ class SolveCall:
         # rows of the whole problem this solve is a batch shard of (0: it is the whole problem): what the library plans its kernels from
         s.global_rows = resolve_global_rows(global_rows, B, row_offset)
         s.samples = S if S > 1 else 0
+        s.members = M if M > 1 else 0
         if kl_column is not None:     # (column, a, b): path-integral accumulator column with the linear prior drift a y + b (snsde.h)
             s.kl_column1, s.kl_prior_a, s.kl_prior_b = int(kl_column[0]) + 1, float(kl_column[1]), float(kl_column[2])
         # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised
@@ -601,7 +625,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16')
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M)
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -663,9 +687,9 @@ class SolveCall:
 
 
 def lean_variant(call):
-    """Which instantiation of the lean kernel the call's forward launches: 'general' (the field's options tested at run time),
+    """Which instantiation of the lean kernel the forward of a SolveCall (or a _lib.Solve descriptor) launches: 'general' (the field's options tested at run time),
     'specialised' (compiled for exactly those options, csrc/snsde_m4_kernel.h: CfgSpec) or 'none' (another kernel)."""
-    return _lib.LEAN_VARIANTS[_lib.lib().snsde_lean_variant(C.byref(call.desc))]
+    return _lib.LEAN_VARIANTS[_lib.lib().snsde_lean_variant(C.byref(_desc(call)))]
 
 
 def _desc(call_or_desc):
@@ -868,6 +892,26 @@ def coeff_gradients(call, adj, delta, stream=None):
                'snsde_coeff_gradients')
     call.keep_cg = (ws, adj, delta)
     return grad
+
+
+def initial_state(weight, bias, coeffs, grid):
+    """weight . X(ts[0]) + bias, (B, H), through the device code a fused z0_linear solve starts from (snsde_initial_state): the
+    same bits as that solve's own initial state, which the tensor-op form `linear(X.evaluate(ts[0]))` only approximates.  weight
+    (H, C), bias (H), coeffs (B, L-1, 4C): contiguous float32 CUDA tensors; grid: the solve's StepGrid."""
+    H, C_ = weight.shape
+    B, L = coeffs.shape[0], coeffs.shape[1] + 1
+    _check_f32('z0 weight', weight, (H, C_))
+    _check_f32('z0 bias', bias, (H,))
+    _check_f32('coeffs', coeffs, (B, L - 1, 4 * C_))
+    y0 = torch.empty((B, H), device=coeffs.device, dtype=torch.float32)
+    s = _lib.Solve()
+    s.model.hidden_channels, s.model.input_channels = H, C_
+    s.batch, s.knots = B, L
+    s.coeffs, s.step_tab, s.y0 = _ptr(coeffs), _ptr(grid.d_step_tab), _ptr(y0)
+    s.z0_weight, s.z0_bias = _ptr(weight), _ptr(bias)
+    stream = torch.cuda.current_stream(coeffs.device)
+    _lib.check(_lib.lib().snsde_initial_state(C.byref(s), C.c_void_p(stream.cuda_stream)), 'snsde_initial_state')
+    return y0
 
 
 def eval_fg(model, flat_params, coeffs, times_host, t, y, kernel='auto'):

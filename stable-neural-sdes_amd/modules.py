@@ -339,6 +339,113 @@ class IstsNeuralSDE(_SDEHead):
         return self._readout(z), z
 
 
+class Ensemble(nn.Module):
+    """M wrappers of one class (NeuralSDE, NeuralSDE_forecasting or IstsNeuralSDE) and one architecture evaluated on one batch
+    together: the call signature is the wrapper's own, every result gains a leading axis of size M.
+
+    Each member's initial state is its own (its `initial_network` on the shared control path, or the caller's z0[m]), ONE
+    torchsde.sdeint_ensemble runs over the members' `func` - a single fused solve where the library plans it, the M ordinary solves
+    otherwise - and each member's own readout follows.  Inference: in eval() and under no_grad the output equals calling the M
+    wrappers one after the other with options={'seed': s, 'row_offset': m B, 'global_rows': M B}, bit for bit (member m's rows are
+    rows m B .. of an M B-row problem).  Training through an ensemble is not built: sdeint_ensemble raises under autograd."""
+
+    KINDS = ()      # (the three wrapper classes: filled below, once they are all defined)
+
+    def __init__(self, models):
+        super().__init__()
+        models = list(models)
+        if not models or type(models[0]) not in self.KINDS or any(type(m) is not type(models[0]) for m in models):
+            raise ValueError("Ensemble takes one or more wrappers of ONE class: NeuralSDE, NeuralSDE_forecasting or IstsNeuralSDE")
+        first = models[0]
+        for m in models[1:]:
+            if (m.initial != first.initial or m.initial_network.weight.shape != first.initial_network.weight.shape
+                    or getattr(m, 'output_time', None) != getattr(first, 'output_time', None)):
+                raise ValueError("the members of an Ensemble have one architecture (same channels, same `initial`, same output_time)")
+        self.models = nn.ModuleList(models)
+
+    def __len__(self):
+        return len(self.models)
+
+    def _member_z0(self, m, times, z0, kwargs, dt):
+        """Member m's initial state, with the bits the member's own call would start from: where that call hands its
+        `initial_network` to the fused solve (_SDEHead._initial_state, and the solve takes it: torchsde._sdeint_hip), the library's
+        stand-alone form of the same launch (engine.initial_state); everywhere else `_prepare_initial_state`."""
+        func, lin = m.func, m.initial_network
+        state, kw = m._initial_state(times, z0, {'options': kwargs.get('options')})
+        opts = kw.get('options') or {}
+        if 'z0_linear' not in opts:
+            return state
+        method, kernel = kwargs['method'], opts.get('kernel', 'auto')
+        coeffs = func.coeffs
+        fused = (opts.get('backend', 'auto') != 'torch' and kwargs.get('bm') is None and kernel == 'auto' and lin.bias is not None
+                 and lin.weight.is_contiguous() and lin.bias.dtype == torch.float32 and coeffs.dim() == 3
+                 and tuple(lin.weight.shape) == (func.hidden_channels, func.input_channels))
+        if fused:
+            grid = engine.step_grid(_HostTimes.get(times), dt, _HostTimes.get(func.times), coeffs.device)
+            # (a hidden size the member's solve zero-pads starts from the tensor-op state: torchsde._sdeint_hip)
+            fused = not (opts.get('precision', 'fp32') == 'fp32' and
+                         engine.padding_plan(engine.recognise(func)[0], int(coeffs.shape[0]), int(coeffs.shape[1]) + 1, grid.N, method) is not None)
+        if not fused:
+            return m._prepare_initial_state(times, None)
+        return engine.initial_state(lin.weight.detach(), lin.bias.detach().contiguous(),
+                                    coeffs.detach().to(torch.float32).contiguous(), grid)
+
+    def _solve(self, times, ts, z0, kwargs, row_out=None, zero_state=False):
+        """(T, M, B, H) - (M, B, H) with row_out - of the members' fields from their own initial states."""
+        head = self.models[0]
+        kwargs, dt = prepare_sde_solver_kwargs(times, kwargs, default_method=head.default_method,
+                                               respect_euler_grid=head.respect_euler_grid)
+        extra = set(kwargs) - {'method', 'options', 'bm', 'dt'}
+        if extra:
+            raise ValueError(f"Ensemble does not take the solver arguments {sorted(extra)}")
+        if zero_state:      # (IstsNeuralSDE with initial=False: nsde_model.py's zero control value)
+            z0s = [m.initial_network(torch.zeros_like(m.func.X.evaluate(times[0]))) for m in self.models]
+        else:
+            z0s = [self._member_z0(m, times, None if z0 is None else z0[i], kwargs, dt) for i, m in enumerate(self.models)]
+        options = dict(kwargs.get('options') or {})
+        if row_out is not None:
+            options['row_out'] = row_out
+        return _torchsde.sdeint_ensemble([m.func for m in self.models], torch.stack(z0s), ts, bm=kwargs.get('bm'),
+                                         method=kwargs['method'], dt=kwargs.get('dt', dt), options=options)
+
+    def forward(self, *args, **kwargs):
+        kind = type(self.models[0])
+        if kind is IstsNeuralSDE:
+            return self._forward_ists(*args, **kwargs)
+        return self._forward_benchmark(kind is NeuralSDE_forecasting, *args, **kwargs)
+
+    def _forward_benchmark(self, forecasting, times, coeffs, final_index, z0=None, stream=False, **kwargs):
+        models = self.models
+        control = (torch.cat(coeffs, dim=-1),) if forecasting else tuple(coeffs)      # (one control path, the same tensors for all)
+        for m in models:
+            m.func.set_X(*control, times)
+        if forecasting:
+            ys = self._solve(times, times, z0, kwargs)
+            zs = [ys[:, i].contiguous().movedim(0, -2) for i in range(len(models))]
+            return torch.stack([m._readout(z[:, z.shape[1] - m.output_time:, :]) for m, z in zip(models, zs)])
+        if stream:
+            ys = self._solve(times, times, z0, kwargs)
+            return torch.stack([m.linear(ys[:, i].contiguous().movedim(0, -2)) for i, m in enumerate(models)])
+        if control[0].is_cuda and all(engine.recognise(m.func) is not None for m in models):
+            ys = self._solve(times, times, z0, kwargs, row_out=final_index)      # each row's own state, selected inside the solve
+            return torch.stack([m._readout(ys[i]) for i, m in enumerate(models)])
+        ts, row_slot = NeuralSDE.output_times(times, final_index)
+        ys = self._solve(times, ts, z0, kwargs)
+        idx = row_slot.reshape(1, -1, 1).expand(1, ys.shape[2], ys.shape[3])
+        return torch.stack([m._readout(ys[:, i].gather(0, idx).squeeze(0)) for i, m in enumerate(models)])
+
+    def _forward_ists(self, coeffs, times, **kwargs):
+        models = self.models
+        for m in models:
+            m.func.set_X(coeffs, times)
+        ys = self._solve(times, times, None, kwargs, zero_state=not models[0].initial)
+        zs = [ys[:, i].contiguous().permute(1, 0, 2) for i in range(len(models))]
+        return torch.stack([m._readout(z) for m, z in zip(models, zs)]), torch.stack(zs)
+
+
+Ensemble.KINDS = (NeuralSDE, NeuralSDE_forecasting, IstsNeuralSDE)
+
+
 def make_sde_model(name, input_channels, output_channels, hidden_channels, hidden_hidden_channels,
                    num_hidden_layers, initial=True):
     """The five SDE entries of ``common_sde.make_model`` (benchmark_classification/common_sde.py:301-342)."""

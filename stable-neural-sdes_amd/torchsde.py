@@ -378,6 +378,127 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
             sde.set_X(*saved)
 
 
+def _same_model(a, b):
+    return all(getattr(a, f) == getattr(b, f) for f, _ in engine._lib.Model._fields_)
+
+
+def _same_control(a, b):
+    """Two members hold the same control path: set_X with the same tensors (the same storage, shape and version)."""
+    for name in ('coeffs', 'times'):
+        x, y = getattr(a, name, None), getattr(b, name, None)
+        if not (torch.is_tensor(x) and torch.is_tensor(y)):
+            return False
+        if x is not y and (x.data_ptr() != y.data_ptr() or tuple(x.shape) != tuple(y.shape) or tuple(x.stride()) != tuple(y.stride())
+                           or x.dtype != y.dtype):
+            return False
+    return True
+
+
+def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
+    """M models of one architecture on one batch in ONE fused solve (inference; include/snsde.h: snsde_solve.members): deep-ensemble
+    prediction, the seed models of one configuration on a test set, the points of a sweep.
+
+    sdes: a sequence of M modules honouring the Diffusion_model contract with equal model structs, all holding the same control
+    path (set_X with the same tensors); y0 (M, B, H).  Returns (T, M, B, H), or (M, B, H) with options['row_out'] of length B.
+    Options: seed, row_offset, global_rows, kernel, precision ('bf16' allowed), exact_order, row_out, strict, backend
+    (and lean_general, the A/B switch).  Member m's rows are rows row_offset + m B .. of the whole problem: the result equals, bit
+    for bit, M ordinary sdeint calls with options row_offset + m B and global_rows (the caller's, else M B).
+
+    Where the library plans it - CUDA float32, no `bm`, B % 4 == 0, engine.forward_path(..., members=M) != 'none' - that is one
+    launch over M B rows with the members' parameter blocks stacked and the control path shared; everywhere else (another kernel,
+    composed or latent fields, members of different architecture, backend='torch', CPU, a supplied `bm`) exactly those M calls run,
+    without a warning: the same result either way.  options={'strict': True} raises NotImplementedError instead of looping.
+    ValueError: a solve that would be differentiated (grad enabled and y0, a member's parameter or the coefficients require it),
+    samples > 1, save_traj, recompute, z0_linear - training through an ensemble is not built."""
+    sdes = list(sdes)
+    M = len(sdes)
+    if M < 1:
+        raise ValueError("sdeint_ensemble needs at least one member")
+    if not torch.is_tensor(y0) or y0.dim() != 3 or y0.shape[0] != M:
+        raise ValueError(f"`y0` must be a 3-dimensional tensor of shape (members, batch, channels) = ({M}, B, H).")
+    options = dict(options or {})
+    if method is None:
+        method = 'srk'
+    if method not in METHODS:
+        raise ValueError(f"Expected method in {METHODS}, but found {method}.")
+    if not (float(dt) > 0):
+        raise ValueError("`dt` must be positive.")
+    backend = options.get('backend', 'auto')
+    if backend not in ('auto', 'hip', 'torch'):
+        raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
+    if 'samples' in options and engine.check_samples(options['samples']) > 1:
+        raise ValueError("sdeint_ensemble does not take samples > 1 (sample paths of an ensemble are not built)")
+    options.pop('samples', None)
+    for name, bad in (('save_traj', bool(options.get('save_traj', False))), ('recompute', _recompute_steps(options) > 0),
+                      ('z0_linear', 'z0_linear' in options), ('sample_grad', bool(options.get('sample_grad', False))),
+                      ('bf16_grad', bool(options.get('bf16_grad', False)))):
+        if bad:
+            raise ValueError(f"sdeint_ensemble is inference only: it does not take {name}")
+    if any(_differentiated(sde, y0) for sde in sdes):
+        raise ValueError("sdeint_ensemble is inference only: y0, the control path or a member's parameter requires grad (use "
+                         "torch.no_grad() or requires_grad_(False)); training through an ensemble is not built")
+    ts = _as_ts(ts, y0)
+    B = int(y0.shape[1])
+    row_offset = _row_offset(options, M * B)
+    global_rows = engine.resolve_global_rows(options.get('global_rows'), M * B, row_offset) or M * B
+    options['seed'] = _philox_key(options, y0.device) if bm is None else options.get('seed')      # (one key for every member)
+    strict = bool(options.get('strict', False))
+    row_out = options.get('row_out')
+    if row_out is not None and row_out.numel() != B:
+        raise ValueError(f"row_out has {row_out.numel()} entries, expected {B} (one per row of a member)")
+
+    def loop(why):
+        if strict:
+            raise NotImplementedError(f"sdeint_ensemble: no fused solve of these {M} members ({why}); drop options['strict'] to run "
+                                      "them as M sdeint calls")
+        opts = {k: v for k, v in options.items() if k not in ('strict', 'lean_general') and v is not None}
+        outs = [sdeint(sde, y0[m], ts, bm=bm, method=method, dt=dt,
+                       options=dict(opts, row_offset=row_offset + m * B, global_rows=global_rows)) for m, sde in enumerate(sdes)]
+        return torch.stack(outs, dim=0 if row_out is not None else 1)
+
+    if backend == 'torch' or not y0.is_cuda:
+        return loop("the tensor-op loop has no fused form" if backend == 'torch' else 'CPU tensors')
+    if bm is not None:
+        return loop('a supplied Brownian object is queried per member')
+    if M == 1 or B % 4:
+        return loop('one member' if M == 1 else f'{B} rows per member are not a whole number of 4-row tiles')
+    recs = [engine.recognise(sde) for sde in sdes]
+    if any(r is None for r in recs):
+        return loop('a member does not honour the Diffusion_model contract')
+    model, layout, numel = recs[0]
+    if not all(_same_model(model, r[0]) for r in recs[1:]):
+        return loop('members of different architecture')
+    if not all(_same_control(sdes[0], sde) for sde in sdes[1:]):
+        return loop('members hold different control paths')
+    coeffs = sdes[0].coeffs
+    if coeffs.dim() != 3 or coeffs.shape[0] != B:
+        raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
+    dev = y0.device
+    kernel, precision = options.get('kernel', 'auto'), options.get('precision', 'fp32')
+    engine.precision_flags(precision)
+    exact_order, lean_general = bool(options.get('exact_order', False)), bool(options.get('lean_general', False))
+    L = int(coeffs.shape[1]) + 1
+    grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sdes[0].times), dev)
+    if engine.forward_path(model, M * B, L, grid.N, method, kernel, precision=precision, global_rows=global_rows, row_offset=row_offset,
+                           lean_general=lean_general, exact_order=exact_order, members=M) == 'none':
+        return loop('the plan arrives at a kernel that does not map rows to members')
+    flat = torch.stack([engine.flatten_params(sde, r[1], r[2], dev) for sde, r in zip(sdes, recs)])      # (M, numel)
+    coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
+    y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
+    rows = None if row_out is None else _device_row_out(options, dev).repeat(M)
+    call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=options['seed'], row_offset=row_offset, kernel=kernel,
+                            exact_order=exact_order, row_out=rows, precision=precision, lean_general=lean_general,
+                            global_rows=global_rows, members=M)
+    try:
+        ys = call.launch()
+    except engine._lib.SnsdeError as exc:
+        if not exc.no_kernel:
+            raise
+        return loop(f'the launch was refused ({exc})')
+    ys = ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
+    return ys.to(y0.dtype)
+
+
 def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoint_adaptive=False, adjoint_rtol=1e-5,
                    adjoint_atol=1e-4, adjoint_options=None, adjoint_params=None, names=None, **kwargs):
     """torchsde.sdeint_adjoint's call contract (in-tree user: torch-ists .../NSDE/latent_sde.py:134-141).  Gradients come
