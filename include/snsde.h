@@ -111,7 +111,10 @@ enum {
      * Milstein, elementwise diffusions, H = 64 / 128, the reference's fields, kl_column1 == 0) and no noise_table is supplied;
      * 0 (never an f32 kernel, never mode 2) for everything else, samples > 1 included.  stage_save / dU_out stay refused, and
      * snsde_coeff_gradients returns SNSDE_ERR_UNSUPPORTED under bf16 operands with or without this flag. */
-    SNSDE_FLAG_BF16_GRAD = 128
+    SNSDE_FLAG_BF16_GRAD = 128,
+    /* Opt-in: a model ensemble (snsde_solve.members = M > 1) may be differentiated (snsde_solve.members, last paragraph).  No
+     * effect when members <= 1.  Together with SNSDE_FLAG_BF16_OPERANDS (an inference-only forward): SNSDE_ERR_UNSUPPORTED. */
+    SNSDE_FLAG_ENSEMBLE_GRAD = 256
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -207,6 +210,26 @@ typedef struct snsde_solve {
                            /* snsde_workspace_bytes = M x (the plan's floats rounded up to a multiple of four, plus the     */
                            /* 64-float tail of every workspace), so every block starts 16-byte aligned; one prepare launch  */
                            /* fills all of them and SNSDE_FLAG_REUSE_PREPARED skips it as for one model.                    */
+                           /* Training through an ensemble is opt-in, SNSDE_FLAG_ENSEMBLE_GRAD; without the flag everything */
+                           /* above holds.  With it act_save, stage_save, traj, dW_out and dU_out are accepted by the lean  */
+                           /* kernel and the general kernel on 4-row tiles (elementwise diffusions, H <= 128); with these   */
+                           /* planes any other plan is SNSDE_PATH_NONE / SNSDE_ERR_UNSUPPORTED.  Every plane is             */
+                           /* (.., batch, H), member-major like ys.  snsde_backward_supported is 1 where the adjoint is the */
+                           /* general MFMA adjoint on 4-row tiles (Euler / Milstein) or its SRK form, 0 for everything else */
+                           /* (kernel = generic / 16-row tiles, wave pairs, diffusion nets, H = 256, the two-tile kernels,  */
+                           /* Milstein with noise_option 7, samples > 1, z0_weight, noise_table, kl_column1, the field      */
+                           /* variants, bf16 operands): never another kernel, no mode 2.  snsde_solve_backward,             */
+                           /* snsde_param_gradients, snsde_backward_with_gradients, their workspace queries and             */
+                           /* snsde_save_layout then take the descriptor; grad_params is (M, snsde_param_numel), block m    */
+                           /* the sum over member m's own passes x Bm reduction rows.  Every result of member m - states,   */
+                           /* saved planes, adjoints, dL/dy0, delta planes, parameter gradients - equals bit for bit that   */
+                           /* of the member-alone shard above: each member is planned as its own solve of Bm rows.  The two */
+                           /* backward workspaces hold one block per member:                                                */
+                           /*   snsde_backward_workspace_bytes        = M x ((the member-alone solve's bytes + 15) & ~15)   */
+                           /*   snsde_param_gradients_workspace_bytes = M x ((the member-alone solve's bytes + 15) & ~15)   */
+                           /* (a block starts 16-byte aligned).  The adjoint's pack launch and the three launches of the    */
+                           /* weight-gradient pass carry the member on a grid axis: no launch per member.                   */
+                           /* snsde_coeff_gradients stays SNSDE_ERR_UNSUPPORTED (workspace query 0) for members > 1.        */
     int64_t  row_offset;   /* global index of local row 0 (batch shards keep the global Philox   */
                            /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
                            /* sees the local batch unless `global_rows` (below) is set           */
@@ -361,13 +384,18 @@ SNSDE_API int    snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int
                                                           /* SRK at H = 64 with a diffusion net: per-tile sums in the backward       */
                                                           /* workspace), delta_save is not written and may be NULL                   */
 SNSDE_API int    snsde_backward_supported(const snsde_solve* s);    /* 1 / 2 / 0, see above; bf16 operands: 0, or 1 under */
-                                                                    /* SNSDE_FLAG_BF16_GRAD where it covers the solve     */
+                                                                    /* SNSDE_FLAG_BF16_GRAD where it covers the solve;    */
+                                                                    /* members > 1: 0, or under SNSDE_FLAG_ENSEMBLE_GRAD  */
+                                                                    /* 1 where the general 4-row-tile adjoint takes it    */
 SNSDE_API size_t snsde_backward_workspace_bytes(const snsde_backward* b);
 /* INVARIANT between forward and backward (mode 1): `fwd.workspace` is untouched AND `fwd.params` holds the values the forward ran
  * with.  The adjoint re-packs its transposed weights from the CURRENT params, but takes the folded first-layer product
  * emb . linear_in (input_option 2 / 4 / 6) from the forward's workspace: an in-place parameter update between the two calls, or a
  * second forward through the same workspace, mixes old and new weights without an error.  (torchsde.sdeint keeps both: the
  * autograd node owns the workspace and runs before the optimizer step.)                                                        */
+/* fwd.members = M > 1 under SNSDE_FLAG_ENSEMBLE_GRAD: grad_ys, adj and delta_save hold the rows of all members like ys; member m's
+ * tiles read block m of fwd.params, of fwd.workspace and of b->workspace.  SNSDE_BWD_ADJ0_ONLY, row_out and supplied dW / dU as
+ * for one model.  Without the flag: SNSDE_ERR_UNSUPPORTED. */
 SNSDE_API int    snsde_solve_backward(const snsde_backward* b, void* hip_stream);
 
 /* Parameter gradients of the fused solve (mode 1 = MFMA path only): after snsde_solve_forward (traj, dW_out, act_save
@@ -379,7 +407,9 @@ SNSDE_API int    snsde_solve_backward(const snsde_backward* b, void* hip_stream)
  * reductions (theta, the time-only noise MLP; Euler and Milstein) and the first-layer/emb algebra.
  * `b` is the descriptor snsde_solve_backward ran with, workspace included: the adjoint's workspace is an INPUT here (its
  * per-workgroup diffusion-side sums; with delta_slots == 0 the per-tile weight-gradient blocks) - SNSDE_ERR_NULL without it,
- * SNSDE_ERR_WORKSPACE when workspace_bytes < snsde_backward_workspace_bytes(b). */
+ * SNSDE_ERR_WORKSPACE when workspace_bytes < snsde_backward_workspace_bytes(b).
+ * fwd.members = M > 1 under SNSDE_FLAG_ENSEMBLE_GRAD: grad_params is (M, snsde_param_numel); block m sums member m's rows only, in
+ * the order the member-alone solve sums them (bit-equal), all members in the same launches. */
 SNSDE_API size_t snsde_param_gradients_workspace_bytes(const snsde_backward* b);
 SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_params, void* workspace, size_t workspace_bytes,
                              void* hip_stream);
@@ -387,7 +417,7 @@ SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_para
 /* snsde_solve_backward followed by snsde_param_gradients as ONE call (mode 1 solves only; same arguments, same results bit for
  * bit): one transition from the host language and one validation instead of two, the launches back to back on the stream.
  * Enqueue-only and capturable like the two calls it replaces; returns SNSDE_ERR_UNSUPPORTED where snsde_backward_supported()
- * != 1 (the caller then uses the separate calls).                                                                            */
+ * != 1 (the caller then uses the separate calls).  A model ensemble under SNSDE_FLAG_ENSEMBLE_GRAD: as the two calls.            */
 SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
                                             void* hip_stream);
 
@@ -407,7 +437,7 @@ SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad
  * (row_offset / global_rows) reproduce the rows of the whole bit for bit.
  * input_option 1 / 3 / 5 (the drift does not read X): grad_coeffs is zero-filled, SNSDE_OK.  SNSDE_ERR_UNSUPPORTED: a solve
  * whose adjoint leaves no delta planes (snsde_save_layout: delta_slots == 0, the H = 64 wave-pair adjoints), mode 2 or 0,
- * delta_save == NULL, fwd.samples > 1 without SNSDE_FLAG_SAMPLE_GRAD, fwd.kl_column1 != 0, the field variants, a supplied noise_table and
+ * delta_save == NULL, fwd.members > 1 (with or without SNSDE_FLAG_ENSEMBLE_GRAD), fwd.samples > 1 without SNSDE_FLAG_SAMPLE_GRAD, fwd.kl_column1 != 0, the field variants, a supplied noise_table and
  * SNSDE_FLAG_BF16_OPERANDS (also under SNSDE_FLAG_BF16_GRAD: the rounded folded control-path weights are not formed here).  SNSDE_ERR_NULL /
  * SNSDE_ERR_WORKSPACE as elsewhere; every check happens before the first launch.  The dependence of y0 on coeffs through a fused
  * z0_weight is not part of this gradient (the host materialises y0 with tensor ops when coeffs require a gradient).

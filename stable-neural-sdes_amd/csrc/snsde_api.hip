@@ -179,11 +179,31 @@ static bool members_ok(const snsde_solve* s) {
     const int32_t M = snsde_members(s);
     return M == 1 || (s->batch % M == 0 && (s->batch / M) % 4 == 0);
 }
+// SNSDE_FLAG_ENSEMBLE_GRAD (snsde.h): the opt-in to training through a model ensemble; nothing without members > 1
+static bool ensemble_grad(const snsde_solve* s) { return snsde_members(s) > 1 && (s->flags & SNSDE_FLAG_ENSEMBLE_GRAD) != 0; }
+static bool members_training(const snsde_solve* s) {
+    return snsde_members(s) > 1 && (s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out);
+}
 // ... an inference-only solve of the members' own fields from the caller's initial states: not combined with sample paths, a fused
-// initial network, a supplied diffusion table (one table, M models), the accumulator column or any training-mode plane
+// initial network, a supplied diffusion table (one table, M models), the accumulator column or - unless the flag opts in - any
+// training-mode plane
 static bool members_refused(const snsde_solve* s) {
-    return snsde_members(s) > 1 && (snsde_samples(s) > 1 || s->z0_weight || s->noise_table || s->kl_column1 != 0 || s->act_save ||
-                                    s->stage_save || s->traj || s->dW_out || s->dU_out);
+    return snsde_members(s) > 1 && (snsde_samples(s) > 1 || s->z0_weight || s->noise_table || s->kl_column1 != 0 ||
+                                    (members_training(s) && !ensemble_grad(s)));
+}
+// ... and the forward plans whose training planes the ensemble adjoint route takes (route_backward): the lean kernel and the general
+// MFMA kernel on 4-row tiles, elementwise diffusions, H <= 128
+static bool ensemble_training_plan(const snsde_mfma::MfmaPlan& p) {
+    return p.ok && p.H <= 128 && p.NN == 0 && (p.kernel == snsde_mfma::FwdKernel::lean || p.kernel == snsde_mfma::FwdKernel::general_m4);
+}
+// One member of an ensemble run alone as a shard of the whole (snsde.h: members): what each member is planned as - its adjoint's
+// workgroups and partial-sum blocks, its weight-gradient tiles and splits.  (row_offset: member 0's; no plan reads it)
+static snsde_solve member_alone(const snsde_solve* s) {
+    snsde_solve one = *s;
+    one.batch = s->batch / snsde_members(s);
+    one.global_rows = snsde_plan_rows(s);
+    one.members = 0;
+    return one;
 }
 
 int snsde_flavor_hint(const snsde_solve* s) {
@@ -209,10 +229,14 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     // training planes of a sampled solve (SNSDE_FLAG_SAMPLE_GRAD): the MFMA kernels the sampled adjoint route covers, or nothing
     const bool strain = samples_training(s);
     if (strain && (variant || s->kl_column1 != 0)) return r;
+    // training planes of an ensemble (SNSDE_FLAG_ENSEMBLE_GRAD): the kernels the ensemble adjoint route covers, or nothing
+    const bool etrain = members_training(s);
+    if (etrain && (variant || (s->flags & SNSDE_FLAG_BF16_OPERANDS))) return r;
     if (k == SNSDE_KERNEL_GENERIC) { if (!(s->flags & SNSDE_FLAG_BF16_OPERANDS) && !strain) r.path = generic; return r; }
     if (!global_rows_ok(s)) return r;
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
     if (strain && !sampled_training_plan(r.plan)) return ForwardRoute{};
+    if (etrain && !ensemble_training_plan(r.plan)) return ForwardRoute{};
     // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor - but not where the
     // plan made for the whole problem (global_rows) names a kernel this shard cannot run, nor where the plan arrives at a kernel
     // that does not address coeffs by sample group (samples): that is no kernel at all
@@ -232,7 +256,31 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
     snsde_mfma::BackwardRoute r{};
     const int hint = snsde_flavor_hint(s), k = s->kernel;
     if (!global_rows_ok(s)) return r;
-    if (snsde_members(s) > 1 || !members_ok(s)) return r;      // model ensembles: an inference-only forward, no adjoint and nothing to plan
+    if (!members_ok(s)) return r;
+    if (snsde_members(s) > 1) {
+        // model ensembles: an inference-only forward, no adjoint and nothing to plan - unless SNSDE_FLAG_ENSEMBLE_GRAD opts in.  Then
+        // mode 1 exactly where the forward plan is the lean or the general kernel on 4-row tiles (make_plan refuses the others) and the
+        // adjoint of ONE member run alone as a shard of the whole is the general MFMA adjoint on 4-row tiles or its SRK form, which
+        // read no coefficients and leave delta planes.  Anything else is no plan (never another kernel, no mode 2)
+        if (!ensemble_grad(s) || members_refused(s) || (s->flags & SNSDE_FLAG_BF16_OPERANDS) || snsde_solve_variant(s) ||
+            k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16 || (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) ||
+            (s->method != SNSDE_EULER && s->method != SNSDE_MILSTEIN && s->method != SNSDE_SRK))
+            return r;
+        const snsde_solve one = member_alone(s);
+        r.fp = make_plan(s, net, hint);
+        if (!ensemble_training_plan(r.fp)) return snsde_mfma::BackwardRoute{};
+        r.rp = make_rev_plan(&one, net, r.fp, hint);
+        if (!r.rp.ok || r.rp.FL != 1 || (r.rp.kernel != snsde_mfma::RevKernel::general && r.rp.kernel != snsde_mfma::RevKernel::general_srk))
+            return snsde_mfma::BackwardRoute{};
+        r.members = snsde_members(s);
+        size_t g = 0;
+        snsde_generic_workspace_floats(&one, net, &g);
+        r.bws_stride = snsde_member_bws_stride((r.rp.workspace_floats > g ? r.rp.workspace_floats : g) + 64);      // (as backward_workspace_bytes sizes one model)
+        r.fws_stride = snsde_member_ws_stride(s, net);
+        if (r.fws_stride == 0) return snsde_mfma::BackwardRoute{};
+        r.mode = 1;
+        return r;
+    }
     const bool sampled = snsde_samples(s) > 1;
     // sample paths: an inference-only forward, no adjoint and nothing to plan - unless SNSDE_FLAG_SAMPLE_GRAD opts in
     if ((sampled && (!sample_grad(s) || (s->flags & SNSDE_FLAG_BF16_OPERANDS))) || !samples_ok(s)) return r;
@@ -272,6 +320,7 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
 
 // (the generic adjoints pack their own weights / tables)
 static size_t backward_workspace_bytes(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r) {
+    if (r.members > 1) return (size_t)r.members * r.bws_stride * sizeof(float);      // (one block per member: snsde_member_bws_stride)
     size_t f = r.rp.ok ? r.rp.workspace_floats : 0, g = 0;
     snsde_generic_workspace_floats(&b->fwd, net, &g);
     return ((f > g ? f : g) + 64) * sizeof(float);
@@ -666,7 +715,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     if (rc) return rc;
     if ((b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) && !bf16_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
     if (snsde_samples(&b->fwd) > 1 && !sample_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (sample paths: inference only without the opt-in)
-    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;                                // (model ensembles: inference only)
+    if (snsde_members(&b->fwd) > 1 && !ensemble_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (model ensembles: inference only without the opt-in)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj) return SNSDE_ERR_NULL;
     // increments: dW_out, or the supplied dW, or - MFMA Euler / Milstein adjoint, Philox with a host key - regenerated in-kernel
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;
@@ -691,8 +740,9 @@ size_t snsde_param_gradients_workspace_bytes(const snsde_backward* b) {
     if (!b || b->struct_size != sizeof(snsde_backward) || b->fwd.struct_size != sizeof(snsde_solve)) return 0;
     SnsdeNet net;
     if (snsde_build_net(b->fwd.model, b->fwd.n_steps, &net)) return 0;
-    if (route_backward(&b->fwd, net).mode != 1) return 0;
-    return snsde_wgrad_workspace_floats(b, net) * sizeof(float);
+    const snsde_mfma::BackwardRoute r = route_backward(&b->fwd, net);
+    if (r.mode != 1) return 0;
+    return snsde_wgrad_workspace_floats(b, net, r.members) * sizeof(float);
 }
 
 // The checks the two parameter-gradient entry points share once the descriptor's pointers are in: the route (MFMA adjoint only),
@@ -705,7 +755,7 @@ static int route_param_gradients(const snsde_backward* b, const SnsdeNet& net, s
     // per-tile weight-gradient blocks themselves): the descriptor must still carry it, at the size the adjoint was given
     if (!b->workspace) return SNSDE_ERR_NULL;
     if (b->workspace_bytes < backward_workspace_bytes(b, net, *r)) return SNSDE_ERR_WORKSPACE;
-    if (pg_workspace_bytes < snsde_wgrad_workspace_floats(b, net) * sizeof(float)) return SNSDE_ERR_WORKSPACE;
+    if (pg_workspace_bytes < snsde_wgrad_workspace_floats(b, net, r->members) * sizeof(float)) return SNSDE_ERR_WORKSPACE;
     return SNSDE_OK;
 }
 
@@ -715,7 +765,7 @@ int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* wor
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
-    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only)
+    if (snsde_members(&b->fwd) > 1 && !ensemble_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only without the opt-in)
     if (!b->adj || !b->fwd.traj || !b->fwd.act_save || !b->fwd.workspace)
         return SNSDE_ERR_NULL;
     SnsdeNet net;
@@ -734,7 +784,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
-    if (snsde_members(&b->fwd) > 1) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only)
+    if (snsde_members(&b->fwd) > 1 && !ensemble_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only without the opt-in)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj || !b->fwd.act_save || !b->fwd.workspace)
         return SNSDE_ERR_NULL;
     if (!b->fwd.dW_out && !b->fwd.dW && b->fwd.seed_dev) return SNSDE_ERR_NULL;
@@ -755,6 +805,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
 static int route_coeff_gradients(const snsde_solve* s, int32_t* delta_slots) {
     if (s->flags & SNSDE_FLAG_BF16_OPERANDS) return SNSDE_ERR_UNSUPPORTED;      // (also under SNSDE_FLAG_BF16_GRAD: M is not rounded here)
     if (s->kl_column1 != 0 || snsde_solve_variant(s)) return SNSDE_ERR_UNSUPPORTED;
+    if (snsde_members(s) > 1) return SNSDE_ERR_UNSUPPORTED;      // (a sum over members of delta_p M_m, one M_m per member: not built)
     SnsdeNet net;
     int rc = snsde_build_net(s->model, s->n_steps, &net);
     if (rc) return rc;

@@ -105,6 +105,10 @@ size_t snsde_mfma_workspace_floats(const snsde_solve* s, const SnsdeNet& net);
 // floats from one member's prepared block to the next (snsde_solve::members > 1): the plan's floats rounded up to a multiple of four
 // (every f32x4 load of a block stays 16-byte aligned) plus the 64-float tail of every workspace; 0: no MFMA plan
 size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net);
+// ... and from one member's block of a BACKWARD-side workspace (the adjoint's, the weight-gradient pass's) to the next, under
+// SNSDE_FLAG_ENSEMBLE_GRAD: `floats` = what the member run alone needs, its 64-float tail included where it has one; rounded up to a
+// multiple of four floats so that every block starts 16-byte aligned (snsde.h: members, the rounding rule of the two queries)
+inline size_t snsde_member_bws_stride(size_t floats_with_tail) { return (floats_with_tail + 3) & ~(size_t)3; }
 int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream);
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)
@@ -119,7 +123,7 @@ size_t snsde_w4_grad_floats(const snsde_solve* s);
 int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* gpart,
                                 const float* dth_part, hipStream_t stream);
 // launchers (snsde_wgrad.hip)
-size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net);
+size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net, int members = 1);      // (members > 1: M blocks of one member's plan)
 int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, float* grad_params,
                        int32_t n_params, float* ws, hipStream_t stream);
 // launchers (snsde_cgrad.hip): dL/d coeffs from the adjoint's delta planes (snsde_coeff_gradients)

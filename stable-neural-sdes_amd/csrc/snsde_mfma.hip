@@ -94,12 +94,17 @@ __device__ __forceinline__ void pack_layer(const float* __restrict__ params, flo
 }
 
 // kernarg offsets of the by-value job structs (their `layer` arrays are indexed by blockIdx.y: snsde_kernarg_element)
-constexpr size_t PACK_JOB_OFF = 24;      // snsde_mfma_pack_kernel(params, ws, fold_src, job, round_bf16)
+constexpr size_t PACK_JOB_OFF = 24;      // snsde_mfma_pack_kernel(params, ws, fold_src, job, round_bf16, strides): the job follows the pointers
 constexpr size_t PREP_JOB_OFF = (16 + sizeof(FoldJob) + alignof(MfmaPackJob) - 1) / alignof(MfmaPackJob) * alignof(MfmaPackJob);
 static_assert(alignof(FoldJob) == 8 && alignof(MfmaPackJob) == 4, "kernarg layout of snsde_prepare_kernel");
 
+// blockIdx.z = the member of a model ensemble under SNSDE_FLAG_ENSEMBLE_GRAD (one model: gridDim.z == 1, strides unused): it packs
+// params + z param_stride (and the folded product of block z of the forward workspace, fold_src + z fold_stride) into ws + z ws_stride
 __global__ void snsde_mfma_pack_kernel(const float* __restrict__ params, float* __restrict__ ws, const float* __restrict__ fold_src,
-                                       MfmaPackJob job, int round_bf16) {
+                                       MfmaPackJob job, int round_bf16, uint32_t param_stride, uint32_t ws_stride, uint32_t fold_stride) {
+    params += (size_t)blockIdx.z * param_stride;
+    ws += (size_t)blockIdx.z * ws_stride;
+    if (fold_src) fold_src += (size_t)blockIdx.z * fold_stride;
     const MfmaLayerPack L = snsde_kernarg_element<MfmaLayerPack>(PACK_JOB_OFF + offsetof(MfmaPackJob, layer), blockIdx.y);
     pack_layer(params, ws, fold_src ? fold_src : ws, job, L, blockIdx.x, gridDim.x, false, round_bf16 != 0);
 }
@@ -214,9 +219,10 @@ __device__ __forceinline__ void fold_block(const float* __restrict__ params, flo
     }
 }
 
-__global__ void snsde_fold_kernel(const float* __restrict__ params, float* __restrict__ ws, FoldJob job) {
+// (blockIdx.z = the member, as in the pack kernel below)
+__global__ void snsde_fold_kernel(const float* __restrict__ params, float* __restrict__ ws, FoldJob job, uint32_t param_stride, uint32_t ws_stride) {
     extern __shared__ float erow[];
-    fold_block(params, ws, job, nullptr, nullptr, erow);
+    fold_block(params + (size_t)blockIdx.z * param_stride, ws + (size_t)blockIdx.z * ws_stride, job, nullptr, nullptr, erow);
 }
 
 // Forward prepare in ONE launch: blockIdx.y 0/1 = folded products (written to the temp the backward reads AND to their
@@ -774,6 +780,15 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     const RevPlan& p = r.rp;
     if (r.mode != 1) return SNSDE_ERR_UNSUPPORTED;      // (the plans also refuse what overflows the kernels' 32-bit save offsets)
     float* ws = static_cast<float*>(b->workspace);
+    // model ensembles (SNSDE_FLAG_ENSEMBLE_GRAD): one block per member in both workspaces, M parameter blocks; p is one member's plan
+    const int members = r.members > 1 ? r.members : 1;
+    const int64_t param_stride = members > 1 ? snsde_param_numel(&s->model) : 0;
+    const size_t ws_stride = members > 1 ? r.bws_stride : 0, fws_stride = members > 1 ? r.fws_stride : 0;
+    if (members > 1 && (members > 65535 || p.FL != 1 || (p.kernel != RevKernel::general && p.kernel != RevKernel::general_srk) ||
+                        ws_stride == 0 || ws_stride >= (1ull << 32) || fws_stride == 0 || fws_stride >= (1ull << 32) ||
+                        (uint64_t)members * ws_stride >= (1ull << 32) || (uint64_t)members * fws_stride >= (1ull << 32) ||
+                        param_stride <= 0 || param_stride >= (1ll << 32) || p.workspace_floats > ws_stride || s->batch % members))
+        return SNSDE_ERR_UNSUPPORTED;
     if (p.kernel == RevKernel::w4_fused) {
         // the wave-pair adjoint reads the nn.Linear layout of `params` itself (columns of the weights): no fold, no pack launch;
         // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (RevPlan::w4_gpart_off)
@@ -796,7 +811,8 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
         fj.src_w[0] = net.in.src_w; fj.K[0] = net.in.K; fj.col[0] = 0; fj.tmp[0] = p.fold_tmp;
         fj.b_in = net.in.src_b; fj.b_init = net.init.src_b; fj.b_emb = net.emb.src_b;
         fj.bias_tmp = p.fold_tmp + p.H * net.in.K;
-        hipLaunchKernelGGL(snsde_fold_kernel, dim3(p.H, 1), dim3(256), 2 * p.H * sizeof(float), stream, s->params, ws, fj);
+        hipLaunchKernelGGL(snsde_fold_kernel, dim3(p.H, 1, members), dim3(256), 2 * p.H * sizeof(float), stream, s->params, ws, fj,
+                           (uint32_t)param_stride, (uint32_t)ws_stride);
     }
     MfmaPackJob job{};
     for (int i = 0; i < p.n_layers; ++i) {
@@ -806,7 +822,8 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     job.n_layers = p.n_layers; job.flavor = p.FL; job.TPW = 1; job.NW = p.NW; job.bias_off = 0; job.H = p.H;
     // (mode 1 after a bf16-operand forward = SNSDE_FLAG_BF16_GRAD: the adjoint multiplies the ROUNDED weights, straight-through)
     const int round_bf16 = fp.kernel == FwdKernel::lean_bf16 ? 1 : 0;
-    hipLaunchKernelGGL(snsde_mfma_pack_kernel, dim3(16, p.n_layers), dim3(256), 0, stream, s->params, ws, fold_src, job, round_bf16);
+    hipLaunchKernelGGL(snsde_mfma_pack_kernel, dim3(16, p.n_layers, members), dim3(256), 0, stream, s->params, ws, fold_src, job, round_bf16,
+                       (uint32_t)param_stride, (uint32_t)ws_stride, (uint32_t)fws_stride);
     RevArgs a{};
     a.params = s->params; a.ws = ws;
     a.gt = s->noise_table ? s->noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s->workspace) + fp.gt_off : nullptr);
@@ -831,6 +848,8 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     a.ds_part = p.ds_off ? ws + p.ds_off : nullptr;
     a.dth_part = p.dth_off ? ws + p.dth_off : nullptr;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = s->model.noise_option; a.off_theta = net.off_theta; a.method = s->method;
+    a.members = members; a.member_rows = members > 1 ? s->batch / members : 0;
+    a.param_stride = (uint32_t)param_stride; a.ws_stride = (uint32_t)ws_stride; a.gt_stride = a.gt ? (uint32_t)fws_stride : 0u;
     for (int i = 0; i < p.n_layers; ++i) a.w_off[i] = p.layer[i].dst;
     // one dispatcher per kernel: what it answers is the launch's answer (a plan and a dispatcher that disagree are an error, never
     // a run of another kernel)

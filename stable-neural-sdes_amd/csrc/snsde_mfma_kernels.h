@@ -1101,7 +1101,20 @@ struct RevArgs {
     int64_t row_offset;
     int32_t acc_col;                   // path-integral accumulator column (-1: none) and its prior drift a y + b
     float acc_a, acc_b;
+    // model ensembles under SNSDE_FLAG_ENSEMBLE_GRAD (snsde_solve::members = M > 1): the member is the second grid axis of the general
+    // adjoint's launches, m = blockIdx.y (one model: a grid of one row, m = 0, member_rows and the strides 0), as in the forward
+    // (MfmaArgs) - tile blockIdx.x of member m covers rows m member_rows + 4 blockIdx.x .. of the (.., B, H) planes and reads
+    // params + m param_stride, ws + m ws_stride (packed transposed weights; ds_part / dth_part lie in the same block: the member's own
+    // nwg = member_rows / 4 partial blocks, indexed by blockIdx.x as in the member's own solve) and gt + m gt_stride (the table inside
+    // block m of the forward workspace); M ws_stride and M gt_stride fit 32 bits (snsde_mfma_backward_launch).  Read by snsde_mfma_reverse_kernel and snsde_mfma_srk_reverse_kernel only.
+    int32_t members, member_rows;
+    uint32_t param_stride, ws_stride, gt_stride;
 };
+
+// float offset of member blockIdx.y's block of the backward workspace (RevArgs::ws_stride; one model: 0).  Formed where it is used
+// and not held in a variable across the step loop: the adjoint kernels run at their scalar-register limit, and a value kept live
+// through the loop cost the y-free and the deepest SRK instantiations a spilled scalar register each (one of them a wave per SIMD)
+__device__ __forceinline__ uint32_t rev_member_ws(const RevArgs& a) { return blockIdx.y * a.ws_stride; }
 
 // d/dx [scale * x * sigmoid(x)]  (LipSwish: scale = 0.909, SiLU: 1)
 __device__ __forceinline__ float swish_grad(float x, float scale) {
@@ -1127,7 +1140,10 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     const int r = FL ? (lane & 3) : (lane & 15);
     const int s = FL ? ((lane >> 2) & 3) : (lane >> 4);
     const int fsub = FL ? 4 * (lane >> 4) : 4 * s;
-    const int row0 = blockIdx.x * M, B = a.B;
+    // model ensembles: blockIdx.y is the member (RevArgs::members; one model: 0) - its first row and its blocks, formed once
+    // (32-bit uniform offsets formed where they are used, not rebased pointers held across the step loop: the kernarg values stay
+    //  re-loadable - the launcher checks that M blocks fit 32 bits)
+    const int row0 = (int)blockIdx.y * a.member_rows + blockIdx.x * M, B = a.B;
     const int row = row0 + r, rowc = row < B ? row : B - 1;
     const bool row_ok = row < B;
     const size_t BH = (size_t)B * H;
@@ -1141,8 +1157,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     uint32_t ring_m0 = 0, ring_ra = 0, ring_lo = 0, ring_hi = 0;
 #pragma unroll
     for (int g = 0; g < NG; ++g) {
-        if constexpr (CF::RING) sbr[g] = lean_uniform(a.ws + a.w_off[g] + (size_t)wave * KUH * 256);
-        else wt[g].load(a.ws + a.w_off[g], wave, lane);
+        if constexpr (CF::RING) sbr[g] = lean_uniform(a.ws + rev_member_ws(a) + a.w_off[g] + (size_t)wave * KUH * 256);
+        else wt[g].load(a.ws + rev_member_ws(a) + a.w_off[g], wave, lane);
     }
     if constexpr (CF::RING) {
         const uint32_t ringb = lean_lds_addr(lds + CF::RING0) + (uint32_t)wave * (8 * 1024);
@@ -1158,7 +1174,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     }
     for (int i = tid; i < NS * M * LDA; i += NT) lds[i] = 0.0f;
 
-    const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
+    const float sig_theta = snsde_sigmoid((a.params + (size_t)blockIdx.y * a.param_stride)[a.off_theta]);
     const bool mul_y = (a.no == 13 || a.no == 17 || a.no == 15 || a.no == 19 || a.no == 3 || a.no == 6 || a.no == 11);
     const bool yfun = (a.no >= 7 && a.no <= 10);     // raw = phi(y): no table, theta is the only diffusion parameter
     const float mil = (a.method == SNSDE_MILSTEIN) ? 0.5f : 0.0f;
@@ -1222,7 +1238,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
             p.z[e] = (a.act + uoff(n, SBH, CF::ZSLOT, BH32))[goff + e];
             if (a.dW) p.dw[e] = (a.dW + uoff(n, BH32))[goff + e];
             if constexpr (NN > 0) p.gq[e] = (a.act + uoff(n, SBH, CF::ZSLOT + NN, BH32))[goff + e];   // diffusion-net output
-            else p.gq[e] = a.gt ? (a.gt + uoff(n, H))[fcol + e] : 0.0f;
+            else p.gq[e] = a.gt ? (a.gt + uoff(n, H, blockIdx.y, a.gt_stride))[fcol + e] : 0.0f;      // (row n of the member's table)
         }
         if constexpr (FL) {
             if (__builtin_expect(a.act_fn != 0, 0)) {      // relu: the signs ride in z's low bits (snsde_pack_signs)
@@ -1401,7 +1417,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
             }
         }
         if (dsum) {     // sum over the tile's rows, one writer lane per feature
-            float* dp = a.ds_part + ((size_t)blockIdx.x * a.N + n) * H + fcol;
+            float* dp = a.ds_part + rev_member_ws(a) + ((size_t)blockIdx.x * a.N + n) * H + fcol;
             if constexpr (FL) {     // rows = lane & 3
                 float v = dsv[0];
                 v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xf, 0xf, false));
@@ -1510,7 +1526,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     if ((dsum || NN > 0 || yfun) && a.dth_part) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) th_acc += __shfl_down(th_acc, off, 64);
-        if (lane == 0) a.dth_part[blockIdx.x * CF::NW + wave] = th_acc;
+        if (lane == 0) (a.dth_part + rev_member_ws(a))[blockIdx.x * CF::NW + wave] = th_acc;
     }
     if constexpr (CF::RING) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the ring's last requests land before the wave ends
 }
@@ -1520,8 +1536,10 @@ int launch_rev(const RevArgs& a, hipStream_t stream) {
     const size_t lds_bytes = (size_t)CF::LDS_FLOATS * sizeof(float);
     static SnsdeLdsAttr lds_attr;   // per instantiation and device
     if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_mfma_reverse_kernel<CF>), lds_bytes, lds_attr)) return rc;
-    const int grid = (a.B + CF::M - 1) / CF::M;
-    hipLaunchKernelGGL(snsde_mfma_reverse_kernel<CF>, dim3(grid), dim3(CF::NT), lds_bytes, stream, a);
+    const int members = a.members > 1 ? a.members : 1;      // (model ensembles: tiles of a member x members; one model: a grid of one row)
+    if (members > 1 && !CF::FL) return SNSDE_ERR_UNSUPPORTED;      // (a 16-row tile would straddle members: route_backward plans 4-row tiles)
+    const int grid = ((members > 1 ? a.member_rows : a.B) + CF::M - 1) / CF::M;
+    hipLaunchKernelGGL(snsde_mfma_reverse_kernel<CF>, dim3(grid, members), dim3(CF::NT), lds_bytes, stream, a);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
@@ -1548,7 +1566,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 3, s = (lane >> 2) & 3, fsub = 4 * (lane >> 4);
-    const int row0 = blockIdx.x * M, B = a.B;
+    // model ensembles: blockIdx.y is the member (RevArgs::members; one model: 0) - its first row and its blocks, formed once
+    const int row0 = (int)blockIdx.y * a.member_rows + blockIdx.x * M, B = a.B;      // (offsets: rev_member_ws, as in the Euler adjoint)
     const int row = row0 + r, rowc = row < B ? row : B - 1;
     const bool row_ok = row < B;
     const size_t BH = (size_t)B * H;
@@ -1560,10 +1579,10 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
 
     Wt<CF::STREAM, KUH, TPW> wt[NG];
 #pragma unroll
-    for (int g = 0; g < NG; ++g) wt[g].load(a.ws + a.w_off[g], wave, lane);
+    for (int g = 0; g < NG; ++g) wt[g].load(a.ws + rev_member_ws(a) + a.w_off[g], wave, lane);
     for (int i = tid; i < NG * M * LDA; i += NT) lds[i] = 0.0f;
 
-    const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
+    const float sig_theta = snsde_sigmoid((a.params + (size_t)blockIdx.y * a.param_stride)[a.off_theta]);
     const bool mul_y = (a.no == 13 || a.no == 17 || a.no == 3 || a.no == 6 || a.no == 11);
     const bool yfun = (a.no >= 7 && a.no <= 10);
     const bool dsum = a.ds_part != nullptr && a.gt != nullptr;
@@ -1692,7 +1711,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
         q.z2 = (a.act + uoff(3 * n + 2, SBH, CF::ZSLOT, BH32))[goff];
         q.t0v = q.t1v = q.t3v = 0.0f;
         if (a.gt) {
-            const float* gp = a.gt + uoff(n, 4 * H) + fcol;
+            const float* gp = a.gt + uoff(n, 4 * H, blockIdx.y, a.gt_stride) + fcol;      // (the member's table)
             q.t0v = gp[0]; q.t1v = gp[H]; q.t3v = gp[3 * H];
         }
     };
@@ -1770,7 +1789,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
             if (dsum) {
                 ds1 = fi3 ? c3 * sgt * (mul_y ? h13 : 1.0f) : 0.0f;
                 const float ds3 = quad_sum(fi2 ? c2 * sgt * (mul_y ? h12 : 1.0f) : 0.0f);
-                if (r == 0) a.ds_part[((size_t)blockIdx.x * 4 * a.N + 4 * n + 3) * H + fcol] = ds3;
+                if (r == 0) (a.ds_part + rev_member_ws(a))[((size_t)blockIdx.x * 4 * a.N + 4 * n + 3) * H + fcol] = ds3;
             }
         }
         // ---- stage 2: drift at (t0 + h/2, H0_2) ----
@@ -1787,7 +1806,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
             if (dsum) {
                 ds1 += fi1 ? c1 * sgt * (mul_y ? h11 : 1.0f) : 0.0f;
                 ds1 = quad_sum(ds1);
-                if (r == 0) a.ds_part[((size_t)blockIdx.x * 4 * a.N + 4 * n + 1) * H + fcol] = ds1;
+                if (r == 0) (a.ds_part + rev_member_ws(a))[((size_t)blockIdx.x * 4 * a.N + 4 * n + 1) * H + fcol] = ds1;
             }
         }
         d = chain(3 * n + 1, fb1, h01, z1, f1, zb1);
@@ -1799,8 +1818,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
             if (!g_raw) th_acc = fmaf(c0, rc0, th_acc);
             const float ds0 = dsum ? quad_sum(fi0 ? c0 * sgt * (mul_y ? y : 1.0f) : 0.0f) : 0.0f;
             if (dsum && r == 0) {
-                a.ds_part[((size_t)blockIdx.x * 4 * a.N + 4 * n) * H + fcol] = ds0;
-                a.ds_part[((size_t)blockIdx.x * 4 * a.N + 4 * n + 2) * H + fcol] = 0.0f;   // slot t0 + h/2: no diffusion evaluation
+                (a.ds_part + rev_member_ws(a))[((size_t)blockIdx.x * 4 * a.N + 4 * n) * H + fcol] = ds0;
+                (a.ds_part + rev_member_ws(a))[((size_t)blockIdx.x * 4 * a.N + 4 * n + 2) * H + fcol] = 0.0f;   // slot t0 + h/2: no diffusion evaluation
             }
         }
         d = chain(3 * n, fb0, y, z0, f0, zb0);
@@ -1811,15 +1830,16 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
     if (tsum && a.dth_part) {
 #pragma unroll
         for (int off = 32; off > 0; off >>= 1) th_acc += __shfl_down(th_acc, off, 64);
-        if (lane == 0) a.dth_part[blockIdx.x * CF::NW + wave] = th_acc;
+        if (lane == 0) (a.dth_part + rev_member_ws(a))[blockIdx.x * CF::NW + wave] = th_acc;
     }
 }
 
 template <class CF>
 int launch_rev_srk(const RevArgs& a, hipStream_t stream) {
     const size_t lds_bytes = (size_t)CF::RING0 * sizeof(float);      // (no weight ring in this kernel)
-    const int grid = (a.B + CF::M - 1) / CF::M;
-    hipLaunchKernelGGL(snsde_mfma_srk_reverse_kernel<CF>, dim3(grid), dim3(CF::NT), lds_bytes, stream, a);
+    const int members = a.members > 1 ? a.members : 1;      // (model ensembles: as launch_rev)
+    const int grid = ((members > 1 ? a.member_rows : a.B) + CF::M - 1) / CF::M;
+    hipLaunchKernelGGL(snsde_mfma_srk_reverse_kernel<CF>, dim3(grid, members), dim3(CF::NT), lds_bytes, stream, a);
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
@@ -1871,7 +1891,11 @@ struct RevPlan {
 // The adjoint of a solve, decided once per entry point (route_backward, snsde_api.hip): the mode snsde_backward_supported reports
 // (0 none, 1 MFMA adjoint, 2 generic adjoint), the forward's plan - the one its launch ran with - and the adjoint's plan.
 // Mode 1 runs rp; the plans are filled in whatever the mode (snsde_backward_workspace_bytes sizes for rp wherever it is ok).
-struct BackwardRoute { int mode; MfmaPlan fp; RevPlan rp; };
+// members > 1 (a model ensemble under SNSDE_FLAG_ENSEMBLE_GRAD): fp is the ensemble forward's plan, rp the adjoint's plan of ONE member
+// run alone as a shard of the whole (batch / M rows: its nwg, its offsets) - every member's block of the backward workspace is laid
+// out by it, bws_stride floats apart (snsde_member_bws_stride); fws_stride: floats between the members' blocks of the forward
+// workspace (snsde_member_ws_stride).  One model: members = 1, strides 0.
+struct BackwardRoute { int mode; MfmaPlan fp; RevPlan rp; int members; size_t bws_stride, fws_stride; };
 
 // Which 4-row-tile configurations the lean kernel (snsde_m4_kernel.h) takes: its resident weights plus one layer's B
 // operands must fit the 256-register budget of two waves per SIMD WITHOUT spilling (its asm-issued loads land in

@@ -72,6 +72,12 @@ struct DArgs {
     int32_t nwg, n_dth, NH;
 };
 
+// model ensembles under SNSDE_FLAG_ENSEMBLE_GRAD (snsde_solve::members = M > 1): floats from one member's block to the next in this
+// pass's workspace (wws), the adjoint's workspace (bws), the parameter / gradient blocks (par) and the forward workspace (fws).  The
+// member is a grid axis of every launch of the pass (blockIdx.z; the epilogue folds it into z, the sigma kernel takes blockIdx.y);
+// one model: that index is 0 and the strides are unused
+struct MStride { uint32_t wws, bws, par, fws; };
+
 struct WArgs {
     const float* delta; const float* act; const float* traj; const float* adj;
     XInfo x;           // control-path columns of the x_kind 2 tiles, evaluated while staging
@@ -79,7 +85,11 @@ struct WArgs {
     int32_t dsum_blocks;
     float* part;       // [tile][split][TILE_FLOATS]
     float* sums;       // dense job matrices
-    int32_t B, H, N, NG, NSAVE, R, ntiles, NP;
+    // B: rows of the (.., B, H) planes = their row stride; Br: the rows reduced per pass; mrows: first plane row of member blockIdx.z,
+    // per member.  One model: Br == B, mrows == 0.  A model ensemble: B = M Bm, Br = mrows = Bm - reduction row r of member m is
+    // pass r / Bm, plane row m Bm + r % Bm, and (x_kind 2) coefficient row r % Bm: the control path is shared
+    int32_t B, H, N, NG, NSAVE, R, ntiles, NP, Br, mrows;
+    MStride ms;
     WTile tile[MAX_TILES];
 };
 
@@ -135,6 +145,8 @@ __device__ __forceinline__ float wgrad_q(float v) { return (float)(__bf16)v; }
 struct GJob {     // C (M x N) = A . B^T (trans 0: A (M, K), B (N, K)) or A^T . B (trans 1: A (K, M), B (K, N); B null = ones)
     const float* A; const float* B; float* C; const float* u; const float* v;   // + u v^T when u != null
     int32_t M, N, K, lda, ldb, ldc, trans;
+    int32_t kA, kB, kC, ku, kv;      // model ensembles: which per-member block each pointer lies in (0 shared, 1 this pass's workspace,
+                                     // 2 the parameter / gradient blocks): member m reads / writes it m strides further on
 };
 constexpr int MAX_GJOBS = 10;
 
@@ -152,6 +164,8 @@ struct AArgs {
     int32_t o_ny0, b_ny0, o_ny1, b_ny1, nn;   // diffusion net on [tau, y] (noise_option 14/15/18/19), dense sums in the parameters' own layout
     int32_t o_ny0b, b_ny0b, o_ny1b, b_ny1b, tail;   // SRK: the sums over the step's fourth evaluation (added to the above)
     int32_t n_jobs;
+    int32_t zper;     // z-planes of ONE model (jobs + assembly planes): blockIdx.z = member * zper + plane
+    MStride ms;
     GJob job[MAX_GJOBS];
 };
 
@@ -216,7 +230,7 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
     const int split = blockIdx.x;
     const int r_begin = split * t.rows_per_split;
     const int r_end = min(t.rows, r_begin + t.rows_per_split);
-    const int B = a.B, H = a.H;
+    const int B = a.Br, H = a.H;      // (B: the rows reduced per pass; the planes' row stride is a.B)
 
     // staging assignment: rows (tid >> 5) and (tid >> 5) + 16 of the chunk, float4 column 4 * (tid & 31), for D and X
     const int c4 = (tid & 31) * 4;
@@ -227,15 +241,16 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
     // two element offsets ADVANCE from chunk to chunk (one integer division per kernel instead of two per chunk and lane: the
     // division and the 64-bit address products were ~3 VALU instructions per MFMA on the issue port the MFMAs share).
     // offset(n0, b) = base + n0 * sn + b * sb per operand; moving on by RC rows adds RC * sb, a wrap into the next pass adds sn - B * sb.
-    const size_t BH = (size_t)B * H;
-    const float* dbase = a.delta + ((size_t)t.poff * a.NG + t.d_slot) * BH + t.h0 + c4;
+    const size_t BH = (size_t)a.B * H;
+    const size_t mrow = (size_t)blockIdx.z * a.mrows * H;      // the member's first row of every plane (one model: 0)
+    const float* dbase = a.delta + ((size_t)t.poff * a.NG + t.d_slot) * BH + mrow + t.h0 + c4;
     const size_t dsn = (size_t)t.pstride * a.NG * BH;
     const float* xbase;
     size_t xsn, xsb = H;
-    if (t.x_kind == 0) { xbase = a.act + ((size_t)t.poff * a.NSAVE + t.x_slot) * BH + t.k0 + c4; xsn = (size_t)t.pstride * a.NSAVE * BH; }
-    else if (t.x_kind == 1) { xbase = a.traj + ((size_t)t.poff * a.NP + t.xplane) * BH + t.k0 + c4; xsn = (size_t)t.pstride * a.NP * BH; }
-    else if (t.x_kind == 3) { xbase = a.delta + ((size_t)t.poff * a.NG + t.x_slot) * BH + t.k0 + c4; xsn = (size_t)t.pstride * a.NG * BH; }
-    else if (t.x_kind == 4) { xbase = a.adj + ((size_t)t.poff + 1) * BH + t.k0 + c4; xsn = (size_t)t.pstride * BH; }
+    if (t.x_kind == 0) { xbase = a.act + ((size_t)t.poff * a.NSAVE + t.x_slot) * BH + mrow + t.k0 + c4; xsn = (size_t)t.pstride * a.NSAVE * BH; }
+    else if (t.x_kind == 1) { xbase = a.traj + ((size_t)t.poff * a.NP + t.xplane) * BH + mrow + t.k0 + c4; xsn = (size_t)t.pstride * a.NP * BH; }
+    else if (t.x_kind == 3) { xbase = a.delta + ((size_t)t.poff * a.NG + t.x_slot) * BH + mrow + t.k0 + c4; xsn = (size_t)t.pstride * a.NG * BH; }
+    else if (t.x_kind == 4) { xbase = a.adj + ((size_t)t.poff + 1) * BH + mrow + t.k0 + c4; xsn = (size_t)t.pstride * BH; }
     else { xbase = nullptr; xsn = 0; xsb = 0; }      // x_kind 2: evaluated from the coefficient rows while staging (xaux_value)
     const size_t dwrap = dsn - (size_t)B * H, xwrap = xsn - (size_t)B * xsb;
     int row_r = r_begin + (tid >> 5);                 // the lane's first row of the coming chunk
@@ -380,7 +395,7 @@ __device__ __forceinline__ void wgrad_body(const WArgs& a, const WTile& t, const
         buf ^= 1;
     }
     // partial tile out: rows 16*strip + 4*lq + v, columns 16*(cg*NKTG + i) + li (strips beyond H: never read by the reduce kernel)
-    float* out = a.part + (size_t)(t.part + split) * TILE_FLOATS;
+    float* out = a.part + (size_t)blockIdx.z * a.ms.wws + (size_t)(t.part + split) * TILE_FLOATS;
     if (active) {
 #pragma unroll
         for (int i = 0; i < NKTG; ++i)
@@ -414,7 +429,9 @@ __device__ __forceinline__ void wgrad_main(const WArgs& a, float* lds) {
     // (the control-path tiles, whose staging evaluates spline pieces, were planned last)
     const int y0 = a.dsum_blocks > 0 ? 1 : 0;
     if ((int)blockIdx.y < y0) {             // the diffusion-side reductions (dsum_block)
-        const DArgs d = snsde_kernarg_element<DArgs>(offsetof(WArgs, dsum), 0);
+        DArgs d = snsde_kernarg_element<DArgs>(offsetof(WArgs, dsum), 0);
+        d.ds_part += (size_t)blockIdx.z * a.ms.bws; d.dth_part += (size_t)blockIdx.z * a.ms.bws;      // (the member's blocks)
+        d.ds += (size_t)blockIdx.z * a.ms.wws; d.dth += (size_t)blockIdx.z * a.ms.wws;
         for (int blk = blockIdx.x; blk < a.dsum_blocks; blk += gridDim.x) dsum_block<NT>(d, blk, a.dsum_blocks, lds);
         return;
     }
@@ -513,6 +530,9 @@ __global__ void __launch_bounds__(256) snsde_wgrad_reduce_kernel(WArgs a, NHArgs
     __shared__ float4 red[256];             // (= 1024 floats: the noise blocks use H + 256 <= 512 of them)
     const int y0 = nh.rows > 0 ? 1 : 0;     // (riders first, as in the GEMM launch)
     if ((int)blockIdx.y < y0) {             // hidden gradient of the time-only noise MLP: nh.rows x nh.nby virtual blocks
+        const size_t mw = (size_t)blockIdx.z * a.ms.wws;      // (the member's blocks; one model: blockIdx.z == 0)
+        nh.params += (size_t)blockIdx.z * a.ms.par; nh.gt += (size_t)blockIdx.z * a.ms.fws;
+        nh.ds += mw; nh.dz1 += mw; nh.dz2 += mw; nh.a1 += mw;
         for (int v = blockIdx.x; v < nh.rows * nh.nby; v += gridDim.x)
             noise_hidden_block(nh, v / nh.nby, v % nh.nby, reinterpret_cast<float*>(red));
         return;
@@ -525,7 +545,7 @@ __global__ void __launch_bounds__(256) snsde_wgrad_reduce_kernel(WArgs a, NHArgs
     // the control-path tile a fifth) are not read either; a float4 never straddles a tile row (TILE is a multiple of 4)
     const bool live = e < TILE * TILE ? ((e % TILE) < t.ncols && t.h0 + e / TILE < a.H) : (e < TILE_FLOATS && t.bias >= 0);
     if (live) {
-        const float* p = a.part + (size_t)t.part * TILE_FLOATS + e;
+        const float* p = a.part + (size_t)blockIdx.z * a.ms.wws + (size_t)t.part * TILE_FLOATS + e;
         int s = g;
         for (; s + 12 < t.nsplit; s += 16) {      // four loads in flight, added in split order
             const float4 v0 = *reinterpret_cast<const float4*>(p + (size_t)s * TILE_FLOATS);
@@ -545,6 +565,7 @@ __global__ void __launch_bounds__(256) snsde_wgrad_reduce_kernel(WArgs a, NHArgs
     red[tid] = acc;
     __syncthreads();
     if (g != 0 || e >= TILE_FLOATS) return;
+    float* const sums = a.sums + (size_t)blockIdx.z * a.ms.wws;
     const float4 r1 = red[tid + 64], r2 = red[tid + 128], r3 = red[tid + 192];
     const float v4[4] = {(acc.x + r1.x) + (r2.x + r3.x), (acc.y + r1.y) + (r2.y + r3.y), (acc.z + r1.z) + (r2.z + r3.z),
                          (acc.w + r1.w) + (r2.w + r3.w)};
@@ -555,11 +576,11 @@ __global__ void __launch_bounds__(256) snsde_wgrad_reduce_kernel(WArgs a, NHArgs
             const int hl = ej / TILE, kl = ej % TILE;
             if (kl >= t.ncols) continue;                       // never written by the GEMM kernel
             const int col = t.kd + kl + (kl >= t.csplit ? t.cshift : 0);
-            if (t.h0 + hl < a.H) a.sums[t.out + (size_t)(t.h0 + hl) * t.ldo + col] = v4[j];
+            if (t.h0 + hl < a.H) sums[t.out + (size_t)(t.h0 + hl) * t.ldo + col] = v4[j];
         } else {
             if (t.bias < 0) continue;
             const int hl = ej - TILE * TILE;
-            if (t.h0 + hl < a.H) a.sums[t.bias + t.h0 + hl] = v4[j];
+            if (t.h0 + hl < a.H) sums[t.bias + t.h0 + hl] = v4[j];
         }
     }
 }
@@ -568,11 +589,12 @@ __global__ void __launch_bounds__(256) snsde_wgrad_reduce_kernel(WArgs a, NHArgs
 
 // closed-form table noise (noise_option 1..6): table[n][f] = exp(sigma) {1, t_n} or exp(sigma_diag[f]) {1, t_n}, so
 // d/d sigma = sum_{n,f} ds table (1..3),  d/d sigma_diag[f] = sum_n ds table (4..6)
-struct SArgs { const float* ds; const float* gt; float* grad; int32_t rows, H, off_sigma, off_sigma_diag, no; };
+struct SArgs { const float* ds; const float* gt; float* grad; int32_t rows, H, off_sigma, off_sigma_diag, no; MStride ms; };
 
 __global__ void __launch_bounds__(256) snsde_sigma_grad_kernel(SArgs a) {
     __shared__ float red[256];
     const int tid = threadIdx.x;
+    a.ds += (size_t)blockIdx.y * a.ms.wws; a.gt += (size_t)blockIdx.y * a.ms.fws; a.grad += (size_t)blockIdx.y * a.ms.par;      // (the member)
     if (a.no <= 3) {             // scalar sigma: one block over every (row, feature)
         float s = 0.0f;
         const int total = a.rows * a.H;
@@ -598,8 +620,10 @@ __global__ void __launch_bounds__(256) snsde_sigma_grad_kernel(SArgs a) {
 // ---- epilogue -------------------------------------------------------------------------------------------------
 
 // dense sums -> flat layout for the parameters that need no further algebra; everything else starts at zero
-__device__ __forceinline__ void assemble_element(const AArgs& a, int p) {
+// mw / mp / mf: the member's offsets into this pass's workspace, the parameter / gradient blocks and the forward workspace (one model: 0)
+__device__ __forceinline__ void assemble_element(const AArgs& a, int p, size_t mw, size_t mp) {
     if (p >= a.P) return;
+    const float* const sums = a.sums + mw;
     // entries a small product of the same launch writes (the folded first layer's algebra, the time-only noise MLP) are theirs
     for (int i = 0; i < a.n_jobs; ++i) {
         const GJob j = snsde_kernarg_element<GJob>(offsetof(AArgs, job), i);
@@ -613,30 +637,30 @@ __device__ __forceinline__ void assemble_element(const AArgs& a, int p) {
     float val = 0.0f;
     auto inside = [&](int off, int count, int& rel) { rel = p - off; return off >= 0 && rel >= 0 && rel < count; };
     int rel;
-    if (inside(net.out.src_w, H * H, rel)) val = a.sums[a.o_out + rel];
-    else if (inside(net.out.src_b, H, rel)) val = a.sums[a.b_out + rel];
-    else if (a.io == 0 && inside(net.init.src_w, H * a.C, rel)) val = a.sums[a.o_first + rel];      // ld_first == C
-    else if (a.io == 0 && inside(net.init.src_b, H, rel)) val = a.sums[a.b_first + rel];
-    else if (a.io != 0 && !emb && inside(net.in.src_w, H * Kin, rel)) val = a.sums[a.o_first + (size_t)(rel / Kin) * a.ld_first + rel % Kin];
-    else if (a.io != 0 && !emb && inside(net.in.src_b, H, rel)) val = a.sums[a.b_first + rel];
-    else if (emb && inside(net.emb.src_b, H, rel)) val = a.sums[a.b_first + rel];
+    if (inside(net.out.src_w, H * H, rel)) val = sums[a.o_out + rel];
+    else if (inside(net.out.src_b, H, rel)) val = sums[a.b_out + rel];
+    else if (a.io == 0 && inside(net.init.src_w, H * a.C, rel)) val = sums[a.o_first + rel];      // ld_first == C
+    else if (a.io == 0 && inside(net.init.src_b, H, rel)) val = sums[a.b_first + rel];
+    else if (a.io != 0 && !emb && inside(net.in.src_w, H * Kin, rel)) val = sums[a.o_first + (size_t)(rel / Kin) * a.ld_first + rel % Kin];
+    else if (a.io != 0 && !emb && inside(net.in.src_b, H, rel)) val = sums[a.b_first + rel];
+    else if (emb && inside(net.emb.src_b, H, rel)) val = sums[a.b_first + rel];
     else if (inside(net.off_theta, 1, rel)) {
         if (a.has_dth) {
-            const float sg = snsde_sigmoid(a.params[net.off_theta]);
-            val = a.dth[0] * sg * (1.0f - sg);
+            const float sg = snsde_sigmoid((a.params + mp)[net.off_theta]);
+            val = (a.dth + mw)[0] * sg * (1.0f - sg);
         }
     } else if (a.nn >= 1 && inside(net.ny0.src_w, H * (H + 2), rel))      // tail 1: SRK's fourth evaluation; 2: Milstein's second-order
-        val = a.sums[a.o_ny0 + rel] + ((a.tail == 1 || (a.tail == 2 && rel % (H + 2) >= 2)) ? a.sums[a.o_ny0b + rel] : 0.0f);   // term (y columns)
-    else if (a.nn >= 1 && inside(net.ny0.src_b, H, rel)) val = a.sums[a.b_ny0 + rel] + (a.tail == 1 ? a.sums[a.b_ny0b + rel] : 0.0f);
-    else if (a.nn == 2 && inside(net.ny1.src_w, H * H, rel)) val = a.sums[a.o_ny1 + rel] + (a.tail ? a.sums[a.o_ny1b + rel] : 0.0f);
-    else if (a.nn == 2 && inside(net.ny1.src_b, H, rel)) val = a.sums[a.b_ny1 + rel] + (a.tail == 1 ? a.sums[a.b_ny1b + rel] : 0.0f);
+        val = sums[a.o_ny0 + rel] + ((a.tail == 1 || (a.tail == 2 && rel % (H + 2) >= 2)) ? sums[a.o_ny0b + rel] : 0.0f);   // term (y columns)
+    else if (a.nn >= 1 && inside(net.ny0.src_b, H, rel)) val = sums[a.b_ny0 + rel] + (a.tail == 1 ? sums[a.b_ny0b + rel] : 0.0f);
+    else if (a.nn == 2 && inside(net.ny1.src_w, H * H, rel)) val = sums[a.o_ny1 + rel] + (a.tail ? sums[a.o_ny1b + rel] : 0.0f);
+    else if (a.nn == 2 && inside(net.ny1.src_b, H, rel)) val = sums[a.b_ny1 + rel] + (a.tail == 1 ? sums[a.b_ny1b + rel] : 0.0f);
     else {
         for (int l = 0; l < a.nhid; ++l) {
-            if (inside(net.hid[l].src_w, H * H, rel)) { val = a.sums[a.o_hid[l] + rel]; break; }
-            if (inside(net.hid[l].src_b, H, rel)) { val = a.sums[a.b_hid[l] + rel]; break; }
+            if (inside(net.hid[l].src_w, H * H, rel)) { val = sums[a.o_hid[l] + rel]; break; }
+            if (inside(net.hid[l].src_b, H, rel)) { val = sums[a.b_hid[l] + rel]; break; }
         }
     }
-    a.grad[p] = val;
+    (a.grad + mp)[p] = val;
 }
 
 // ONE epilogue launch: the small products (K, M, N of a few hundred) and, in extra z-planes, the assembly of the dense sums into the
@@ -648,13 +672,20 @@ __device__ __forceinline__ void assemble_element(const AArgs& a, int p) {
 constexpr int SGK = 136;
 __global__ void __launch_bounds__(256) snsde_epilogue_kernel(AArgs a) {
     __shared__ float As[SGK][33], Bs[SGK][33];      // [k][m], [k][n]
-    if ((int)blockIdx.z >= a.n_jobs) {      // planes behind the jobs: dense sums -> flat layout (independent of the products: one launch)
+    // model ensembles: the member is folded into z (one model: zper == gridDim.z, member 0)
+    const int mem = (int)blockIdx.z / a.zper, zz = (int)blockIdx.z - mem * a.zper;
+    const size_t moff[3] = {0, (size_t)mem * a.ms.wws, (size_t)mem * a.ms.par};
+    if (zz >= a.n_jobs) {      // planes behind the jobs: dense sums -> flat layout (independent of the products: one launch)
         const int per_plane = gridDim.x * gridDim.y;
-        const int v = ((int)blockIdx.z - a.n_jobs) * per_plane + blockIdx.y * gridDim.x + blockIdx.x;
-        assemble_element(a, v * 256 + threadIdx.x);
+        const int v = (zz - a.n_jobs) * per_plane + blockIdx.y * gridDim.x + blockIdx.x;
+        assemble_element(a, v * 256 + threadIdx.x, moff[1], moff[2]);
         return;
     }
-    const GJob j = snsde_kernarg_element<GJob>(offsetof(AArgs, job), blockIdx.z);
+    GJob j = snsde_kernarg_element<GJob>(offsetof(AArgs, job), zz);
+    j.A += j.kA == 1 ? moff[1] : (j.kA == 2 ? moff[2] : 0);
+    if (j.B) j.B += j.kB == 1 ? moff[1] : (j.kB == 2 ? moff[2] : 0);
+    j.C += j.kC == 1 ? moff[1] : (j.kC == 2 ? moff[2] : 0);
+    if (j.u) { j.u += j.ku == 1 ? moff[1] : (j.ku == 2 ? moff[2] : 0); j.v += j.kv == 1 ? moff[1] : (j.kv == 2 ? moff[2] : 0); }
     const int m0 = blockIdx.y * 32, n0 = blockIdx.x * 32;
     if (m0 >= j.M || n0 >= j.N) return;
     const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;     // 32 x 8
@@ -880,9 +911,23 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
 
 }  // namespace
 
-size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net) {
+// model ensembles (SNSDE_FLAG_ENSEMBLE_GRAD): every member is planned as its own solve of batch / M rows - its tiles, its R-splits
+// (the order its partial sums are added in), its sums - so that block m of the gradient equals the member-alone pass bit for bit
+static snsde_backward wgrad_member_alone(const snsde_backward* b, int members) {
+    snsde_backward one = *b;
+    if (members > 1) {
+        one.fwd.batch = b->fwd.batch / members;
+        one.fwd.global_rows = snsde_plan_rows(&b->fwd);
+        one.fwd.members = 0;
+    }
+    return one;
+}
+
+size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net, int members) {
     WPlan w;
-    return make_wplan(b, net, &w) ? w.total_floats : 0;
+    const snsde_backward one = wgrad_member_alone(b, members);
+    if (!make_wplan(&one, net, &w)) return 0;
+    return members > 1 ? (size_t)members * snsde_member_bws_stride(w.total_floats) : w.total_floats;
 }
 
 // The whole parameter pass as THREE launches on the caller's stream (round 3: up to nine, two of them on a side stream):
@@ -904,8 +949,21 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     }
     WPlan plan;
     WPlan* wp = &plan;
-    if (!make_wplan(b, net, wp)) return SNSDE_ERR_UNSUPPORTED;
+    // model ensembles: one member's plan (wgrad_member_alone) runs for every member, the member on a grid axis of each launch - its
+    // block of this workspace, of the adjoint's and of the forward's, its parameter and gradient blocks.  No loop over members here
+    const int members = r.members > 1 ? r.members : 1;
+    const snsde_backward one = wgrad_member_alone(b, members);
+    if (!make_wplan(&one, net, wp)) return SNSDE_ERR_UNSUPPORTED;
     const snsde_solve& s = b->fwd;
+    const int Bm = s.batch / members;      // rows reduced per pass (one model: the batch)
+    MStride ms{};
+    if (members > 1) {
+        const size_t wws = snsde_member_bws_stride(wp->total_floats);
+        if (members > 65535 || s.batch % members || n_params <= 0 || wws >= (1ull << 32) || r.bws_stride >= (1ull << 32) || r.fws_stride >= (1ull << 32) ||
+            s.noise_table || b->grad_noise_table)
+            return SNSDE_ERR_UNSUPPORTED;
+        ms = MStride{(uint32_t)wws, (uint32_t)r.bws_stride, (uint32_t)n_params, (uint32_t)r.fws_stride};
+    }
     const int H = s.model.hidden_channels, C = s.model.input_channels, io = s.model.input_option, no = s.model.noise_option;
     WArgs a{};
     a.delta = b->delta_save; a.act = s.act_save; a.traj = s.traj;
@@ -919,12 +977,13 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     }
     const bool smooth = s.model.activation != SNSDE_ACT_RELU;      // act_save then also holds the NL pre-activations per step
     a.B = s.batch; a.H = H; a.N = wp->n_pass; a.NG = wp->ndelta;
+    a.Br = Bm; a.mrows = members > 1 ? Bm : 0; a.ms = ms;
     a.NSAVE = wp->nact + (smooth ? s.model.num_hidden_layers + (snsde_noise_net_layers(no) == 2 ? (srk ? 2 : 1) : 0) : 0);      // (SRK: + the fourth evaluation's)
     a.adj = b->adj;
-    a.R = wp->n_pass * s.batch; a.ntiles = wp->ntiles; a.NP = wp->NP;
+    a.R = wp->n_pass * Bm; a.ntiles = wp->ntiles; a.NP = wp->NP;
     const bool xq = fp.kernel == snsde_mfma::FwdKernel::lean_bf16;      // (mode 1 after a bf16-operand forward: SNSDE_FLAG_BF16_GRAD)
     for (int i = 0; i < wp->ntiles; ++i) a.tile[i] = wp->tile[i];
-    a.x = XInfo{s.coeffs, pass_tab, s.batch, C, s.knots - 1, wp->t_col0, wp->xt, wp->x_col0, wp->x_cols,
+    a.x = XInfo{s.coeffs, pass_tab, Bm, C, s.knots - 1, wp->t_col0, wp->xt, wp->x_col0, wp->x_cols,
                 s.model.time_feature == SNSDE_TIME_RAW ? 1 : 0, wp->n_col0, snsde_samples(&s)};
     AArgs aa = wp->aa;
     const float* gt = s.noise_table ? s.noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s.workspace) + fp.gt_off : nullptr);
@@ -954,7 +1013,7 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
         const int want = a.dsum_blocks < 64 ? a.dsum_blocks : 64;
         if (gx < want) gx = want;
     }
-    const dim3 wgrid(gx, wp->ntiles + (a.dsum_blocks > 0 ? 1 : 0));
+    const dim3 wgrid(gx, wp->ntiles + (a.dsum_blocks > 0 ? 1 : 0), members);
     if (xq) hipLaunchKernelGGL(snsde_wgrad_bf16_kernel, wgrid, dim3(NT), lds_bytes, stream, a);
     else hipLaunchKernelGGL(snsde_wgrad_kernel, wgrid, dim3(NT), lds_bytes, stream, a);
     NHArgs nh{};
@@ -963,7 +1022,7 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
         nh = NHArgs{s.params, ds, gt, aa.tau, aa.dz1, aa.dz2, aa.a1, H, aa.tau_stride, net.nt0.src_w, net.nt0.src_b, net.nt1.src_w,
                     wp->n_trow, (H + 63) / 64};
     }
-    hipLaunchKernelGGL(snsde_wgrad_reduce_kernel, dim3((TILE_FLOATS / 4 + 63) / 64, wp->ntiles + (nh.rows > 0 ? 1 : 0)), dim3(256), 0, stream,
+    hipLaunchKernelGGL(snsde_wgrad_reduce_kernel, dim3((TILE_FLOATS / 4 + 63) / 64, wp->ntiles + (nh.rows > 0 ? 1 : 0), members), dim3(256), 0, stream,
                        a, nh);
 
     // small products straight into the flat gradient (the assembly planes of the same launch write every other entry)
@@ -972,6 +1031,13 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
                        const float* u, const float* v) {
         GJob& j = aa.job[nj++];
         j.A = A; j.B = B; j.C = Cm; j.u = u; j.v = v; j.M = M; j.N = N; j.K = K; j.lda = lda; j.ldb = ldb; j.ldc = ldc; j.trans = trans;
+        // (the per-member block each pointer lies in: this workspace, the parameters / the gradient, or shared - the time features)
+        auto kind = [&](const float* q) {
+            if (q >= ws && q < ws + wp->total_floats) return 1;
+            if ((q >= s.params && q < s.params + n_params) || (q >= grad_params && q < grad_params + n_params)) return 2;
+            return 0;
+        };
+        j.kA = kind(A); j.kB = B ? kind(B) : 0; j.kC = kind(Cm); j.ku = u ? kind(u) : 0; j.kv = v ? kind(v) : 0;
     };
     const bool emb = (io == 2 || io == 4 || io == 6);
     int maxM = 32, maxN = 32;
@@ -1005,13 +1071,15 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     }
     const int gxe = (maxN + 31) / 32, gye = (maxM + 31) / 32;
     const int planes = ((n_params + 255) / 256 + gxe * gye - 1) / (gxe * gye);      // assembly blocks, gxe x gye of them per z-plane
-    hipLaunchKernelGGL(snsde_epilogue_kernel, dim3(gxe, gye, nj + planes), dim3(256), 0, stream, aa);
+    aa.zper = nj + planes; aa.ms = ms;
+    if ((long)members * aa.zper > 65535) return SNSDE_ERR_UNSUPPORTED;
+    hipLaunchKernelGGL(snsde_epilogue_kernel, dim3(gxe, gye, members * aa.zper), dim3(256), 0, stream, aa);
     if (no >= 1 && no <= 6) {     // after the assembly (which zero-fills sigma / sigma_diag)
         SArgs sg{};
         sg.ds = ds; sg.gt = gt; sg.grad = grad_params; sg.rows = wp->n_trow; sg.H = H; sg.no = no;
-        sg.off_sigma = net.off_sigma; sg.off_sigma_diag = net.off_sigma_diag;
+        sg.off_sigma = net.off_sigma; sg.off_sigma_diag = net.off_sigma_diag; sg.ms = ms;
         if ((no <= 3 ? net.off_sigma : net.off_sigma_diag) < 0) return SNSDE_ERR_UNSUPPORTED;
-        hipLaunchKernelGGL(snsde_sigma_grad_kernel, dim3(no <= 3 ? 1 : (H + 63) / 64), dim3(256), 0, stream, sg);
+        hipLaunchKernelGGL(snsde_sigma_grad_kernel, dim3(no <= 3 ? 1 : (H + 63) / 64, members), dim3(256), 0, stream, sg);
     }
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }

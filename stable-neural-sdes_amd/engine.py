@@ -201,9 +201,16 @@ def check_sample_grad(sample_grad):
     return sample_grad
 
 
+def check_ensemble_grad(ensemble_grad):
+    """The `ensemble_grad` option (training through a model ensemble, SNSDE_FLAG_ENSEMBLE_GRAD): a bool, ValueError otherwise."""
+    if not isinstance(ensemble_grad, bool):
+        raise ValueError(f"ensemble_grad must be a bool (differentiate a solve of `members` models), got {ensemble_grad!r}")
+    return ensemble_grad
+
+
 def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                      row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                     members=0):
+                     members=0, ensemble_grad=False):
     """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
     device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
     s = _lib.Solve()
@@ -215,6 +222,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
     s.kernel = _lib.KERNELS[kernel]
     s.flags = precision_flags(precision, bf16_grad) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
     s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
+    s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
@@ -223,16 +231,17 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                  row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                 members=0):
+                 members=0, ensemble_grad=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
     at does not map paths to input rows.  sample_grad: SNSDE_FLAG_SAMPLE_GRAD; training: the solve writes its training planes
     (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers; a bf16 solve under bf16_grad
     only: SNSDE_FLAG_BF16_GRAD).  members: models of one architecture in the call (include/snsde.h; `batch` then counts the rows
-    of all members); 'none' where the plan arrives at a kernel that does not map rows to members."""
+    of all members); 'none' where the plan arrives at a kernel that does not map rows to members.  ensemble_grad:
+    SNSDE_FLAG_ENSEMBLE_GRAD - an ensemble has training planes under it only, on the kernels the ensemble adjoint route covers."""
     s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
-                         exact_order, sample_grad, training, bf16_grad, members)
+                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad)
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
 
@@ -544,7 +553,7 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0):
+                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -556,12 +565,14 @@ class SolveCall:
             raise ValueError(f'samples={samples!r}: the {B} rows of y0 are paths, a whole number of groups of `samples` per input row')
         if S > 1 and (((save_traj or save_dW or save_act) and not sample_grad) or z0_linear is not None):
             raise ValueError('samples > 1 is inference only: no saved trajectory, increments or activations, and y0 is the caller\'s')
-        # members = M > 1 (a model ensemble, inference): flat_params is (M, numel), y0 / dW / dU / row_out and the result hold the rows
+        # members = M > 1 (a model ensemble; inference unless ensemble_grad opts in, SNSDE_FLAG_ENSEMBLE_GRAD): flat_params is (M, numel), y0 / dW / dU / row_out and the result hold the rows
         # of all members, member-major (B = M Bm rows), coeffs is the members' shared control path (Bm rows)
         M = int(members) if members else 1
         if M < 1 or B % M or (M > 1 and (B // M) % 4):
             raise ValueError(f'members={members!r}: the {B} rows of y0 are those of all members, each a whole number of 4-row tiles')
-        if M > 1 and (S > 1 or save_traj or save_dW or save_act or z0_linear is not None or noise_table is not None or kl_column is not None):
+        ensemble_grad = bool(ensemble_grad) and M > 1      # (no effect on one model)
+        if M > 1 and (S > 1 or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
+                      or kl_column is not None):
             raise ValueError('members > 1 is inference only: no samples, saved planes, fused initial network, supplied noise table or '
                              'accumulator column')
         _check_f32('y0', y0, (B, model.hidden_channels))
@@ -602,6 +613,8 @@ class SolveCall:
             self.base_flags |= _lib.FLAG_LEAN_GENERAL
         if sample_grad and S > 1:      # (SNSDE_FLAG_SAMPLE_GRAD: no effect on one path per row)
             self.base_flags |= _lib.FLAG_SAMPLE_GRAD
+        if ensemble_grad:
+            self.base_flags |= _lib.FLAG_ENSEMBLE_GRAD
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -625,7 +638,8 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M)
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad)
+        self.members = M
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
             if lay is None:
@@ -733,18 +747,21 @@ _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per c
 
 
 def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
-                  samples=0, sample_grad=False, precision='fp32', bf16_grad=False):
+                  samples=0, sample_grad=False, precision='fp32', bf16_grad=False, members=0, ensemble_grad=False):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
     supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none); samples: paths
     per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD).  precision='bf16': 0, or under bf16_grad
-    (SNSDE_FLAG_BF16_GRAD) 1 where the bf16 lean kernel runs the forward and the general MFMA adjoint its backward."""
+    (SNSDE_FLAG_BF16_GRAD) 1 where the bf16 lean kernel runs the forward and the general MFMA adjoint its backward.  members: models
+    in the call (`batch` counts the rows of all of them) - 0 without ensemble_grad (SNSDE_FLAG_ENSEMBLE_GRAD), 1 or 0 with it."""
+    members = int(members) if members and int(members) > 1 else 0
+    ensemble_grad = bool(ensemble_grad) and members > 1
     samples = int(samples) if samples and int(samples) > 1 else 0
     sample_grad = bool(sample_grad) and samples > 1
     pflags = precision_flags(precision, bf16_grad)
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
            model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad,
-           pflags)
+           pflags, members, ensemble_grad)
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -753,6 +770,8 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
         s.kernel = _lib.KERNELS[kernel]
         s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0) | pflags
+        s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
+        s.members = members
         s.samples = samples
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
         if kl_column is not None:
@@ -816,7 +835,8 @@ def param_gradients(call, adj, delta, stream=None, want_table_grad=False):
     if nbytes == 0:
         raise NotImplementedError('snsde_param_gradients covers the MFMA-path configurations only')
     ws = torch.empty(nbytes, device=adj.device, dtype=torch.uint8)
-    grad = torch.empty(call.keep[0].numel(), device=adj.device, dtype=torch.float32)
+    grad = torch.empty(tuple(call.keep[0].shape) if getattr(call, 'members', 1) > 1 else call.keep[0].numel(),      # (an ensemble: (M, numel))
+                       device=adj.device, dtype=torch.float32)
     stream = torch.cuda.current_stream(adj.device) if stream is None else stream
     _lib.check(L.snsde_param_gradients(C.byref(b), _ptr(grad), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)),
                'snsde_param_gradients')
@@ -859,7 +879,8 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
     ws = torch.empty(sizes[0], device=dev, dtype=torch.uint8)
     b.workspace, b.workspace_bytes = _ptr(ws), ws.numel()
     pws = torch.empty(sizes[1], device=dev, dtype=torch.uint8)
-    grad = torch.empty(call.keep[0].numel(), device=dev, dtype=torch.float32)
+    grad = torch.empty(tuple(call.keep[0].shape) if getattr(call, 'members', 1) > 1 else call.keep[0].numel(),      # (an ensemble: (M, numel))
+                       device=dev, dtype=torch.float32)
     stream = torch.cuda.current_stream(dev) if stream is None else stream
     _lib.check(L.snsde_backward_with_gradients(C.byref(b), _ptr(grad), _ptr(pws), pws.numel(), C.c_void_p(stream.cuda_stream)),
                'snsde_backward_with_gradients')

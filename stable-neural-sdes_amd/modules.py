@@ -347,7 +347,11 @@ class Ensemble(nn.Module):
     torchsde.sdeint_ensemble runs over the members' `func` - a single fused solve where the library plans it, the M ordinary solves
     otherwise - and each member's own readout follows.  Inference: in eval() and under no_grad the output equals calling the M
     wrappers one after the other with options={'seed': s, 'row_offset': m B, 'global_rows': M B}, bit for bit (member m's rows are
-    rows m B .. of an M B-row problem).  Training through an ensemble is not built: sdeint_ensemble raises under autograd."""
+    rows m B .. of an M B-row problem).  Training through an ensemble is an opt-in, options={'ensemble_grad': True}
+    (torchsde.sdeint_ensemble): in train() with gradients required each member's initial state is the differentiable tensor-op form
+    (`_prepare_initial_state`: `_initial_state` never hands `initial_network` to the solve under grad), the readouts stay the
+    members' own, and outputs and every member's parameter gradients equal the M wrapper calls in training mode with the options
+    above.  Without the opt-in sdeint_ensemble raises under autograd."""
 
     KINDS = ()      # (the three wrapper classes: filled below, once they are all defined)
 

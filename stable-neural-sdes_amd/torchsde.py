@@ -395,7 +395,8 @@ def _same_control(a, b):
 
 
 def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
-    """M models of one architecture on one batch in ONE fused solve (inference; include/snsde.h: snsde_solve.members): deep-ensemble
+    """M models of one architecture on one batch in ONE fused solve (include/snsde.h: snsde_solve.members; inference unless
+    options={'ensemble_grad': True}): deep-ensemble
     prediction, the seed models of one configuration on a test set, the points of a sweep.
 
     sdes: a sequence of M modules honouring the Diffusion_model contract with equal model structs, all holding the same control
@@ -408,8 +409,19 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     launch over M B rows with the members' parameter blocks stacked and the control path shared; everywhere else (another kernel,
     composed or latent fields, members of different architecture, backend='torch', CPU, a supplied `bm`) exactly those M calls run,
     without a warning: the same result either way.  options={'strict': True} raises NotImplementedError instead of looping.
-    ValueError: a solve that would be differentiated (grad enabled and y0, a member's parameter or the coefficients require it),
-    samples > 1, save_traj, recompute, z0_linear - training through an ensemble is not built."""
+    ValueError: a solve that would be differentiated (grad enabled and y0, a member's parameter or the coefficients require it)
+    without the opt-in below, samples > 1, save_traj, recompute, z0_linear.
+
+    options={'ensemble_grad': True} (SNSDE_FLAG_ENSEMBLE_GRAD) opts in to training: under autograd the result is differentiable
+    with respect to y0 (M, B, H), every member's parameters and the shared coefficients.  Where the library plans the ensemble
+    adjoint (engine.backward_mode(..., members=M, ensemble_grad=True) == 1: the lean / general 4-row-tile kernels, elementwise
+    diffusions, H <= 128) one autograd node runs ONE fused training forward and ONE snsde_backward_with_gradients for all members;
+    member m's outputs and gradients equal, bit for bit, its own differentiable sdeint at row_offset + m B with the same global_rows.
+    Everywhere else (CPU, backend='torch', a supplied bm, an uncovered plan, B % 4 != 0, different architectures, coefficients that
+    require grad) exactly those M differentiable sdeint calls run and are stacked - autograd then sums coeffs.grad over the members;
+    options={'strict': True} raises NotImplementedError instead.  ValueError together with ensemble_grad: samples > 1, save_traj,
+    recompute (the option or SNSDE_RECOMPUTE_STEPS), z0_linear, sample_grad, bf16_grad, precision='bf16' under autograd,
+    param_pass='torch'."""
     sdes = list(sdes)
     M = len(sdes)
     if M < 1:
@@ -429,14 +441,26 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     if 'samples' in options and engine.check_samples(options['samples']) > 1:
         raise ValueError("sdeint_ensemble does not take samples > 1 (sample paths of an ensemble are not built)")
     options.pop('samples', None)
+    ensemble_grad = engine.check_ensemble_grad(options.pop('ensemble_grad')) if 'ensemble_grad' in options else False
+    needs_grad = any(_differentiated(sde, y0) for sde in sdes)
+    if ensemble_grad:
+        for name, bad in (('save_traj', bool(options.get('save_traj', False))),
+                          ("recompute (options['recompute'] or SNSDE_RECOMPUTE_STEPS in the environment)", _recompute_steps(options) > 0),
+                          ('z0_linear', 'z0_linear' in options), ('sample_grad', bool(options.get('sample_grad', False))),
+                          ('bf16_grad', bool(options.get('bf16_grad', False))),
+                          ("precision='bf16' under autograd", needs_grad and options.get('precision', 'fp32') == 'bf16'),
+                          ("param_pass='torch'", options.get('param_pass', 'hip') == 'torch')):
+            if bad:
+                raise ValueError(f"ensemble_grad=True (training through an ensemble of {M} members) does not take {name}")
     for name, bad in (('save_traj', bool(options.get('save_traj', False))), ('recompute', _recompute_steps(options) > 0),
                       ('z0_linear', 'z0_linear' in options), ('sample_grad', bool(options.get('sample_grad', False))),
                       ('bf16_grad', bool(options.get('bf16_grad', False)))):
         if bad:
             raise ValueError(f"sdeint_ensemble is inference only: it does not take {name}")
-    if any(_differentiated(sde, y0) for sde in sdes):
+    if needs_grad and not ensemble_grad:
         raise ValueError("sdeint_ensemble is inference only: y0, the control path or a member's parameter requires grad (use "
                          "torch.no_grad() or requires_grad_(False)); training through an ensemble is not built")
+    needs_grad = needs_grad and ensemble_grad
     ts = _as_ts(ts, y0)
     B = int(y0.shape[1])
     row_offset = _row_offset(options, M * B)
@@ -470,6 +494,8 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
         return loop('members of different architecture')
     if not all(_same_control(sdes[0], sde) for sde in sdes[1:]):
         return loop('members hold different control paths')
+    if needs_grad and _coeffs_need_grad(sdes[0]):
+        return loop('the control path requires grad (dL/dcoeffs of an ensemble is the sum of the members\' own)')
     coeffs = sdes[0].coeffs
     if coeffs.dim() != 3 or coeffs.shape[0] != B:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
@@ -482,6 +508,19 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     if engine.forward_path(model, M * B, L, grid.N, method, kernel, precision=precision, global_rows=global_rows, row_offset=row_offset,
                            lean_general=lean_general, exact_order=exact_order, members=M) == 'none':
         return loop('the plan arrives at a kernel that does not map rows to members')
+    if needs_grad:
+        # the ensemble adjoint route (mode 1 with delta planes for every member), or the M differentiable solves
+        if precision != 'fp32' or engine.backward_mode(model, M * B, L, grid, method, kernel, exact_order, global_rows=global_rows,
+                                                       members=M, ensemble_grad=True) != 1:
+            return loop('no fused adjoint plans this ensemble')
+        pidxs = [engine.param_index(sde, r[1]) for sde, r in zip(sdes, recs)]
+        counts = [len(p.params) for p in pidxs]
+        eopt = _EnsembleOptions(kernel=kernel, exact_order=exact_order, param_pass=options.get('param_pass', 'hip'), row_offset=row_offset,
+                                global_rows=global_rows, seed=options['seed'],
+                                row_out=None if row_out is None else _device_row_out(options, dev).repeat(M))
+        ys = _FusedEnsembleSolve.apply(sdes, recs, coeffs.detach().to(device=dev, dtype=torch.float32).contiguous(), grid, method, eopt,
+                                       counts, y0, *[p for pi in pidxs for p in pi.params])
+        return ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
     flat = torch.stack([engine.flatten_params(sde, r[1], r[2], dev) for sde, r in zip(sdes, recs)])      # (M, numel)
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
@@ -497,6 +536,50 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
         return loop(f'the launch was refused ({exc})')
     ys = ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
     return ys.to(y0.dtype)
+
+
+# What the fused ensemble node reads from `options`, resolved once by sdeint_ensemble
+_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out'))
+
+
+class _FusedEnsembleSolve(torch.autograd.Function):
+    """Differentiable fused solve of M members (options={'ensemble_grad': True}, mode 1 only): forward = ONE training-mode solve
+    with members = M (engine.SolveCall(..., ensemble_grad=True)), backward = ONE snsde_backward_with_gradients (param_pass='split':
+    the two C calls) whose (M, numel) gradient is handed to each member's parameters block by block.  The increment-keeping rule is
+    _FusedSolve.forward's (keep_dw)."""
+
+    NO_GRAD_INPUTS = 7      # sdes .. counts; y0 and the members' parameters follow
+
+    @staticmethod
+    def forward(ctx, sdes, recs, coeffs, grid, method, opt, counts, y0, *params):
+        model, layout, numel = recs[0]
+        M, B = int(y0.shape[0]), int(y0.shape[1])
+        dev = y0.device
+        flat = torch.stack([engine.flatten_params(sde, r[1], r[2], dev) for sde, r in zip(sdes, recs)])      # (M, numel)
+        y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
+        keep_dw = not (method in ('euler', 'milstein') and not torch.is_tensor(opt.seed) and opt.param_pass in ('hip', 'split')
+                       and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
+        call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=opt.seed, row_offset=opt.row_offset, kernel=opt.kernel,
+                                save_traj=True, save_dW=keep_dw, save_act=True, exact_order=opt.exact_order, row_out=opt.row_out,
+                                global_rows=opt.global_rows, members=M, ensemble_grad=True)
+        ys = call.launch()
+        ctx.call, ctx.sdes, ctx.layouts, ctx.counts = call, sdes, [r[1] for r in recs], counts
+        ctx.param_pass, ctx.y0_shape, ctx.y0_dtype = opt.param_pass, tuple(y0.shape), y0.dtype
+        return ys.to(y0.dtype) if y0.dtype != ys.dtype else ys.detach()
+
+    @staticmethod
+    def backward(ctx, grad_ys):
+        call = ctx.call
+        grad_ys = grad_ys.to(torch.float32).contiguous()
+        if ctx.param_pass == 'split':      # the two C calls one after the other, every a_n written
+            adj, delta = engine.solve_backward(call, grad_ys, save_delta=True, adj0_only=False)
+            flat = engine.param_gradients(call, adj, delta)
+        else:
+            adj, flat = engine.backward_with_gradients(call, grad_ys, adj0_only=True)
+        grads = []
+        for m, (sde, layout) in enumerate(zip(ctx.sdes, ctx.layouts)):
+            grads.extend(engine.param_index(sde, layout).grads_from_flat(flat[m]))
+        return (None,) * _FusedEnsembleSolve.NO_GRAD_INPUTS + (adj[0].reshape(ctx.y0_shape).to(ctx.y0_dtype),) + tuple(grads)
 
 
 def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoint_adaptive=False, adjoint_rtol=1e-5,
