@@ -114,7 +114,12 @@ enum {
     SNSDE_FLAG_BF16_GRAD = 128,
     /* Opt-in: a model ensemble (snsde_solve.members = M > 1) may be differentiated (snsde_solve.members, last paragraph).  No
      * effect when members <= 1.  Together with SNSDE_FLAG_BF16_OPERANDS (an inference-only forward): SNSDE_ERR_UNSUPPORTED. */
-    SNSDE_FLAG_ENSEMBLE_GRAD = 256
+    SNSDE_FLAG_ENSEMBLE_GRAD = 256,
+    /* Opt-in: sample paths of a model ensemble - members = M > 1 together with samples = S > 1 in one solve (M x S paths per
+     * input row; snsde_solve.members, the paragraph on sample paths).  No effect when members <= 1 or samples <= 1; without it
+     * the combination stays SNSDE_PATH_NONE / SNSDE_ERR_UNSUPPORTED.  Training through it needs this flag together with
+     * SNSDE_FLAG_ENSEMBLE_GRAD and SNSDE_FLAG_SAMPLE_GRAD: each of the three keeps its own meaning. */
+    SNSDE_FLAG_ENSEMBLE_SAMPLES = 512
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -230,7 +235,22 @@ typedef struct snsde_solve {
                            /* (a block starts 16-byte aligned).  The adjoint's pack launch and the three launches of the    */
                            /* weight-gradient pass carry the member on a grid axis: no launch per member.                   */
                            /* snsde_coeff_gradients stays SNSDE_ERR_UNSUPPORTED (workspace query 0) for members > 1.        */
-    int64_t  row_offset;   /* global index of local row 0 (batch shards keep the global Philox   */
+                           /* Sample paths of an ensemble are opt-in, SNSDE_FLAG_ENSEMBLE_SAMPLES; without the flag         */
+                           /* samples > 1 stays refused as above.  With it and samples = S > 1: `batch` counts all paths of */
+                           /* all members, member-major - row r = m Bm + p, Bm = batch / M paths per member, p = b S + s;   */
+                           /* `coeffs` is (Bm / S, L-1, 4C), shared, and row r reads coefficient row (r - m Bm) / S;        */
+                           /* everything per row stays per row and the Philox counter stays (row_offset + r, ..).           */
+                           /* SNSDE_ERR_DIMS also where Bm % S != 0 (and, as for samples alone, row_offset % S or           */
+                           /* global_rows % S != 0).  Member m's rows equal, bit for bit, the SAMPLED solve of member m     */
+                           /* alone run as a shard: members = 0, samples = S, batch = Bm, params = block m, row_offset +    */
+                           /* m Bm, the same global_rows.  Kernels: those that take both options - the lean kernel and the  */
+                           /* general kernel on 4-row tiles; workspace sizes are those of `members`.  Training needs        */
+                           /* SNSDE_FLAG_ENSEMBLE_SAMPLES | SNSDE_FLAG_ENSEMBLE_GRAD | SNSDE_FLAG_SAMPLE_GRAD together and  */
+                           /* is covered exactly where SNSDE_FLAG_ENSEMBLE_GRAD covers the ensemble; each member is planned */
+                           /* as its own sampled solve of Bm paths and every result equals that solve's bit for bit.  The   */
+                           /* saved planes are per path (memory grows S times).  z0_weight, noise_table, kl_column1,        */
+                           /* snsde_eval_fg and snsde_coeff_gradients stay refused.                                         */
+    int64_t  row_offset;  /* global index of local row 0 (batch shards keep the global Philox   */
                            /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
                            /* sees the local batch unless `global_rows` (below) is set           */
     uint64_t seed;         /* Philox key                                                         */
@@ -318,7 +338,9 @@ typedef struct snsde_solve {
      * is no plan: never another kernel.  snsde_solve_backward, snsde_param_gradients, snsde_backward_with_gradients,
      * snsde_coeff_gradients, their workspace queries and snsde_save_layout then take the descriptor; the adjoints, delta planes and
      * parameter gradients equal those of the replicated solve bit for bit, and grad_coeffs is (batch / S, L-1, 4C): the sum over
-     * the S paths of an input row, formed in place (snsde_coeff_gradients). */
+     * the S paths of an input row, formed in place (snsde_coeff_gradients).
+     * Together with members = M > 1: refused, unless SNSDE_FLAG_ENSEMBLE_SAMPLES opts in (snsde_solve.members, last paragraph:
+     * the sample groups then count from each member's first row, and Bm = batch / M must be a multiple of S as well). */
     int32_t        samples;
     int32_t        reserved3;  /* must be 0                                                          */
 } snsde_solve;
@@ -603,6 +625,32 @@ SNSDE_API int snsde_sample_stats(const float* ys, int64_t groups, int32_t sample
  * w - walks s in order; every element of grad_ys is written.  Enqueue-only, no workspace, capturable, deterministic. */
 SNSDE_API int snsde_sample_stats_backward(const float* grad_mean, const float* grad_var, const float* ys, const float* mean,
                                           int64_t groups, int32_t samples, int32_t width, float* grad_ys, void* hip_stream);
+
+/* ---- statistics over the sample paths of a model ensemble --------------------------------------
+ * ys viewed as (outer, members, groups, samples, width) = (outer, M, G, S, W): a (T, M, B S, H) result of a solve with
+ * members = M and samples = S under SNSDE_FLAG_ENSEMBLE_SAMPLES (outer = T, groups = B), or a stacked (M, B S, out) readout
+ * (outer = 1).  Outputs (outer, groups, width), each optional (NULL = not wanted).  Per member, exactly as snsde_sample_stats
+ * walks them (the same bits):
+ *     mean_m = (sum_s x) / S, s ascending;      var_m = (sum_s fmaf(d, d, .)) / (S - 1), d = x - mean_m
+ * and across members, m ascending:
+ *     mean    = (sum_m mean_m) / M
+ *     within  = (sum_m var_m) / M                         the aleatoric part (spread of the noise)
+ *     between = (sum_m fmaf(e, e, .)) / (M - 1), e = mean_m - mean      the epistemic part (spread between the models)
+ * within + between is the law-of-total-variance estimate of the predictive variance.  `within` with samples < 2 or `between`
+ * with members < 2 is SNSDE_ERR_DIMS.  One lane per output element (four adjacent ones with 16-byte accesses where width % 4
+ * == 0 and the pointers are 16-byte aligned); no atomics, no dependence on the grid: the same bits on every launch.
+ * Enqueue-only, no workspace, capturable.  All pointers device, fp32, contiguous. */
+SNSDE_API int snsde_ensemble_stats(const float* ys, int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
+                                   float* mean, float* within, float* between, void* hip_stream);
+
+/* Adjoint of snsde_ensemble_stats: grad_mean, grad_within, grad_between are (outer, groups, width), each may be NULL (none),
+ *     grad_ys[o, m, g, s, w] = grad_mean / (M S) + grad_within 2 (x - mean_m) / ((S - 1) M) + grad_between 2 (mean_m - mean) / ((M - 1) S)
+ * with the member means recomputed from ys in the forward's order (ys is read only with grad_within or grad_between; the
+ * deviations sum to zero, so the terms through the means of the means vanish).  The same lane-per-element ownership; every
+ * element of grad_ys is written.  grad_within with samples < 2 or grad_between with members < 2 is SNSDE_ERR_DIMS. */
+SNSDE_API int snsde_ensemble_stats_backward(const float* grad_mean, const float* grad_within, const float* grad_between, const float* ys,
+                                            int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
+                                            float* grad_ys, void* hip_stream);
 
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /

@@ -22,6 +22,7 @@ FLAG_LEAN_GENERAL = 32      # the lean kernel's general instantiation where a sp
 FLAG_SAMPLE_GRAD = 64       # opt-in: a solve of samples = S > 1 paths per input row may be differentiated (include/snsde.h)
 FLAG_BF16_GRAD = 128        # opt-in: training through the bf16-operand forward (straight-through gradient; with FLAG_BF16_OPERANDS only)
 FLAG_ENSEMBLE_GRAD = 256    # opt-in: a solve of members = M > 1 models may be differentiated (include/snsde.h)
+FLAG_ENSEMBLE_SAMPLES = 512 # opt-in: members = M > 1 together with samples = S > 1 in one solve (include/snsde.h)
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 # snsde_forward_kernel / snsde_backward_kernel (SNSDE_FWD_* / SNSDE_REV_*): the names of csrc/snsde_mfma_kernels.h FwdKernel / RevKernel
 FWD_KERNELS = ('none', 'generic', 'generic_srk', 'w4', 'm4n', 'lean', 'lean_two_tile_h128', 'lean_two_tile_h256', 'lean_streamed_h256',
@@ -105,7 +106,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_backward_kernel', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_initial_state', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
-           'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward')
+           'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -180,6 +181,10 @@ def lib():
     L.snsde_backward_workspace_bytes.restype = C.c_size_t
     L.snsde_solve_backward.argtypes = [C.POINTER(Backward), C.c_void_p]
     L.snsde_sample_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.snsde_ensemble_stats.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p]
+    L.snsde_ensemble_stats_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int64, C.c_int32,
+                                                C.c_int32, C.c_void_p, C.c_void_p]
     L.snsde_sample_stats_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
                                               C.c_void_p]
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]

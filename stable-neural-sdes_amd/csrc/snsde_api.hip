@@ -173,22 +173,29 @@ static bool sampled_training_plan(const snsde_mfma::MfmaPlan& p) {
                                                p.kernel == snsde_mfma::FwdKernel::general_m16);
 }
 
-// members (snsde.h): M models in one call - whole members, each a whole number of 4-row tiles
+// SNSDE_FLAG_ENSEMBLE_SAMPLES (snsde.h): the opt-in to sample paths of a model ensemble; nothing without members > 1 and samples > 1
+static bool ensemble_samples(const snsde_solve* s) {
+    return snsde_members(s) > 1 && snsde_samples(s) > 1 && (s->flags & SNSDE_FLAG_ENSEMBLE_SAMPLES) != 0;
+}
+// members (snsde.h): M models in one call - whole members, each a whole number of 4-row tiles and, with sample paths under
+// SNSDE_FLAG_ENSEMBLE_SAMPLES, of sample groups (a group never straddles two members)
 static bool members_ok(const snsde_solve* s) {
     if (s->members < 0) return false;
     const int32_t M = snsde_members(s);
-    return M == 1 || (s->batch % M == 0 && (s->batch / M) % 4 == 0);
+    if (M == 1) return true;
+    if (s->batch % M != 0 || (s->batch / M) % 4 != 0) return false;
+    return !ensemble_samples(s) || (s->batch / M) % snsde_samples(s) == 0;
 }
 // SNSDE_FLAG_ENSEMBLE_GRAD (snsde.h): the opt-in to training through a model ensemble; nothing without members > 1
 static bool ensemble_grad(const snsde_solve* s) { return snsde_members(s) > 1 && (s->flags & SNSDE_FLAG_ENSEMBLE_GRAD) != 0; }
 static bool members_training(const snsde_solve* s) {
     return snsde_members(s) > 1 && (s->act_save || s->stage_save || s->traj || s->dW_out || s->dU_out);
 }
-// ... an inference-only solve of the members' own fields from the caller's initial states: not combined with sample paths, a fused
-// initial network, a supplied diffusion table (one table, M models), the accumulator column or - unless the flag opts in - any
-// training-mode plane
+// ... an inference-only solve of the members' own fields from the caller's initial states: not combined with sample paths (unless
+// SNSDE_FLAG_ENSEMBLE_SAMPLES opts in), a fused initial network, a supplied diffusion table (one table, M models), the accumulator
+// column or - unless the flag opts in - any training-mode plane
 static bool members_refused(const snsde_solve* s) {
-    return snsde_members(s) > 1 && (snsde_samples(s) > 1 || s->z0_weight || s->noise_table || s->kl_column1 != 0 ||
+    return snsde_members(s) > 1 && ((snsde_samples(s) > 1 && !ensemble_samples(s)) || s->z0_weight || s->noise_table || s->kl_column1 != 0 ||
                                     (members_training(s) && !ensemble_grad(s)));
 }
 // ... and the forward plans whose training planes the ensemble adjoint route takes (route_backward): the lean kernel and the general
@@ -197,7 +204,8 @@ static bool ensemble_training_plan(const snsde_mfma::MfmaPlan& p) {
     return p.ok && p.H <= 128 && p.NN == 0 && (p.kernel == snsde_mfma::FwdKernel::lean || p.kernel == snsde_mfma::FwdKernel::general_m4);
 }
 // One member of an ensemble run alone as a shard of the whole (snsde.h: members): what each member is planned as - its adjoint's
-// workgroups and partial-sum blocks, its weight-gradient tiles and splits.  (row_offset: member 0's; no plan reads it)
+// workgroups and partial-sum blocks, its weight-gradient tiles and splits.  (row_offset: member 0's; no plan reads it.)  `samples`
+// stays: under SNSDE_FLAG_ENSEMBLE_SAMPLES the member alone is a sampled solve of its batch / M paths
 static snsde_solve member_alone(const snsde_solve* s) {
     snsde_solve one = *s;
     one.batch = s->batch / snsde_members(s);
@@ -262,6 +270,9 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
         // mode 1 exactly where the forward plan is the lean or the general kernel on 4-row tiles (make_plan refuses the others) and the
         // adjoint of ONE member run alone as a shard of the whole is the general MFMA adjoint on 4-row tiles or its SRK form, which
         // read no coefficients and leave delta planes.  Anything else is no plan (never another kernel, no mode 2)
+        // Sample paths of the ensemble (SNSDE_FLAG_ENSEMBLE_SAMPLES, else refused): SNSDE_FLAG_SAMPLE_GRAD as well - the member alone
+        // is then planned as a sampled solve, whose adjoint route asks for these same two adjoints
+        if (!samples_ok(s) || (snsde_samples(s) > 1 && !sample_grad(s))) return r;
         if (!ensemble_grad(s) || members_refused(s) || (s->flags & SNSDE_FLAG_BF16_OPERANDS) || snsde_solve_variant(s) ||
             k == SNSDE_KERNEL_GENERIC || k == SNSDE_KERNEL_MFMA_M16 || (s->method == SNSDE_MILSTEIN && s->model.noise_option == 7) ||
             (s->method != SNSDE_EULER && s->method != SNSDE_MILSTEIN && s->method != SNSDE_SRK))

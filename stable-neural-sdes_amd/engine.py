@@ -208,9 +208,16 @@ def check_ensemble_grad(ensemble_grad):
     return ensemble_grad
 
 
+def check_ensemble_samples(ensemble_samples):
+    """The `ensemble_samples` option (sample paths of a model ensemble, SNSDE_FLAG_ENSEMBLE_SAMPLES): a bool, ValueError otherwise."""
+    if not isinstance(ensemble_samples, bool):
+        raise ValueError(f"ensemble_samples must be a bool (`samples` paths per input row for each of `members` models), got {ensemble_samples!r}")
+    return ensemble_samples
+
+
 def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                      row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                     members=0, ensemble_grad=False):
+                     members=0, ensemble_grad=False, ensemble_samples=False):
     """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
     device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
     s = _lib.Solve()
@@ -223,6 +230,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
     s.flags = precision_flags(precision, bf16_grad) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
     s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
     s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
+    s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
@@ -231,7 +239,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                  row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                 members=0, ensemble_grad=False):
+                 members=0, ensemble_grad=False, ensemble_samples=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
@@ -239,9 +247,10 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     (a sampled solve has them under sample_grad only, on the kernels the sampled adjoint route covers; a bf16 solve under bf16_grad
     only: SNSDE_FLAG_BF16_GRAD).  members: models of one architecture in the call (include/snsde.h; `batch` then counts the rows
     of all members); 'none' where the plan arrives at a kernel that does not map rows to members.  ensemble_grad:
-    SNSDE_FLAG_ENSEMBLE_GRAD - an ensemble has training planes under it only, on the kernels the ensemble adjoint route covers."""
+    SNSDE_FLAG_ENSEMBLE_GRAD - an ensemble has training planes under it only, on the kernels the ensemble adjoint route covers.
+    ensemble_samples: SNSDE_FLAG_ENSEMBLE_SAMPLES - members > 1 together with samples > 1 ('none' without it)."""
     s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
-                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad)
+                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples)
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
 
@@ -553,7 +562,8 @@ class SolveCall:
     def __init__(self, model, flat_params, coeffs, grid, y0, dW=None, method='euler', seed=0, row_offset=0,
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
-                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False):
+                 lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False,
+                 ensemble_samples=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -571,9 +581,13 @@ class SolveCall:
         if M < 1 or B % M or (M > 1 and (B // M) % 4):
             raise ValueError(f'members={members!r}: the {B} rows of y0 are those of all members, each a whole number of 4-row tiles')
         ensemble_grad = bool(ensemble_grad) and M > 1      # (no effect on one model)
-        if M > 1 and (S > 1 or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
+        # members and samples together (SNSDE_FLAG_ENSEMBLE_SAMPLES): row m Bm + b S + s, coeffs (Bm / S rows) shared by all members
+        ensemble_samples = bool(ensemble_samples) and M > 1 and S > 1      # (no effect on one model or one path per row)
+        if ensemble_samples and (B // M) % S:
+            raise ValueError(f'members={members!r}, samples={samples!r}: the {B // M} rows of a member are a whole number of groups of `samples` paths')
+        if M > 1 and ((S > 1 and not ensemble_samples) or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
                       or kl_column is not None):
-            raise ValueError('members > 1 is inference only: no samples, saved planes, fused initial network, supplied noise table or '
+            raise ValueError('members > 1 is inference only: no samples (without ensemble_samples), saved planes, fused initial network, supplied noise table or '
                              'accumulator column')
         _check_f32('y0', y0, (B, model.hidden_channels))
         _check_f32('coeffs', coeffs, (B // S // M, L - 1, 4 * C_))
@@ -615,6 +629,8 @@ class SolveCall:
             self.base_flags |= _lib.FLAG_SAMPLE_GRAD
         if ensemble_grad:
             self.base_flags |= _lib.FLAG_ENSEMBLE_GRAD
+        if ensemble_samples:
+            self.base_flags |= _lib.FLAG_ENSEMBLE_SAMPLES
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -638,7 +654,7 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad)
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad, ensemble_samples)
         self.members = M
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
@@ -747,21 +763,24 @@ _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per c
 
 
 def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
-                  samples=0, sample_grad=False, precision='fp32', bf16_grad=False, members=0, ensemble_grad=False):
+                  samples=0, sample_grad=False, precision='fp32', bf16_grad=False, members=0, ensemble_grad=False,
+                  ensemble_samples=False):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
     supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none); samples: paths
     per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD).  precision='bf16': 0, or under bf16_grad
     (SNSDE_FLAG_BF16_GRAD) 1 where the bf16 lean kernel runs the forward and the general MFMA adjoint its backward.  members: models
-    in the call (`batch` counts the rows of all of them) - 0 without ensemble_grad (SNSDE_FLAG_ENSEMBLE_GRAD), 1 or 0 with it."""
+    in the call (`batch` counts the rows of all of them) - 0 without ensemble_grad (SNSDE_FLAG_ENSEMBLE_GRAD), 1 or 0 with it.  members and
+    samples together: 0 unless ensemble_samples (SNSDE_FLAG_ENSEMBLE_SAMPLES), ensemble_grad and sample_grad are all set."""
     members = int(members) if members and int(members) > 1 else 0
     ensemble_grad = bool(ensemble_grad) and members > 1
     samples = int(samples) if samples and int(samples) > 1 else 0
     sample_grad = bool(sample_grad) and samples > 1
+    ensemble_samples = bool(ensemble_samples) and members > 1 and samples > 1
     pflags = precision_flags(precision, bf16_grad)
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
            model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad,
-           pflags, members, ensemble_grad)
+           pflags, members, ensemble_grad, ensemble_samples)
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -771,6 +790,7 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.kernel = _lib.KERNELS[kernel]
         s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0) | pflags
         s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
+        s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
         s.members = members
         s.samples = samples
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
@@ -1086,6 +1106,98 @@ class _SampleStats(torch.autograd.Function):
         gm = torch.zeros_like(mean) if grad_mean is None else grad_mean.to(torch.float32).contiguous()
         gv = grad_var.to(torch.float32).contiguous() if ctx.var and grad_var is not None else None
         return sample_stats_backward(gm, gv, ys, mean, ctx.S), None, None
+
+
+def ensemble_stats(ys, members, samples, within=True, between=True):
+    """Predictive mean and the two parts of the predictive variance of a sampled ensemble solve (sdeint_ensemble with
+    options={'samples': S, 'ensemble_samples': True}): ys is (..., M, B S, W) - the (T, M, B S, H) result, or a stacked (M, B S, out)
+    readout - with path index b S + s inside a member.  Returns (mean, within, between), each (..., B, W):
+        mean_m, var_m   member m's mean and unbiased variance over its S paths (sample_stats of member m: the same bits)
+        mean            their mean over the members
+        within          the mean of var_m: the aleatoric part, the spread of the noise (None when within=False)
+        between         the unbiased variance of mean_m over the members: the epistemic part (None when between=False)
+    and within + between is the law-of-total-variance estimate.  CUDA float32 input: one launch of snsde_ensemble_stats (one lane
+    per output element walks members and samples in order: deterministic) - inside an autograd node whose backward is
+    snsde_ensemble_stats_backward when the input requires grad; other tensors: the same sums in torch."""
+    S = check_samples(samples)
+    if isinstance(members, bool) or not isinstance(members, int) or members < 1:
+        raise ValueError(f'members must be an integer >= 1 (models of the ensemble), got {members!r}')
+    M = members
+    if ys.dim() < 3 or ys.shape[-3] != M or ys.shape[-2] % S:
+        raise ValueError(f'ys has shape {tuple(ys.shape)}: expected (..., members, rows, width) with members = {M} and a whole number '
+                         f'of groups of {S} paths per member')
+    if within and S < 2:
+        raise ValueError('the within-member variance needs samples >= 2')
+    if between and M < 2:
+        raise ValueError('the between-member variance needs members >= 2')
+    W, G = ys.shape[-1], ys.shape[-2] // S
+    lead = tuple(ys.shape[:-3])
+    out_shape = lead + (G, W)
+    native = ys.is_cuda and ys.dtype == torch.float32 and ys.numel() > 0
+    if native and ys.requires_grad and torch.is_grad_enabled():
+        mean, wout, bout = _EnsembleStats.apply(ys, M, S, bool(within), bool(between))      # (the kernels below inside one autograd node)
+        return mean, (wout if within else None), (bout if between else None)
+    if not native:
+        v = ys.reshape(lead + (M, G, S, W))
+        mm = v.sum(dim=-2) / S
+        mean = mm.sum(dim=-3) / M
+        wout = ((v - mm.unsqueeze(-2)).square().sum(dim=-2) / (S - 1)).sum(dim=-3) / M if within else None
+        bout = (mm - mean.unsqueeze(-3)).square().sum(dim=-3) / (M - 1) if between else None
+        return mean, wout, bout
+    ys = ys.contiguous()
+    outer = ys.numel() // (M * G * S * W)
+    mean = torch.empty(out_shape, device=ys.device, dtype=torch.float32)
+    wout = torch.empty(out_shape, device=ys.device, dtype=torch.float32) if within else None
+    bout = torch.empty(out_shape, device=ys.device, dtype=torch.float32) if between else None
+    _lib.check(_lib.lib().snsde_ensemble_stats(_ptr(ys), outer, M, G, S, W, _ptr(mean), _ptr(wout), _ptr(bout),
+                                               C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_ensemble_stats')
+    return mean, wout, bout
+
+
+def ensemble_stats_backward(grad_mean, grad_within, grad_between, ys, members, samples):
+    """dL/d ys of `ensemble_stats` from dL/d mean, dL/d within and dL/d between (None: no such term): one launch of
+    snsde_ensemble_stats_backward.  ys (..., M, B S, W), the gradients (..., B, W): contiguous float32 CUDA tensors."""
+    M, S, W = int(members), int(samples), ys.shape[-1]
+    _check_f32('ys', ys)
+    G = ys.shape[-2] // S
+    shape = tuple(ys.shape[:-3]) + (G, W)
+    for name, g in (('grad_mean', grad_mean), ('grad_within', grad_within), ('grad_between', grad_between)):
+        if g is not None:
+            _check_f32(name, g, shape)
+    out = torch.empty_like(ys)
+    _lib.check(_lib.lib().snsde_ensemble_stats_backward(_ptr(grad_mean), _ptr(grad_within), _ptr(grad_between), _ptr(ys),
+                                                        ys.numel() // (M * G * S * W), M, G, S, W, _ptr(out),
+                                                        C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_ensemble_stats_backward')
+    return out
+
+
+class _EnsembleStats(torch.autograd.Function):
+    """ensemble_stats of a CUDA float32 tensor that requires grad: the forward kernel, and snsde_ensemble_stats_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ys, M, S, within, between):
+        ysc = ys.detach().contiguous()
+        with torch.no_grad():
+            mean, wout, bout = ensemble_stats(ysc, M, S, within, between)
+        ctx.M, ctx.S, ctx.within, ctx.between = M, S, within, between
+        ctx.save_for_backward(ysc)
+        if not within:
+            wout = mean.new_empty(0)
+            ctx.mark_non_differentiable(wout)
+        if not between:
+            bout = mean.new_empty(0)
+            ctx.mark_non_differentiable(bout)
+        return mean, wout, bout
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mean, grad_within, grad_between):
+        ys, = ctx.saved_tensors
+        gm = None if grad_mean is None else grad_mean.to(torch.float32).contiguous()
+        gw = grad_within.to(torch.float32).contiguous() if ctx.within and grad_within is not None else None
+        gb = grad_between.to(torch.float32).contiguous() if ctx.between and grad_between is not None else None
+        return ensemble_stats_backward(gm, gw, gb, ys, ctx.M, ctx.S), None, None, None, None
 
 
 def spline_grad_native():

@@ -351,7 +351,11 @@ class Ensemble(nn.Module):
     (torchsde.sdeint_ensemble): in train() with gradients required each member's initial state is the differentiable tensor-op form
     (`_prepare_initial_state`: `_initial_state` never hands `initial_network` to the solve under grad), the readouts stay the
     members' own, and outputs and every member's parameter gradients equal the M wrapper calls in training mode with the options
-    above.  Without the opt-in sdeint_ensemble raises under autograd."""
+    above.  Without the opt-in sdeint_ensemble raises under autograd.
+    options={'samples': S, 'ensemble_samples': True} (with 'ensemble_grad' and 'sample_grad' under autograd) pass through to
+    sdeint_ensemble: S Brownian paths per input row for every member.  Each member's initial state stays one row per input row
+    (the solve expands it), the readouts return one row per path as the wrappers do for `samples`, and every output is
+    (M, B S, ..) - equal to the M wrapper calls with options={'samples': S, 'row_offset': m B S, 'global_rows': M B S}."""
 
     KINDS = ()      # (the three wrapper classes: filled below, once they are all defined)
 
@@ -384,6 +388,8 @@ class Ensemble(nn.Module):
         fused = (opts.get('backend', 'auto') != 'torch' and kwargs.get('bm') is None and kernel == 'auto' and lin.bias is not None
                  and lin.weight.is_contiguous() and lin.bias.dtype == torch.float32 and coeffs.dim() == 3
                  and tuple(lin.weight.shape) == (func.hidden_channels, func.input_channels))
+        if int(opts.get('samples') or 1) > 1:      # (sample paths: the member's own call materialises z0 with tensor ops, torchsde._sdeint_samples)
+            fused = False
         if fused:
             grid = engine.step_grid(_HostTimes.get(times), dt, _HostTimes.get(func.times), coeffs.device)
             # (a hidden size the member's solve zero-pads starts from the tensor-op state: torchsde._sdeint_hip)
@@ -435,6 +441,8 @@ class Ensemble(nn.Module):
             return torch.stack([m._readout(ys[i]) for i, m in enumerate(models)])
         ts, row_slot = NeuralSDE.output_times(times, final_index)
         ys = self._solve(times, ts, z0, kwargs)
+        if row_slot.numel() != ys.shape[2]:      # options={'samples': S, 'ensemble_samples': True}: S paths per row, path-major
+            row_slot = row_slot.repeat_interleave(ys.shape[2] // row_slot.numel())
         idx = row_slot.reshape(1, -1, 1).expand(1, ys.shape[2], ys.shape[3])
         return torch.stack([m._readout(ys[:, i].gather(0, idx).squeeze(0)) for i, m in enumerate(models)])
 

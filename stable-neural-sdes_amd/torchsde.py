@@ -421,7 +421,17 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     require grad) exactly those M differentiable sdeint calls run and are stacked - autograd then sums coeffs.grad over the members;
     options={'strict': True} raises NotImplementedError instead.  ValueError together with ensemble_grad: samples > 1, save_traj,
     recompute (the option or SNSDE_RECOMPUTE_STEPS), z0_linear, sample_grad, bf16_grad, precision='bf16' under autograd,
-    param_pass='torch'."""
+    param_pass='torch'.
+
+    options={'samples': S, 'ensemble_samples': True} (SNSDE_FLAG_ENSEMBLE_SAMPLES) opts in to S Brownian paths per input row for
+    every member: y0 is (M, B, H) - expanded path-major, path b S + s, as sdeint's `samples` does - or already (M, B S, H), a
+    row_out has length B or B S, the control path stays (B, L-1, 4C) and the result is (T, M, B S, H); engine.ensemble_stats turns
+    it into the predictive mean and the within- / between-member variance.  Member m's rows equal, bit for bit, its own sampled
+    sdeint (options samples=S, row_offset + m B S, the same global_rows).  Under autograd it needs ensemble_grad=True and
+    sample_grad=True as well (ValueError otherwise); where engine.backward_mode(..., members=M, samples=S, ensemble_samples=True,
+    ensemble_grad=True, sample_grad=True) == 1 the one fused node runs.  The loop route - taken in the same cases as above, with
+    (B S) % 4 != 0 in place of B % 4 != 0 - runs those M sampled sdeint calls (with sample_grad under autograd): the same result.
+    Without ensemble_samples, samples > 1 raises ValueError; sample_grad without samples > 1 and ensemble_samples stays a conflict."""
     sdes = list(sdes)
     M = len(sdes)
     if M < 1:
@@ -438,10 +448,17 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     backend = options.get('backend', 'auto')
     if backend not in ('auto', 'hip', 'torch'):
         raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
-    if 'samples' in options and engine.check_samples(options['samples']) > 1:
-        raise ValueError("sdeint_ensemble does not take samples > 1 (sample paths of an ensemble are not built)")
-    options.pop('samples', None)
+    S = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
+    ensemble_samples = engine.check_ensemble_samples(options.pop('ensemble_samples')) if 'ensemble_samples' in options else False
+    if S > 1 and not ensemble_samples:
+        raise ValueError("sdeint_ensemble does not take samples > 1 (sample paths of an ensemble are not built) without the opt-in "
+                         "options={'ensemble_samples': True}")
+    ensemble_samples = ensemble_samples and S > 1      # (no effect on one path per row)
     ensemble_grad = engine.check_ensemble_grad(options.pop('ensemble_grad')) if 'ensemble_grad' in options else False
+    if ensemble_samples:      # (sample_grad is this route's own option then; everywhere else it stays the conflict it was)
+        sample_grad = engine.check_sample_grad(options.pop('sample_grad')) if 'sample_grad' in options else False
+    else:
+        sample_grad = False
     needs_grad = any(_differentiated(sde, y0) for sde in sdes)
     if ensemble_grad:
         for name, bad in (('save_traj', bool(options.get('save_traj', False))),
@@ -460,11 +477,33 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     if needs_grad and not ensemble_grad:
         raise ValueError("sdeint_ensemble is inference only: y0, the control path or a member's parameter requires grad (use "
                          "torch.no_grad() or requires_grad_(False)); training through an ensemble is not built")
+    if needs_grad and ensemble_samples and not sample_grad:
+        raise ValueError(f"samples={S} paths per input row of an ensemble are inference only: y0, the control path or a member's parameter "
+                         "requires grad (opt in to training through them with options={'ensemble_grad': True, 'sample_grad': True})")
     needs_grad = needs_grad and ensemble_grad
     ts = _as_ts(ts, y0)
     B = int(y0.shape[1])
+    if ensemble_samples:
+        # y0 (M, B, H) - one row per input row, expanded path-major like _sdeint_samples does - or already (M, B S, H); a row_out of
+        # length B likewise.  From here on B counts the PATHS of a member
+        c0 = getattr(sdes[0], 'coeffs', None)
+        rows_in = int(c0.shape[0]) if torch.is_tensor(c0) and c0.dim() == 3 else B
+        if B == rows_in:
+            y0 = y0.repeat_interleave(S, dim=1)
+        elif B != rows_in * S:
+            raise ValueError(f"samples={S}: y0 has {B} rows per member, expected {rows_in} (one per input row) or {rows_in * S} (one per path)")
+        B = rows_in * S
+        if options.get('row_out') is not None:
+            ro = options['row_out']
+            if ro.numel() == rows_in:
+                options['row_out'] = ro.repeat_interleave(S)
+            elif ro.numel() != B:
+                raise ValueError(f"samples={S}: row_out has {ro.numel()} entries, expected {rows_in} or {B}")
     row_offset = _row_offset(options, M * B)
     global_rows = engine.resolve_global_rows(options.get('global_rows'), M * B, row_offset) or M * B
+    if ensemble_samples and (row_offset % S or global_rows % S):
+        raise ValueError(f"samples={S}: row_offset={row_offset} and global_rows={global_rows} must be multiples of samples (whole groups "
+                         "of paths per shard)")
     options['seed'] = _philox_key(options, y0.device) if bm is None else options.get('seed')      # (one key for every member)
     strict = bool(options.get('strict', False))
     row_out = options.get('row_out')
@@ -476,6 +515,10 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
             raise NotImplementedError(f"sdeint_ensemble: no fused solve of these {M} members ({why}); drop options['strict'] to run "
                                       "them as M sdeint calls")
         opts = {k: v for k, v in options.items() if k not in ('strict', 'lean_general') and v is not None}
+        if ensemble_samples:      # the M sampled solves (differentiable ones under sample_grad), each a shard of the whole
+            opts['samples'] = S
+            if needs_grad:
+                opts['sample_grad'] = True
         outs = [sdeint(sde, y0[m], ts, bm=bm, method=method, dt=dt,
                        options=dict(opts, row_offset=row_offset + m * B, global_rows=global_rows)) for m, sde in enumerate(sdes)]
         return torch.stack(outs, dim=0 if row_out is not None else 1)
@@ -497,7 +540,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     if needs_grad and _coeffs_need_grad(sdes[0]):
         return loop('the control path requires grad (dL/dcoeffs of an ensemble is the sum of the members\' own)')
     coeffs = sdes[0].coeffs
-    if coeffs.dim() != 3 or coeffs.shape[0] != B:
+    if coeffs.dim() != 3 or coeffs.shape[0] != B // S:
         raise ValueError("sde.coeffs must have shape (batch, len(times) - 1, 4 * input_channels)")
     dev = y0.device
     kernel, precision = options.get('kernel', 'auto'), options.get('precision', 'fp32')
@@ -506,18 +549,21 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     L = int(coeffs.shape[1]) + 1
     grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sdes[0].times), dev)
     if engine.forward_path(model, M * B, L, grid.N, method, kernel, precision=precision, global_rows=global_rows, row_offset=row_offset,
-                           lean_general=lean_general, exact_order=exact_order, members=M) == 'none':
+                           lean_general=lean_general, exact_order=exact_order, members=M, samples=S if ensemble_samples else 0,
+                           ensemble_samples=ensemble_samples) == 'none':
         return loop('the plan arrives at a kernel that does not map rows to members')
     if needs_grad:
         # the ensemble adjoint route (mode 1 with delta planes for every member), or the M differentiable solves
         if precision != 'fp32' or engine.backward_mode(model, M * B, L, grid, method, kernel, exact_order, global_rows=global_rows,
-                                                       members=M, ensemble_grad=True) != 1:
+                                                       members=M, ensemble_grad=True, samples=S if ensemble_samples else 0,
+                                                       sample_grad=ensemble_samples, ensemble_samples=ensemble_samples) != 1:
             return loop('no fused adjoint plans this ensemble')
         pidxs = [engine.param_index(sde, r[1]) for sde, r in zip(sdes, recs)]
         counts = [len(p.params) for p in pidxs]
         eopt = _EnsembleOptions(kernel=kernel, exact_order=exact_order, param_pass=options.get('param_pass', 'hip'), row_offset=row_offset,
                                 global_rows=global_rows, seed=options['seed'],
-                                row_out=None if row_out is None else _device_row_out(options, dev).repeat(M))
+                                row_out=None if row_out is None else _device_row_out(options, dev).repeat(M),
+                                samples=S if ensemble_samples else 0)
         ys = _FusedEnsembleSolve.apply(sdes, recs, coeffs.detach().to(device=dev, dtype=torch.float32).contiguous(), grid, method, eopt,
                                        counts, y0, *[p for pi in pidxs for p in pi.params])
         return ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
@@ -527,7 +573,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     rows = None if row_out is None else _device_row_out(options, dev).repeat(M)
     call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=options['seed'], row_offset=row_offset, kernel=kernel,
                             exact_order=exact_order, row_out=rows, precision=precision, lean_general=lean_general,
-                            global_rows=global_rows, members=M)
+                            global_rows=global_rows, members=M, samples=S if ensemble_samples else 0, ensemble_samples=ensemble_samples)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
@@ -539,7 +585,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
 
 
 # What the fused ensemble node reads from `options`, resolved once by sdeint_ensemble
-_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out'))
+_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out', 'samples'))
 
 
 class _FusedEnsembleSolve(torch.autograd.Function):
@@ -561,7 +607,8 @@ class _FusedEnsembleSolve(torch.autograd.Function):
                        and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
         call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=opt.seed, row_offset=opt.row_offset, kernel=opt.kernel,
                                 save_traj=True, save_dW=keep_dw, save_act=True, exact_order=opt.exact_order, row_out=opt.row_out,
-                                global_rows=opt.global_rows, members=M, ensemble_grad=True)
+                                global_rows=opt.global_rows, members=M, ensemble_grad=True, samples=opt.samples,
+                                sample_grad=opt.samples > 1, ensemble_samples=opt.samples > 1)
         ys = call.launch()
         ctx.call, ctx.sdes, ctx.layouts, ctx.counts = call, sdes, [r[1] for r in recs], counts
         ctx.param_pass, ctx.y0_shape, ctx.y0_dtype = opt.param_pass, tuple(y0.shape), y0.dtype
