@@ -119,7 +119,13 @@ enum {
      * input row; snsde_solve.members, the paragraph on sample paths).  No effect when members <= 1 or samples <= 1; without it
      * the combination stays SNSDE_PATH_NONE / SNSDE_ERR_UNSUPPORTED.  Training through it needs this flag together with
      * SNSDE_FLAG_ENSEMBLE_GRAD and SNSDE_FLAG_SAMPLE_GRAD: each of the three keeps its own meaning. */
-    SNSDE_FLAG_ENSEMBLE_SAMPLES = 512
+    SNSDE_FLAG_ENSEMBLE_SAMPLES = 512,
+    /* Opt-in: a model ensemble (snsde_solve.members = M > 1) on the kernels of the diffusion nets (noise_option 14 / 15 / 18 / 19)
+     * - the wave pairs (SNSDE_FWD_W4) and the diffusion-net 4-row tiles (SNSDE_FWD_M4N); snsde_solve.members, last paragraph.  No
+     * effect when members <= 1; without it a plan that arrives at these kernels stays SNSDE_PATH_NONE for M > 1.  Inference only:
+     * with training planes, with or without SNSDE_FLAG_ENSEMBLE_GRAD, such an ensemble stays SNSDE_PATH_NONE and
+     * snsde_backward_supported stays 0.  Sample paths of such an ensemble need SNSDE_FLAG_ENSEMBLE_SAMPLES as well. */
+    SNSDE_FLAG_ENSEMBLE_NETS = 1024
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -250,6 +256,19 @@ typedef struct snsde_solve {
                            /* as its own sampled solve of Bm paths and every result equals that solve's bit for bit.  The   */
                            /* saved planes are per path (memory grows S times).  z0_weight, noise_table, kl_column1,        */
                            /* snsde_eval_fg and snsde_coeff_gradients stay refused.                                         */
+                           /* The diffusion-net kernels are opt-in, SNSDE_FLAG_ENSEMBLE_NETS; without the flag a plan that  */
+                           /* arrives at them stays no plan, as above.  With it the ensemble also runs on the wave pairs    */
+                           /* (SNSDE_FWD_W4: H = 64, Euler / SRK; a pair reads params + m x snsde_param_numel, no workspace */
+                           /* block) and on the diffusion-net 4-row tiles (SNSDE_FWD_M4N: SRK, Milstein, Euler at H = 128   */
+                           /* or with a wide control path, H = 16 .. 128; the member is the launch's second grid axis and   */
+                           /* the prepare launch packs every layer of the plan, the transposed ones of Milstein included,   */
+                           /* into each member's block).  The contract, the dimension errors and the workspace rule are     */
+                           /* those above.  With SNSDE_FLAG_ENSEMBLE_SAMPLES as well these two kernels take samples = S > 1 */
+                           /* of the ensemble (coefficient row (r - m Bm) / S; the member alone is then the ordinary solve  */
+                           /* of Bm rows on coefficients replicated S times: plain samples > 1 on one model stays refused   */
+                           /* on these kernels).  Still refused under the flag: z0_weight, noise_table, kl_column1, bf16    */
+                           /* operands, the field variants, kernel = generic / 16-row tiles, and every training plane, with */
+                           /* or without SNSDE_FLAG_ENSEMBLE_GRAD (snsde_backward_supported == 0).                          */
     int64_t  row_offset;  /* global index of local row 0 (batch shards keep the global Philox   */
                            /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
                            /* sees the local batch unless `global_rows` (below) is set           */

@@ -167,7 +167,15 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 3, s = (lane >> 2) & 3, fsub = 4 * (lane >> 4);
-    const int row0 = blockIdx.x * M, B = a.B, C = a.C;
+    // model ensembles (SNSDE_FLAG_ENSEMBLE_NETS): blockIdx.y is the member (MfmaArgs::members; one model: 0) - its first row, its
+    // parameter and workspace blocks, as in snsde_mfma_kernel.  (The SRK pass table a.step_tab is block 0's for every member.)
+    const uint32_t mem = blockIdx.y;
+    // (the member's first row in tiles: member_rows % 4 == 0, and the compiler keeps the fact that row0 is a multiple of four - formed as
+    //  mem * member_rows, three H = 64 / 128 instantiations under SRK spilled one to four more registers)
+    const int mrow0 = (int)(mem * ((uint32_t)a.member_rows >> 2)) * M;
+    const int row0 = mrow0 + blockIdx.x * M, B = a.B, C = a.C;
+    const float* const params = a.params + (size_t)mem * a.param_stride;
+    const float* const ws = a.ws + (size_t)mem * a.ws_stride;
     const int row = row0 + r, rowc = row < B ? row : B - 1;
     const bool row_ok = row < B;
     const size_t BH = (size_t)B * H;
@@ -188,22 +196,22 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
     {
         int li = 0;
         auto slice = [&](int ix, int ku) { return wlds + CF::lds_w_off(ix) + wave * ku * 256; };
-        if constexpr (CF::EMB) { wx.load(a.ws + a.w_off[li], wave, lane, slice(0, KUX)); ++li; }
-        wy.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_Y, KUY));
-        if constexpr (NHID > 0) wh0.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_H0, KUH));
-        if constexpr (NHID > 1) wh1.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_H0 + 1, KUH));
-        if constexpr (NHID > 2) wh2.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_H0 + 2, KUH));
-        wo.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_O, KUH));
-        wn0.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_N0, KUN));
-        if constexpr (NN > 1) wn1.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_N1, KUH));
-        if constexpr (MIL && NN > 1) wn1t.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_N1T, KUH));
-        if constexpr (MIL) wn0t.load(a.ws + a.w_off[li++], wave, lane, slice(CF::IX_N0T, KUH));
+        if constexpr (CF::EMB) { wx.load(ws + a.w_off[li], wave, lane, slice(0, KUX)); ++li; }
+        wy.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_Y, KUY));
+        if constexpr (NHID > 0) wh0.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_H0, KUH));
+        if constexpr (NHID > 1) wh1.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_H0 + 1, KUH));
+        if constexpr (NHID > 2) wh2.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_H0 + 2, KUH));
+        wo.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_O, KUH));
+        wn0.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_N0, KUN));
+        if constexpr (NN > 1) wn1.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_N1, KUH));
+        if constexpr (MIL && NN > 1) wn1t.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_N1T, KUH));
+        if constexpr (MIL) wn0t.load(ws + a.w_off[li++], wave, lane, slice(CF::IX_N0T, KUH));
     }
 
     for (int i = tid; i < CF::LDS_ACT - (CF::ROWCH + 1) * SNSDE_STEP_STRIDE; i += NT) lds[i] = 0.0f;
     __syncthreads();
 
-    const float sig_theta = snsde_sigmoid(a.params[a.off_theta]);
+    const float sig_theta = snsde_sigmoid(params[a.off_theta]);
     const int no = a.no;
     const bool mul_y = (no == 15 || no == 19);
     // field variants (tutorial-style NeuralSDEFunc, fields.py): LipSwish / SiLU instead of relu, f = z, g = the net's LINEAR output
@@ -225,7 +233,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
 
     float bias_own[CF::NLAYER];
 #pragma unroll
-    for (int l = 0; l < CF::NLAYER; ++l) bias_own[l] = a.ws[a.bias_off + l * H + fcol];
+    for (int l = 0; l < CF::NLAYER; ++l) bias_own[l] = ws[a.bias_off + l * H + fcol];
     constexpr int NROW = NHID + 2;      // bias row of the net's first layer
 
     float yv = a.y0[goff];
@@ -239,30 +247,35 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
         }
     }
 
-    // spline items of this thread
-    int xr[CF::XI], xc[CF::XI];
+    // spline items of this thread: xc the channel, xp = 4 x (the coeffs row of the item) + its row in the tile - the coeffs row is the
+    // item's row, ragged tail clamped, counted from the member's first row, over the paths per input row (one register, as the row
+    // in the tile alone was: the H = 128 instantiations have none to spare)
+    int xp[CF::XI], xc[CF::XI];
     bool xok[CF::XI];
-    float ca[CF::XI], cb[CF::XI], cc[CF::XI], cd[CF::XI];
 #pragma unroll
     for (int i = 0; i < CF::XI; ++i) {
         const int it = tid + i * NT;
-        xr[i] = it / C; xc[i] = it - xr[i] * C;
+        int xr = it / C;
+        xc[i] = it - xr * C;
         xok[i] = CF::EMB && it < M * C;
-        if (!xok[i]) { xr[i] = 0; xc[i] = 0; }
+        if (!xok[i]) { xr = 0; xc[i] = 0; }
+        const int rp = (row0 + xr < B ? row0 + xr : B - 1) - mrow0;
+        xp[i] = 4 * (a.samples > 1 ? (int)((uint32_t)rp / (uint32_t)a.samples) : rp) + xr;
     }
+
+    float ca[CF::XI], cb[CF::XI], cc[CF::XI], cd[CF::XI];
     auto load_coeffs = [&](int idx) {
 #pragma unroll
         for (int i = 0; i < CF::XI; ++i)
             if (xok[i]) {
-                const int rr = row0 + xr[i] < B ? row0 + xr[i] : B - 1;
-                const float* cp = a.coeffs + ((size_t)rr * (a.L - 1) + idx) * (4 * C) + xc[i];
+                const float* cp = a.coeffs + ((size_t)(xp[i] >> 2) * (a.L - 1) + idx) * (4 * C) + xc[i];
                 ca[i] = cp[0]; cb[i] = cp[C]; cc[i] = cp[2 * C]; cd[i] = cp[3 * C];
             }
     };
     auto store_x = [&](float frac) {
 #pragma unroll
         for (int i = 0; i < CF::XI; ++i)
-            if (xok[i]) xbuf[xr[i] * LDX + xc[i]] = snsde_spline_eval(ca[i], cb[i], cc[i], cd[i], frac);
+            if (xok[i]) xbuf[(xp[i] & 3) * LDX + xc[i]] = snsde_spline_eval(ca[i], cb[i], cc[i], cd[i], frac);
     };
     {   // pass 0 inputs
         const float* st = a.step_tab;
@@ -607,7 +620,9 @@ int launch_m4n(const MfmaArgs& a, hipStream_t stream) {
         const size_t lds_bytes = (size_t)CF::LDS_FLOATS * sizeof(float);
         static SnsdeLdsAttr lds_attr;   // per instantiation and device
         if (const int rc = snsde_lds_attr(reinterpret_cast<const void*>(snsde_m4n_kernel<CF>), lds_bytes, lds_attr)) return rc;
-        hipLaunchKernelGGL(snsde_m4n_kernel<CF>, dim3((a.B + 3) / 4), dim3(CF::NT), lds_bytes, stream, a);
+        // (an ensemble: the tiles of one member x the members - member_rows % 4 == 0, no ragged tile)
+        const dim3 grid = a.members > 1 ? dim3((a.member_rows + 3) / 4, a.members) : dim3((a.B + 3) / 4);
+        hipLaunchKernelGGL(snsde_m4n_kernel<CF>, grid, dim3(CF::NT), lds_bytes, stream, a);
         return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
     }
 }

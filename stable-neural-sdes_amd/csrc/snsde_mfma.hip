@@ -497,14 +497,19 @@ MfmaPlan make_plan(const snsde_solve* s, const SnsdeNet& net, int flavor_hint) {
         s->method == SNSDE_EULER && !s->dW && s->kl_column1 == 0)
         p.LEAN_SPEC = io == 6 ? 2 : 1;
     // model ensembles (snsde_solve::members): the kernels that map a tile to its member in their prologue - the lean kernel and the
-    // general kernel, 4-row tiles (a tile never straddles two members) - or no plan
-    if (snsde_members(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4) {
+    // general kernel, 4-row tiles (a tile never straddles two members) - or no plan.  SNSDE_FLAG_ENSEMBLE_NETS adds the kernels of
+    // the diffusion nets: the wave pairs (a pair's member from its first row) and snsde_m4n_kernel on the reference's own fields
+    const bool ensemble_nets = snsde_members(s) > 1 && (s->flags & SNSDE_FLAG_ENSEMBLE_NETS) != 0 &&
+                               (p.kernel == FwdKernel::w4 || (p.kernel == FwdKernel::m4n && !variant));
+    if (snsde_members(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4 &&
+        !ensemble_nets) {
         p.members_refused = true;
         return p;
     }
-    // sample paths (snsde_solve::samples): the kernels that map path p to coeffs row p / S in their prologue, or no plan
+    // sample paths (snsde_solve::samples): the kernels that map path p to coeffs row p / S in their prologue, or no plan.  Of an
+    // ensemble under both flags: the wave pairs (they read no coefficients) and snsde_m4n_kernel (the row counted from the member's first)
     if (snsde_samples(s) > 1 && p.kernel != FwdKernel::lean && p.kernel != FwdKernel::lean_bf16 && p.kernel != FwdKernel::general_m4 &&
-        p.kernel != FwdKernel::general_m16) {
+        p.kernel != FwdKernel::general_m16 && !(ensemble_nets && (s->flags & SNSDE_FLAG_ENSEMBLE_SAMPLES) != 0)) {
         p.samples_refused = true;
         return p;
     }

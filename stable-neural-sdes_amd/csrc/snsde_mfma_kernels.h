@@ -99,12 +99,14 @@ struct MfmaArgs {
     int32_t acc_col;                        // path-integral accumulator column (snsde_solve.kl_column1 - 1), -1: none
     float acc_a, acc_b;                     // its linear prior drift a y + b
     int32_t samples;                        // paths per input row, >= 1 (snsde_solve::samples): path p reads coeffs row p / samples;
-                                            // read by the lean and the general kernel only (make_plan refuses the others)
+                                            // read by the lean and the general kernel (make_plan refuses the others) and, for an
+                                            // ensemble under SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_SAMPLES, by snsde_m4n_kernel
     // model ensembles (snsde_solve::members = M > 1): the member is the launch's second grid axis, m = blockIdx.y (one model: a
     // grid of one row, m = 0 and the strides are 0) - tile blockIdx.x of member m covers rows m member_rows + 4 blockIdx.x .., reads
     // params + m param_stride, ws + m ws_stride and coefficient rows counted from the member's first row.  No division and no branch:
     // a `row0 / member_rows` behind a uniform test put a dependent kernarg load in front of every other load of the prologue.  Read by
-    // the lean kernel and the general kernel only (make_plan refuses the others for M > 1), once per workgroup before the step loop
+    // the lean kernel, the general kernel and - under SNSDE_FLAG_ENSEMBLE_NETS - snsde_m4n_kernel (make_plan refuses the others for
+    // M > 1; the wave pairs carry the same three fields in W4Args), once per workgroup before the step loop
     int32_t members, member_rows;           // member_rows: rows per member (batch / M; one model: unused, m = 0)
     uint32_t param_stride, ws_stride;       // floats
 };

@@ -23,13 +23,23 @@ static bool config_ok(const snsde_solve* s, const SnsdeNet& net) {
 static bool shape_ok(const snsde_solve* s, const SnsdeNet& net) {
     if (!config_ok(s, net)) return false;
     if (s->batch < 4) return false;      // (a tile is four rows; ragged tails overlap the previous tile)
+    if (snsde_members(s) > 1 && s->batch / snsde_members(s) < 4) return false;      // (... and so is the smallest member of an ensemble)
     if ((uint64_t)16 * (uint64_t)s->batch * 64u >= (1ull << 32)) return false;   // 32-bit save offsets (uoff)
     return true;
 }
 
 template <int NHID, int NN, bool TIME>
 static int launch(const W4Args& a, hipStream_t st) {
-    const dim3 grid((a.B + 7) / 8), block(256);
+    const dim3 block(256);
+    if (a.members > 1) {      // a model ensemble: the ENS instantiations, ceil(member_rows / 8) workgroups x members (inference: snsde_w4_launch)
+        const dim3 grid((a.member_rows + 7) / 8, a.members);
+        if (a.srk_tab) {
+            constexpr size_t lds_bytes = (size_t)w4srk_fwd_lds_floats<NHID, false>() * sizeof(float);
+            hipLaunchKernelGGL((snsde_w4_srk_kernel<CfgW<NHID, NN, TIME, false>, true>), grid, block, lds_bytes, st, a);
+        } else hipLaunchKernelGGL((snsde_w4_euler_kernel<CfgW<NHID, NN, TIME, false>, true>), grid, block, 0, st, a);
+        return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
+    }
+    const dim3 grid((a.B + 7) / 8);
     if (a.srk_tab) {
         if (a.act_save) {      // (training mode parks the drift wave's first matrix: more than 64 KB of dynamic LDS)
             const size_t lds_bytes = (size_t)w4srk_fwd_lds_floats<NHID, true>() * sizeof(float);
@@ -101,6 +111,11 @@ int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t strea
     a.seed_dev = s->seed_dev;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
     a.nsave = snsde_act_slots(&m);
+    if (const int members = snsde_members(s); members > 1) {      // (SNSDE_FLAG_ENSEMBLE_NETS: make_plan; inference only)
+        const int64_t stride = snsde_param_numel(&m);
+        if (s->act_save || s->batch % members || (s->batch / members) % 4 || stride <= 0 || stride >= (1ll << 32)) return SNSDE_ERR_UNSUPPORTED;
+        a.members = members; a.member_rows = s->batch / members; a.param_stride = (uint32_t)stride;
+    }
     if (s->method == SNSDE_SRK) { a.srk_tab = s->srk_tab; a.dU = s->dU; a.dU_out = s->dU_out; a.stage_save = s->stage_save; }
     a.off_theta = net.off_theta;
     a.w_in = net.in.src_w; a.b_in = net.in.src_b; a.k_in = net.in.K; a.t_in = net.in.tshift;

@@ -59,7 +59,23 @@ struct W4Args {
     int32_t w_hid[3], b_hid[3];
     int32_t w_out, b_out;
     int32_t w_n0, b_n0, w_n1, b_n1;       // noise_y[.0] (64, 66) and noise_y.2 (64, 64)
+    // model ensembles (snsde_solve::members = M > 1 under SNSDE_FLAG_ENSEMBLE_NETS): the ENS instantiations of the two forward
+    // kernels (inference only) - the member is the launch's second grid axis, m = blockIdx.y, with ceil(member_rows / 8) workgroups
+    // each; its pairs cover rows m member_rows .. and read params + m x param_stride.  One model: the kernels as they were (ENS =
+    // false: these three fields are not read)
+    int32_t members, member_rows;
+    uint32_t param_stride;                // floats
 };
+
+// the first row of a pair: one model - tile blockIdx.x * 2 + pair, the ragged rule on the last four rows of the batch (see
+// snsde_w4_euler_kernel); an ensemble - the same inside member blockIdx.y, the ragged rule on the MEMBER's last four rows (a surplus
+// pair of an odd tile count moves back onto them and stores the same bits twice)
+template <bool ENS>
+__device__ __forceinline__ int pair_row0(int B, int member_rows, int pair) {
+    const int row_t = (blockIdx.x * 2 + pair) * 4;
+    if constexpr (ENS) return (int)blockIdx.y * member_rows + (row_t + 4 <= member_rows ? row_t : member_rows - 4);
+    else return row_t + 4 <= B ? row_t : B - 4;
+}
 
 // D = A(4 rows, column k: block ABID of the A register, broadcast) x B(W^T row k) + C
 template <int ABID>
@@ -152,8 +168,13 @@ struct CfgW {
 #define W4_T(i)
 #endif
 
-template <class CF>
+// ENS: the instantiations a model ensemble runs (W4Args::members; inference).  They are instantiations of their own so that the
+// one-model kernels stay the code they were, instruction for instruction: folded into one kernel, eleven scalar instructions more in
+// the prologue shifted the step loop's code and the K4 Euler solve with two outputs measured 2 % slower (102.9 -> 105.1 us at 2048
+// rows, two sessions) although no instruction of the loop had changed.
+template <class CF, bool ENS = false>
 __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
+    static_assert(!(ENS && CF::SAVE), "ensembles on the wave pairs are inference only");
 #ifdef W4_TRACE
     float tr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tr_last = __builtin_readcyclecounter();
@@ -176,10 +197,9 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
     // masking rows - those rows are then solved twice, bit-identically (same global row => same inputs and Philox counters), and
     // stored twice with the same values; no per-row validity tests, branches or SGPR masks anywhere in the loop (B >= 4: host side).
     const int B = a.B;
-    const int row_t = (blockIdx.x * 2 + pair) * 4;
-    const int row0 = row_t + 4 <= B ? row_t : B - 4;
+    const int row0 = pair_row0<ENS>(B, a.member_rows, pair);
     const uint32_t BH = (uint32_t)B * H;
-    const float* P = a.params;
+    const float* P = ENS ? a.params + (size_t)blockIdx.y * a.param_stride : a.params;      // (wave-uniform, formed once)
 
     float y[4], yt[4];
 #pragma unroll
@@ -470,8 +490,9 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
 // =====================================================================================================================================
 template <int NHID, bool SAVE> __host__ __device__ constexpr int w4srk_fwd_lds_floats() { return 2 * 12 * 256 + 2 * 4096 + ((SAVE && NHID >= 1) ? 2 * 4096 : 0); }
 
-template <class CF>
+template <class CF, bool ENS = false>      // (ENS: see snsde_w4_euler_kernel)
 __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
+    static_assert(!(ENS && CF::SAVE), "ensembles on the wave pairs are inference only");
     constexpr int H = 64, NHID = CF::NHID, NN = CF::NN;
     constexpr bool TIME = CF::TIME, SAVE = CF::SAVE;
     constexpr int NSAVE = NHID + 2 + 2 * NN, ZSLOT = NHID + 1, NP = 3;
@@ -494,10 +515,9 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
     float (*zstash)[2][4][4][H] = reinterpret_cast<float (*)[2][4][4][H]>(w4srk_fwd_lds + 2 * XN * 256 + pair * 4096);
     float* wpark = w4srk_fwd_lds + 2 * XN * 256 + 2 * 4096 + pair * 4096;      // [16][64][4]
     const int B = a.B;
-    const int row_t = (blockIdx.x * 2 + pair) * 4;
-    const int row0 = row_t + 4 <= B ? row_t : B - 4;       // (ragged tail: see snsde_w4_euler_kernel)
+    const int row0 = pair_row0<ENS>(B, a.member_rows, pair);       // (ragged tail: see snsde_w4_euler_kernel)
     const uint32_t BH = (uint32_t)B * H;
-    const float* P = a.params;
+    const float* P = ENS ? a.params + (size_t)blockIdx.y * a.param_stride : a.params;
     typedef const float __attribute__((address_space(4)))* CP;
     const CP step_tab_c = (CP)(uintptr_t)a.step_tab, out_w_c = (CP)(uintptr_t)a.out_w, srk_c = (CP)(uintptr_t)a.srk_tab;
     const uint32_t lo = (uint32_t)(row0 * H + lane);

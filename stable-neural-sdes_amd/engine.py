@@ -215,9 +215,17 @@ def check_ensemble_samples(ensemble_samples):
     return ensemble_samples
 
 
+def check_ensemble_nets(ensemble_nets):
+    """The `ensemble_nets` option (a model ensemble on the wave-pair and diffusion-net kernels, SNSDE_FLAG_ENSEMBLE_NETS): a bool,
+    ValueError otherwise."""
+    if not isinstance(ensemble_nets, bool):
+        raise ValueError(f"ensemble_nets must be a bool (`members` models on the diffusion-net kernels in one solve), got {ensemble_nets!r}")
+    return ensemble_nets
+
+
 def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                      row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                     members=0, ensemble_grad=False, ensemble_samples=False):
+                     members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False):
     """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
     device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
     s = _lib.Solve()
@@ -231,6 +239,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
     s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
     s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
     s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
+    s.flags |= _lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
@@ -239,7 +248,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                  row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                 members=0, ensemble_grad=False, ensemble_samples=False):
+                 members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
@@ -248,9 +257,10 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     only: SNSDE_FLAG_BF16_GRAD).  members: models of one architecture in the call (include/snsde.h; `batch` then counts the rows
     of all members); 'none' where the plan arrives at a kernel that does not map rows to members.  ensemble_grad:
     SNSDE_FLAG_ENSEMBLE_GRAD - an ensemble has training planes under it only, on the kernels the ensemble adjoint route covers.
-    ensemble_samples: SNSDE_FLAG_ENSEMBLE_SAMPLES - members > 1 together with samples > 1 ('none' without it)."""
+    ensemble_samples: SNSDE_FLAG_ENSEMBLE_SAMPLES - members > 1 together with samples > 1 ('none' without it).
+    ensemble_nets: SNSDE_FLAG_ENSEMBLE_NETS - members > 1 on the wave pairs ('w4') and the diffusion-net tiles ('none' without it)."""
     s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
-                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples)
+                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples, ensemble_nets)
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
 
@@ -563,7 +573,7 @@ class SolveCall:
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
                  lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False,
-                 ensemble_samples=False):
+                 ensemble_samples=False, ensemble_nets=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -583,6 +593,8 @@ class SolveCall:
         ensemble_grad = bool(ensemble_grad) and M > 1      # (no effect on one model)
         # members and samples together (SNSDE_FLAG_ENSEMBLE_SAMPLES): row m Bm + b S + s, coeffs (Bm / S rows) shared by all members
         ensemble_samples = bool(ensemble_samples) and M > 1 and S > 1      # (no effect on one model or one path per row)
+        # the ensemble on the wave-pair / diffusion-net kernels (SNSDE_FLAG_ENSEMBLE_NETS)
+        ensemble_nets = bool(ensemble_nets) and M > 1      # (no effect on one model)
         if ensemble_samples and (B // M) % S:
             raise ValueError(f'members={members!r}, samples={samples!r}: the {B // M} rows of a member are a whole number of groups of `samples` paths')
         if M > 1 and ((S > 1 and not ensemble_samples) or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
@@ -631,6 +643,8 @@ class SolveCall:
             self.base_flags |= _lib.FLAG_ENSEMBLE_GRAD
         if ensemble_samples:
             self.base_flags |= _lib.FLAG_ENSEMBLE_SAMPLES
+        if ensemble_nets:
+            self.base_flags |= _lib.FLAG_ENSEMBLE_NETS
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -654,7 +668,8 @@ class SolveCall:
                         model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad, ensemble_samples)
+                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad, ensemble_samples,
+                        ensemble_nets)
         self.members = M
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
@@ -726,12 +741,17 @@ def _desc(call_or_desc):
     return call_or_desc.desc if hasattr(call_or_desc, 'desc') else call_or_desc
 
 
-def forward_kernel(call_or_desc, keys=False):
+def forward_kernel(call_or_desc, keys=False, ensemble_nets=False):
     """Name of the exact kernel the forward of a SolveCall (or a _lib.Solve descriptor) launches (_lib.FWD_KERNELS: the
     enumerators of csrc/snsde_mfma_kernels.h FwdKernel, 'generic', 'generic_srk' or 'none'); forward_path folds several of them into
-    one family.  keys=True: (name, NHID, KUXT) - the plan's keys of the two-tile kernels' instantiation lists, -1 off the MFMA routes."""
+    one family.  keys=True: (name, NHID, KUXT) - the plan's keys of the two-tile kernels' instantiation lists, -1 off the MFMA routes.
+    ensemble_nets=True: the answer for the descriptor with SNSDE_FLAG_ENSEMBLE_NETS set (a copy; the descriptor is left alone)."""
     nhid, kuxt = C.c_int32(), C.c_int32()
-    name = _lib.FWD_KERNELS[_lib.lib().snsde_forward_kernel(C.byref(_desc(call_or_desc)), C.byref(nhid), C.byref(kuxt))]
+    desc = _desc(call_or_desc)
+    if ensemble_nets:
+        desc = type(desc).from_buffer_copy(desc)
+        desc.flags |= _lib.FLAG_ENSEMBLE_NETS
+    name = _lib.FWD_KERNELS[_lib.lib().snsde_forward_kernel(C.byref(desc), C.byref(nhid), C.byref(kuxt))]
     return (name, nhid.value, kuxt.value) if keys else name
 
 

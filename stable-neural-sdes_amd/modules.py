@@ -355,7 +355,10 @@ class Ensemble(nn.Module):
     options={'samples': S, 'ensemble_samples': True} (with 'ensemble_grad' and 'sample_grad' under autograd) pass through to
     sdeint_ensemble: S Brownian paths per input row for every member.  Each member's initial state stays one row per input row
     (the solve expands it), the readouts return one row per path as the wrappers do for `samples`, and every output is
-    (M, B S, ..) - equal to the M wrapper calls with options={'samples': S, 'row_offset': m B S, 'global_rows': M B S}."""
+    (M, B S, ..) - equal to the M wrapper calls with options={'samples': S, 'row_offset': m B S, 'global_rows': M B S}.
+    options={'ensemble_nets': True} passes through unchanged as well: members whose field has a diffusion net (noise_option 14 / 15 /
+    18 / 19) then take the fused solve on the wave-pair / diffusion-net kernels in eval(); in train() under autograd (with
+    'ensemble_grad') they run the M differentiable solves, as without the option."""
 
     KINDS = ()      # (the three wrapper classes: filled below, once they are all defined)
 

@@ -431,7 +431,14 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     sample_grad=True as well (ValueError otherwise); where engine.backward_mode(..., members=M, samples=S, ensemble_samples=True,
     ensemble_grad=True, sample_grad=True) == 1 the one fused node runs.  The loop route - taken in the same cases as above, with
     (B S) % 4 != 0 in place of B % 4 != 0 - runs those M sampled sdeint calls (with sample_grad under autograd): the same result.
-    Without ensemble_samples, samples > 1 raises ValueError; sample_grad without samples > 1 and ensemble_samples stays a conflict."""
+    Without ensemble_samples, samples > 1 raises ValueError; sample_grad without samples > 1 and ensemble_samples stays a conflict.
+
+    options={'ensemble_nets': True} (SNSDE_FLAG_ENSEMBLE_NETS) opts in to the fused solve on the kernels of the diffusion nets
+    (noise_option 14 / 15 / 18 / 19): the wave pairs at H = 64 (Euler, SRK) and the diffusion-net 4-row tiles (SRK, Milstein, Euler
+    at H = 128 or with a wide control path).  Without it those plans keep the loop of M calls (engine.forward_path(..., members=M)
+    == 'none'); with it engine.forward_path(..., members=M, ensemble_nets=True) decides, and the contract is the one above, bit for
+    bit, `samples` with ensemble_samples included.  Inference only: under autograd (with ensemble_grad) such an ensemble runs the M
+    differentiable sdeint calls, as every plan without a fused adjoint does.  A bool, ValueError otherwise; no effect elsewhere."""
     sdes = list(sdes)
     M = len(sdes)
     if M < 1:
@@ -455,6 +462,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
                          "options={'ensemble_samples': True}")
     ensemble_samples = ensemble_samples and S > 1      # (no effect on one path per row)
     ensemble_grad = engine.check_ensemble_grad(options.pop('ensemble_grad')) if 'ensemble_grad' in options else False
+    ensemble_nets = engine.check_ensemble_nets(options.pop('ensemble_nets')) if 'ensemble_nets' in options else False
     if ensemble_samples:      # (sample_grad is this route's own option then; everywhere else it stays the conflict it was)
         sample_grad = engine.check_sample_grad(options.pop('sample_grad')) if 'sample_grad' in options else False
     else:
@@ -550,7 +558,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sdes[0].times), dev)
     if engine.forward_path(model, M * B, L, grid.N, method, kernel, precision=precision, global_rows=global_rows, row_offset=row_offset,
                            lean_general=lean_general, exact_order=exact_order, members=M, samples=S if ensemble_samples else 0,
-                           ensemble_samples=ensemble_samples) == 'none':
+                           ensemble_samples=ensemble_samples, ensemble_nets=ensemble_nets) == 'none':
         return loop('the plan arrives at a kernel that does not map rows to members')
     if needs_grad:
         # the ensemble adjoint route (mode 1 with delta planes for every member), or the M differentiable solves
@@ -573,7 +581,8 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     rows = None if row_out is None else _device_row_out(options, dev).repeat(M)
     call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=options['seed'], row_offset=row_offset, kernel=kernel,
                             exact_order=exact_order, row_out=rows, precision=precision, lean_general=lean_general,
-                            global_rows=global_rows, members=M, samples=S if ensemble_samples else 0, ensemble_samples=ensemble_samples)
+                            global_rows=global_rows, members=M, samples=S if ensemble_samples else 0, ensemble_samples=ensemble_samples,
+                            ensemble_nets=ensemble_nets)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
