@@ -352,8 +352,8 @@ template <class CF> constexpr bool lean_spec_geo() {
 
 // Cycle timeline (development builds, -DLEAN_TRACE): s_memtime stamps at LT(i) are left in flight (no s_waitcnt) and collected
 // in three groups behind the step's barriers (whose own s_waitcnt lgkmcnt(0) has already drained the queue there), so they do
-// not drain the LDS queue the way TRACE() does.  The kernel has no registers to spare (251 of 256 VGPRs, SGPRs at the limit, and
-// loop-carried scalars of this loop are VGPRs to hipcc), so nothing is carried: each collected stamp's low word is added into a
+// not drain the LDS queue the way TRACE() does.  The kernel has no registers to spare (VGPRs and SGPRs near their limits; when this
+// was written the loop-carried scalars of this loop were VGPRs to hipcc, see n_end), so nothing is carried: each collected stamp's low word is added into a
 // per-lane LDS slot with a fire-and-forget ds_add_u32 (conflict-free, 12 x NT words behind the kernel's own LDS); phase i =
 // sum_i - sum_{i-1} (mod 2^32); the wrap-around phase 9 -> 0 from the sums of stamp 0 over steps >= 1 and stamp 9 over steps
 // <= N - 2 (slots 10 / 11).  Cost: 2 instructions per stamp and step (the traced kernel runs ~15 % slower than the plain one).
@@ -682,23 +682,29 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     int n = 0;
     float yold = yv;
     for (int ko = 0; ko < a.T - 1; ++ko) {
-    const int n_end = a.out_step[ko];
+    // out_step[ko] is the same for every lane, but the kernel stores to global memory, so hipcc cannot issue this load on the scalar
+    // unit: left as a plain load the bound is a VGPR, n <= n_end a v_cmp, the step loop an exec-masked one and the step counter n
+    // and everything derived from it (table rows, ring slots, the refill / batch / Philox tests) per-lane VALU work on the port the
+    // MFMAs need.  readfirstlane makes the bound, and with it the counter and the loop branch, scalar.  Do not simplify it away.
+    const int n_end = __builtin_amdgcn_readfirstlane(a.out_step[ko]);
     for (; n <= n_end; ++n) {
         const int rbase = (n / CF::ROWCH) * CF::ROWCH;
         if (n > 0 && n == rbase) {               // next chunk of step-table rows (every wave is past the closing barrier)
-            fill_rows(rbase);
+            int rb = rbase;      // opaque to hipcc: derived from n, fill_rows' first row becomes a VGPR induction variable with a
+            asm volatile("" : "+s"(rb));      // v_add in every step; from rb it is formed here, once per chunk
+            fill_rows(rb);
             __syncthreads();
         }
         const bool more = n + 1 < N;
-        // training-mode stores: per-step bases as SCALAR values (readfirstlane makes the step number an SGPR to hipcc, uoff's
-        // 32 x 32 -> 64-bit products then run on the scalar unit).  Formed from the loop counter directly, every store paid two
+        // training-mode stores: per-step bases as SCALAR values (the step number is an SGPR since the loop bound is one, see n_end;
+        // uoff's 32 x 32 -> 64-bit products then run on the scalar unit).  Formed from a VGPR counter, every store paid two
         // quarter-rate v_mul_lo_u32, a v_mad_u64_u32 and four more VALU instructions for its address (~40 VALU instructions per
         // wave-step for five stores, on the issue port the MFMAs share).
         [[maybe_unused]] float* act_n = nullptr;
         [[maybe_unused]] uint32_t nu = 0;
         [[maybe_unused]] uint32_t sgn = 0;
         if constexpr (SAVE) {
-            nu = (uint32_t)__builtin_amdgcn_readfirstlane(n);
+            nu = (uint32_t)n;
             act_n = a.act_save + uoff((int)nu, (uint32_t)CF::NSAVE * (uint32_t)BH);
         }
         LT(0)
@@ -758,8 +764,8 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
             {
                 const int n1 = more ? n + 1 : n;          // (the last step prefetches its own inputs again: never used)
                 dw_nxt = next_dw(n1, qa[1]);
-                // (the row base on the scalar unit: n1 is uniform, and formed in VGPRs its 64-bit product costs ~5 VALU per step)
-                if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)(uint32_t)__builtin_amdgcn_readfirstlane(n1) * H);
+                // (the row base is formed on the scalar unit: n1 is an SGPR like n; in VGPRs its 64-bit product costs ~5 VALU per step)
+                if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)(uint32_t)n1 * H);
             }
         };
         uint32_t cur = arow;

@@ -308,11 +308,17 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
     int n = 0;
     float yold[2] = {yv[0], yv[1]};
     for (int ko = 0; ko < a.T - 1; ++ko) {
-    const int n_end = a.out_step[ko];
+    // out_step[ko] is the same for every lane, but the kernel stores to global memory, so hipcc cannot issue this load on the scalar
+    // unit: left as a plain load the bound is a VGPR, n <= n_end a v_cmp, the step loop an exec-masked one and the step counter n
+    // and everything derived from it (table rows, ring slots, the refill / batch / Philox tests) per-lane VALU work on the port the
+    // MFMAs need.  readfirstlane makes the bound, and with it the counter and the loop branch, scalar.  Do not simplify it away.
+    const int n_end = __builtin_amdgcn_readfirstlane(a.out_step[ko]);
     for (; n <= n_end; ++n) {
         const int rbase = (n / CF::ROWCH) * CF::ROWCH;
         if (n > 0 && n == rbase) {
-            fill_rows(rbase);
+            int rb = rbase;      // (opaque to hipcc, as in snsde_m4_kernel.h: no per-step VGPR induction variable for the first row)
+            asm volatile("" : "+s"(rb));
+            fill_rows(rb);
             __syncthreads();
         }
         const bool more = n + 1 < N;
@@ -320,7 +326,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
         [[maybe_unused]] uint32_t nu = 0;
         [[maybe_unused]] uint32_t sgn[2] = {0u, 0u};
         if constexpr (SAVE) {
-            nu = (uint32_t)__builtin_amdgcn_readfirstlane(n);
+            nu = (uint32_t)n;
             act_n = a.act_save + uoff((int)nu, (uint32_t)CF::NSAVE * (uint32_t)BH);
         }
         // ---- top: the first layer's B operands; the [X(t_n) | tau_n] part of both tiles covers their latency ----------------------
