@@ -124,8 +124,14 @@ enum {
      * - the wave pairs (SNSDE_FWD_W4) and the diffusion-net 4-row tiles (SNSDE_FWD_M4N); snsde_solve.members, last paragraph.  No
      * effect when members <= 1; without it a plan that arrives at these kernels stays SNSDE_PATH_NONE for M > 1.  Inference only:
      * with training planes, with or without SNSDE_FLAG_ENSEMBLE_GRAD, such an ensemble stays SNSDE_PATH_NONE and
-     * snsde_backward_supported stays 0.  Sample paths of such an ensemble need SNSDE_FLAG_ENSEMBLE_SAMPLES as well. */
-    SNSDE_FLAG_ENSEMBLE_NETS = 1024
+     * snsde_backward_supported stays 0 (SNSDE_FLAG_ENSEMBLE_NETS_GRAD opts in for the wave pairs).  Sample paths of such an
+     * ensemble need SNSDE_FLAG_ENSEMBLE_SAMPLES as well. */
+    SNSDE_FLAG_ENSEMBLE_NETS = 1024,
+    /* Opt-in: training through a model ensemble on the wave pairs (SNSDE_FWD_W4 / SNSDE_REV_W4_FUSED: H = 64, diffusion nets, Euler
+     * or SRK; snsde_solve.members, last paragraph).  Meaningful only with members > 1 and both SNSDE_FLAG_ENSEMBLE_NETS and
+     * SNSDE_FLAG_ENSEMBLE_GRAD set; each of the three keeps its own meaning.  Alone, or with only one of the other two, it changes
+     * no answer. */
+    SNSDE_FLAG_ENSEMBLE_NETS_GRAD = 2048
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -269,6 +275,21 @@ typedef struct snsde_solve {
                            /* on these kernels).  Still refused under the flag: z0_weight, noise_table, kl_column1, bf16    */
                            /* operands, the field variants, kernel = generic / 16-row tiles, and every training plane, with */
                            /* or without SNSDE_FLAG_ENSEMBLE_GRAD (snsde_backward_supported == 0).                          */
+                           /* Training through the wave pairs is opt-in once more, SNSDE_FLAG_ENSEMBLE_NETS_GRAD together   */
+                           /* with SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_GRAD; without all three everything above  */
+                           /* holds.  With them the training planes are accepted where the plan arrives at SNSDE_FWD_W4,    */
+                           /* and snsde_backward_supported is 1 where the adjoint of the member run alone is                */
+                           /* SNSDE_REV_W4_FUSED (Euler or SRK; snsde_backward_kernel reports it, snsde_save_layout answers */
+                           /* delta_slots == 0: delta_save is not written).  The member is the second grid axis of the      */
+                           /* forward, of the adjoint and of the two reduction launches: one launch each for all members.   */
+                           /* The contract is the one above: states, saved planes, adjoints, dL/dy0 and block m of          */
+                           /* grad_params equal the member-alone shard's bit for bit.  snsde_backward_workspace_bytes = M x */
+                           /* ((the member-alone solve's bytes + 15) & ~15) as above - each block holds that member's theta */
+                           /* partials and per-tile gradient blocks, laid out as the member alone lays them out;            */
+                           /* snsde_workspace_bytes is the ensemble's.  Still 0 / SNSDE_PATH_NONE under the three flags:    */
+                           /* the diffusion-net 4-row tiles (Milstein, H = 16 / 32 / 128), samples > 1, bf16 operands, the  */
+                           /* field variants, kernel = generic / 4-row / 16-row tiles, z0_weight, noise_table, kl_column1.  */
+                           /* Never another kernel, no mode 2.                                                              */
     int64_t  row_offset;  /* global index of local row 0 (batch shards keep the global Philox   */
                            /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
                            /* sees the local batch unless `global_rows` (below) is set           */
@@ -427,7 +448,9 @@ SNSDE_API int    snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int
 SNSDE_API int    snsde_backward_supported(const snsde_solve* s);    /* 1 / 2 / 0, see above; bf16 operands: 0, or 1 under */
                                                                     /* SNSDE_FLAG_BF16_GRAD where it covers the solve;    */
                                                                     /* members > 1: 0, or under SNSDE_FLAG_ENSEMBLE_GRAD  */
-                                                                    /* 1 where the general 4-row-tile adjoint takes it    */
+                                                                    /* 1 where the general 4-row-tile adjoint takes it,   */
+                                                                    /* with SNSDE_FLAG_ENSEMBLE_NETS and _NETS_GRAD as    */
+                                                                    /* well 1 where the wave-pair adjoint takes it        */
 SNSDE_API size_t snsde_backward_workspace_bytes(const snsde_backward* b);
 /* INVARIANT between forward and backward (mode 1): `fwd.workspace` is untouched AND `fwd.params` holds the values the forward ran
  * with.  The adjoint re-packs its transposed weights from the CURRENT params, but takes the folded first-layer product
@@ -436,7 +459,9 @@ SNSDE_API size_t snsde_backward_workspace_bytes(const snsde_backward* b);
  * autograd node owns the workspace and runs before the optimizer step.)                                                        */
 /* fwd.members = M > 1 under SNSDE_FLAG_ENSEMBLE_GRAD: grad_ys, adj and delta_save hold the rows of all members like ys; member m's
  * tiles read block m of fwd.params, of fwd.workspace and of b->workspace.  SNSDE_BWD_ADJ0_ONLY, row_out and supplied dW / dU as
- * for one model.  Without the flag: SNSDE_ERR_UNSUPPORTED. */
+ * for one model.  Without the flag: SNSDE_ERR_UNSUPPORTED.  On the wave pairs (SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_GRAD |
+ * SNSDE_FLAG_ENSEMBLE_NETS_GRAD): no delta planes; member m's pairs leave their theta partials and gradient blocks in block m of
+ * b->workspace. */
 SNSDE_API int    snsde_solve_backward(const snsde_backward* b, void* hip_stream);
 
 /* Parameter gradients of the fused solve (mode 1 = MFMA path only): after snsde_solve_forward (traj, dW_out, act_save
@@ -450,7 +475,8 @@ SNSDE_API int    snsde_solve_backward(const snsde_backward* b, void* hip_stream)
  * per-workgroup diffusion-side sums; with delta_slots == 0 the per-tile weight-gradient blocks) - SNSDE_ERR_NULL without it,
  * SNSDE_ERR_WORKSPACE when workspace_bytes < snsde_backward_workspace_bytes(b).
  * fwd.members = M > 1 under SNSDE_FLAG_ENSEMBLE_GRAD: grad_params is (M, snsde_param_numel); block m sums member m's rows only, in
- * the order the member-alone solve sums them (bit-equal), all members in the same launches. */
+ * the order the member-alone solve sums them (bit-equal), all members in the same launches (the wave pairs under
+ * SNSDE_FLAG_ENSEMBLE_NETS_GRAD: one zero fill and the two reduction launches, the member on their third grid axis). */
 SNSDE_API size_t snsde_param_gradients_workspace_bytes(const snsde_backward* b);
 SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_params, void* workspace, size_t workspace_bytes,
                              void* hip_stream);
@@ -458,7 +484,8 @@ SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_para
 /* snsde_solve_backward followed by snsde_param_gradients as ONE call (mode 1 solves only; same arguments, same results bit for
  * bit): one transition from the host language and one validation instead of two, the launches back to back on the stream.
  * Enqueue-only and capturable like the two calls it replaces; returns SNSDE_ERR_UNSUPPORTED where snsde_backward_supported()
- * != 1 (the caller then uses the separate calls).  A model ensemble under SNSDE_FLAG_ENSEMBLE_GRAD: as the two calls.            */
+ * != 1 (the caller then uses the separate calls).  A model ensemble under SNSDE_FLAG_ENSEMBLE_GRAD (on the wave pairs: with
+ * SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_NETS_GRAD): as the two calls.                                                    */
 SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
                                             void* hip_stream);
 

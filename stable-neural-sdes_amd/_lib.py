@@ -24,6 +24,7 @@ FLAG_BF16_GRAD = 128        # opt-in: training through the bf16-operand forward 
 FLAG_ENSEMBLE_GRAD = 256    # opt-in: a solve of members = M > 1 models may be differentiated (include/snsde.h)
 FLAG_ENSEMBLE_SAMPLES = 512 # opt-in: members = M > 1 together with samples = S > 1 in one solve (include/snsde.h)
 FLAG_ENSEMBLE_NETS = 1024   # opt-in: members = M > 1 on the wave-pair and diffusion-net kernels (include/snsde.h)
+FLAG_ENSEMBLE_NETS_GRAD = 2048   # opt-in: training through members = M > 1 on the wave pairs (with the two flags above it)
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 # snsde_forward_kernel / snsde_backward_kernel (SNSDE_FWD_* / SNSDE_REV_*): the names of csrc/snsde_mfma_kernels.h FwdKernel / RevKernel
 FWD_KERNELS = ('none', 'generic', 'generic_srk', 'w4', 'm4n', 'lean', 'lean_two_tile_h128', 'lean_two_tile_h256', 'lean_streamed_h256',

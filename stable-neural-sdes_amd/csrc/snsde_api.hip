@@ -200,7 +200,14 @@ static bool members_refused(const snsde_solve* s) {
 }
 // ... and the forward plans whose training planes the ensemble adjoint route takes (route_backward): the lean kernel and the general
 // MFMA kernel on 4-row tiles, elementwise diffusions, H <= 128
-static bool ensemble_training_plan(const snsde_mfma::MfmaPlan& p) {
+// SNSDE_FLAG_ENSEMBLE_NETS_GRAD (snsde.h) adds the wave pairs - with all three of ENSEMBLE_NETS | ENSEMBLE_GRAD | ENSEMBLE_NETS_GRAD
+// set, nothing otherwise - whose adjoints carry the member on their second grid axis (snsde_w4_kernel.h: ENS)
+static bool ensemble_nets_grad(const snsde_solve* s) {
+    constexpr uint32_t all = SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_GRAD | SNSDE_FLAG_ENSEMBLE_NETS_GRAD;
+    return snsde_members(s) > 1 && (s->flags & all) == all;
+}
+static bool ensemble_training_plan(const snsde_solve* s, const snsde_mfma::MfmaPlan& p) {
+    if (p.ok && p.kernel == snsde_mfma::FwdKernel::w4) return ensemble_nets_grad(s) && snsde_samples(s) <= 1;
     return p.ok && p.H <= 128 && p.NN == 0 && (p.kernel == snsde_mfma::FwdKernel::lean || p.kernel == snsde_mfma::FwdKernel::general_m4);
 }
 // One member of an ensemble run alone as a shard of the whole (snsde.h: members): what each member is planned as - its adjoint's
@@ -244,7 +251,7 @@ static ForwardRoute route_forward(const snsde_solve* s, const SnsdeNet& net) {
     if (!global_rows_ok(s)) return r;
     r.plan = make_plan(s, net, snsde_flavor_hint(s));
     if (strain && !sampled_training_plan(r.plan)) return ForwardRoute{};
-    if (etrain && !ensemble_training_plan(r.plan)) return ForwardRoute{};
+    if (etrain && !ensemble_training_plan(s, r.plan)) return ForwardRoute{};
     // `auto` falls back to the generic family (SRK: its SRK variant) where no MFMA kernel takes the descriptor - but not where the
     // plan made for the whole problem (global_rows) names a kernel this shard cannot run, nor where the plan arrives at a kernel
     // that does not address coeffs by sample group (samples): that is no kernel at all
@@ -269,7 +276,10 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
         // model ensembles: an inference-only forward, no adjoint and nothing to plan - unless SNSDE_FLAG_ENSEMBLE_GRAD opts in.  Then
         // mode 1 exactly where the forward plan is the lean or the general kernel on 4-row tiles (make_plan refuses the others) and the
         // adjoint of ONE member run alone as a shard of the whole is the general MFMA adjoint on 4-row tiles or its SRK form, which
-        // read no coefficients and leave delta planes.  Anything else is no plan (never another kernel, no mode 2)
+        // read no coefficients and leave delta planes.  Under SNSDE_FLAG_ENSEMBLE_NETS_GRAD (ensemble_nets_grad) also where the
+        // forward plan is the wave pairs and the member alone takes the wave-pair adjoint with the weight gradients inside (Euler or
+        // SRK; never its delta-plane variant): each block of the backward workspace then also holds that member's per-tile gradient
+        // blocks (RevPlan::w4_gpart_off).  Anything else is no plan (never another kernel, no mode 2)
         // Sample paths of the ensemble (SNSDE_FLAG_ENSEMBLE_SAMPLES, else refused): SNSDE_FLAG_SAMPLE_GRAD as well - the member alone
         // is then planned as a sampled solve, whose adjoint route asks for these same two adjoints
         if (!samples_ok(s) || (snsde_samples(s) > 1 && !sample_grad(s))) return r;
@@ -279,9 +289,12 @@ static snsde_mfma::BackwardRoute route_backward(const snsde_solve* s, const Snsd
             return r;
         const snsde_solve one = member_alone(s);
         r.fp = make_plan(s, net, hint);
-        if (!ensemble_training_plan(r.fp)) return snsde_mfma::BackwardRoute{};
+        if (!ensemble_training_plan(s, r.fp)) return snsde_mfma::BackwardRoute{};
         r.rp = make_rev_plan(&one, net, r.fp, hint);
-        if (!r.rp.ok || r.rp.FL != 1 || (r.rp.kernel != snsde_mfma::RevKernel::general && r.rp.kernel != snsde_mfma::RevKernel::general_srk))
+        const bool pairs = r.fp.kernel == snsde_mfma::FwdKernel::w4;
+        if (!r.rp.ok || r.rp.FL != 1 ||
+            (pairs ? r.rp.kernel != snsde_mfma::RevKernel::w4_fused || (s->method != SNSDE_EULER && s->method != SNSDE_SRK)
+                   : (r.rp.kernel != snsde_mfma::RevKernel::general && r.rp.kernel != snsde_mfma::RevKernel::general_srk)))
             return snsde_mfma::BackwardRoute{};
         r.members = snsde_members(s);
         size_t g = 0;

@@ -118,10 +118,13 @@ int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t strea
 bool snsde_w4_rev_supported(const snsde_solve* s, const SnsdeNet& net);       // adjoint of the Euler solve on the same wave pairs
 // gpart != null: the weight gradients are accumulated inside the adjoint (per-tile blocks in gpart, snsde_w4_grad_floats floats) and
 // snsde_w4_grad_reduce_launch forms dL/d params from them; no delta planes are written
-int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth_part, float* gpart, hipStream_t stream);
+// members > 1 (SNSDE_FLAG_ENSEMBLE_NETS_GRAD): dth_part / gpart are member 0's, the members' blocks ws_stride floats apart
+// (snsde_member_bws_stride); every block is laid out and indexed as the member run alone lays it out
+int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth_part, float* gpart, hipStream_t stream, int members = 1,
+                        size_t ws_stride = 0);
 size_t snsde_w4_grad_floats(const snsde_solve* s);
 int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* gpart,
-                                const float* dth_part, hipStream_t stream);
+                                const float* dth_part, hipStream_t stream, int members = 1, size_t ws_stride = 0);
 // launchers (snsde_wgrad.hip)
 size_t snsde_wgrad_workspace_floats(const snsde_backward* b, const SnsdeNet& net, int members = 1);      // (members > 1: M blocks of one member's plan)
 int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, float* grad_params,

@@ -789,7 +789,8 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     const int members = r.members > 1 ? r.members : 1;
     const int64_t param_stride = members > 1 ? snsde_param_numel(&s->model) : 0;
     const size_t ws_stride = members > 1 ? r.bws_stride : 0, fws_stride = members > 1 ? r.fws_stride : 0;
-    if (members > 1 && (members > 65535 || p.FL != 1 || (p.kernel != RevKernel::general && p.kernel != RevKernel::general_srk) ||
+    if (members > 1 && (members > 65535 || p.FL != 1 ||
+                        (p.kernel != RevKernel::general && p.kernel != RevKernel::general_srk && p.kernel != RevKernel::w4_fused) ||
                         ws_stride == 0 || ws_stride >= (1ull << 32) || fws_stride == 0 || fws_stride >= (1ull << 32) ||
                         (uint64_t)members * ws_stride >= (1ull << 32) || (uint64_t)members * fws_stride >= (1ull << 32) ||
                         param_stride <= 0 || param_stride >= (1ll << 32) || p.workspace_floats > ws_stride || s->batch % members))
@@ -798,7 +799,8 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
         // the wave-pair adjoint reads the nn.Linear layout of `params` itself (columns of the weights): no fold, no pack launch;
         // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (RevPlan::w4_gpart_off)
         if (!(s->dW_out ? s->dW_out : s->dW) && s->seed_dev) return SNSDE_ERR_NULL;
-        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + p.w4_gpart_off, stream);
+        // (a model ensemble, SNSDE_FLAG_ENSEMBLE_NETS_GRAD: member m's pairs write into block m, ws_stride floats on)
+        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + p.w4_gpart_off, stream, members, ws_stride);
     }
     // first_y = emb[:, 0:H] . linear_in (all columns; the pack step picks the y columns).  A forward that ran with the folded first
     // layer left exactly this product in ITS workspace (piece `in` of snsde_prepare_kernel, same (H, K_in) layout): the pack

@@ -60,9 +60,10 @@ struct W4Args {
     int32_t w_out, b_out;
     int32_t w_n0, b_n0, w_n1, b_n1;       // noise_y[.0] (64, 66) and noise_y.2 (64, 64)
     // model ensembles (snsde_solve::members = M > 1 under SNSDE_FLAG_ENSEMBLE_NETS): the ENS instantiations of the two forward
-    // kernels (inference only) - the member is the launch's second grid axis, m = blockIdx.y, with ceil(member_rows / 8) workgroups
-    // each; its pairs cover rows m member_rows .. and read params + m x param_stride.  One model: the kernels as they were (ENS =
-    // false: these three fields are not read)
+    // kernels (inference; their training forms under SNSDE_FLAG_ENSEMBLE_NETS_GRAD) - the member is the launch's second grid axis, m = blockIdx.y, with
+    // ceil(member_rows / 8) workgroups each; its pairs cover rows m member_rows .. and read params + m x param_stride; every plane
+    // (outputs, training saves) is addressed by the global row with the whole batch's plane stride.  One model: the kernels as they
+    // were (ENS = false: these three fields are not read)
     int32_t members, member_rows;
     uint32_t param_stride;                // floats
 };
@@ -168,13 +169,12 @@ struct CfgW {
 #define W4_T(i)
 #endif
 
-// ENS: the instantiations a model ensemble runs (W4Args::members; inference).  They are instantiations of their own so that the
+// ENS: the instantiations a model ensemble runs (W4Args::members).  They are instantiations of their own so that the
 // one-model kernels stay the code they were, instruction for instruction: folded into one kernel, eleven scalar instructions more in
 // the prologue shifted the step loop's code and the K4 Euler solve with two outputs measured 2 % slower (102.9 -> 105.1 us at 2048
 // rows, two sessions) although no instruction of the loop had changed.
 template <class CF, bool ENS = false>
 __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
-    static_assert(!(ENS && CF::SAVE), "ensembles on the wave pairs are inference only");
 #ifdef W4_TRACE
     float tr_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
     long long tr_last = __builtin_readcyclecounter();
@@ -492,7 +492,6 @@ template <int NHID, bool SAVE> __host__ __device__ constexpr int w4srk_fwd_lds_f
 
 template <class CF, bool ENS = false>      // (ENS: see snsde_w4_euler_kernel)
 __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
-    static_assert(!(ENS && CF::SAVE), "ensembles on the wave pairs are inference only");
     constexpr int H = 64, NHID = CF::NHID, NN = CF::NN;
     constexpr bool TIME = CF::TIME, SAVE = CF::SAVE;
     constexpr int NSAVE = NHID + 2 + 2 * NN, ZSLOT = NHID + 1, NP = 3;
@@ -876,6 +875,11 @@ struct W4RevArgs {
     int64_t row_offset;
     int32_t B, N, T, no, geo, nsave, nslots, adj0_only, off_theta;
     int32_t w_in, k_in, t_in, w_hid[3], w_out, w_n0, w_n1;
+    // model ensembles under SNSDE_FLAG_ENSEMBLE_NETS_GRAD (the ENS instantiations; one model: not read): member m = blockIdx.y owns rows
+    // m member_rows .., reads params + m x param_stride and leaves its theta sums and gradient blocks in block m of the backward
+    // workspace (dth_part / gpart + m x ws_stride), indexed by the tile INSIDE the member - as the member run alone indexes them
+    int32_t member_rows;
+    uint32_t param_stride, ws_stride;     // floats
 };
 
 // FUSED = the weight gradients inside the adjoint (round 5; VERDICT r4 item 4 in the form that fits this layout).  The tile adjoint
@@ -905,8 +909,12 @@ __device__ __forceinline__ void outer64(const float (&in)[4], const float (&dl)[
     (outer4<KQ>(in, dl, acc[KQ]), ...);
 }
 
-template <class CF, bool FUSED>
+// ENS: the instantiations a model ensemble trains through (SNSDE_FLAG_ENSEMBLE_NETS_GRAD; W4RevArgs::member_rows) - of their own, as
+// the forward's are, so that the one-model adjoints stay the code they were.  The member is the second grid axis; the tile, the
+// ragged rule, `live` and the dead surplus pair of an odd tile count are the MEMBER's, the rows and every plane global.
+template <class CF, bool FUSED, bool ENS = false>
 __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_kernel(W4RevArgs a) {
+    static_assert(FUSED || !ENS, "ensembles: the fused adjoint only");
 #ifdef W4_TRACE
     float tr_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
     long long tr_last = __builtin_readcyclecounter();
@@ -934,16 +942,17 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
     float (*xchg)[4][H] = xchg_all[pair];
     float (*zblk)[4][H] = zblk_all[pair];
     const int B = a.B;
-    const int tile = blockIdx.x * 2 + pair;
+    const int tile = blockIdx.x * 2 + pair;                // (ENS: the tile inside member blockIdx.y)
     const int row_t = tile * 4;
-    const int row0 = row_t + 4 <= B ? row_t : B - 4;       // ragged tail: moved back onto the last four rows (see the forward) ...
-    const bool live = row_t < B;                           // (the idle second pair of an odd tile count repeats the last tile)
+    const int rows = ENS ? a.member_rows : B, base = ENS ? (int)blockIdx.y * a.member_rows : 0;
+    const int row0 = base + (row_t + 4 <= rows ? row_t : rows - 4);      // ragged tail: moved back onto the last four rows (see the forward) ...
+    const bool live = row_t < rows;                        // (the idle second pair of an odd tile count repeats the last tile)
     float rowf[4];                                         // ... whose repeated rows must not enter the theta sum twice
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rowf[i] = (live && row0 + i >= row_t) ? 1.0f : 0.0f;
+    for (int i = 0; i < 4; ++i) rowf[i] = (live && row0 + i >= base + row_t) ? 1.0f : 0.0f;
     const uint32_t BH = (uint32_t)B * H;
     const uint32_t SBH = (uint32_t)a.nsave * BH, DBH = (uint32_t)a.nslots * BH;
-    const float* P = a.params;
+    const float* P = ENS ? a.params + (size_t)blockIdx.y * a.param_stride : a.params;      // (wave-uniform, formed once: the prologue's loads)
     typedef const float __attribute__((address_space(4)))* CP;
     const CP step_tab_c = (CP)(uintptr_t)a.step_tab, out_w_c = (CP)(uintptr_t)a.out_w;
     const uint32_t lo = (uint32_t)(row0 * H + lane);
@@ -1125,7 +1134,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
             for (int i = 0; i < 4; ++i) adj[i] += g0[i];
             store4(a.adj, adj);
         }
-        if (a.dth_part && live && lane < 3) a.dth_part[(size_t)tile * 4 + 1 + lane] = 0.0f;
+        if (a.dth_part && live && lane < 3) (a.dth_part + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0))[(size_t)tile * 4 + 1 + lane] = 0.0f;
 #ifdef W4_TRACE
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + 0 * 64 + lane] = v; }
 #endif
@@ -1210,7 +1219,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
         if (a.dth_part) {
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) th_acc += __shfl_down(th_acc, off, 64);
-            if (lane == 0 && live) a.dth_part[(size_t)tile * 4] = th_acc;
+            if (lane == 0 && live) (a.dth_part + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0))[(size_t)tile * 4] = th_acc;
         }
 #ifdef W4_TRACE
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + 1 * 64 + lane] = v; }
@@ -1278,7 +1287,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + wave * 64 + lane] = v; }
 #endif
         if (live && a.gpart) {
-            float* blk = a.gpart + (size_t)tile * w4g_block_floats(NHID, NN);
+            float* blk = a.gpart + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0) + (size_t)tile * w4g_block_floats(NHID, NN);
 #pragma unroll
             for (int g = 0; g < NLG; ++g) {
                 if (g < nl) {
@@ -1326,6 +1335,8 @@ struct W4SrkRevArgs {
     const int32_t* row_out;
     int32_t B, N, T, no, geo, nsave, adj0_only, off_theta;
     int32_t w_in, k_in, t_in, w_hid[3], w_out, w_n0, w_n1;
+    int32_t member_rows;                  // model ensembles (the ENS instantiations): see W4RevArgs
+    uint32_t param_stride, ws_stride;
 };
 
 template <int NHID, int NN, bool MULY = false> __host__ __device__ constexpr int w4srk_rev_lds_floats() {
@@ -1336,7 +1347,7 @@ template <int NHID, int NN, bool MULY = false> __host__ __device__ constexpr int
 //  the state planes they need are twelve / sixteen resident registers the other models do not have room for)
 template <int NHID_, int NN_, bool GEO_, bool MULY_> struct CfgSR { static constexpr int NHID = NHID_, NN = NN_; static constexpr bool GEO = GEO_, MULY = MULY_; };
 
-template <class CF>
+template <class CF, bool ENS = false>      // (ENS: see snsde_w4_euler_reverse_kernel)
 __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevArgs a) {
 #ifdef W4_TRACE
     float tr_acc[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -1369,14 +1380,15 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
     const int B = a.B;
     const int tile = blockIdx.x * 2 + pair;
     const int row_t = tile * 4;
-    const int row0 = row_t + 4 <= B ? row_t : B - 4;
-    const bool live = row_t < B;
+    const int rows = ENS ? a.member_rows : B, base = ENS ? (int)blockIdx.y * a.member_rows : 0;
+    const int row0 = base + (row_t + 4 <= rows ? row_t : rows - 4);
+    const bool live = row_t < rows;
     float rowf[4];
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rowf[i] = (live && row0 + i >= row_t) ? 1.0f : 0.0f;
+    for (int i = 0; i < 4; ++i) rowf[i] = (live && row0 + i >= base + row_t) ? 1.0f : 0.0f;
     const uint32_t BH = (uint32_t)B * H;
     const uint32_t SBH = (uint32_t)a.nsave * BH, PBH = (uint32_t)NP * BH;
-    const float* P = a.params;
+    const float* P = ENS ? a.params + (size_t)blockIdx.y * a.param_stride : a.params;
     typedef const float __attribute__((address_space(4)))* CP;
     const CP step_tab_c = (CP)(uintptr_t)a.step_tab, out_w_c = (CP)(uintptr_t)a.out_w, srk_c = (CP)(uintptr_t)a.srk_tab;
     const uint32_t lo = (uint32_t)(row0 * H + lane);
@@ -1610,7 +1622,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
             for (int i = 0; i < 4; ++i) adj[i] += g0[i];
             store4(a.adj, adj);
         }
-        if (a.dth_part && live && lane < 3) a.dth_part[(size_t)tile * 4 + 1 + lane] = 0.0f;
+        if (a.dth_part && live && lane < 3) (a.dth_part + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0))[(size_t)tile * 4 + 1 + lane] = 0.0f;
 #ifdef W4_TRACE
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + 0 * 64 + lane] = v; }
 #endif
@@ -1747,7 +1759,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
         if (a.dth_part) {
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) th_acc += __shfl_down(th_acc, off, 64);
-            if (lane == 0 && live) a.dth_part[(size_t)tile * 4] = th_acc;
+            if (lane == 0 && live) (a.dth_part + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0))[(size_t)tile * 4] = th_acc;
         }
 #ifdef W4_TRACE
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + 1 * 64 + lane] = v; }
@@ -1834,7 +1846,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
         if (blockIdx.x == 0 && pair == 0 && lane < 12 && !a.adj0_only) { float v = 0; for (int i = 0; i < 12; ++i) v = lane == i ? tr_acc[i] : v; a.adj[uoff(2, BH) + wave * 64 + lane] = v; }
 #endif
         if (live && a.gpart) {
-            float* blk = a.gpart + (size_t)tile * w4g_block_floats(NHID, NN);
+            float* blk = a.gpart + (ENS ? (size_t)blockIdx.y * a.ws_stride : 0) + (size_t)tile * w4g_block_floats(NHID, NN);
 #pragma unroll
             for (int g = 0; g < NLG; ++g) {
                 if (g < nl) {
@@ -1896,6 +1908,61 @@ __global__ void __launch_bounds__(256) snsde_w4_grad_reduce2_kernel(W4GReduce r)
         if (g.kind == 0) r.grad[g.dst + (q & 63) * g.ld + g.col + (q >> 6)] = s;
         else if (g.kind == 1) r.grad[g.dst + q] = s;
         else r.grad[g.dst + q * g.ld + g.col] = s;
+        return;
+    }
+}
+
+// ... of a model ensemble under SNSDE_FLAG_ENSEMBLE_NETS_GRAD: the same two sums with the member on blockIdx.z.  tiles, nsplit, block and
+// n_dth are the member's own, so every sum runs in the order the member alone runs it - on block z of the backward workspace (ms.ws
+// floats apart), of `params` (ms.param) and of `grad` (ms.grad).  Kernels of their own, so that the one-model reductions above stay
+// the code they were (written through a shared body their register allocation moved)
+struct W4GStrides { uint32_t ws, param, grad; };
+__global__ void __launch_bounds__(256) snsde_w4_grad_reduce1_ens_kernel(W4GReduce r, W4GStrides ms) {
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= r.block) return;
+    const size_t mo = (size_t)blockIdx.z * ms.ws;
+    const float* gpart = r.gpart + mo;
+    const int per = (r.tiles + r.nsplit - 1) / r.nsplit, t0 = blockIdx.y * per, t1 = min(t0 + per, r.tiles);
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int t = t0;
+    for (; t + 3 < t1; t += 4) {        // (the association of snsde_w4_grad_reduce1_kernel)
+        s0 += gpart[(size_t)t * r.block + e]; s1 += gpart[(size_t)(t + 1) * r.block + e];
+        s2 += gpart[(size_t)(t + 2) * r.block + e]; s3 += gpart[(size_t)(t + 3) * r.block + e];
+    }
+    for (; t < t1; ++t) s0 += gpart[(size_t)t * r.block + e];
+    (r.part2 + mo)[(size_t)blockIdx.y * r.block + e] = (s0 + s1) + (s2 + s3);
+}
+__global__ void __launch_bounds__(256) snsde_w4_grad_reduce2_ens_kernel(W4GReduce r, W4GStrides ms) {
+    float* grad = r.grad + (size_t)blockIdx.z * ms.grad;
+    const size_t mo = (size_t)blockIdx.z * ms.ws;
+    if (blockIdx.x == gridDim.x - 1) {      // last block: the member's theta from its per-tile sums
+        __shared__ float red[256];
+        const float* dth_part = r.dth_part + mo;
+        float s = 0.0f;
+        for (int i = threadIdx.x; i < r.n_dth; i += 256) s += dth_part[i];
+        red[threadIdx.x] = s;
+        __syncthreads();
+        for (int o = 128; o > 0; o >>= 1) { if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o]; __syncthreads(); }
+        if (threadIdx.x == 0) {
+            const float sg = snsde_sigmoid((r.params + (size_t)blockIdx.z * ms.param)[r.off_theta]);
+            grad[r.off_theta] = red[0] * sg * (1.0f - sg);
+        }
+        return;
+    }
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= r.block) return;
+    const float* part2 = r.part2 + mo;
+    float s = 0.0f;
+    for (int k = 0; k < r.nsplit; ++k) s += part2[(size_t)k * r.block + e];
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+        if (i >= r.nseg) break;
+        const W4GSeg g = r.seg[i];
+        const int len = g.kind == 0 ? 4096 : 64, q = e - g.src;
+        if (q < 0 || q >= len) continue;
+        if (g.kind == 0) grad[g.dst + (q & 63) * g.ld + g.col + (q >> 6)] = s;
+        else if (g.kind == 1) grad[g.dst + q] = s;
+        else grad[g.dst + q * g.ld + g.col] = s;
         return;
     }
 }

@@ -945,7 +945,8 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
     if (r.mode != 1) return SNSDE_ERR_UNSUPPORTED;
     if (rp.kernel == RevKernel::w4_fused) {   // fused weight gradients (snsde_w4_kernel.h): the sums are in the BACKWARD workspace, per tile
         float* bws = static_cast<float*>(b->workspace);
-        return snsde_w4_grad_reduce_launch(b, net, grad_params, n_params, bws + rp.w4_gpart_off, bws + rp.dth_off, stream);
+        return snsde_w4_grad_reduce_launch(b, net, grad_params, n_params, bws + rp.w4_gpart_off, bws + rp.dth_off, stream,
+                                           r.members > 1 ? r.members : 1, r.members > 1 ? r.bws_stride : 0);
     }
     WPlan plan;
     WPlan* wp = &plan;

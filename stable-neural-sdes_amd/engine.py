@@ -223,9 +223,17 @@ def check_ensemble_nets(ensemble_nets):
     return ensemble_nets
 
 
+def check_ensemble_nets_grad(ensemble_nets_grad):
+    """The `ensemble_nets_grad` option (training through a model ensemble on the wave-pair kernels, SNSDE_FLAG_ENSEMBLE_NETS_GRAD;
+    meaningful together with `ensemble_nets` and `ensemble_grad`): a bool, ValueError otherwise."""
+    if not isinstance(ensemble_nets_grad, bool):
+        raise ValueError(f"ensemble_nets_grad must be a bool (differentiate `members` models on the wave-pair kernels), got {ensemble_nets_grad!r}")
+    return ensemble_nets_grad
+
+
 def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                      row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                     members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False):
+                     members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
     """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
     device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
     s = _lib.Solve()
@@ -240,6 +248,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
     s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
     s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
     s.flags |= _lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0
+    s.flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0
     if training:      # (only their presence matters to the query)
         s.traj = s.act_save = C.c_void_p(16)
     s.noise_table = C.c_void_p(16) if table else None
@@ -248,7 +257,7 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
                  row_offset=0, samples=0, lean_general=False, exact_order=False, sample_grad=False, training=False, bf16_grad=False,
-                 members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False):
+                 members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
     """Name of the kernel family a forward solve of this shape takes (_lib.PATHS; host-side query).  global_rows: the rows of the
     whole problem this solve is a batch shard of (the planner then chooses as for that many rows on one device); 0: none.
     samples: Brownian paths per input row (include/snsde.h; `batch` then counts paths); 'none' where the kernel the plan arrives
@@ -258,9 +267,11 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     of all members); 'none' where the plan arrives at a kernel that does not map rows to members.  ensemble_grad:
     SNSDE_FLAG_ENSEMBLE_GRAD - an ensemble has training planes under it only, on the kernels the ensemble adjoint route covers.
     ensemble_samples: SNSDE_FLAG_ENSEMBLE_SAMPLES - members > 1 together with samples > 1 ('none' without it).
-    ensemble_nets: SNSDE_FLAG_ENSEMBLE_NETS - members > 1 on the wave pairs ('w4') and the diffusion-net tiles ('none' without it)."""
+    ensemble_nets: SNSDE_FLAG_ENSEMBLE_NETS - members > 1 on the wave pairs ('w4') and the diffusion-net tiles ('none' without it).
+    ensemble_nets_grad: SNSDE_FLAG_ENSEMBLE_NETS_GRAD - with ensemble_nets and ensemble_grad, training planes of an ensemble on 'w4'."""
     s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
-                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples, ensemble_nets)
+                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples, ensemble_nets,
+                         ensemble_nets_grad)
     return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
 
 
@@ -573,7 +584,7 @@ class SolveCall:
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
                  lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False,
-                 ensemble_samples=False, ensemble_nets=False):
+                 ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -595,6 +606,8 @@ class SolveCall:
         ensemble_samples = bool(ensemble_samples) and M > 1 and S > 1      # (no effect on one model or one path per row)
         # the ensemble on the wave-pair / diffusion-net kernels (SNSDE_FLAG_ENSEMBLE_NETS)
         ensemble_nets = bool(ensemble_nets) and M > 1      # (no effect on one model)
+        # ... and training through it on the wave pairs (SNSDE_FLAG_ENSEMBLE_NETS_GRAD; the library reads it with the other two set)
+        ensemble_nets_grad = bool(ensemble_nets_grad) and M > 1
         if ensemble_samples and (B // M) % S:
             raise ValueError(f'members={members!r}, samples={samples!r}: the {B // M} rows of a member are a whole number of groups of `samples` paths')
         if M > 1 and ((S > 1 and not ensemble_samples) or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
@@ -645,6 +658,8 @@ class SolveCall:
             self.base_flags |= _lib.FLAG_ENSEMBLE_SAMPLES
         if ensemble_nets:
             self.base_flags |= _lib.FLAG_ENSEMBLE_NETS
+        if ensemble_nets_grad:
+            self.base_flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD
         s.flags = self.base_flags
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -669,7 +684,7 @@ class SolveCall:
                         model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
                         dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
                         precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad, ensemble_samples,
-                        ensemble_nets)
+                        ensemble_nets, ensemble_nets_grad)
         self.members = M
         if save_act:
             lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
@@ -741,16 +756,17 @@ def _desc(call_or_desc):
     return call_or_desc.desc if hasattr(call_or_desc, 'desc') else call_or_desc
 
 
-def forward_kernel(call_or_desc, keys=False, ensemble_nets=False):
+def forward_kernel(call_or_desc, keys=False, ensemble_nets=False, ensemble_nets_grad=False):
     """Name of the exact kernel the forward of a SolveCall (or a _lib.Solve descriptor) launches (_lib.FWD_KERNELS: the
     enumerators of csrc/snsde_mfma_kernels.h FwdKernel, 'generic', 'generic_srk' or 'none'); forward_path folds several of them into
     one family.  keys=True: (name, NHID, KUXT) - the plan's keys of the two-tile kernels' instantiation lists, -1 off the MFMA routes.
-    ensemble_nets=True: the answer for the descriptor with SNSDE_FLAG_ENSEMBLE_NETS set (a copy; the descriptor is left alone)."""
+    ensemble_nets=True / ensemble_nets_grad=True: the answer for the descriptor with SNSDE_FLAG_ENSEMBLE_NETS /
+    SNSDE_FLAG_ENSEMBLE_NETS_GRAD set (a copy; the descriptor is left alone)."""
     nhid, kuxt = C.c_int32(), C.c_int32()
     desc = _desc(call_or_desc)
-    if ensemble_nets:
+    if ensemble_nets or ensemble_nets_grad:
         desc = type(desc).from_buffer_copy(desc)
-        desc.flags |= _lib.FLAG_ENSEMBLE_NETS
+        desc.flags |= (_lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0) | (_lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0)
     name = _lib.FWD_KERNELS[_lib.lib().snsde_forward_kernel(C.byref(desc), C.byref(nhid), C.byref(kuxt))]
     return (name, nhid.value, kuxt.value) if keys else name
 
@@ -784,23 +800,27 @@ _SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per c
 
 def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
                   samples=0, sample_grad=False, precision='fp32', bf16_grad=False, members=0, ensemble_grad=False,
-                  ensemble_samples=False):
+                  ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
     """backward_supported for a solve that has not been allocated yet (memoised per configuration); table: the solve
     supplies a noise_table; global_rows: the rows of the whole problem the solve is a batch shard of (0: none); samples: paths
     per input row (`batch` counts paths) - 0 without sample_grad (SNSDE_FLAG_SAMPLE_GRAD).  precision='bf16': 0, or under bf16_grad
     (SNSDE_FLAG_BF16_GRAD) 1 where the bf16 lean kernel runs the forward and the general MFMA adjoint its backward.  members: models
     in the call (`batch` counts the rows of all of them) - 0 without ensemble_grad (SNSDE_FLAG_ENSEMBLE_GRAD), 1 or 0 with it.  members and
-    samples together: 0 unless ensemble_samples (SNSDE_FLAG_ENSEMBLE_SAMPLES), ensemble_grad and sample_grad are all set."""
+    samples together: 0 unless ensemble_samples (SNSDE_FLAG_ENSEMBLE_SAMPLES), ensemble_grad and sample_grad are all set.
+    ensemble_nets / ensemble_nets_grad (SNSDE_FLAG_ENSEMBLE_NETS / SNSDE_FLAG_ENSEMBLE_NETS_GRAD): with ensemble_grad, 1 where the
+    ensemble runs on the wave pairs and each member's adjoint is the fused wave-pair adjoint; without all three, as above."""
     members = int(members) if members and int(members) > 1 else 0
     ensemble_grad = bool(ensemble_grad) and members > 1
     samples = int(samples) if samples and int(samples) > 1 else 0
     sample_grad = bool(sample_grad) and samples > 1
     ensemble_samples = bool(ensemble_samples) and members > 1 and samples > 1
+    ensemble_nets = bool(ensemble_nets) and members > 1
+    ensemble_nets_grad = bool(ensemble_nets_grad) and members > 1
     pflags = precision_flags(precision, bf16_grad)
     key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
            model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
            model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad,
-           pflags, members, ensemble_grad, ensemble_samples)
+           pflags, members, ensemble_grad, ensemble_samples, ensemble_nets, ensemble_nets_grad)
     hit = _MODE_CACHE.get(key)
     if hit is None:
         s = _lib.Solve()
@@ -811,6 +831,8 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
         s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0) | pflags
         s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
         s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
+        s.flags |= _lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0
+        s.flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0
         s.members = members
         s.samples = samples
         s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)

@@ -358,7 +358,8 @@ class Ensemble(nn.Module):
     (M, B S, ..) - equal to the M wrapper calls with options={'samples': S, 'row_offset': m B S, 'global_rows': M B S}.
     options={'ensemble_nets': True} passes through unchanged as well: members whose field has a diffusion net (noise_option 14 / 15 /
     18 / 19) then take the fused solve on the wave-pair / diffusion-net kernels in eval(); in train() under autograd (with
-    'ensemble_grad') they run the M differentiable solves, as without the option."""
+    'ensemble_grad') they run the M differentiable solves, as without the option - unless 'ensemble_nets_grad': True is passed as
+    well: members on the wave pairs (H = 64, Euler / SRK) then train through one fused forward and one fused backward per step."""
 
     KINDS = ()      # (the three wrapper classes: filled below, once they are all defined)
 

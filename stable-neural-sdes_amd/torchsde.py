@@ -438,7 +438,15 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     at H = 128 or with a wide control path).  Without it those plans keep the loop of M calls (engine.forward_path(..., members=M)
     == 'none'); with it engine.forward_path(..., members=M, ensemble_nets=True) decides, and the contract is the one above, bit for
     bit, `samples` with ensemble_samples included.  Inference only: under autograd (with ensemble_grad) such an ensemble runs the M
-    differentiable sdeint calls, as every plan without a fused adjoint does.  A bool, ValueError otherwise; no effect elsewhere."""
+    differentiable sdeint calls, as every plan without a fused adjoint does.  A bool, ValueError otherwise; no effect elsewhere.
+
+    options={'ensemble_nets': True, 'ensemble_grad': True, 'ensemble_nets_grad': True} (SNSDE_FLAG_ENSEMBLE_NETS_GRAD) opts in to
+    training through such an ensemble on the wave pairs (H = 64, Euler / SRK): where engine.backward_mode(..., members=M,
+    ensemble_grad=True, ensemble_nets=True, ensemble_nets_grad=True) == 1 the one fused node runs - one training forward and one
+    snsde_backward_with_gradients for all members, block m of the gradient to member m's parameters, bit for bit the member's own
+    differentiable sdeint at row_offset + m B.  Everywhere else (the diffusion-net 4-row tiles, `samples`, coefficients that require
+    grad, ...) the M differentiable calls run as above and `strict` raises.  ensemble_nets_grad without ensemble_nets and
+    ensemble_grad raises ValueError (it names the missing option); a bool, ValueError otherwise."""
     sdes = list(sdes)
     M = len(sdes)
     if M < 1:
@@ -463,6 +471,12 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     ensemble_samples = ensemble_samples and S > 1      # (no effect on one path per row)
     ensemble_grad = engine.check_ensemble_grad(options.pop('ensemble_grad')) if 'ensemble_grad' in options else False
     ensemble_nets = engine.check_ensemble_nets(options.pop('ensemble_nets')) if 'ensemble_nets' in options else False
+    ensemble_nets_grad = engine.check_ensemble_nets_grad(options.pop('ensemble_nets_grad')) if 'ensemble_nets_grad' in options else False
+    if ensemble_nets_grad:
+        missing = [n for n, on in (('ensemble_nets', ensemble_nets), ('ensemble_grad', ensemble_grad)) if not on]
+        if missing:
+            raise ValueError("ensemble_nets_grad=True (training through an ensemble on the wave-pair kernels) also needs "
+                             + " and ".join(f"options={{'{n}': True}}" for n in missing))
     if ensemble_samples:      # (sample_grad is this route's own option then; everywhere else it stays the conflict it was)
         sample_grad = engine.check_sample_grad(options.pop('sample_grad')) if 'sample_grad' in options else False
     else:
@@ -564,14 +578,15 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
         # the ensemble adjoint route (mode 1 with delta planes for every member), or the M differentiable solves
         if precision != 'fp32' or engine.backward_mode(model, M * B, L, grid, method, kernel, exact_order, global_rows=global_rows,
                                                        members=M, ensemble_grad=True, samples=S if ensemble_samples else 0,
-                                                       sample_grad=ensemble_samples, ensemble_samples=ensemble_samples) != 1:
+                                                       sample_grad=ensemble_samples, ensemble_samples=ensemble_samples,
+                                                       ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad) != 1:
             return loop('no fused adjoint plans this ensemble')
         pidxs = [engine.param_index(sde, r[1]) for sde, r in zip(sdes, recs)]
         counts = [len(p.params) for p in pidxs]
         eopt = _EnsembleOptions(kernel=kernel, exact_order=exact_order, param_pass=options.get('param_pass', 'hip'), row_offset=row_offset,
                                 global_rows=global_rows, seed=options['seed'],
                                 row_out=None if row_out is None else _device_row_out(options, dev).repeat(M),
-                                samples=S if ensemble_samples else 0)
+                                samples=S if ensemble_samples else 0, ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad)
         ys = _FusedEnsembleSolve.apply(sdes, recs, coeffs.detach().to(device=dev, dtype=torch.float32).contiguous(), grid, method, eopt,
                                        counts, y0, *[p for pi in pidxs for p in pi.params])
         return ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
@@ -594,7 +609,8 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
 
 
 # What the fused ensemble node reads from `options`, resolved once by sdeint_ensemble
-_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out', 'samples'))
+_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out', 'samples',
+                                                               'ensemble_nets', 'ensemble_nets_grad'))
 
 
 class _FusedEnsembleSolve(torch.autograd.Function):
@@ -617,7 +633,8 @@ class _FusedEnsembleSolve(torch.autograd.Function):
         call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=opt.seed, row_offset=opt.row_offset, kernel=opt.kernel,
                                 save_traj=True, save_dW=keep_dw, save_act=True, exact_order=opt.exact_order, row_out=opt.row_out,
                                 global_rows=opt.global_rows, members=M, ensemble_grad=True, samples=opt.samples,
-                                sample_grad=opt.samples > 1, ensemble_samples=opt.samples > 1)
+                                sample_grad=opt.samples > 1, ensemble_samples=opt.samples > 1, ensemble_nets=opt.ensemble_nets,
+                                ensemble_nets_grad=opt.ensemble_nets_grad)
         ys = call.launch()
         ctx.call, ctx.sdes, ctx.layouts, ctx.counts = call, sdes, [r[1] for r in recs], counts
         ctx.param_pass, ctx.y0_shape, ctx.y0_dtype = opt.param_pass, tuple(y0.shape), y0.dtype
