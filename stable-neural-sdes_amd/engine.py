@@ -5,6 +5,9 @@ libsnsde.so (HIP).  Nothing here falls back to CPU math.
 """
 import os
 import ctypes as C
+import collections
+import functools
+import struct
 from collections import OrderedDict
 
 import numpy as np
@@ -161,13 +164,6 @@ def precision_flags(precision, bf16_grad=False):
     return _lib.FLAG_BF16_OPERANDS | (_lib.FLAG_BF16_GRAD if bf16_grad else 0)
 
 
-def check_bf16_grad(bf16_grad):
-    """The `bf16_grad` option (training through the bf16-operand forward, SNSDE_FLAG_BF16_GRAD): a bool, ValueError otherwise."""
-    if not isinstance(bf16_grad, bool):
-        raise ValueError(f"bf16_grad must be a bool (differentiate a precision='bf16' solve), got {bf16_grad!r}")
-    return bf16_grad
-
-
 def resolve_global_rows(global_rows, batch, row_offset=0):
     """The `global_rows` of a descriptor (include/snsde.h) from what a caller passed: None / 0 = this call is the whole problem;
     'world' = world_size x the local batch under an initialised process group (equal shards), else the local batch; an integer =
@@ -194,41 +190,103 @@ def check_samples(samples):
     return samples
 
 
-def check_sample_grad(sample_grad):
-    """The `sample_grad` option (training through sample paths, SNSDE_FLAG_SAMPLE_GRAD): a bool, ValueError otherwise."""
-    if not isinstance(sample_grad, bool):
-        raise ValueError(f"sample_grad must be a bool (differentiate a solve of `samples` paths per input row), got {sample_grad!r}")
-    return sample_grad
+def _check_bool_option(name, value, what):
+    """An opt-in switch of a solve: a bool, ValueError otherwise."""
+    if not isinstance(value, bool):
+        raise ValueError(f"{name} must be a bool ({what}), got {value!r}")
+    return value
 
 
-def check_ensemble_grad(ensemble_grad):
-    """The `ensemble_grad` option (training through a model ensemble, SNSDE_FLAG_ENSEMBLE_GRAD): a bool, ValueError otherwise."""
-    if not isinstance(ensemble_grad, bool):
-        raise ValueError(f"ensemble_grad must be a bool (differentiate a solve of `members` models), got {ensemble_grad!r}")
-    return ensemble_grad
+# the opt-ins as sdeint / sdeint_ensemble check them (SNSDE_FLAG_SAMPLE_GRAD, _BF16_GRAD, _ENSEMBLE_GRAD, _ENSEMBLE_SAMPLES,
+# _ENSEMBLE_NETS, _ENSEMBLE_NETS_GRAD - the last meaningful together with ensemble_nets and ensemble_grad)
+check_sample_grad = functools.partial(_check_bool_option, 'sample_grad', what='differentiate a solve of `samples` paths per input row')
+check_bf16_grad = functools.partial(_check_bool_option, 'bf16_grad', what="differentiate a precision='bf16' solve")
+check_ensemble_grad = functools.partial(_check_bool_option, 'ensemble_grad', what='differentiate a solve of `members` models')
+check_ensemble_samples = functools.partial(_check_bool_option, 'ensemble_samples',
+                                           what='`samples` paths per input row for each of `members` models')
+check_ensemble_nets = functools.partial(_check_bool_option, 'ensemble_nets', what='`members` models on the diffusion-net kernels in one solve')
+check_ensemble_nets_grad = functools.partial(_check_bool_option, 'ensemble_nets_grad',
+                                             what='differentiate `members` models on the wave-pair kernels')
+
+_METHODS = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}
+# The one place where an option name meets its SNSDE_FLAG_* bit (the two bf16 bits: precision_flags; SNSDE_FLAG_REUSE_PREPARED is
+# no configuration: SolveCall.launch sets it per launch)
+_FLAG_TABLE = (('exact_order', _lib.FLAG_EXACT_ORDER), ('stream_all', _lib.FLAG_STREAM_ALL), ('two_tile', _lib.FLAG_TWO_TILE),
+               ('lean_general', _lib.FLAG_LEAN_GENERAL), ('sample_grad', _lib.FLAG_SAMPLE_GRAD), ('ensemble_grad', _lib.FLAG_ENSEMBLE_GRAD),
+               ('ensemble_samples', _lib.FLAG_ENSEMBLE_SAMPLES), ('ensemble_nets', _lib.FLAG_ENSEMBLE_NETS),
+               ('ensemble_nets_grad', _lib.FLAG_ENSEMBLE_NETS_GRAD))
+_PRESENT = C.c_void_p(16)      # a pointer of which a host-side query reads the presence only
+_MODEL_INTS = struct.Struct(f'{len(_lib.Model._fields_)}i')
 
 
-def check_ensemble_samples(ensemble_samples):
-    """The `ensemble_samples` option (sample paths of a model ensemble, SNSDE_FLAG_ENSEMBLE_SAMPLES): a bool, ValueError otherwise."""
-    if not isinstance(ensemble_samples, bool):
-        raise ValueError(f"ensemble_samples must be a bool (`samples` paths per input row for each of `members` models), got {ensemble_samples!r}")
-    return ensemble_samples
+def _option_flags(is_set):
+    """The SNSDE_FLAG_* bits of the _FLAG_TABLE switches that `is_set(name)` holds for."""
+    return sum(bit for name, bit in _FLAG_TABLE if is_set(name))
 
 
-def check_ensemble_nets(ensemble_nets):
-    """The `ensemble_nets` option (a model ensemble on the wave-pair and diffusion-net kernels, SNSDE_FLAG_ENSEMBLE_NETS): a bool,
-    ValueError otherwise."""
-    if not isinstance(ensemble_nets, bool):
-        raise ValueError(f"ensemble_nets must be a bool (`members` models on the diffusion-net kernels in one solve), got {ensemble_nets!r}")
-    return ensemble_nets
+class SolveConfig(collections.namedtuple('SolveConfig', (
+        'model', 'batch', 'knots', 'n_steps', 'n_out', 'method', 'kernel', 'precision', 'exact_order', 'stream_all', 'two_tile', 'lean_general',
+        'sample_grad', 'bf16_grad', 'ensemble_grad', 'ensemble_samples', 'ensemble_nets', 'ensemble_nets_grad', 'samples', 'members',
+        'global_rows', 'dW', 'noise_table', 'row_out', 'seed_dev', 'training', 'kl_column'))):
+    """Everything the library's plan reads of a solve, and nothing else: hashable, so it is also the key of every memo of a
+    host-side query.  model: the ten integers of _lib.Model; samples / members: 0, or > 1; dW .. training: the presence of what the
+    plan looks at (supplied increments, the noise table, the per-row output selection, a device-resident seed, the training planes).
+    Built by `SolveConfig.of`, which normalises (`replace` goes through it again).  Not in it: row_offset (no plan reads it, and the
+    members of an ensemble's loop route would each get an entry of their own) and the value of the seed."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, model, batch, knots, n_steps, n_out=2, method='euler', kernel='auto', precision='fp32', exact_order=False,
+           stream_all=False, two_tile=False, lean_general=False, sample_grad=False, bf16_grad=False, ensemble_grad=False,
+           ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False, samples=0, members=0, global_rows=0, dW=False,
+           noise_table=False, row_out=False, seed_dev=False, training=False, kl_column=None):
+        """The normalised record: samples / members are 0 unless > 1, and an opt-in that means nothing without its carrier is
+        dropped (sample_grad: samples > 1; the ensemble_*: members > 1, ensemble_samples also samples > 1; bf16_grad:
+        precision='bf16').  KeyError for an unknown method or kernel, ValueError for an unknown precision."""
+        _METHODS[method], _lib.KERNELS[kernel], precision in PRECISIONS or precision_flags(precision)
+        samples, members = int(samples or 0), int(members or 0)
+        sampled, ensemble = samples > 1, members > 1
+        if not isinstance(model, tuple):
+            model = _MODEL_INTS.unpack(model)
+        return cls(model, batch, knots, n_steps, n_out, method, kernel, precision, bool(exact_order), bool(stream_all), bool(two_tile),
+                   bool(lean_general), sampled and bool(sample_grad), precision == 'bf16' and bool(bf16_grad), ensemble and bool(ensemble_grad),
+                   ensemble and sampled and bool(ensemble_samples), ensemble and bool(ensemble_nets), ensemble and bool(ensemble_nets_grad),
+                   samples if sampled else 0, members if ensemble else 0, int(global_rows), bool(dW), bool(noise_table), bool(row_out),
+                   bool(seed_dev), bool(training), None if kl_column is None else int(kl_column))
+
+    def replace(self, **changes):
+        """This record with `changes`, normalised again."""
+        return SolveConfig.of(**dict(self._asdict(), **changes))
+
+    @property
+    def flags(self):
+        """The descriptor's flags: precision_flags and the _FLAG_TABLE bits of the switches."""
+        return precision_flags(self.precision, self.bf16_grad) | _option_flags(self.__getattribute__)
 
 
-def check_ensemble_nets_grad(ensemble_nets_grad):
-    """The `ensemble_nets_grad` option (training through a model ensemble on the wave-pair kernels, SNSDE_FLAG_ENSEMBLE_NETS_GRAD;
-    meaningful together with `ensemble_nets` and `ensemble_grad`): a bool, ValueError otherwise."""
-    if not isinstance(ensemble_nets_grad, bool):
-        raise ValueError(f"ensemble_nets_grad must be a bool (differentiate `members` models on the wave-pair kernels), got {ensemble_nets_grad!r}")
-    return ensemble_nets_grad
+def _describe(config, row_offset=0, planes=True):
+    """The _lib.Solve of a SolveConfig: every configuration field, and _PRESENT in each pointer whose presence the plan reads.
+    The one place a plan descriptor is made - a query asks with it as it is, SolveCall then writes its buffers over the
+    placeholders.  row_offset: written where the caller has one (no plan reads it).  planes=False leaves the training planes
+    null (SolveCall asks for its save layout before it has allocated them)."""
+    s = _lib.Solve()
+    s.model = _lib.Model(*config.model)
+    s.batch, s.knots, s.n_steps, s.n_out = config.batch, config.knots, config.n_steps, config.n_out
+    s.method, s.kernel, s.flags = _METHODS[config.method], _lib.KERNELS[config.kernel], config.flags
+    s.row_offset, s.global_rows, s.samples, s.members = int(row_offset), config.global_rows, config.samples, config.members
+    if config.training and planes:
+        s.traj = s.act_save = _PRESENT
+    if config.dW:
+        s.dW = _PRESENT
+    if config.noise_table:
+        s.noise_table = _PRESENT
+    if config.row_out:
+        s.row_out = _PRESENT
+    if config.seed_dev:
+        s.seed_dev = _PRESENT
+    if config.kl_column is not None:
+        s.kl_column1 = config.kl_column + 1
+    return s
 
 
 def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
@@ -236,23 +294,11 @@ def query_descriptor(model, batch, knots, n_steps, method='euler', kernel='auto'
                      members=0, ensemble_grad=False, ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
     """The _lib.Solve descriptor of a solve that has not been allocated, as the host-side queries of the library read it (no
     device pointer is real): what forward_path asks about, and what forward_kernel / _lib.lib().snsde_workspace_bytes take."""
-    s = _lib.Solve()
-    s.model = model
-    s.batch, s.knots, s.n_steps, s.n_out = int(batch), int(knots), int(n_steps), 2
-    s.row_offset, s.global_rows, s.samples = int(row_offset), int(global_rows), int(samples)
-    s.members = int(members)
-    s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
-    s.kernel = _lib.KERNELS[kernel]
-    s.flags = precision_flags(precision, bf16_grad) | (_lib.FLAG_LEAN_GENERAL if lean_general else 0) | (_lib.FLAG_EXACT_ORDER if exact_order else 0)
-    s.flags |= _lib.FLAG_SAMPLE_GRAD if sample_grad else 0
-    s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
-    s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
-    s.flags |= _lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0
-    s.flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0
-    if training:      # (only their presence matters to the query)
-        s.traj = s.act_save = C.c_void_p(16)
-    s.noise_table = C.c_void_p(16) if table else None
-    return s
+    return _describe(SolveConfig.of(model, batch, knots, n_steps, 2, method, kernel, precision, exact_order=exact_order,
+                                    lean_general=lean_general, sample_grad=sample_grad, bf16_grad=bf16_grad, ensemble_grad=ensemble_grad,
+                                    ensemble_samples=ensemble_samples, ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad,
+                                    samples=samples, members=members, global_rows=global_rows, noise_table=table, training=training),
+                     row_offset)
 
 
 def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, precision='fp32', global_rows=0,
@@ -269,10 +315,7 @@ def forward_path(model, batch, knots, n_steps, method='euler', kernel='auto', ta
     ensemble_samples: SNSDE_FLAG_ENSEMBLE_SAMPLES - members > 1 together with samples > 1 ('none' without it).
     ensemble_nets: SNSDE_FLAG_ENSEMBLE_NETS - members > 1 on the wave pairs ('w4') and the diffusion-net tiles ('none' without it).
     ensemble_nets_grad: SNSDE_FLAG_ENSEMBLE_NETS_GRAD - with ensemble_nets and ensemble_grad, training planes of an ensemble on 'w4'."""
-    s = query_descriptor(model, batch, knots, n_steps, method, kernel, table, precision, global_rows, row_offset, samples, lean_general,
-                         exact_order, sample_grad, training, bf16_grad, members, ensemble_grad, ensemble_samples, ensemble_nets,
-                         ensemble_nets_grad)
-    return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(s))]
+    return _lib.PATHS[_lib.lib().snsde_forward_path(C.byref(query_descriptor(**locals())))]
 
 
 def shard_refused(model, batch, knots, n_steps, method='euler', kernel='auto', table=False, global_rows=0, row_offset=0):
@@ -508,8 +551,8 @@ def backward_recompute(call, grad_ys, chunk, stream=None):
         # the chunk reads the parent's increments in place (no second copy: the adjoint takes `dW` where there is no `dW_out`), and
         # its adjoint + weight-gradient pass are one C call
         c = SolveCall(model, flat, coeffs, sub, call.traj[n0], dW=call.dW_out[n0:n1], method=method, kernel='auto',
-                      save_traj=True, save_dW=False, save_act=True, exact_order=bool(call.base_flags & _lib.FLAG_EXACT_ORDER),
-                      global_rows=int(call.desc.global_rows))
+                      save_traj=True, save_dW=False, save_act=True, exact_order=call.config.exact_order,
+                      global_rows=call.config.global_rows)
         c.launch(stream)
         adj, part = backward_with_gradients(c, g, stream=stream, adj0_only=adj0_suffices(c))
         total = part if total is None else total.add_(part)
@@ -601,14 +644,8 @@ class SolveCall:
         M = int(members) if members else 1
         if M < 1 or B % M or (M > 1 and (B // M) % 4):
             raise ValueError(f'members={members!r}: the {B} rows of y0 are those of all members, each a whole number of 4-row tiles')
-        ensemble_grad = bool(ensemble_grad) and M > 1      # (no effect on one model)
         # members and samples together (SNSDE_FLAG_ENSEMBLE_SAMPLES): row m Bm + b S + s, coeffs (Bm / S rows) shared by all members
-        ensemble_samples = bool(ensemble_samples) and M > 1 and S > 1      # (no effect on one model or one path per row)
-        # the ensemble on the wave-pair / diffusion-net kernels (SNSDE_FLAG_ENSEMBLE_NETS)
-        ensemble_nets = bool(ensemble_nets) and M > 1      # (no effect on one model)
-        # ... and training through it on the wave pairs (SNSDE_FLAG_ENSEMBLE_NETS_GRAD; the library reads it with the other two set)
-        ensemble_nets_grad = bool(ensemble_nets_grad) and M > 1
-        if ensemble_samples and (B // M) % S:
+        if M > 1 and S > 1 and ensemble_samples and (B // M) % S:
             raise ValueError(f'members={members!r}, samples={samples!r}: the {B // M} rows of a member are a whole number of groups of `samples` paths')
         if M > 1 and ((S > 1 and not ensemble_samples) or ((save_traj or save_dW or save_act) and not ensemble_grad) or z0_linear is not None or noise_table is not None
                       or kl_column is not None):
@@ -638,29 +675,19 @@ class SolveCall:
         self.traj = torch.empty((grid.N + 1, B, H), device=dev, dtype=torch.float32) if save_traj else None
         self.dW_out = torch.empty((grid.N, B, H), device=dev, dtype=torch.float32) if save_dW else None
         self.act_save = self.stage_save = None
-        s = _lib.Solve()
-        s.model = model
-        s.batch, s.knots, s.n_steps, s.n_out = B, L, grid.N, grid.T
-        s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
-        # (kernel selector, flags and the kind of Philox key BEFORE the layout query below: which adjoint a solve gets - and with it
-        #  whether it needs delta planes at all - depends on them)
-        s.kernel = _lib.KERNELS[kernel]
-        self.base_flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_STREAM_ALL if stream_all else 0) | (_lib.FLAG_TWO_TILE if two_tile else 0)
-        # bf16: inference only (the library refuses training outputs and every backward) unless bf16_grad opts in (SNSDE_FLAG_BF16_GRAD)
-        self.base_flags |= precision_flags(precision, bf16_grad)
-        if lean_general:    # (SNSDE_FLAG_LEAN_GENERAL: the lean kernel's general instantiation; same results bit for bit)
-            self.base_flags |= _lib.FLAG_LEAN_GENERAL
-        if sample_grad and S > 1:      # (SNSDE_FLAG_SAMPLE_GRAD: no effect on one path per row)
-            self.base_flags |= _lib.FLAG_SAMPLE_GRAD
-        if ensemble_grad:
-            self.base_flags |= _lib.FLAG_ENSEMBLE_GRAD
-        if ensemble_samples:
-            self.base_flags |= _lib.FLAG_ENSEMBLE_SAMPLES
-        if ensemble_nets:
-            self.base_flags |= _lib.FLAG_ENSEMBLE_NETS
-        if ensemble_nets_grad:
-            self.base_flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD
-        s.flags = self.base_flags
+        # the record normalises: an opt-in without its carrier (samples > 1, members > 1, precision='bf16') has no effect.  (kernel
+        #  selector, flags and the kind of Philox key go in BEFORE the layout / workspace queries below: which adjoint a solve gets - and
+        #  with it whether it needs delta planes at all - depends on them, on the supplied increments, the noise table, the accumulator
+        #  column and the per-row output selection.)  global_rows: rows of the whole problem this solve is a batch shard of (0: it is the
+        #  whole problem) - what the library plans its kernels from
+        cfg = SolveConfig.of(model, B, L, grid.N, grid.T, method, kernel, precision, exact_order, stream_all, two_tile, lean_general,
+                             sample_grad, bf16_grad, ensemble_grad, ensemble_samples, ensemble_nets, ensemble_nets_grad, S, M,
+                             resolve_global_rows(global_rows, B, row_offset), dW is not None, noise_table is not None, row_out is not None,
+                             torch.is_tensor(seed), bool(save_traj or save_dW or save_act), None if kl_column is None else kl_column[0])
+        # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised by the record
+        self.config = self.cfg_key = cfg
+        s = _describe(cfg, row_offset, planes=False)
+        self.base_flags, self.members = s.flags, M
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
                 raise ValueError('a tensor seed must be a one-element int64 CUDA tensor')
@@ -668,30 +695,16 @@ class SolveCall:
             s.seed_dev = _ptr(seed)
         else:
             s.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
-        # every configuration field the plan looks at goes in BEFORE the layout / workspace queries (which adjoint a solve gets
-        # depends on the supplied increments, the noise table, the accumulator column and the per-row output selection)
         s.dW, s.row_out, s.noise_table = _ptr(dW), _ptr(row_out), _ptr(noise_table)
-        s.row_offset = int(row_offset)
-        # rows of the whole problem this solve is a batch shard of (0: it is the whole problem): what the library plans its kernels from
-        s.global_rows = resolve_global_rows(global_rows, B, row_offset)
-        s.samples = S if S > 1 else 0
-        s.members = M if M > 1 else 0
         if kl_column is not None:     # (column, a, b): path-integral accumulator column with the linear prior drift a y + b (snsde.h)
-            s.kl_column1, s.kl_prior_a, s.kl_prior_b = int(kl_column[0]) + 1, float(kl_column[1]), float(kl_column[2])
-        # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised
-        self.cfg_key = (model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
-                        model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
-                        model.time_feature, B, L, grid.N, grid.T, method, kernel, bool(exact_order), noise_table is not None,
-                        dW is not None, row_out is not None, None if kl_column is None else int(kl_column[0]), torch.is_tensor(seed),
-                        precision, int(s.global_rows), S, bool(sample_grad) and S > 1, bool(bf16_grad) and precision == 'bf16', M, ensemble_grad, ensemble_samples,
-                        ensemble_nets, ensemble_nets_grad)
-        self.members = M
+            s.kl_prior_a, s.kl_prior_b = float(kl_column[1]), float(kl_column[2])
+        self.delta_slots = 0          # (delta planes of the adjoint: snsde_save_layout, solves with save_act)
         if save_act:
-            lay = _SIZE_CACHE.get(('layout',) + self.cfg_key)
+            lay = _SIZE_CACHE.get(('layout', cfg))
             if lay is None:
                 slots, planes, dslots = C.c_int32(), C.c_int32(), C.c_int32()
                 _lib.check(_lib.lib().snsde_save_layout(C.byref(s), C.byref(slots), C.byref(planes), C.byref(dslots)), 'snsde_save_layout')
-                lay = _SIZE_CACHE[('layout',) + self.cfg_key] = (slots.value, planes.value, dslots.value)
+                lay = _SIZE_CACHE[('layout', cfg)] = (slots.value, planes.value, dslots.value)
             nslots, nplanes, self.delta_slots = lay
             passes = 3 * grid.N if method == 'srk' else grid.N      # SRK: three drift passes per step
             self.act_save = torch.empty((passes, nslots, B, H), device=dev, dtype=torch.float32)
@@ -711,9 +724,9 @@ class SolveCall:
         s.stage_save = _ptr(self.stage_save)
         if z0_linear is not None:
             s.z0_weight, s.z0_bias = _ptr(z0_linear[0]), _ptr(z0_linear[1])
-        nbytes = _SIZE_CACHE.get(('fwd',) + self.cfg_key)
+        nbytes = _SIZE_CACHE.get(('fwd', cfg))
         if nbytes is None:
-            nbytes = _SIZE_CACHE[('fwd',) + self.cfg_key] = int(_lib.lib().snsde_workspace_bytes(C.byref(s)))
+            nbytes = _SIZE_CACHE[('fwd', cfg)] = int(_lib.lib().snsde_workspace_bytes(C.byref(s)))
         self.workspace = torch.empty(max(nbytes, 256), device=dev, dtype=torch.uint8)
         s.workspace = _ptr(self.workspace)
         s.workspace_bytes = self.workspace.numel()
@@ -766,7 +779,7 @@ def forward_kernel(call_or_desc, keys=False, ensemble_nets=False, ensemble_nets_
     desc = _desc(call_or_desc)
     if ensemble_nets or ensemble_nets_grad:
         desc = type(desc).from_buffer_copy(desc)
-        desc.flags |= (_lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0) | (_lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0)
+        desc.flags |= _option_flags(dict(ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad).get)
     name = _lib.FWD_KERNELS[_lib.lib().snsde_forward_kernel(C.byref(desc), C.byref(nhid), C.byref(kuxt))]
     return (name, nhid.value, kuxt.value) if keys else name
 
@@ -795,7 +808,7 @@ class _BoundedCache(dict):
 
 
 _MODE_CACHE = _BoundedCache()
-_SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per configuration (SolveCall.cfg_key)
+_SIZE_CACHE = _BoundedCache()      # host-side size queries of the library per configuration (SolveCall.config)
 
 
 def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=False, table=False, kl_column=None, global_rows=0,
@@ -809,38 +822,15 @@ def backward_mode(model, batch, knots, grid, method, kernel='auto', exact_order=
     samples together: 0 unless ensemble_samples (SNSDE_FLAG_ENSEMBLE_SAMPLES), ensemble_grad and sample_grad are all set.
     ensemble_nets / ensemble_nets_grad (SNSDE_FLAG_ENSEMBLE_NETS / SNSDE_FLAG_ENSEMBLE_NETS_GRAD): with ensemble_grad, 1 where the
     ensemble runs on the wave pairs and each member's adjoint is the fused wave-pair adjoint; without all three, as above."""
-    members = int(members) if members and int(members) > 1 else 0
-    ensemble_grad = bool(ensemble_grad) and members > 1
-    samples = int(samples) if samples and int(samples) > 1 else 0
-    sample_grad = bool(sample_grad) and samples > 1
-    ensemble_samples = bool(ensemble_samples) and members > 1 and samples > 1
-    ensemble_nets = bool(ensemble_nets) and members > 1
-    ensemble_nets_grad = bool(ensemble_nets_grad) and members > 1
-    pflags = precision_flags(precision, bf16_grad)
-    key = (table, model.input_channels, model.hidden_channels, model.hidden_hidden_channels, model.num_hidden_layers,
-           model.input_option, model.noise_option, model.activation, model.drift_output, model.diffusion_output,
-           model.time_feature, batch, knots, grid.N, grid.T, method, kernel, exact_order, kl_column, int(global_rows), samples, sample_grad,
-           pflags, members, ensemble_grad, ensemble_samples, ensemble_nets, ensemble_nets_grad)
-    hit = _MODE_CACHE.get(key)
+    # (no lean_general and no training planes: neither moves the adjoint's plan; no row_offset: the caller has checked global_rows
+    #  against it)
+    cfg = SolveConfig.of(model, batch, knots, grid.N, grid.T, method, kernel, precision, exact_order=exact_order, sample_grad=sample_grad,
+                         bf16_grad=bf16_grad, ensemble_grad=ensemble_grad, ensemble_samples=ensemble_samples, ensemble_nets=ensemble_nets,
+                         ensemble_nets_grad=ensemble_nets_grad, samples=samples, members=members, global_rows=global_rows,
+                         noise_table=table, kl_column=kl_column)
+    hit = _MODE_CACHE.get(cfg)
     if hit is None:
-        s = _lib.Solve()
-        s.model = model
-        s.batch, s.knots, s.n_steps, s.n_out = batch, knots, grid.N, grid.T
-        s.method = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}[method]
-        s.kernel = _lib.KERNELS[kernel]
-        s.flags = (_lib.FLAG_EXACT_ORDER if exact_order else 0) | (_lib.FLAG_SAMPLE_GRAD if sample_grad else 0) | pflags
-        s.flags |= _lib.FLAG_ENSEMBLE_GRAD if ensemble_grad else 0
-        s.flags |= _lib.FLAG_ENSEMBLE_SAMPLES if ensemble_samples else 0
-        s.flags |= _lib.FLAG_ENSEMBLE_NETS if ensemble_nets else 0
-        s.flags |= _lib.FLAG_ENSEMBLE_NETS_GRAD if ensemble_nets_grad else 0
-        s.members = members
-        s.samples = samples
-        s.noise_table = C.c_void_p(16) if table else None      # (only its presence matters to the query)
-        if kl_column is not None:
-            s.kl_column1 = int(kl_column) + 1
-        s.global_rows = int(global_rows)      # (the query needs no row_offset: the caller has checked global_rows against it)
-        hit = int(_lib.lib().snsde_backward_supported(C.byref(s)))
-        _MODE_CACHE[key] = hit
+        hit = _MODE_CACHE[cfg] = int(_lib.lib().snsde_backward_supported(C.byref(_describe(cfg))))
     return hit
 
 
@@ -850,6 +840,36 @@ def adj0_suffices(call):
     return not (call.desc.method == _lib.MILSTEIN and call.model.noise_option in (14, 15, 18, 19))
 
 
+def _backward_setup(call, adj=None, delta=None, adj0_only=False, want_delta=False, want_table_grad=False, want_grad=False):
+    """What the three backward entry points share: the _lib.Backward bound to the solve's descriptor (with its base flags) and the
+    buffers it names.  Returns (descriptor, adj, delta, table gradient, parameter gradient):
+      adj    the caller's, else (N + 1, B, H) - (1, B, H) under adj0_only (BWD_ADJ0_ONLY)
+      delta  the caller's, else under want_delta the (passes, delta slots, B, H) planes of snsde_save_layout - None at 0 slots (the
+             adjoint of such a solve sums the weight gradients itself, include/snsde.h)
+      table gradient (want_table_grad: solves with a supplied noise_table)  zeros (N, H); SRK: one row per stage time, (4 N, H)
+      parameter gradient (want_grad)  numel floats; an ensemble: (M, numel)"""
+    dev = call.traj.device
+    b = _lib.Backward()
+    b.fwd = call.desc
+    b.fwd.flags = call.base_flags
+    if adj is None:
+        adj = torch.empty_like(call.traj[:1]) if adj0_only else torch.empty_like(call.traj)
+        b.flags = _lib.BWD_ADJ0_ONLY if adj0_only else 0
+    if delta is None and want_delta and call.delta_slots != 0:
+        passes, _, B, H = call.act_save.shape
+        delta = torch.empty((passes, call.delta_slots, B, H), device=dev, dtype=torch.float32)
+    b.adj, b.delta_save = _ptr(adj), _ptr(delta)
+    tab_grad = grad = None
+    if want_table_grad:
+        rows = call.grid.N * (4 if call.config.method == 'srk' else 1)
+        tab_grad = torch.zeros((rows, call.model.hidden_channels), device=dev, dtype=torch.float32)
+        b.grad_noise_table = _ptr(tab_grad)
+    if want_grad:
+        flat = call.keep[0]
+        grad = torch.empty(tuple(flat.shape) if call.members > 1 else flat.numel(), device=dev, dtype=torch.float32)
+    return b, adj, delta, tab_grad, grad
+
+
 def solve_backward(call, grad_ys, stream=None, save_delta=False, adj0_only=False):
     """Adjoint recursion over a finished training-mode solve (SolveCall with save_traj/save_dW/save_act):
     returns adj (N+1, B, H), adj[n] = dL/dy_n; adj[0] is the gradient w.r.t. y0.  adj0_only (MFMA adjoint kernels, mode 1,
@@ -857,16 +877,8 @@ def solve_backward(call, grad_ys, stream=None, save_delta=False, adj0_only=False
     if call.traj is None:
         raise ValueError('backward needs a solve run with save_traj (and save_act on the MFMA path)')
     _check_f32('grad_ys', grad_ys, tuple(call.ys.shape))
-    b = _lib.Backward()
-    b.fwd = call.desc
-    b.fwd.flags = call.base_flags
-    adj = torch.empty_like(call.traj[:1]) if adj0_only else torch.empty_like(call.traj)
-    b.flags = _lib.BWD_ADJ0_ONLY if adj0_only else 0
-    delta = None
-    if save_delta and call.act_save is not None and getattr(call, 'delta_slots', 1) != 0:      # (passes, delta slots, B, H): snsde_save_layout
-        shp = call.act_save.shape                                                                # (0 slots: the adjoint sums the weight gradients itself)
-        delta = torch.empty((shp[0], getattr(call, 'delta_slots', shp[1]), shp[2], shp[3]), device=call.act_save.device, dtype=torch.float32)
-    b.grad_ys, b.adj, b.delta_save = _ptr(grad_ys), _ptr(adj), _ptr(delta)
+    b, adj, delta, _, _ = _backward_setup(call, adj0_only=adj0_only, want_delta=save_delta and call.act_save is not None)
+    b.grad_ys = _ptr(grad_ys)
     nbytes = _lib.lib().snsde_backward_workspace_bytes(C.byref(b))
     ws = torch.empty(max(nbytes, 256), device=adj.device, dtype=torch.uint8)
     b.workspace, b.workspace_bytes = _ptr(ws), ws.numel()
@@ -881,15 +893,7 @@ def param_gradients(call, adj, delta, stream=None, want_table_grad=False):
     """Flat parameter gradient (the C ABI's layout) of a finished MFMA-path solve + adjoint: snsde_param_gradients
     (split-R MFMA weight-gradient GEMMs, diffusion reductions, first-layer algebra), all on the device.
     want_table_grad (solves with a supplied noise_table): returns (grad, dL/d noise_table (N, H); SRK: (4 N, H))."""
-    b = _lib.Backward()
-    b.fwd = call.desc
-    b.fwd.flags = call.base_flags
-    b.adj, b.delta_save = _ptr(adj), _ptr(delta)
-    tab_grad = None
-    if want_table_grad:
-        rows = call.grid.N * (4 if call.desc.method == _lib.SRK else 1)      # SRK: one row per stage time
-        tab_grad = torch.zeros((rows, call.model.hidden_channels), device=adj.device, dtype=torch.float32)
-        b.grad_noise_table = _ptr(tab_grad)
+    b, _, _, tab_grad, grad = _backward_setup(call, adj=adj, delta=delta, want_table_grad=want_table_grad, want_grad=True)
     bws = call.keep_bwd[0]          # the adjoint's workspace: holds its per-workgroup diffusion-side sums
     b.workspace, b.workspace_bytes = _ptr(bws), bws.numel()
     L = _lib.lib()
@@ -897,8 +901,6 @@ def param_gradients(call, adj, delta, stream=None, want_table_grad=False):
     if nbytes == 0:
         raise NotImplementedError('snsde_param_gradients covers the MFMA-path configurations only')
     ws = torch.empty(nbytes, device=adj.device, dtype=torch.uint8)
-    grad = torch.empty(tuple(call.keep[0].shape) if getattr(call, 'members', 1) > 1 else call.keep[0].numel(),      # (an ensemble: (M, numel))
-                       device=adj.device, dtype=torch.float32)
     stream = torch.cuda.current_stream(adj.device) if stream is None else stream
     _lib.check(L.snsde_param_gradients(C.byref(b), _ptr(grad), _ptr(ws), ws.numel(), C.c_void_p(stream.cuda_stream)),
                'snsde_param_gradients')
@@ -914,23 +916,10 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
         raise ValueError('backward needs a solve run with save_traj and save_act')
     _check_f32('grad_ys', grad_ys, tuple(call.ys.shape))
     dev = call.traj.device
-    b = _lib.Backward()
-    b.fwd = call.desc
-    b.fwd.flags = call.base_flags
-    adj = torch.empty_like(call.traj[:1]) if adj0_only else torch.empty_like(call.traj)
-    b.flags = _lib.BWD_ADJ0_ONLY if adj0_only else 0
-    shp = call.act_save.shape
-    delta = None          # (0 delta slots: the adjoint of this solve sums the weight gradients itself, include/snsde.h)
-    if getattr(call, 'delta_slots', shp[1]) != 0:
-        delta = torch.empty((shp[0], getattr(call, 'delta_slots', shp[1]), shp[2], shp[3]), device=dev, dtype=torch.float32)
-    b.grad_ys, b.adj, b.delta_save = _ptr(grad_ys), _ptr(adj), _ptr(delta)
+    b, adj, delta, tab_grad, grad = _backward_setup(call, adj0_only=adj0_only, want_delta=True, want_table_grad=want_table_grad, want_grad=True)
+    b.grad_ys = _ptr(grad_ys)
     L = _lib.lib()
-    tab_grad = None
-    if want_table_grad:
-        rows = call.grid.N * (4 if call.desc.method == _lib.SRK else 1)      # SRK: one row per stage time
-        tab_grad = torch.zeros((rows, call.model.hidden_channels), device=dev, dtype=torch.float32)
-        b.grad_noise_table = _ptr(tab_grad)
-    key = ('bwd', adj0_only, want_table_grad) + call.cfg_key
+    key = ('bwd', adj0_only, want_table_grad, call.config)
     sizes = _SIZE_CACHE.get(key)
     if sizes is None:
         b.workspace, b.workspace_bytes = C.c_void_p(16), 1 << 40      # (only its presence matters to the size queries)
@@ -941,8 +930,6 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
     ws = torch.empty(sizes[0], device=dev, dtype=torch.uint8)
     b.workspace, b.workspace_bytes = _ptr(ws), ws.numel()
     pws = torch.empty(sizes[1], device=dev, dtype=torch.uint8)
-    grad = torch.empty(tuple(call.keep[0].shape) if getattr(call, 'members', 1) > 1 else call.keep[0].numel(),      # (an ensemble: (M, numel))
-                       device=dev, dtype=torch.float32)
     stream = torch.cuda.current_stream(dev) if stream is None else stream
     _lib.check(L.snsde_backward_with_gradients(C.byref(b), _ptr(grad), _ptr(pws), pws.numel(), C.c_void_p(stream.cuda_stream)),
                'snsde_backward_with_gradients')
@@ -964,7 +951,7 @@ def coeff_gradients(call, adj, delta, stream=None):
     b.delta_save = _ptr(delta)
     coeffs = call.keep[1]
     L = _lib.lib()
-    key = ('cgrad',) + call.cfg_key
+    key = ('cgrad', call.config)
     nbytes = _SIZE_CACHE.get(key)
     if nbytes is None:
         nbytes = _SIZE_CACHE[key] = int(L.snsde_coeff_gradients_workspace_bytes(C.byref(b)))

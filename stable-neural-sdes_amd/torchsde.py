@@ -353,13 +353,12 @@ def _sdeint_samples(sde, y0, ts, bm, method, dt, options, names, S, sample_grad=
         padded = precision == 'fp32' and kernel == 'auto' and engine.padding_plan(model, B * S, L, grid.N, method) is not None
         # (options['recompute'] was refused above; its process-wide equivalent, which the ordinary solve honours, is left: recompute
         #  mode re-runs the forward chunk by chunk on one coefficient row per path, so such a process trains on the replicated route)
+        eng = dict(method=method, kernel=kernel, exact_order=bool(options.get('exact_order', False)), global_rows=int(options['global_rows']),
+                   samples=S)      # (the engine's options of this solve: what both queries are asked with)
         if needs_grad:      # the sampled adjoint route (mode 1 with delta planes), or the replicated differentiable solve below
-            fused = not padded and not _recompute_steps(options) and engine.backward_mode(model, B * S, L, grid, method, kernel, bool(options.get('exact_order', False)),
-                                                        global_rows=int(options['global_rows']), samples=S, sample_grad=True) == 1
+            fused = not padded and not _recompute_steps(options) and engine.backward_mode(model, B * S, L, grid, sample_grad=True, **eng) == 1
         else:
-            fused = not padded and engine.forward_path(model, B * S, L, grid.N, method, kernel, precision=precision,
-                                                       global_rows=int(options['global_rows']), row_offset=row_offset, samples=S,
-                                                       exact_order=bool(options.get('exact_order', False))) != 'none'
+            fused = not padded and engine.forward_path(model, B * S, L, grid.N, precision=precision, row_offset=row_offset, **eng) != 'none'
         if fused:
             try:
                 return _sdeint_hip(sde, rec, y0, ts, bm, method, dt, dict(options, samples=S, sample_grad=needs_grad))
@@ -570,23 +569,22 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     exact_order, lean_general = bool(options.get('exact_order', False)), bool(options.get('lean_general', False))
     L = int(coeffs.shape[1]) + 1
     grid = engine.step_grid(_HostTimes.get(ts), dt, _HostTimes.get(sdes[0].times), dev)
-    if engine.forward_path(model, M * B, L, grid.N, method, kernel, precision=precision, global_rows=global_rows, row_offset=row_offset,
-                           lean_general=lean_general, exact_order=exact_order, members=M, samples=S if ensemble_samples else 0,
-                           ensemble_samples=ensemble_samples, ensemble_nets=ensemble_nets) == 'none':
+    # the engine's options of this solve, built once: the path query, the mode query and the launch all take them
+    eng = dict(method=method, kernel=kernel, precision=precision, exact_order=exact_order, lean_general=lean_general, global_rows=global_rows,
+               members=M, samples=S if ensemble_samples else 0, ensemble_samples=ensemble_samples, ensemble_nets=ensemble_nets)
+    if engine.forward_path(model, M * B, L, grid.N, row_offset=row_offset, **eng) == 'none':
         return loop('the plan arrives at a kernel that does not map rows to members')
     if needs_grad:
         # the ensemble adjoint route (mode 1 with delta planes for every member), or the M differentiable solves
-        if precision != 'fp32' or engine.backward_mode(model, M * B, L, grid, method, kernel, exact_order, global_rows=global_rows,
-                                                       members=M, ensemble_grad=True, samples=S if ensemble_samples else 0,
-                                                       sample_grad=ensemble_samples, ensemble_samples=ensemble_samples,
-                                                       ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad) != 1:
+        # (the training solve: fp32, with its opt-ins and without lean_general, which neither the mode query nor the node passes)
+        train = dict(eng, ensemble_grad=True, sample_grad=ensemble_samples, ensemble_nets_grad=ensemble_nets_grad)
+        del train['lean_general']
+        if precision != 'fp32' or engine.backward_mode(model, M * B, L, grid, **train) != 1:
             return loop('no fused adjoint plans this ensemble')
         pidxs = [engine.param_index(sde, r[1]) for sde, r in zip(sdes, recs)]
         counts = [len(p.params) for p in pidxs]
-        eopt = _EnsembleOptions(kernel=kernel, exact_order=exact_order, param_pass=options.get('param_pass', 'hip'), row_offset=row_offset,
-                                global_rows=global_rows, seed=options['seed'],
-                                row_out=None if row_out is None else _device_row_out(options, dev).repeat(M),
-                                samples=S if ensemble_samples else 0, ensemble_nets=ensemble_nets, ensemble_nets_grad=ensemble_nets_grad)
+        eopt = _EnsembleOptions(engine=train, param_pass=options.get('param_pass', 'hip'), row_offset=row_offset, seed=options['seed'],
+                                row_out=None if row_out is None else _device_row_out(options, dev).repeat(M))
         ys = _FusedEnsembleSolve.apply(sdes, recs, coeffs.detach().to(device=dev, dtype=torch.float32).contiguous(), grid, method, eopt,
                                        counts, y0, *[p for pi in pidxs for p in pi.params])
         return ys.reshape(M, B, -1) if row_out is not None else ys.reshape(grid.T, M, B, -1)
@@ -594,10 +592,7 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
     rows = None if row_out is None else _device_row_out(options, dev).repeat(M)
-    call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=options['seed'], row_offset=row_offset, kernel=kernel,
-                            exact_order=exact_order, row_out=rows, precision=precision, lean_general=lean_general,
-                            global_rows=global_rows, members=M, samples=S if ensemble_samples else 0, ensemble_samples=ensemble_samples,
-                            ensemble_nets=ensemble_nets)
+    call = engine.SolveCall(model, flat, coeffs, grid, y0c, seed=options['seed'], row_offset=row_offset, row_out=rows, **eng)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
@@ -608,14 +603,14 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     return ys.to(y0.dtype)
 
 
-# What the fused ensemble node reads from `options`, resolved once by sdeint_ensemble
-_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('kernel', 'exact_order', 'param_pass', 'row_offset', 'global_rows', 'seed', 'row_out', 'samples',
-                                                               'ensemble_nets', 'ensemble_nets_grad'))
+# What the fused ensemble node reads from `options`, resolved once by sdeint_ensemble: `engine`, the engine's options of the training
+# solve (the keywords its mode query was asked with and its SolveCall takes), and what is no engine configuration
+_EnsembleOptions = collections.namedtuple('_EnsembleOptions', ('engine', 'param_pass', 'row_offset', 'seed', 'row_out'))
 
 
 class _FusedEnsembleSolve(torch.autograd.Function):
     """Differentiable fused solve of M members (options={'ensemble_grad': True}, mode 1 only): forward = ONE training-mode solve
-    with members = M (engine.SolveCall(..., ensemble_grad=True)), backward = ONE snsde_backward_with_gradients (param_pass='split':
+    with members = M (engine.SolveCall(..., **opt.engine): ensemble_grad=True), backward = ONE snsde_backward_with_gradients (param_pass='split':
     the two C calls) whose (M, numel) gradient is handed to each member's parameters block by block.  The increment-keeping rule is
     _FusedSolve.forward's (keep_dw)."""
 
@@ -630,11 +625,8 @@ class _FusedEnsembleSolve(torch.autograd.Function):
         y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
         keep_dw = not (method in ('euler', 'milstein') and not torch.is_tensor(opt.seed) and opt.param_pass in ('hip', 'split')
                        and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
-        call = engine.SolveCall(model, flat, coeffs, grid, y0c, method=method, seed=opt.seed, row_offset=opt.row_offset, kernel=opt.kernel,
-                                save_traj=True, save_dW=keep_dw, save_act=True, exact_order=opt.exact_order, row_out=opt.row_out,
-                                global_rows=opt.global_rows, members=M, ensemble_grad=True, samples=opt.samples,
-                                sample_grad=opt.samples > 1, ensemble_samples=opt.samples > 1, ensemble_nets=opt.ensemble_nets,
-                                ensemble_nets_grad=opt.ensemble_nets_grad)
+        call = engine.SolveCall(model, flat, coeffs, grid, y0c, seed=opt.seed, row_offset=opt.row_offset, save_traj=True, save_dW=keep_dw,
+                                save_act=True, row_out=opt.row_out, **opt.engine)
         ys = call.launch()
         ctx.call, ctx.sdes, ctx.layouts, ctx.counts = call, sdes, [r[1] for r in recs], counts
         ctx.param_pass, ctx.y0_shape, ctx.y0_dtype = opt.param_pass, tuple(y0.shape), y0.dtype
@@ -701,10 +693,11 @@ class _DrawnIncrements:
 
 
 # What a fused solve reads from `options`, resolved once by _sdeint_hip: _FusedSolve.forward and _sdeint_padded take this record
-# and the backward mode decided beside it, never the dict
+# and the backward mode decided beside it, never the dict.  `engine`: the engine's options of the solve - the keywords the mode
+# query is asked with and SolveCall takes (method, kernel, precision, exact_order, global_rows, samples, sample_grad, bf16_grad);
+# the rest is no engine configuration, but for lean_general, which only the sampled node passes on
 _FusedOptions = collections.namedtuple('_FusedOptions', (
-    'kernel', 'precision', 'exact_order', 'save_traj', 'strict', 'param_pass', 'recompute', 'samples', 'sample_grad', 'lean_general',
-    'row_offset', 'global_rows', 'row_out', 'seed', 'bf16_grad'))
+    'engine', 'save_traj', 'strict', 'param_pass', 'recompute', 'lean_general', 'row_offset', 'row_out', 'seed'))
 
 
 def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
@@ -737,48 +730,48 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     row_offset = _row_offset(options, B)
     # options={'global_rows': N | 'world'}: the rows of the whole problem this batch is a shard of - the library then plans its
     # kernels as for N rows on one device, and the shards reproduce the unsharded solve bit for bit (opt-in; default: the local batch)
+    kernel, precision = options.get('kernel', 'auto'), options.get('precision', 'fp32')
+    global_rows = engine.resolve_global_rows(options.get('global_rows'), B, row_offset)
+    bf16_grad = bool(options.get('bf16_grad', False)) and precision == 'bf16'
+    eng = dict(method=method, kernel=kernel, precision=precision, exact_order=bool(options.get('exact_order', False)), global_rows=global_rows,
+               samples=samples, sample_grad=bool(options.get('sample_grad', False)), bf16_grad=bf16_grad)
     opt = _FusedOptions(
-        seed=_philox_key(options, dev), kernel=options.get('kernel', 'auto'), precision=options.get('precision', 'fp32'),
-        exact_order=bool(options.get('exact_order', False)), save_traj=bool(options.get('save_traj', False)),
+        engine=eng, seed=_philox_key(options, dev), save_traj=bool(options.get('save_traj', False)),
         strict=bool(options.get('strict', False)), param_pass=options.get('param_pass', 'hip'), recompute=_recompute_steps(options),
-        samples=samples, sample_grad=bool(options.get('sample_grad', False)), lean_general=bool(options.get('lean_general', False)),
-        row_offset=row_offset, global_rows=engine.resolve_global_rows(options.get('global_rows'), B, row_offset),
-        row_out=_device_row_out(options, dev), bf16_grad=bool(options.get('bf16_grad', False)) and options.get('precision', 'fp32') == 'bf16')
-    if opt.precision == 'bf16':
-        if needs_grad and not opt.bf16_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
+        lean_general=bool(options.get('lean_general', False)), row_offset=row_offset, row_out=_device_row_out(options, dev))
+    if precision == 'bf16':
+        if needs_grad and not bf16_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
             raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad")
-        if opt.save_traj and not (needs_grad and opt.bf16_grad):
+        if opt.save_traj and not (needs_grad and bf16_grad):
             raise ValueError("precision='bf16' is inference only: save_traj is a training output")
-        engine.check_bf16(model, B, L, grid.N, method, opt.kernel)
+        engine.check_bf16(model, B, L, grid.N, method, kernel)
         # training (bf16_grad): the bf16 kernel with the fused MFMA adjoint behind it, or an error - whatever `strict` says, the
         # tensor-op loop cannot round operands and no f32 kernel stands in
-        if needs_grad and engine.backward_mode(model, B, L, grid, method, opt.kernel, opt.exact_order, global_rows=opt.global_rows,
-                                               precision='bf16', bf16_grad=True) != 1:
+        if needs_grad and engine.backward_mode(model, B, L, grid, **eng) != 1:      # (bf16_grad: one path per row, _bf16_grad_conflicts)
             raise ValueError(f"bf16_grad=True does not cover this configuration (hidden_channels={model.hidden_channels}, "
                              f"num_hidden_layers={model.num_hidden_layers}, input_option={model.input_option}, "
-                             f"noise_option={model.noise_option}, method={method!r}, kernel={opt.kernel!r}): no fused adjoint plans "
+                             f"noise_option={model.noise_option}, method={method!r}, kernel={kernel!r}): no fused adjoint plans "
                              "this bf16-operand solve")
-    if engine.shard_refused(model, B, L, grid.N, method, opt.kernel, global_rows=opt.global_rows, row_offset=opt.row_offset):
+    if engine.shard_refused(model, B, L, grid.N, method, kernel, global_rows=global_rows, row_offset=row_offset):
         # the kernel planned for the whole problem cannot run this shard (a wave-pair plan, fewer than four rows): an error with or
         # without `strict` - another kernel or the tensor-op loop would not reproduce the unsharded solve
         raise engine._lib.SnsdeError(engine._lib.SNSDE_ERR_UNSUPPORTED,
-                                     f"global_rows={opt.global_rows}: the kernel planned for the whole problem cannot run this "
+                                     f"global_rows={global_rows}: the kernel planned for the whole problem cannot run this "
                                      f"{B}-row shard")
     # (options['recompute'] alone, not _recompute_steps: its process-wide equivalent moves no model off the padded solve, which
     #  never recomputes)
-    if opt.precision == 'fp32' and opt.kernel == 'auto' and not opt.save_traj and not options.get('recompute') and samples == 1:
+    if precision == 'fp32' and kernel == 'auto' and not opt.save_traj and not options.get('recompute') and samples == 1:
         pad = engine.padding_plan(model, B, L, grid.N, method)
         if pad is not None and coeff_grad:      # (the padded solve's autograd node has no coefficient gradient: the fallback rule)
             _unfused_coeff_grad(sde, f"hidden_channels={model.hidden_channels} (a zero-padded solve)", options)
             return loop()
         # a hidden size without MFMA instantiation: solve the zero-padded model (exact) - in training, where its adjoint is the MFMA one
-        if pad is not None and (not needs_grad or engine.backward_mode(pad[0], B, L, grid, method, global_rows=opt.global_rows) == 1):
+        if pad is not None and (not needs_grad or engine.backward_mode(pad[0], B, L, grid, method, global_rows=global_rows) == 1):
             if z0_lin is not None:
                 y0, z0_lin = _materialise_z0(sde, y0, ts, z0_lin), None
             return _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad)
     if needs_grad:
-        mode = engine.backward_mode(model, B, L, grid, method, opt.kernel, opt.exact_order, global_rows=opt.global_rows,
-                                    samples=samples, sample_grad=opt.sample_grad, precision=opt.precision, bf16_grad=opt.bf16_grad)
+        mode = engine.backward_mode(model, B, L, grid, **eng)
         if samples > 1 and mode != 1:      # (_sdeint_samples asked the same query: the sampled node is mode 1 or not built at all)
             raise engine._lib.SnsdeError(engine._lib.SNSDE_ERR_UNSUPPORTED, f"samples={samples}: no fused adjoint plans this sampled solve")
         if mode == 0 and opt.strict:
@@ -809,16 +802,16 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         _unfused_coeff_grad(sde, what, options)
         return loop()
     flat = engine.flatten_params(sde, layout, numel, dev)
-    call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=opt.seed, row_offset=opt.row_offset,
-                            kernel=opt.kernel, save_traj=opt.save_traj, exact_order=opt.exact_order, dU=dU, row_out=opt.row_out,
+    call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, seed=opt.seed, row_offset=opt.row_offset, save_traj=opt.save_traj, dU=dU,
+                            row_out=opt.row_out,
                             z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
-                            precision=opt.precision, global_rows=opt.global_rows, samples=samples)
+                            **dict(eng, sample_grad=False, bf16_grad=False))      # (inference: the training opt-ins stay off)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
         if samples > 1:              # (the path query accepted this solve: a refusal now is an error, not another route)
             raise
-        if opt.precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
+        if precision == 'bf16':      # (checked above; a refusal here is not answered with an fp32 solve either)
             raise ValueError(f"precision='bf16': the solve was refused ({exc})") from exc
         # a valid request no kernel covers (Milstein with noise_option 7, sqrt(y)): same behaviour as the gradient path, the
         # unfused tensor-op loop, unless strict
@@ -1061,11 +1054,11 @@ def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_g
     widen = lambda t: None if t is None else torch.nn.functional.pad(t, (0, P - H)).contiguous()
     if needs_grad:
         ys = _ComposedSolve.apply(model_p, coeffs, grid, widen(dW), method, opt.seed, opt.row_offset, opt.row_out,
-                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, opt.global_rows)
+                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, opt.engine['global_rows'])
     else:
         call = engine.SolveCall(model_p, flat, coeffs, grid, widen(y0.detach().to(torch.float32)), dW=widen(dW), method=method,
                                 seed=opt.seed, row_offset=opt.row_offset, dU=widen(dU), row_out=opt.row_out,
-                                global_rows=opt.global_rows)
+                                global_rows=opt.engine['global_rows'])
         ys = call.launch().to(y0.dtype)
     return ys[..., :H]
 
@@ -1115,7 +1108,8 @@ class _FusedSolve(torch.autograd.Function):
         dW, dU = increments
         flat = engine.flatten_params(sde, layout, numel, y0.device)
         y0c = y0.detach().to(torch.float32).contiguous()
-        samples = opt.samples if opt.sample_grad else 1      # (sampled training: _sdeint_samples)
+        eng = opt.engine
+        samples = eng['samples'] if eng['sample_grad'] else 1      # (sampled training: _sdeint_samples)
         # recompute mode (_recompute_steps: options={'recompute': steps per chunk} or the environment): keep states and increments only,
         # re-run the forward kernel chunk by chunk inside backward (engine.backward_recompute)
         ctx.recompute = 0
@@ -1131,13 +1125,12 @@ class _FusedSolve(torch.autograd.Function):
         keep_dw = not (save_act and method in ('euler', 'milstein') and not (nets and method == 'milstein')
                        and not torch.is_tensor(opt.seed) and opt.param_pass in ('hip', 'split')
                        and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
-        call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, method=method, seed=opt.seed, row_offset=opt.row_offset,
-                                kernel=opt.kernel, save_traj=True, save_dW=keep_dw, save_act=save_act, exact_order=opt.exact_order,
-                                row_out=opt.row_out, dU=dU, global_rows=opt.global_rows, samples=samples, sample_grad=samples > 1,
+        call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, seed=opt.seed, row_offset=opt.row_offset, save_traj=True,
+                                save_dW=keep_dw, save_act=save_act, row_out=opt.row_out, dU=dU,
                                 lean_general=samples > 1 and opt.lean_general,      # (the sampled route's A/B switch)
-                                precision=opt.precision, bf16_grad=opt.bf16_grad)   # (bf16 reaches here under bf16_grad, mode 1, only)
+                                **dict(eng, samples=samples, sample_grad=samples > 1))   # (bf16 reaches here under bf16_grad, mode 1, only)
         ctx.coeffs_dtype = None if coeffs_src is None else coeffs_src.dtype
-        if coeffs_src is not None and mode == 1 and getattr(call, 'delta_slots', 1) == 0:
+        if coeffs_src is not None and mode == 1 and call.act_save is not None and call.delta_slots == 0:
             raise _NoCoeffGradient()      # (before the launch: _sdeint_hip applies the fallback rule)
         ctx.mode, ctx.method = mode, method
         ctx.param_pass = opt.param_pass
