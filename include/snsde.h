@@ -387,6 +387,25 @@ typedef struct snsde_solve {
 
 SNSDE_API size_t snsde_workspace_bytes(const snsde_solve* s);
 SNSDE_API int    snsde_solve_forward(const snsde_solve* s, void* hip_stream);
+/* Resumable solves: the same solve, drawing its Brownian path from global solver step `step_offset` = n0 on.  Like row_offset and
+ * seed, n0 is a coordinate of the random stream, not a plan input: it is no descriptor field, no planning query reads it and the
+ * route - the kernel snsde_forward_kernel / snsde_lean_variant name for the descriptor - is the same at every offset.
+ * Philox counters: local solver step i of this call draws the normals the library specifies for global step n0 + i - counter
+ * (row_offset + row, (n0 + i) >> 2, col, stream), output element (n0 + i) & 3 - for both streams (0: the increment, 1: the normal of
+ * the SRK space-time Levy area).  Everything else stays local to the call: step_tab, srk_tab, out_step, out_w, noise_table, supplied
+ * dW / dU, traj, dW_out, dU_out and ys are indexed by the local step as in snsde_solve_forward.  With a supplied dW the offset only
+ * moves what is still drawn (under SRK nothing: dU is required then).
+ * Cutting a solve: cut a solve of N steps at 0 = c_0 < c_1 < .. < c_k = N; chunk j gets rows c_j .. c_{j+1} - 1 of the step table
+ * (and of srk_tab), step_offset = c_j, y0 = the state after step c_j - 1, and the same seed, row_offset, global_rows, samples and
+ * members.  Every chunk then reproduces the states of the uncut solve bit for bit, on the same kernel.
+ * snsde_solve_forward(s, st) is snsde_solve_forward_at(s, 0, st): the same launches, the same bits.
+ * SNSDE_ERR_DIMS: step_offset < 0 or step_offset + n_steps > INT32_MAX.  SNSDE_ERR_UNSUPPORTED for step_offset != 0 with act_save or
+ * stage_save (no adjoint regenerates offset increments: a continued solve has no backward) or with z0_weight (a continuation starts
+ * from the caller's state, not from X(ts[0])).  traj, dW_out and dU_out are plain outputs, accepted wherever the offset-0 solve of
+ * the same descriptor accepts them.  Every check is made before the first launch; all other validation and routing is that of
+ * snsde_solve_forward.  The backward entry points take no offset: a descriptor that was run at n0 != 0 must not be handed to them.
+ * Enqueue-only and capturable; the offset is a launch argument and is frozen into a recording. */
+SNSDE_API int    snsde_solve_forward_at(const snsde_solve* s, int64_t step_offset, void* hip_stream);
 /* The initial state of a solve with z0_weight / z0_bias as a launch of its own: y0 (B, H, an OUTPUT as there) = z0_weight .
  * X(ts[0]) + z0_bias, through the device code the forward's prepare launch runs - the same bits.  For callers that need the state
  * a fused z0_weight solve would start from where the solve itself cannot form it (a model ensemble takes the caller's y0 and

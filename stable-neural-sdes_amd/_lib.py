@@ -108,7 +108,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_backward_kernel', 'snsde_readout_head', 'snsde_save_layout',
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_initial_state', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
-           'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward')
+           'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward',
+           'snsde_solve_forward_at')
 
 
 MAX_AFFINE_JOBS = 12
@@ -147,6 +148,7 @@ def lib():
     L.snsde_workspace_bytes.argtypes = [C.POINTER(Solve)]
     L.snsde_workspace_bytes.restype = C.c_size_t
     L.snsde_solve_forward.argtypes = [C.POINTER(Solve), C.c_void_p]
+    L.snsde_solve_forward_at.argtypes = [C.POINTER(Solve), C.c_int64, C.c_void_p]      # (descriptor, step_offset, stream)
     L.snsde_initial_state.argtypes = [C.POINTER(Solve), C.c_void_p]
     L.snsde_spline_evaluate.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float,
                                         C.c_int32, C.c_void_p, C.c_void_p]

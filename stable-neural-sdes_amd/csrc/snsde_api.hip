@@ -563,22 +563,30 @@ size_t snsde_workspace_bytes(const snsde_solve* s) {
     return (f + 64) * sizeof(float);
 }
 
-int snsde_solve_forward(const snsde_solve* s, void* hip_stream) {
+// One launch path for both forward entry points: step_offset = n0 is a stream coordinate (like row_offset and seed), not a plan input -
+// route_forward never sees it; the kernels add it to the local step index at their Philox sites only (include/snsde.h).
+int snsde_solve_forward_at(const snsde_solve* s, int64_t step_offset, void* hip_stream) {
     int rc = validate_solve(s, false);
     if (rc) return rc;
     if (s->kernel < SNSDE_KERNEL_AUTO || s->kernel > SNSDE_KERNEL_MFMA_W4) return SNSDE_ERR_OPTION;
+    if (step_offset < 0 || step_offset + (int64_t)s->n_steps > (int64_t)INT32_MAX) return SNSDE_ERR_DIMS;
+    // a continued solve has no backward (no adjoint regenerates offset increments) and starts from the caller's state
+    if (step_offset != 0 && (s->act_save || s->stage_save || s->z0_weight)) return SNSDE_ERR_UNSUPPORTED;
     if (s->workspace_bytes < snsde_workspace_bytes(s)) return SNSDE_ERR_WORKSPACE;
     SnsdeNet net;
     rc = snsde_build_net(s->model, s->n_steps, &net);
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
+    const int n0 = (int)step_offset;
     const ForwardRoute r = route_forward(s, net);
     if (r.path == SNSDE_PATH_NONE) return SNSDE_ERR_UNSUPPORTED;
-    if (r.plan.ok) return snsde_mfma_launch(s, net, r.plan, st);
+    if (r.plan.ok) return snsde_mfma_launch(s, net, r.plan, st, n0);
     if (s->z0_weight && (rc = snsde_z0_launch(s, st)) != SNSDE_OK) return rc;
-    if (r.path == SNSDE_PATH_GENERIC_SRK) return snsde_srk_launch(s, net, st);
-    return snsde_generic_launch(s, net, st, 0, nullptr, nullptr, nullptr, nullptr);
+    if (r.path == SNSDE_PATH_GENERIC_SRK) return snsde_srk_launch(s, net, st, n0);
+    return snsde_generic_launch(s, net, st, 0, nullptr, nullptr, nullptr, nullptr, n0);
 }
+
+int snsde_solve_forward(const snsde_solve* s, void* hip_stream) { return snsde_solve_forward_at(s, 0, hip_stream); }
 
 int snsde_initial_state(const snsde_solve* s, void* hip_stream) {
     if (!s) return SNSDE_ERR_NULL;

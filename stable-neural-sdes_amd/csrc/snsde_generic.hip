@@ -78,6 +78,7 @@ struct GenericArgs {
     float* eval_g;
     int32_t ldy, ldw, ldx;  // LDS row strides (floats, multiples of 4)
     int32_t samples;        // paths per input row, >= 1 (snsde_solve::samples); the forward kernels read it, the adjoints do not
+    int32_t step_offset = 0;   // resumed solves (snsde_solve_forward_at): local step n draws global step step_offset + n (forward kernels only)
 };
 
 // coeffs row of a path: row / samples (sample paths share their input row's control path)
@@ -255,11 +256,12 @@ __global__ void __launch_bounds__(GT) snsde_generic_kernel(GenericArgs a) {
             float zn[4] = {0.f, 0.f, 0.f, 0.f};
             if (!a.eval_mode && a.dW == nullptr) {
                 // (row, 4-step block, column) -> 4 normals; this kernel recomputes the call each step and keeps z[n&3]
+                const int gn = a.step_offset + n;      // (resumed solves: the global step)
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     float z4[4];
-                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(n >> 2), (uint32_t)(4 * q + e), z4);
-                    zn[e] = (n & 3) == 0 ? z4[0] : (n & 3) == 1 ? z4[1] : (n & 3) == 2 ? z4[2] : z4[3];
+                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(gn >> 2), (uint32_t)(4 * q + e), z4);
+                    zn[e] = (gn & 3) == 0 ? z4[0] : (gn & 3) == 1 ? z4[1] : (gn & 3) == 2 ? z4[2] : z4[3];
                 }
             }
 #pragma unroll
@@ -487,9 +489,10 @@ __global__ void __launch_bounds__(GW) snsde_generic_srk_kernel(SrkArgs sa) {
                 if (a.dW) { dw = a.dW[off]; du = sa.dU[off]; }
                 else {
                     float z4[4], x4[4];
-                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(n >> 2), (uint32_t)j, z4, 0u);
-                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(n >> 2), (uint32_t)j, x4, 1u);
-                    const int k = n & 3;
+                    const int gn = a.step_offset + n;      // (resumed solves: the global step)
+                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(gn >> 2), (uint32_t)j, z4, 0u);
+                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(gn >> 2), (uint32_t)j, x4, 1u);
+                    const int k = gn & 3;
                     dw = (k == 0 ? z4[0] : k == 1 ? z4[1] : k == 2 ? z4[2] : z4[3]) * rdt;
                     const float xi = k == 0 ? x4[0] : k == 1 ? x4[1] : k == 2 ? x4[2] : x4[3];
                     du = h * fmaf(sqrtf(h / 12.0f), xi, 0.5f * dw);
@@ -717,8 +720,9 @@ __global__ void __launch_bounds__(GW) snsde_generic_milnet_kernel(GenericArgs a)
                 if (a.dW) dw = a.dW[(size_t)n * BH + (size_t)row * H + j];
                 else {
                     float z4[4];
-                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(n >> 2), (uint32_t)j, z4);
-                    dw = ((n & 3) == 0 ? z4[0] : (n & 3) == 1 ? z4[1] : (n & 3) == 2 ? z4[2] : z4[3]) * sqh;
+                    const int gn = a.step_offset + n;      // (resumed solves: the global step)
+                    snsde_philox_normal4(a.seed_dev ? *a.seed_dev : a.seed, (uint32_t)(a.row_offset + row), (uint32_t)(gn >> 2), (uint32_t)j, z4);
+                    dw = ((gn & 3) == 0 ? z4[0] : (gn & 3) == 1 ? z4[1] : (gn & 3) == 2 ? z4[2] : z4[3]) * sqh;
                 }
                 if (a.dW_out) a.dW_out[(size_t)n * BH + (size_t)row * H + j] = dw;
             }
@@ -1495,7 +1499,7 @@ int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, si
 }
 
 int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int eval_mode,
-                         const float* eval_y, float* eval_f, float* eval_g, const float* step_row_dev) {
+                         const float* eval_y, float* eval_f, float* eval_g, const float* step_row_dev, int step_offset) {
     const snsde_model& m = s->model;
     float* ws = static_cast<float*>(s->workspace);
     // 1. pack weights (W^T, K padded, time features rotated last)
@@ -1538,6 +1542,7 @@ int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t 
     a.row_offset = s->row_offset;
     a.seed = s->seed; a.seed_dev = s->seed_dev;
     a.samples = snsde_samples(s);
+    a.step_offset = eval_mode ? 0 : step_offset;
     a.eval_mode = eval_mode;
     a.eval_f = eval_f;
     a.eval_g = eval_g;
@@ -1662,7 +1667,7 @@ int snsde_generic_backward_launch(const snsde_backward* b, const SnsdeNet& net, 
     return hipGetLastError() == hipSuccess ? SNSDE_OK : SNSDE_ERR_LAUNCH;
 }
 
-int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream) {
+int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int step_offset) {
     const snsde_model& m = s->model;
     float* ws = static_cast<float*>(s->workspace);
     if (!(s->flags & SNSDE_FLAG_REUSE_PREPARED)) {
@@ -1686,7 +1691,7 @@ int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stre
     a.params = s->params; a.ws = ws; a.coeffs = s->coeffs; a.step_tab = s->step_tab; a.out_step = s->out_step;
     a.out_w = s->out_w; a.y0 = s->y0; a.dW = s->dW; a.ys = s->ys; a.traj = s->traj; a.dW_out = s->dW_out;
     a.row_out = s->row_out; a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.eval_mode = 0; a.eval_f = nullptr; a.eval_g = nullptr;
-    a.samples = snsde_samples(s);
+    a.samples = snsde_samples(s); a.step_offset = step_offset;
     const int H = m.hidden_channels, HH = m.hidden_hidden_channels;
     a.ldy = round4(H + 2);
     const int wmax = 2 * H > HH ? 2 * H : HH;

@@ -86,10 +86,11 @@ inline int32_t snsde_members(const snsde_solve* s) { return s->members > 1 ? s->
 // launchers (snsde_generic.hip)
 int snsde_generic_workspace_floats(const snsde_solve* s, const SnsdeNet& net, size_t* floats);
 int snsde_generic_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int eval_mode,
-                         const float* eval_y, float* eval_f, float* eval_g, const float* step_row_dev);
+                         const float* eval_y, float* eval_f, float* eval_g, const float* step_row_dev, int step_offset = 0);
 bool snsde_generic_backward_supported(const snsde_solve* s);
 int snsde_generic_backward_launch(const snsde_backward* b, const SnsdeNet& net, hipStream_t stream);
-int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
+// step_offset (every forward launcher): snsde_solve_forward_at's n0 - local step i draws the normals of global step n0 + i (snsde.h)
+int snsde_srk_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int step_offset = 0);
 int snsde_time_table_srk_launch(const float* params, const float* srk_tab, float* gt, const SnsdeNet& net, int H, int no,
                                 int n_rows, hipStream_t stream, int members = 1, size_t param_stride = 0, size_t gt_stride = 0);
 // tile-flavour hint of s->kernel (-1: chosen from the batch, 0: 16-row tiles, 1: 4-row tiles, 2: wave pairs), the same for the
@@ -109,12 +110,12 @@ size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net);
 // SNSDE_FLAG_ENSEMBLE_GRAD: `floats` = what the member run alone needs, its 64-float tail included where it has one; rounded up to a
 // multiple of four floats so that every block starts 16-byte aligned (snsde.h: members, the rounding rule of the two queries)
 inline size_t snsde_member_bws_stride(size_t floats_with_tail) { return (floats_with_tail + 3) & ~(size_t)3; }
-int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream);
+int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream, int step_offset = 0);
 int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net);
 bool snsde_w4_config_supported(const snsde_solve* s, const SnsdeNet& net);    // ... whatever the local batch (what a plan for the whole problem asks)
-int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream);
+int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int step_offset = 0);
 bool snsde_w4_rev_supported(const snsde_solve* s, const SnsdeNet& net);       // adjoint of the Euler solve on the same wave pairs
 // gpart != null: the weight gradients are accumulated inside the adjoint (per-tile blocks in gpart, snsde_w4_grad_floats floats) and
 // snsde_w4_grad_reduce_launch forms dL/d params from them; no delta planes are written

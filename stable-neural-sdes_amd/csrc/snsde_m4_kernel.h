@@ -585,14 +585,19 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
 
     // Brownian increment of step i for the owned element (Philox: ZB blocks of 4 steps generated together and parked
     // in this wave's LDS stash; else the supplied increments)
-    auto next_dw = [&](int i, float sqh) -> float {
+    // Resumed solves (MfmaArgs::step_offset = n0): the batches are cut on the GLOBAL step g = n0 + i, and the prologue's call
+    // (`first`, a constant there) fills the batch that contains n0 whatever its phase.  n0 is a kernel argument: g, k and the refill
+    // test stay on the scalar unit like i itself.
+    const int n0 = a.step_offset;
+    auto next_dw = [&](int i, float sqh, auto first) -> float {
         if (__builtin_expect(phx, 1)) {
-            const int k = (int)((uint32_t)i % (uint32_t)(4 * CF::ZB));      // (i >= 0: a mask, not a signed remainder)
-            if (__builtin_expect(k == 0 && !(LEAN_KO(SP) && i > 0), 0)) {
+            const int g = n0 + i;
+            const int k = (int)((uint32_t)g % (uint32_t)(4 * CF::ZB));      // (g >= 0: a mask, not a signed remainder)
+            if (__builtin_expect((k == 0 || first.value) && !(LEAN_KO(SP) && i > 0), 0)) {
                 float zq[4 * CF::ZB];
 #pragma unroll
                 for (int bb = 0; bb < CF::ZB; ++bb)
-                    snsde_philox_normal4(seed, grow, (uint32_t)((i >> 2) + bb), (uint32_t)fo, &zq[4 * bb]);
+                    snsde_philox_normal4(seed, grow, (uint32_t)(((g - k) >> 2) + bb), (uint32_t)fo, &zq[4 * bb]);
 #pragma unroll
                 for (int j = 0; j < 4 * CF::ZB; ++j) zstash[j * 64 + lane] = zq[j];
             }
@@ -636,7 +641,7 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         float dummy = 0.0f;
         vm_wait(dummy, gt_cur);
         store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);     // X(t_0): slot 0 (CfgSpec: the four lanes of an entry store the same value)
-        dw_cur = next_dw(0, g0[6]);
+        dw_cur = next_dw(0, g0[6], std::true_type{});
         if (tab) lean_gload(gt_cur, fo4, gt);
         if constexpr (SP) {      // the pieces of X(t_{1+k}) for the batch of step 0
             const int m = 1 + q < N - 1 ? 1 + q : N - 1;
@@ -763,7 +768,7 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         auto prep = [&]() {
             {
                 const int n1 = more ? n + 1 : n;          // (the last step prefetches its own inputs again: never used)
-                dw_nxt = next_dw(n1, qa[1]);
+                dw_nxt = next_dw(n1, qa[1], std::false_type{});
                 // (the row base is formed on the scalar unit: n1 is an SGPR like n; in VGPRs its 64-bit product costs ~5 VALU per step)
                 if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)(uint32_t)n1 * H);
             }

@@ -227,6 +227,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
     auto dactf = [&](float x) { return __builtin_expect(act_fn != 0, 0) ? swish_grad(x, act_scale) : (x > 0.0f ? 1.0f : 0.0f); };
     const bool geo = a.lean_geo != 0;
     const uint32_t grow = (uint32_t)(a.row_offset + row);
+    const int n0 = a.step_offset;      // resumed solves: the global index of local step 0 (MfmaArgs)
     const uint64_t seed = a.seed_dev ? *a.seed_dev : a.seed;
     const int rslot = a.row_out ? a.row_out[rowc] : -1;
     const bool phx = a.dW == nullptr;
@@ -404,11 +405,11 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
         if constexpr (SRK) {
             if (stage == 0) {
                 if (phx) {
-                    if ((ns & 3) == 0) {
-                        snsde_philox_normal4(seed, grow, (uint32_t)(ns >> 2), (uint32_t)fcol, sk_z, 0u);
-                        snsde_philox_normal4(seed, grow, (uint32_t)(ns >> 2), (uint32_t)fcol, sk_x, 1u);
+                    const int gs = n0 + ns, k = gs & 3;      // global step (resumed solves); the first step fills its block whatever its phase
+                    if (k == 0 || n == 0) {
+                        snsde_philox_normal4(seed, grow, (uint32_t)(gs >> 2), (uint32_t)fcol, sk_z, 0u);
+                        snsde_philox_normal4(seed, grow, (uint32_t)(gs >> 2), (uint32_t)fcol, sk_x, 1u);
                     }
-                    const int k = ns & 3;
                     const float zz = k == 0 ? sk_z[0] : (k == 1 ? sk_z[1] : (k == 2 ? sk_z[2] : sk_z[3]));
                     const float xi = k == 0 ? sk_x[0] : (k == 1 ? sk_x[1] : (k == 2 ? sk_x[2] : sk_x[3]));
                     sk_dw = zz * sqh;
@@ -421,8 +422,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
             dw = sk_dw;
         } else {
             if (phx) {
-                if ((n & 3) == 0) snsde_philox_normal4(seed, grow, (uint32_t)(n >> 2), (uint32_t)fcol, sk_z, 0u);
-                const int k = n & 3;
+                const int gn = n0 + n, k = gn & 3;      // global step (resumed solves); the first step fills its block whatever its phase
+                if (k == 0 || n == 0) snsde_philox_normal4(seed, grow, (uint32_t)(gn >> 2), (uint32_t)fcol, sk_z, 0u);
                 dw = (k == 0 ? sk_z[0] : (k == 1 ? sk_z[1] : (k == 2 ? sk_z[2] : sk_z[3]))) * sqh;
             } else {
                 dw = a.dW[(size_t)n * BH + goff];

@@ -298,13 +298,16 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_kernel(MfmaArgs a) {
     // Brownian increments of step i for the two owned elements: one Philox block per element and four steps, kept in registers
     // (same counters as every other kernel: bit-identical increments)
     // (the normals of four steps live in the wave's LDS stash: the 256-register budget goes to resident weights)
-    auto next_dw = [&](int i, float sqh, float& out0, float& out1) {
+    // (resumed solves: MfmaArgs::step_offset = n0 - the blocks are cut on the global step g = n0 + i; the prologue's call, `first`,
+    //  fills the block / batch that contains n0 whatever its phase; n0 is a kernel argument, so g and the tests stay scalar)
+    const int n0 = a.step_offset;
+    auto next_dw = [&](int i, float sqh, float& out0, float& out1, auto first) {
         if (__builtin_expect(phx, 1)) {
-            const int k = i & 3;
-            if (k == 0) {
+            const int g = n0 + i, k = g & 3;
+            if (k == 0 || first.value) {
                 float z0[4], z1[4];
-                snsde_philox_normal4(seed, grow, (uint32_t)(i >> 2), (uint32_t)fo[0], z0);
-                snsde_philox_normal4(seed, grow, (uint32_t)(i >> 2), (uint32_t)fo[1], z1);
+                snsde_philox_normal4(seed, grow, (uint32_t)(g >> 2), (uint32_t)fo[0], z0);
+                snsde_philox_normal4(seed, grow, (uint32_t)(g >> 2), (uint32_t)fo[1], z1);
 #pragma unroll
                 for (int kk = 0; kk < 4; ++kk) { zst[kk * 64] = z0[kk]; zst[(4 + kk) * 64] = z1[kk]; }
             }
@@ -349,7 +352,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_kernel(MfmaArgs a) {
         float du0 = 0.0f, du1 = 0.0f;
         vm_wait_all(du0, du1, gt_cur[0], gt_cur[1]);
         store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);
-        next_dw(0, g0[6], dw_cur[0], dw_cur[1]);
+        next_dw(0, g0[6], dw_cur[0], dw_cur[1], std::true_type{});
         if (tab) { lean_gload(gt_cur[0], fo4[0], gt); lean_gload(gt_cur[1], fo4[1], gt); }
         load_coeffs(__float_as_int(a.step_tab[(size_t)(N > 1 ? 1 : 0) * SNSDE_STEP_STRIDE + 5]));
         vm_wait_all(dw_cur[0], dw_cur[1], gt_cur[0], gt_cur[1]);
@@ -416,7 +419,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_kernel(MfmaArgs a) {
         float dw_nxt[2] = {0.f, 0.f}, gt_nxt[2] = {0.f, 0.f};
         auto prep = [&]() {
             const int n1 = more ? n + 1 : n;
-            next_dw(n1, qa[1], dw_nxt[0], dw_nxt[1]);
+            next_dw(n1, qa[1], dw_nxt[0], dw_nxt[1], std::false_type{});
             if (__builtin_expect(tab, 1)) { lean_gload(gt_nxt[0], fo4[0], gt + (size_t)n1 * H); lean_gload(gt_nxt[1], fo4[1], gt + (size_t)n1 * H); }
         };
         constexpr int OFFA = (8 * LDX + 4 * LDY) * 4, OFFB = OFFA + 4 * LDA * 4;     // bufA / bufB rows from the y rows, bytes

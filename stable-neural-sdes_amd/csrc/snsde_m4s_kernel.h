@@ -115,7 +115,6 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
     const bool phx = a.dW == nullptr;
     const uint32_t grow = (uint32_t)(a.row_offset + row);
     const uint64_t seed = a.seed_dev ? *a.seed_dev : a.seed;
-    const int rslot = a.row_out ? a.row_out[rowc] : -1;
 
     float yv = a.y0[goff];
     ybuf[r * LDY + fo] = yv;
@@ -168,10 +167,13 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
     // Brownian increment of step i: one Philox block gives the element's normals of four consecutive steps, kept in
     // registers (same counters as every other kernel: bit-identical increments)
     float zr[4] = {0.f, 0.f, 0.f, 0.f};
-    auto next_dw = [&](int i, float sqh) -> float {
+    // (resumed solves: MfmaArgs::step_offset = n0 - the blocks are cut on the global step g = n0 + i; the prologue's call, `first`,
+    //  fills the block / batch that contains n0 whatever its phase; n0 is a kernel argument, so g and the tests stay scalar)
+    const int n0 = a.step_offset;
+    auto next_dw = [&](int i, float sqh, auto first) -> float {
         if (__builtin_expect(phx, 1)) {
-            const int k = i & 3;
-            if (k == 0) snsde_philox_normal4(seed, grow, (uint32_t)(i >> 2), (uint32_t)fo, zr);
+            const int g = n0 + i, k = g & 3;
+            if (k == 0 || first.value) snsde_philox_normal4(seed, grow, (uint32_t)(g >> 2), (uint32_t)fo, zr);
             const float z = k == 0 ? zr[0] : (k == 1 ? zr[1] : (k == 2 ? zr[2] : zr[3]));
             return z * sqh;
         }
@@ -213,7 +215,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
         float dummy = 0.0f;
         vm_wait_all(dummy, gt_cur);
         store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);
-        dw_cur = next_dw(0, g0[6]);
+        dw_cur = next_dw(0, g0[6], std::true_type{});
         if (tab) lean_gload(gt_cur, fo4, gt);
         load_coeffs(__float_as_int(a.step_tab[(size_t)(N > 1 ? 1 : 0) * SNSDE_STEP_STRIDE + 5]));
         vm_wait_all(dw_cur, gt_cur);
@@ -275,7 +277,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
         float dw_nxt = 0.0f, gt_nxt = 0.0f;
         auto prep = [&]() {
             const int n1 = more ? n + 1 : n;
-            dw_nxt = next_dw(n1, qa[1]);
+            dw_nxt = next_dw(n1, qa[1], std::false_type{});
             if (__builtin_expect(tab, 1)) lean_gload(gt_nxt, fo4, gt + (size_t)n1 * H);
         };
         constexpr int OFFA = (8 * LDX + 4 * LDY) * 4, OFFB = OFFA + 4 * LDA * 4;     // bufA / bufB rows from the y rows, bytes
@@ -332,7 +334,14 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
         const float w0 = a.out_w[2 * ko], w1 = a.out_w[2 * ko + 1];
         const float o = (w0 == 0.0f) ? yv : snsde_interp_out(w0, w1, yold, yv);
         if (!a.row_out) a.ys[(size_t)(ko + 1) * BH + goff] = o;
-        else if (rslot == ko + 1) a.ys[goff] = o;
+        else {
+            // the row's output slot is read here, once per output, from a row index formed again out of the thread id (opaque to hipcc:
+            // carried across the step loop, either value spills at this kernel's 128 registers)
+            int t = threadIdx.x;
+            asm volatile("" : "+v"(t));
+            const int rw = row0 + (t & 3);
+            if (a.row_out[rw < B ? rw : B - 1] == ko + 1) a.ys[goff] = o;
+        }
     }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the ring's last refills (never consumed) land before the wave ends

@@ -233,16 +233,20 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
 
     // Brownian increments of step i for the two owned elements (Philox: ZB blocks of 4 steps generated together and parked in this
     // wave's LDS stash; else the supplied increments)
-    auto next_dw = [&](int i, float sqh, float& out0, float& out1) {
+    // (resumed solves: MfmaArgs::step_offset = n0 - the blocks are cut on the global step g = n0 + i; the prologue's call, `first`,
+    //  fills the block / batch that contains n0 whatever its phase; n0 is a kernel argument, so g and the tests stay scalar)
+    const int n0 = a.step_offset;
+    auto next_dw = [&](int i, float sqh, float& out0, float& out1, auto first) {
         if (__builtin_expect(phx, 1)) {
-            const int k = i % (4 * CF::ZB);
-            if (__builtin_expect(k == 0, 0)) {
+            const int g = n0 + i;
+            const int k = (int)((uint32_t)g % (uint32_t)(4 * CF::ZB));
+            if (__builtin_expect(k == 0 || first.value, 0)) {
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     float zq[4 * CF::ZB];
 #pragma unroll
                     for (int bb = 0; bb < CF::ZB; ++bb)
-                        snsde_philox_normal4(seed, grow, (uint32_t)((i >> 2) + bb), (uint32_t)fo[j], &zq[4 * bb]);
+                        snsde_philox_normal4(seed, grow, (uint32_t)(((g - k) >> 2) + bb), (uint32_t)fo[j], &zq[4 * bb]);
 #pragma unroll
                     for (int m = 0; m < 4 * CF::ZB; ++m) zst[(j * 4 * CF::ZB + m) * 64] = zq[m];
                 }
@@ -288,7 +292,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
         float du0 = 0.0f, du1 = 0.0f;
         vm_wait(du0, du1, gt_cur[0], gt_cur[1]);
         store_xt(xbuf, g0[4], a.raw_time ? g0[0] : g0[2], a.raw_time ? 0.0f : g0[3]);
-        next_dw(0, g0[6], dw_cur[0], dw_cur[1]);
+        next_dw(0, g0[6], dw_cur[0], dw_cur[1], std::true_type{});
         if (tab) { lean_gload(gt_cur[0], fo4[0], gt); lean_gload(gt_cur[1], fo4[1], gt); }
         load_coeffs(__float_as_int(a.step_tab[(size_t)(N > 1 ? 1 : 0) * SNSDE_STEP_STRIDE + 5]));
         vm_wait(dw_cur[0], dw_cur[1], gt_cur[0], gt_cur[1]);
@@ -360,7 +364,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
         float dw_nxt[2] = {0.f, 0.f}, gt_nxt[2] = {0.f, 0.f};
         auto prep = [&]() {
             const int n1 = more ? n + 1 : n;
-            next_dw(n1, qa[1], dw_nxt[0], dw_nxt[1]);
+            next_dw(n1, qa[1], dw_nxt[0], dw_nxt[1], std::false_type{});
             if (__builtin_expect(tab, 1)) { lean_gload(gt_nxt[0], fo4[0], gt + (size_t)n1 * H); lean_gload(gt_nxt[1], fo4[1], gt + (size_t)n1 * H); }
         };
         uint32_t cur = arow;

@@ -656,7 +656,7 @@ size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net) {
     return f ? ((f + 3) & ~(size_t)3) + 64 : 0;
 }
 
-int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& p, hipStream_t stream) {
+int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan& p, hipStream_t stream, int step_offset) {
     if (!p.ok) return SNSDE_ERR_UNSUPPORTED;
     float* ws = static_cast<float*>(s->workspace);
     // model ensembles: one prepared block per member, M parameter blocks (one model: one block, strides unused)
@@ -671,7 +671,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
     if (w4 && !s->act_save) {
         // inference on the wave-owns-rows kernel: it reads the nn.Linear layout of `params` itself - no packing, no tables
         if (s->z0_weight) { const int rc = snsde_z0_launch(s, stream); if (rc) return rc; }
-        return snsde_w4_launch(s, net, stream);
+        return snsde_w4_launch(s, net, stream, step_offset);
     }
     if (!(s->flags & SNSDE_FLAG_REUSE_PREPARED)) {
         MfmaPackJob job{};
@@ -723,7 +723,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         const int rc = snsde_z0_launch(s, stream);
         if (rc) return rc;
     }
-    if (w4) return snsde_w4_launch(s, net, stream);      // (training: the prepare launch above keeps the workspace as the adjoint expects it)
+    if (w4) return snsde_w4_launch(s, net, stream, step_offset);      // (training: the prepare launch above keeps the workspace as the adjoint expects it)
     MfmaArgs a{};
     a.params = s->params; a.ws = ws; a.coeffs = s->coeffs; a.step_tab = s->step_tab; a.out_step = s->out_step;
     a.out_w = s->out_w; a.y0 = s->y0; a.dW = s->dW; a.ys = s->ys; a.traj = s->traj; a.dW_out = s->dW_out;
@@ -735,7 +735,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
         a.act = s->model.activation; a.f_out = s->model.drift_output; a.g_out = s->model.diffusion_output;
         a.raw_time = s->model.time_feature; a.gt_ext = s->noise_table;       // (N, 4, H): the table at the four stage times
     }
-    a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.samples = snsde_samples(s);
+    a.row_offset = s->row_offset; a.seed = s->seed; a.seed_dev = s->seed_dev; a.samples = snsde_samples(s); a.step_offset = step_offset;
     a.members = members; a.member_rows = members > 1 ? s->batch / members : 0; a.param_stride = (uint32_t)param_stride; a.ws_stride = (uint32_t)ws_stride;
     a.acc_col = s->kl_column1 - 1; a.acc_a = s->kl_prior_a; a.acc_b = s->kl_prior_b;
     a.B = s->batch; a.L = s->knots; a.C = s->model.input_channels; a.N = s->n_steps; a.T = s->n_out;

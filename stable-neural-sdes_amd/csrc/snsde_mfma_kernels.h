@@ -109,6 +109,11 @@ struct MfmaArgs {
     // M > 1; the wave pairs carry the same three fields in W4Args), once per workgroup before the step loop
     int32_t members, member_rows;           // member_rows: rows per member (batch / M; one model: unused, m = 0)
     uint32_t param_stride, ws_stride;       // floats
+    // resumed solves (snsde_solve_forward_at): local step n draws the normals of global step step_offset + n - Philox counter
+    // (row_offset + row, (step_offset + n) >> 2, col, stream), element (step_offset + n) & 3.  Uniform (a kernel argument: scalar unit);
+    // read at the Philox sites only - tables, outputs and saved planes stay indexed by the local step.  A kernel that keeps the normals
+    // of a block (or a batch of blocks) fills, on its first step, the block (batch) that CONTAINS step_offset, whatever its phase
+    int32_t step_offset;
 };
 
 __host__ __device__ constexpr int ld_for(int K, int pad) { return ((K - pad + 63) / 64) * 64 + pad; }
@@ -547,6 +552,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     const uint64_t seed = a.seed_dev ? *a.seed_dev : a.seed;
     const int rslot = a.row_out ? a.row_out[rowc] : -1;     // per-row output selection (ys is (B, H))
     const bool phx = a.dW == nullptr;                       // in-kernel Philox increments (else the supplied ones)
+    const int n0 = a.step_offset;                           // resumed solves: the global index of local step 0 (MfmaArgs)
 
     // store one layer output fragment (bias came in through the accumulator init) as 16 B per lane
     int save_step = 0;   // current step, for the optional activation save
@@ -674,11 +680,11 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
 #pragma unroll
                     for (int e = 0; e < EPT; ++e) {
                         if (phx) {
-                            if ((ns & 3) == 0) {
-                                snsde_philox_normal4(seed, grow, (uint32_t)(ns >> 2), (uint32_t)(fcol[0] + e), sk_z[e], 0u);
-                                snsde_philox_normal4(seed, grow, (uint32_t)(ns >> 2), (uint32_t)(fcol[0] + e), sk_x[e], 1u);
+                            const int gs = n0 + ns, k = gs & 3;      // global step (resumed solves); the first step fills its block whatever its phase
+                            if (k == 0 || n == 0) {
+                                snsde_philox_normal4(seed, grow, (uint32_t)(gs >> 2), (uint32_t)(fcol[0] + e), sk_z[e], 0u);
+                                snsde_philox_normal4(seed, grow, (uint32_t)(gs >> 2), (uint32_t)(fcol[0] + e), sk_x[e], 1u);
                             }
-                            const int k = ns & 3;
                             const float z = k == 0 ? sk_z[e][0] : (k == 1 ? sk_z[e][1] : (k == 2 ? sk_z[e][2] : sk_z[e][3]));
                             const float xi = k == 0 ? sk_x[e][0] : (k == 1 ? sk_x[e][1] : (k == 2 ? sk_x[e][2] : sk_x[e][3]));
                             sk_dw[e] = z * sqh;
@@ -697,15 +703,16 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
             } else if (phx) {
                 // ZB independent Philox calls (ZB blocks of 4 steps) are generated together (their round chains interleave)
                 // and parked in this wave's private LDS stash [4*ZB steps][64 lanes][EPT]; each step reads back one entry.
+                // (resumed solves: batches are cut on the GLOBAL step n0 + n; the first step fills the batch that contains it)
                 constexpr int ZB = CF::ZB;
-                const int k = n % (4 * ZB);
-                if (k == 0) {
+                const int gn = n0 + n, k = (int)((uint32_t)gn % (uint32_t)(4 * ZB));
+                if (k == 0 || n == 0) {
                     float zq[EPT][4 * ZB];
     #pragma unroll
                     for (int e = 0; e < EPT; ++e)
     #pragma unroll
                         for (int bb = 0; bb < ZB; ++bb)
-                            snsde_philox_normal4(seed, grow, (uint32_t)((n >> 2) + bb), (uint32_t)(fcol[0] + e), &zq[e][4 * bb]);
+                            snsde_philox_normal4(seed, grow, (uint32_t)(((gn - k) >> 2) + bb), (uint32_t)(fcol[0] + e), &zq[e][4 * bb]);
     #pragma unroll
                     for (int i = 0; i < 4 * ZB; ++i) {
                         if constexpr (FL) zstash[i * 64 + lane] = zq[0][i];

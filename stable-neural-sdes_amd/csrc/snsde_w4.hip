@@ -128,7 +128,7 @@ static int srk_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* d
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net) { return snsde_w4::shape_ok(s, net); }
 bool snsde_w4_config_supported(const snsde_solve* s, const SnsdeNet& net) { return snsde_w4::config_ok(s, net); }
 
-int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream) {
+int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t stream, int step_offset) {
     using namespace snsde_w4;
     if (!shape_ok(s, net)) return SNSDE_ERR_UNSUPPORTED;
     if (s->method == SNSDE_SRK && (!s->srk_tab || (s->dW && !s->dU))) return SNSDE_ERR_NULL;
@@ -136,7 +136,7 @@ int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t strea
     W4Args a{};
     a.params = s->params; a.step_tab = s->step_tab; a.out_w = s->out_w; a.y0 = s->y0; a.dW = s->dW; a.ys = s->ys; a.traj = s->traj;
     a.dW_out = s->dW_out; a.act_save = s->act_save; a.row_out = s->row_out; a.row_offset = s->row_offset; a.seed = s->seed;
-    a.seed_dev = s->seed_dev;
+    a.seed_dev = s->seed_dev; a.step_offset = step_offset;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
     a.nsave = snsde_act_slots(&m);
     if (const int members = snsde_members(s); members > 1) {

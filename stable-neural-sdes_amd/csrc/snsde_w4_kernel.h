@@ -66,6 +66,9 @@ struct W4Args {
     // were (ENS = false: these three fields are not read)
     int32_t members, member_rows;
     uint32_t param_stride;                // floats
+    // resumed solves (snsde_solve_forward_at): local step n draws the normals of global step step_offset + n; the tables, the outputs
+    // and every saved plane stay indexed by the local step
+    int32_t step_offset;
 };
 
 // the first row of a pair: one model - tile blockIdx.x * 2 + pair, the ragged rule on the last four rows of the batch (see
@@ -249,12 +252,14 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
     // (Measured and dropped: rows 0, 1 refilled by the drift wave - its 245 registers then spill; 2048 rows 113 -> 119 us.)
     const bool phx = a.dW == nullptr;
     const uint64_t seed = a.seed_dev ? *a.seed_dev : a.seed;
-    auto philox_refill = [&](int n) {
-        const int k = n & 3, blk = n >> 2;
+    // Resumed solves (W4Args::step_offset = n0): blocks, rows and parities are those of the GLOBAL step g = n0 + n.  The prologue fills
+    // block n0 >> 2 and the rows of the next block that the steps n0 - (n0 & 3) .. n0 - 1 would have refilled; n0 is uniform.
+    const int n0 = a.step_offset;
+    auto philox_fill = [&](int k, int blk) {      // row k of block blk
         float zz[4];
-        snsde_philox_normal4(seed, (uint32_t)(a.row_offset + row0 + k), (uint32_t)(blk + 1), (uint32_t)lane, zz, 0u);
+        snsde_philox_normal4(seed, (uint32_t)(a.row_offset + row0 + k), (uint32_t)blk, (uint32_t)lane, zz, 0u);
 #pragma unroll
-        for (int e = 0; e < 4; ++e) zstash[(blk + 1) & 1][k][e][lane] = zz[e];
+        for (int e = 0; e < 4; ++e) zstash[blk & 1][k][e][lane] = zz[e];
     };
     if (wave == 0) {
         // ================================ drift wave ================================
@@ -400,14 +405,10 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
         }
         const float sig_theta = snsde_sigmoid(P[a.off_theta]);
         const bool mul_y = a.no == 15 || a.no == 19;
-        if (phx) {       // block 0 (the drift wave's first read of the stash is behind step 0's barrier)
+        if (phx) {       // the first block (the drift wave's first read of the stash is behind step 0's barrier)
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                float zz[4];
-                snsde_philox_normal4(seed, (uint32_t)(a.row_offset + row0 + i), 0u, (uint32_t)lane, zz, 0u);
-#pragma unroll
-                for (int e = 0; e < 4; ++e) zstash[0][i][e][lane] = zz[e];
-            }
+            for (int i = 0; i < 4; ++i) philox_fill(i, n0 >> 2);
+            for (int i = 0; i < (n0 & 3); ++i) philox_fill(i, (n0 >> 2) + 1);
         }
         Row nxt = load_row(0);
         for (int n = 0; n < n_steps; ++n) {
@@ -416,10 +417,10 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
             float dw[4];
             W4_T(0)
             if (phx) {
-                const int k = n & 3, blk = n >> 2;
+                const int k = (n0 + n) & 3, blk = (n0 + n) >> 2;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dw[i] = zstash[blk & 1][i][k][lane] * cur.sqh;
-                philox_refill(n);
+                philox_fill(k, blk + 1);
             } else {
 #pragma unroll
                 for (int i = 0; i < 4; ++i) dw[i] = (a.dW + uoff(n, BH))[lo + (uint32_t)(i * H)];
@@ -708,9 +709,13 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
                 for (int e = 0; e < 4; ++e) zstash[sidx][blk & 1][row_k][e][lane] = zz[e];
             }
         };
+        // (resumed solves, W4Args::step_offset = n0: blocks, rows and parities are those of the global step n0 + n; the prologue fills
+        //  block n0 >> 2 and the rows of the next block that the steps n0 - (n0 & 3) .. n0 - 1 would have refilled)
+        const int n0 = a.step_offset;
         if (phx) {
 #pragma unroll
-            for (int i = 0; i < 4; ++i) refill(i, 0);
+            for (int i = 0; i < 4; ++i) refill(i, n0 >> 2);
+            for (int i = 0; i < (n0 & 3); ++i) refill(i, (n0 >> 2) + 1);
         }
         // one net evaluation at (sn, cs) on the state x: g into `g`; training: the net slots of `pass` (slot0 / slot0 + 1) and the hidden
         // sign word into exchange plane `splane`
@@ -764,7 +769,7 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
             const float rh = 1.0f / h, rsqh = 1.0f / sqh;
             float ik[4], ik0[4];
             if (phx) {
-                const int k = n & 3, blk = n >> 2;
+                const int k = (n0 + n) & 3, blk = (n0 + n) >> 2;
                 const float sh12 = sqrtf(h / 12.0f);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {

@@ -455,6 +455,14 @@ class StepGrid:
             self.d_out_w = torch.from_numpy(self.out_w).to(device)
 
 
+def grid_steps(ts_host, dt):
+    """The number of solver steps of the fixed-step grid over `ts_host` (snsde_grid_count; host only)."""
+    ts32 = np.ascontiguousarray(ts_host, dtype=np.float32)
+    n = C.c_int32()
+    _lib.check(_lib.lib().snsde_grid_count(ts32.ctypes.data, ts32.shape[0], float(dt), C.byref(n)), 'snsde_grid_count')
+    return n.value
+
+
 def sub_grid(grid, n0, n1):
     """The solver steps n0 .. n1-1 of `grid` as a StepGrid of their own: the SAME step rows (times, step sizes, spline
     intervals), the parent's outputs that fall inside, and one more output at the end of the last step.  Returns
@@ -617,6 +625,16 @@ def _check_f32(name, t, shape=None):
         raise ValueError(f'{name} has shape {tuple(t.shape)}, expected {tuple(shape)}')
 
 
+def check_step_offset(step_offset, n_steps=0):
+    """`step_offset` of a resumed solve as a non-negative int whose last global step, step_offset + n_steps, fits 31 bits (the
+    Philox counter word and the library's check); ValueError otherwise."""
+    if isinstance(step_offset, bool) or not isinstance(step_offset, (int, np.integer)) or int(step_offset) < 0:
+        raise ValueError(f'step_offset={step_offset!r}: the global index of this solve\'s first step, a non-negative int')
+    if int(step_offset) + int(n_steps) > 2 ** 31 - 1:
+        raise ValueError(f'step_offset={step_offset!r}: step_offset + n_steps = {int(step_offset) + int(n_steps)} exceeds 2**31 - 1')
+    return int(step_offset)
+
+
 class SolveCall:
     """A fully prepared solve: owns references to every device buffer named in the descriptor so the
     launch itself is one C call that only enqueues kernels (hipGraph-capturable).
@@ -627,7 +645,7 @@ class SolveCall:
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
                  lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False,
-                 ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False):
+                 ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False, step_offset=0):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -659,6 +677,12 @@ class SolveCall:
         if dW is not None:
             _check_f32('dW', dW, (grid.N, B, H))
         self.model, self.grid = model, grid
+        # step_offset = n0 (resumable solves, snsde_solve_forward_at): local step i draws the normals of global step n0 + i.  A stream
+        # coordinate like row_offset and seed - kept on the call, not in SolveConfig: no plan and no size query reads it
+        self.step_offset = check_step_offset(step_offset, grid.N)
+        if self.step_offset and (save_act or z0_linear is not None):
+            raise ValueError('step_offset != 0 is inference only: a continued solve has no backward (no saved activations) and starts '
+                             'from the caller\'s state (no fused initial network)')
         if dU is not None:
             _check_f32('dU', dU, (grid.N, B, H))
         if row_out is not None:
@@ -752,8 +776,8 @@ class SolveCall:
         if auto_reuse and not reuse_prepared and not capturing and getattr(self, '_prep_key', None) == key:
             reuse_prepared = True
         self.desc.flags = self.base_flags | (_lib.FLAG_REUSE_PREPARED if reuse_prepared else 0)
-        _lib.check(_lib.lib().snsde_solve_forward(C.byref(self.desc), C.c_void_p(stream.cuda_stream)),
-                   'snsde_solve_forward')
+        _lib.check(_lib.lib().snsde_solve_forward_at(C.byref(self.desc), C.c_int64(self.step_offset), C.c_void_p(stream.cuda_stream)),
+                   'snsde_solve_forward_at')
         if not capturing:             # a recorded prepare launch has not run: it prepared nothing an eager launch could reuse
             self._prep_key = key
         return self.ys

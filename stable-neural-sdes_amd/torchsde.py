@@ -28,6 +28,9 @@ Fixed-step semantics (restated from torchsde 0.2.5; its source 
 reference tree): time accumulates in float32 by repeated ``curr_t + dt`` clamped to ``ts[-1]``;
 outputs are linearly interpolated between the two solver states bracketing each ``ts[k]``;
 Euler ``y + f*h + g*dW``; Milstein adds ``0.5 * g * dg/dy * (dW^2 - h)`` (Ito, diagonal noise).
+
+Of torchsde's other keywords, ``extra=True`` / ``extra_solver_state`` are implemented (resumable solves: ``sdeint``'s docstring);
+``adaptive=True`` and ``logqp=True`` raise NotImplementedError.
 """
 import collections
 import os
@@ -211,14 +214,97 @@ def _differentiated(sde, y0, params=None):
     return torch.is_grad_enabled() and (y0.requires_grad or any(p.requires_grad for p in params) or _coeffs_need_grad(sde))
 
 
+_NO_GENERATOR_CONTINUATION = ("sdeint: options['step_offset'] != 0 (a continued Brownian path) needs the fused solve, whose kernels draw "
+                              "the Philox increments of the global steps, or a caller-supplied `bm`, which carries the path itself; {what} "
+                              "would draw from a torch generator and continue on different noise")
+
+
+def _continued_without_path(options, bm, what):
+    """A route that draws its increments from a torch generator cannot continue a path: NotImplementedError for step_offset != 0
+    without a caller's `bm` (never a silent continuation on different noise)."""
+    if bm is None and int(options.get('step_offset') or 0) != 0:
+        raise NotImplementedError(_NO_GENERATOR_CONTINUATION.format(what=what))
+
+
+def _seed_bits(seed):
+    """A Philox key as the int64 whose 64 bits it is (what the solver state stores; SolveCall masks it back)."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s >= (1 << 63) else s
+
+
+def _read_solver_state(state):
+    """(steps taken so far, key bits, keyed) of an `extra_solver_state`; ValueError if it is not what `extra=True` returned."""
+    ok = (isinstance(state, (tuple, list)) and len(state) == 1 and torch.is_tensor(state[0]) and state[0].dtype == torch.int64
+          and state[0].device.type == 'cpu' and tuple(state[0].shape) == (3,))
+    if ok:
+        taken, key, keyed = (int(v) for v in state[0].tolist())
+        ok = taken >= 0 and keyed in (0, 1)
+    if not ok:
+        raise ValueError("extra_solver_state is malformed: expected the 1-tuple sdeint(..., extra=True) returned, one int64 CPU tensor "
+                         "[steps taken so far, Philox key, keyed]")
+    return taken, key, keyed
+
+
 def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5, atol=1e-4, dt_min=1e-5,
            options=None, names=None, logqp=False, extra=False, extra_solver_state=None, **unused_kwargs):
+    """torchsde.sdeint's call contract (module docstring).  Resumable solves, torchsde's keywords:
+
+    ``extra=True`` returns ``(ys, state)``; ``extra_solver_state=state`` continues the SAME Brownian path from ``ys[-1]``: the
+    next call's ``y0``.  ``state`` is a 1-tuple holding one int64 CPU tensor [steps taken so far, Philox key, keyed] (opaque to
+    callers): keyed = 1 - the kernels drew from that key (options['seed'], or the fresh draw of the first call, returned instead
+    of discarded); keyed = 0 - a ``bm`` was supplied and carries the path.  A continued call runs with
+    options['step_offset'] = steps taken so far and the stored key: local step i draws the normals of global step
+    step_offset + i (include/snsde.h: snsde_solve_forward_at).  The pieces equal the single call over the concatenated ``ts`` bit
+    for bit exactly when every cut time is a step boundary of the single call's grid; otherwise the single call interpolates across
+    the cut while the pieces land on it, as in torchsde.  Between the pieces ``sde.set_X`` may be called with a longer coefficient
+    tensor and longer ``times`` (streaming: the causal Hermite path keeps the coefficients of its existing intervals).
+    Inference only: a differentiated call with step_offset != 0 is a ValueError.  A route that would draw from a torch generator
+    (the tensor-op loop without ``bm``, the latent route, the "no kernel covers it" fallback) raises NotImplementedError for
+    step_offset != 0.  options={'step_offset': n0} is the same knob without the state (with a ``bm`` it has no effect on the
+    increments).  A device-tensor seed (graph capture) with ``extra=True`` is a ValueError: the host does not know the key."""
     if unused_kwargs:
         warnings.warn(f"Unexpected arguments {unused_kwargs}")
     if adaptive:
         raise NotImplementedError("adaptive stepping is not implemented; the reference only uses fixed dt")
-    if logqp or extra or extra_solver_state is not None:
-        raise NotImplementedError("logqp / extra solver state are not implemented")
+    if logqp:
+        raise NotImplementedError("logqp is not implemented")
+    if not extra and extra_solver_state is None:
+        return _sdeint(sde, y0, ts, bm, method, dt, options, names)
+    options = dict(options or {})
+    keyed = 1 if bm is None else 0
+    if extra_solver_state is not None:
+        taken, key, was_keyed = _read_solver_state(extra_solver_state)
+        if was_keyed != keyed:
+            raise ValueError("extra_solver_state and `bm` disagree: " +
+                             ("the state continues a path the kernels drew from a Philox key, this call supplies a `bm`" if was_keyed else
+                              "the state continues the path of a supplied `bm`, this call has none"))
+        if options.get('step_offset') is not None and options['step_offset'] != taken:
+            raise ValueError(f"options['step_offset']={options['step_offset']!r} disagrees with extra_solver_state "
+                             f"({taken} steps taken so far)")
+        seed = options.get('seed')
+        if keyed and seed is not None and (torch.is_tensor(seed) or _seed_bits(seed) != key):
+            raise ValueError(f"options['seed']={seed!r} disagrees with the Philox key of extra_solver_state")
+        options['step_offset'] = taken
+        if keyed:
+            options['seed'] = key
+    else:
+        taken = engine.check_step_offset(options.get('step_offset') or 0)
+    if keyed:
+        seed = options.get('seed')
+        capturing = torch.is_tensor(y0) and y0.is_cuda and torch.cuda.is_current_stream_capturing()
+        if torch.is_tensor(seed) or (seed is None and capturing):
+            raise ValueError("extra=True / extra_solver_state with a device-resident Philox key (a tensor seed, graph capture): the host "
+                             "does not know the key a continuation would need; pass an int options['seed']")
+        if seed is None:
+            options['seed'] = _fresh_seed()      # (the call's own fresh draw, made here so that the state can return it)
+    ys = _sdeint(sde, y0, ts, bm, method, dt, options, names)
+    if not extra:
+        return ys
+    steps = engine.grid_steps(_HostTimes.get(_as_ts(ts, y0)), float(dt))
+    return ys, (torch.tensor([taken + steps, _seed_bits(options['seed']) if keyed else 0, keyed], dtype=torch.int64),)
+
+
+def _sdeint(sde, y0, ts, bm, method, dt, options, names):
     if not torch.is_tensor(y0) or y0.dim() != 2:
         raise ValueError("`y0` must be a 2-dimensional tensor of shape (batch, channels).")
     ts = _as_ts(ts, y0)
@@ -232,6 +318,12 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     backend = options.get('backend', 'auto')
     if backend not in ('auto', 'hip', 'torch'):
         raise ValueError("options['backend'] must be 'auto', 'hip' or 'torch'")
+    # options={'step_offset': n0}: this call's first step is global step n0 of its Brownian path (a continued solve; inference).
+    # Checked for every backend; from here on an int that every route finds in `options`
+    step_offset = options['step_offset'] = engine.check_step_offset(options.get('step_offset') or 0)
+    if step_offset and _differentiated(sde, y0):
+        raise ValueError(f"step_offset={step_offset} is inference only: y0, the control path or a parameter requires grad (use "
+                         "torch.no_grad() or requires_grad_(False)); a continued solve has no backward")
     # options={'samples': S}: S Brownian paths per input row (inference; _sdeint_samples).  Checked for every backend; 1 = no option
     # options={'sample_grad': True}: such a solve may be differentiated (opt-in: its training planes are per path).  No effect on 1
     samples = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
@@ -522,6 +614,11 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
                 raise ValueError(f"samples={S}: row_out has {ro.numel()} entries, expected {rows_in} or {B}")
     row_offset = _row_offset(options, M * B)
     global_rows = engine.resolve_global_rows(options.get('global_rows'), M * B, row_offset) or M * B
+    # options={'step_offset': n0}: a continued solve (sdeint's docstring) - handed to the fused call and to the loop of M solves alike
+    step_offset = options['step_offset'] = engine.check_step_offset(options.get('step_offset') or 0)
+    if step_offset and needs_grad:
+        raise ValueError(f"step_offset={step_offset} is inference only: y0, the control path or a member's parameter requires grad; a "
+                         "continued solve has no backward")
     if ensemble_samples and (row_offset % S or global_rows % S):
         raise ValueError(f"samples={S}: row_offset={row_offset} and global_rows={global_rows} must be multiples of samples (whole groups "
                          "of paths per shard)")
@@ -592,7 +689,8 @@ def sdeint_ensemble(sdes, y0, ts, bm=None, method=None, dt=1e-3, options=None):
     coeffs = coeffs.detach().to(device=dev, dtype=torch.float32).contiguous()
     y0c = y0.detach().to(torch.float32).reshape(M * B, -1).contiguous()
     rows = None if row_out is None else _device_row_out(options, dev).repeat(M)
-    call = engine.SolveCall(model, flat, coeffs, grid, y0c, seed=options['seed'], row_offset=row_offset, row_out=rows, **eng)
+    call = engine.SolveCall(model, flat, coeffs, grid, y0c, seed=options['seed'], row_offset=row_offset, row_out=rows, step_offset=step_offset,
+                            **eng)
     try:
         ys = call.launch()
     except engine._lib.SnsdeError as exc:
@@ -725,7 +823,11 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     # (without `bm` the kernels draw Philox increments: nothing to draw here)
     dW, dU = _draw_increments(bm, grid, y0, method, dtype=torch.float32, philox=True, host_times=True)
 
+    step_offset = int(options.get('step_offset') or 0)      # (a continued solve: inference, the launch below)
+
     def loop():      # the tensor-op loop on the same device, on the increments already drawn (and on y0 as it is by then)
+        if dW is None:
+            _continued_without_path(options, None, 'the tensor-op loop this configuration falls back to (no kernel covers it)')
         return _sdeint_torch(sde, y0, ts, bm if dW is None else _DrawnIncrements(dW, dU), method, dt, options, None)
     row_offset = _row_offset(options, B)
     # options={'global_rows': N | 'world'}: the rows of the whole problem this batch is a shard of - the library then plans its
@@ -769,7 +871,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         if pad is not None and (not needs_grad or engine.backward_mode(pad[0], B, L, grid, method, global_rows=global_rows) == 1):
             if z0_lin is not None:
                 y0, z0_lin = _materialise_z0(sde, y0, ts, z0_lin), None
-            return _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad)
+            return _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad, step_offset)
     if needs_grad:
         mode = engine.backward_mode(model, B, L, grid, **eng)
         if samples > 1 and mode != 1:      # (_sdeint_samples asked the same query: the sampled node is mode 1 or not built at all)
@@ -803,7 +905,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
         return loop()
     flat = engine.flatten_params(sde, layout, numel, dev)
     call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, seed=opt.seed, row_offset=opt.row_offset, save_traj=opt.save_traj, dU=dU,
-                            row_out=opt.row_out,
+                            row_out=opt.row_out, step_offset=step_offset,
                             z0_linear=None if z0_lin is None else (z0_lin.weight.detach(), z0_lin.bias.detach().contiguous()),
                             **dict(eng, sample_grad=False, bf16_grad=False))      # (inference: the training opt-ins stay off)
     try:
@@ -874,7 +976,7 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
     flat, tab = field.inference_inputs(tab_times, dev)
     call = engine.SolveCall(field.model, flat, coeffs, grid, y0.detach().to(torch.float32).contiguous(), dW=dW, dU=dU,
                             method=method, seed=seed, row_offset=row_offset, row_out=row_out, noise_table=tab,
-                            global_rows=global_rows)
+                            global_rows=global_rows, step_offset=int(options.get('step_offset') or 0))
     try:
         return call.launch().to(y0.dtype)
     except engine._lib.SnsdeError as exc:
@@ -922,6 +1024,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
     fused adjoint as output gradients.  N sequential launches of ~25-100 kernels become one solve + one batched step.
     Falls back to the tensor-op loop (same increments) for anything it does not recognise."""
     from . import fields
+    _continued_without_path(options, bm, 'the latent route')
     field = None
     if y0.dim() == 2 and y0.shape[1] >= 2 and not torch.cuda.is_current_stream_capturing() and 'row_out' not in options:
         field = fields.compose_latent(sde, names, int(y0.shape[1]))
@@ -1044,7 +1147,7 @@ def _sdeint_latent(sde, y0, ts, bm, method, dt, options, names):
     return torch.cat([y0.unsqueeze(0).to(aug.dtype), outs], dim=0)
 
 
-def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad):
+def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_grad, step_offset=0):
     """Solve the zero-padded model (engine.padding_plan) on the MFMA kernels and drop the padded state components.  opt: the
     _FusedOptions of _sdeint_hip, which has also checked that a training solve of the padded model has the MFMA adjoint."""
     model, layout, _ = rec
@@ -1058,7 +1161,7 @@ def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_g
     else:
         call = engine.SolveCall(model_p, flat, coeffs, grid, widen(y0.detach().to(torch.float32)), dW=widen(dW), method=method,
                                 seed=opt.seed, row_offset=opt.row_offset, dU=widen(dU), row_out=opt.row_out,
-                                global_rows=opt.engine['global_rows'])
+                                global_rows=opt.engine['global_rows'], step_offset=step_offset)
         ys = call.launch().to(y0.dtype)
     return ys[..., :H]
 
@@ -1458,6 +1561,7 @@ def _srk_step(f, g, t0, h, y, I_k, I_k0):
 
 def _sdeint_torch(sde, y0, ts, bm, method, dt, options, names):
     """Unfused scheme on tensor ops (arbitrary sde, CPU plumbing, autograd)."""
+    _continued_without_path(options, bm, 'the tensor-op loop')
     f = _call(sde, names, 'drift', 'f')
     g = _call(sde, names, 'diffusion', 'g')
     noise_type = getattr(sde, 'noise_type', 'diagonal')
