@@ -10,8 +10,13 @@
 //     occupying a 16-wide block of their own: 4 MFMAs per wave-step fewer;
 //   * layer biases enter through the accumulator operand of each chain's first MFMA (k-slot 0 lanes hold the bias):
 //     no bias add;
-//   * the diffusion g(t_n, y_n) and y_n + g dW_n are evaluated at the TOP of the step (they need only y_n) while the
-//     first layer's B operands are in flight; only  reduce -> tanh -> fma  follows the last GEMM;
+//   * the diffusion g(t_n, y_n) and y_n + g dW_n need only y_n: written at the top of the step, and placed by hipcc behind
+//     the hidden layer's operand reads (window A) beside the next step's increment and noise-table fetch (LEAN_GPART_MODE
+//     below pins it elsewhere; no placement measured faster); only  reduce -> tanh -> fma  follows the last GEMM;
+//   * the B operands of the y, hidden and output layers are the same 4 x H floats for every wave: each wave fetches them
+//     with ONE 64-lane ds_read_b128 per four k-blocks (lane group g reads k-block 4 j + g) and its MFMAs broadcast one
+//     lane group each (blgp 4 + g), instead of one read by lanes 0-15 per k-block (LEAN_WIDE_READS): a quarter of the
+//     LDS instructions queued behind every layer barrier, which is where both waves of a SIMD wait;
 //   * tanh = copysign((1 - t) / (1 + t), x), t = 2^(-2 log2e |x|): 7 VALU ops, absolute error <= ~4e-8 (the |x| < 0.25
 //     polynomial branch of fast_tanh bought relative accuracy the Euler update cannot see); nan_to_num of the raw
 //     diffusion folds into it (NaN -> v_max(NaN, 0) = 0, +-inf -> t = 0 -> +-1 = tanh(sigmoid(theta) FLT_MAX));
@@ -223,6 +228,41 @@ __device__ __forceinline__ void lean_gemm(const float (&w)[KU * 4], LeanB<KU>& b
     lean_gemm_from<Y, KU, 0>(w, b, c, d);
 }
 
+// Wide operand reads (LEAN_WIDE_READS, f32 operands, KU a multiple of 4): ONE ds_read_b128 by all 64 lanes fetches four k-blocks -
+// lane group g = lane >> 4 reads k-block 4 j + g (address + 64 g bytes) - instead of four reads by lanes 0-15, and the MFMAs of
+// k-block 4 j + g broadcast that group's registers (blgp: 4 + g).  Same operands into the same MFMAs in the same order; a quarter of
+// the LDS instructions behind every layer barrier (8 waves x 8 reads of the same 2 KB at H = 128 otherwise) and 6 x 4 fewer VGPRs.
+template <int KW> struct LeanBW { f32x4 v[KW]; };
+__device__ __forceinline__ void lean_read_bw(uint32_t a, LeanBW<1>& b) {
+    asm volatile("ds_read_b128 %0, %[a]" : "=&v"(b.v[0]) : [a] "v"(a));
+}
+__device__ __forceinline__ void lean_read_bw(uint32_t a, LeanBW<2>& b) {
+    asm volatile("ds_read_b128 %0, %[a]\n\tds_read_b128 %1, %[a] offset:256" : "=&v"(b.v[0]), "=&v"(b.v[1]) : [a] "v"(a));
+}
+template <int G>
+__device__ __forceinline__ void lean_mfma_group(const float* w, const f32x4& b, f32x4& c, f32x4& d) {
+    c = __builtin_amdgcn_mfma_f32_4x4x1f32(w[0], b[0], c, 0, 0, 4 + G);
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(w[1], b[1], d, 0, 0, 4 + G);
+    c = __builtin_amdgcn_mfma_f32_4x4x1f32(w[2], b[2], c, 0, 0, 4 + G);
+    d = __builtin_amdgcn_mfma_f32_4x4x1f32(w[3], b[3], d, 0, 0, 4 + G);
+}
+template <int Y, int KU, int J>
+__device__ __forceinline__ void lean_gemm_from(const float (&w)[KU * 4], LeanBW<KU / 4>& b, f32x4& c, f32x4& d) {
+    if constexpr (J < KU / 4) {
+        lean_wait1<Y + KU / 4 - 1 - J>(b.v[J]);
+        lean_mfma_group<0>(w + 16 * J, b.v[J], c, d);
+        lean_mfma_group<1>(w + 16 * J + 4, b.v[J], c, d);
+        lean_mfma_group<2>(w + 16 * J + 8, b.v[J], c, d);
+        lean_mfma_group<3>(w + 16 * J + 12, b.v[J], c, d);
+        __builtin_amdgcn_sched_barrier(0);
+        lean_gemm_from<Y, KU, J + 1>(w, b, c, d);
+    }
+}
+template <int Y, int KU>
+__device__ __forceinline__ void lean_gemm(const float (&w)[KU * 4], LeanBW<KU / 4>& b, f32x4& c, f32x4& d) {
+    lean_gemm_from<Y, KU, 0>(w, b, c, d);
+}
+
 // ---- bf16 operands (SNSDE_FLAG_BF16_OPERANDS; instantiated as CfgBf16<CfgL<..>> in snsde_m4b_h*.hip) ----------------------
 // Only the two MFMA operands are bf16 (round to nearest even): the resident weights and the LDS copies of the layer inputs
 // [X(t) | sin t, cos t], y and the hidden activations.  Accumulators, biases, the diffusion, the update and every value a lane
@@ -404,6 +444,38 @@ template <class CF> constexpr bool lean_spec_geo() {
 #endif
 #ifndef LEAN_TANH_G
 #define LEAN_TANH_G lean_tanh_rel<true>
+#else
+#define LEAN_TANH_G_CUSTOM 1
+#endif
+
+// Where the chain-independent VALU work of a step sits (development A/B like LEAN_PRIO_MODE: build.py variant NAME -DLEAN_GPART_MODE=k;
+// DESIGN.md section 3.1, profiles/lean_windows_*.txt).  f32 MFMAs and VALU instructions share one issue port, so this work is free
+// only while BOTH waves of a SIMD wait for LDS: in the operand-read windows behind the layer barriers.  The diffusion term
+// ypart = y + g(t_n, y_n) dW_n needs only y_n and is consumed by the update at the very end of the step, so it may sit in any of them:
+//   0  where hipcc puts it: written at the top of the step, sunk by the compiler behind the hidden layer's operand reads (window A),
+//      on top of prep() - the placement of the releases before this switch existed;
+//   1  split: raw, the polynomial branch and the exponential of the tanh in window A; reciprocal, select and the fma in window B
+//      (behind the output layer's operand reads, which carried nothing);
+//   2  all of it in window B;
+//   3  all of it at the top (behind the [X | tau] MFMAs, while the y operands are in flight), pinned.
+// Same operations in the same order on every value in every mode.  Modes 1 - 3 pin the pieces: their inputs and outputs pass through
+// empty asm volatile statements, which keep their order among the asm-issued reads and waits of the window (sched_barrier alone does
+// not hold a computation whose only consumer is a basic block further down: hipcc sinks it).
+#ifndef LEAN_GPART_MODE
+#define LEAN_GPART_MODE 0
+#endif
+#if LEAN_GPART_MODE == 1 && defined(LEAN_TANH_G_CUSTOM)
+#error "LEAN_GPART_MODE 1 splits lean_tanh_rel<true> by hand: no LEAN_TANH_G override with it"
+#endif
+// Where the next step's table row (qa, qb) and [X | tau] operands (bx) are read: 0 = between the y store and the closing barrier
+// (the last wave to arrive puts their latency on the step's critical path), 1 = right behind the output layer's operand reads, counted
+// in that layer's lean_gemm<Y> (LDS returns in order): they land under its MFMAs and the closing barrier waits for the y store alone.
+#ifndef LEAN_CARRY_MODE
+#define LEAN_CARRY_MODE 0
+#endif
+// 1: the y / hidden / output layers' operands through the wide reads above (LeanBW) where KUH is a multiple of 4 and the operands are f32
+#ifndef LEAN_WIDE_READS
+#define LEAN_WIDE_READS 1
 #endif
 
 template <class CF>
@@ -632,6 +704,35 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         return yp;
     };
 
+    // LEAN_GPART_MODE 1: gpart cut in two for the table noises with the tanh output (every CfgSpec launch; the general instantiation's
+    // other families - y-only closed forms, raw output - leave the head empty and run gpart whole in the tail).  gx = sig_theta raw,
+    // gpl = the polynomial branch, ge = 2^(-2 log2e |gx|): lean_tanh_rel<true>'s own operations, cut between the exponential and the reciprocal.
+    [[maybe_unused]] const bool gsplit = !yfun && !g_raw;
+    [[maybe_unused]] auto gpart_head = [&](float y, float gtv, float& gx, float& gpl, float& ge) {
+        if (__builtin_expect(gsplit, 1)) {
+            const float raw = mul_y ? gtv * y : gtv;
+            gx = sig_theta * raw;
+            const float x2 = gx * gx;
+            float p = fmaf(x2, -0.053968253968253971f, 0.13333333333333333f);
+            p = fmaf(x2, p, -0.33333333333333333f);
+            gpl = fmaf(gx * x2, p, gx);
+            ge = __builtin_amdgcn_exp2f(fabsf(gx) * -2.8853900817779268f);
+        }
+    };
+    [[maybe_unused]] auto gpart_tail = [&](float y, float gtv, float dwv, float hh, float gx, float gpl, float ge) -> float {
+        if (__builtin_expect(!gsplit, 0)) return gpart(y, gtv, dwv, hh);
+        float qv = (1.0f - ge) * __builtin_amdgcn_rcpf(1.0f + ge);
+        qv = __builtin_copysignf(__builtin_fmaxf(qv, 0.0f), gx);
+        const float g = fabsf(gx) < 0.125f ? gpl : qv;
+        float yp = fmaf(g, dwv, y);
+        if (__builtin_expect(mil, 0)) {
+            const float raw = mul_y ? gtv * y : gtv;
+            const float draw = (mul_y && snsde_finite(raw)) ? gtv : 0.0f;
+            yp = fmaf(0.5f * (g * ((1.0f - g * g) * sig_theta * draw)), fmaf(dwv, dwv, -hh), yp);
+        }
+        return yp;
+    };
+
     // ---- inputs of step 0; pieces of X(t_1) ---------------------------------------------------------------------------
     float dw_cur, gt_cur = 0.0f;
     f32x4 qa, qb;       // the table row of the step about to run: (h_n, sqrt h_{n+1}, -, -), (sin, cos, frac of step n+1, idx of step n+2)
@@ -672,6 +773,12 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
     //  mode forward at K2.  With the counted-vmcnt experiment at vm_wait this rules out both the store instruction count / segment
     //  width and the acknowledgement drain as the source of the ~4 us per plane and 100 steps that every per-step store costs here.)
 
+    constexpr bool WIDE = LEAN_WIDE_READS != 0 && !BF && KUH % 4 == 0;
+    using LayerB = std::conditional_t<WIDE, LeanBW<(KUH >= 4 ? KUH / 4 : 1)>, LeanBt<BF, KUH>>;      // B operands of a y / hidden / output layer
+    auto read_layer = [&](uint32_t addr, LayerB& b) {
+        if constexpr (WIDE) lean_read_bw(addr + (uint32_t)q * 64u, b);      // lane group q: k-blocks q, 4 + q
+        else lean_read_b(addr, b);
+    };
     LeanBt<BF, (KUXT > 0 ? KUXT : 1)> bx{};    // [X(t_n) | tau_n] operands of the step about to start
     if constexpr (KUXT > 0) lean_read_b_carried(xrow, bx);
     if constexpr (SP) {
@@ -715,8 +822,8 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         LT(0)
         // ---- top: the first layer's B operands, then the table quads of the coming steps (asm: the compiler never waits
         //      on them; they have landed once the first layer's last s_waitcnt has passed) ------------------------------------
-        LeanBt<BF, KUH> by;
-        if constexpr (YIN) lean_read_b(yrow, by);
+        LayerB by;
+        if constexpr (YIN) read_layer(yrow, by);
         asm volatile("" : "+v"(qa), "+v"(qb));      // (read before the closing barrier of the previous step: landed)
         const float h = qa[0];
         __builtin_amdgcn_sched_barrier(0);
@@ -725,7 +832,20 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         f32x4 c = bfr[0], d = zero4;
         if constexpr (KUXT > 0) lean_gemm<15, KUXT>(wxt, bx, c, d);
         // ---- in the shadow of those reads: diffusion, y + g dW; X(t_{n+1}) and the fetch of X(t_{n+2})'s pieces -----------
-        const float ypart = gpart(yv, gt_cur, dw_cur, h);
+        // (LEAN_GPART_MODE: 0 leaves the placement to hipcc, 3 pins it here, 1 / 2 evaluate it behind the later layers' operand reads)
+        float ypart = 0.0f;
+        [[maybe_unused]] float gx = 0.0f, gpl = 0.0f, ge = 0.0f;
+        constexpr int GPM = LEAN_GPART_MODE == 1 && NHID == 0 ? 2 : LEAN_GPART_MODE;     // (no hidden layer: windows A and B are one)
+        auto gp_in = [&]() { asm volatile("" : "+v"(yv), "+v"(gt_cur), "+v"(dw_cur)); };
+        if constexpr (GPM == 0) ypart = gpart(yv, gt_cur, dw_cur, h);
+        if constexpr (GPM == 3) { gp_in(); ypart = gpart(yv, gt_cur, dw_cur, h); asm volatile("" : "+v"(ypart)); }
+        // the next step's table row and [X | tau] operands, in place (LEAN_CARRY_MODE)
+        auto carry = [&]() {
+            asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16"
+                         : "+v"(qa), "+v"(qb) : "v"(lean_lds_addr(rowtab + (n + 1 - rbase) * RS)));
+            if constexpr (KUXT > 0) lean_read_b_carried(xrow + ((n + 1) & (XS - 1)) * (4 * LDX * 4), bx);
+        };
+        constexpr int YC = LEAN_CARRY_MODE == 1 ? 2 + KUXT : 0;      // LDS reads carry() leaves in flight behind a layer's operand reads
         if constexpr (SP) {
             // every fourth step: X(t_{n+1+k}) out of the pieces fetched four steps ago, with (sin, cos, frac) of step n + 1 + k from table
             // row n + k; then the pieces of X(t_{n+5+k}), whose interval is in row n + 3 + k (rows past the last step repeat it:
@@ -777,10 +897,13 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
 #pragma unroll
         for (int l = 0; l < NHID; ++l) {
             const bool toB = (l % 2 == 0);
-            LeanBt<BF, KUH> bh;
-            lean_read_b(cur, bh);
+            LayerB bh;
+            read_layer(cur, bh);
             __builtin_amdgcn_sched_barrier(0);
             if (l == 0) prep();
+            if constexpr (GPM == 1) {      // window A's share of the diffusion term
+                if (l == 0) { gp_in(); gpart_head(yv, gt_cur, gx, gpl, ge); asm volatile("" : "+v"(gx), "+v"(gpl), "+v"(ge)); }
+            }
             __builtin_amdgcn_sched_barrier(0);
             if (l == 0) { LT(5) }
             c = bfr[1 + l]; d = zero4;
@@ -802,13 +925,24 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         }
         // ---- output layer, f, update -------------------------------------------------------------------------------
         {
-            LeanBt<BF, KUH> bo;
-            lean_read_b(cur, bo);
+            LayerB bo;
+            read_layer(cur, bo);
             __builtin_amdgcn_sched_barrier(0);
             if (NHID == 0) prep();
+            // window B.  The carried reads come first (they are counted in lean_gemm's Y: every LDS operation between a layer's
+            // operand reads and its MFMAs must be); the update's h = qa[0] was copied out at the top of the step.  Row n + 1 of the
+            // chunk's table was filled behind the refill's own barrier, X(t_{n+1}) was stored before barrier A of this step at the
+            // latest (xbuf's declaration), and the slot is not overwritten before the top of step n + 1, behind the closing barrier.
+            if constexpr (LEAN_CARRY_MODE == 1) carry();
+            if constexpr (GPM == 2) { gp_in(); ypart = gpart(yv, gt_cur, dw_cur, h); asm volatile("" : "+v"(ypart)); }
+            if constexpr (GPM == 1) {
+                asm volatile("" : "+v"(gx), "+v"(gpl), "+v"(ge), "+v"(dw_cur));
+                ypart = gpart_tail(yv, gt_cur, dw_cur, h, gx, gpl, ge);
+                asm volatile("" : "+v"(ypart));
+            }
             __builtin_amdgcn_sched_barrier(0);
             c = bfr[NHID + 1]; d = zero4;
-            lean_gemm<0, KUH>(wo, bo, c, d);
+            lean_gemm<YC, KUH>(wo, bo, c, d);
         }
         LT(8)
         vm_wait(dw_nxt, gt_nxt);      // this step's prefetches (issued one to three phases ago)
@@ -851,11 +985,9 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
             }
         }
         dw_cur = dw_nxt; gt_cur = gt_nxt;
-        // the next step's table row and [X | tau] operands (written before this step's first barrier), in place; they
-        // land before the closing barrier releases (its s_waitcnt lgkmcnt(0))
-        asm volatile("ds_read_b128 %0, %2\n\tds_read_b128 %1, %2 offset:16"
-                     : "+v"(qa), "+v"(qb) : "v"(lean_lds_addr(rowtab + (n + 1 - rbase) * RS)));
-        if constexpr (KUXT > 0) lean_read_b_carried(xrow + ((n + 1) & (XS - 1)) * (4 * LDX * 4), bx);
+        // (LEAN_CARRY_MODE 0: the next step's table row and [X | tau] operands here; they land before the closing barrier releases -
+        //  its s_waitcnt lgkmcnt(0), which in mode 1 still covers whatever of them the output layer's last wait left in flight)
+        if constexpr (LEAN_CARRY_MODE == 0) carry();
         LT(9)
         __syncthreads();
         LT_COLLECT

@@ -10,7 +10,7 @@ Two views of the same kernel:
     > 20 MFMAs, with the blocks the compiler laid out behind its back edge.  step_loop() / loop_exits() / left_on() /
     smem_after_first_barrier() work on it: a loop left through s_cbranch_scc* has its counter and bound on the scalar unit, one
     left through s_cbranch_exec* / vcc* is an exec-masked (divergent-form) loop around the layer MFMAs.
-The functions are imported by tests/test_scalar_step_loop_cpu.py."""
+The functions are imported by tests/test_scalar_step_loop_cpu.py and tests/test_lean_windows_cpu.py."""
 import re
 import sys
 from collections import Counter
@@ -177,6 +177,30 @@ def smem_after_first_barrier(loop):
     return [x for x in ins[first:] if x.startswith(('s_load', 's_buffer_load'))]
 
 
+def operand_windows(loop):
+    """The operand-read windows of the step loop in layout order: behind every s_barrier but the last (the closing barrier, followed by
+    the back edge), the instructions from the first ds_read_b128 / ds_read_b64 (a layer's B operands) up to, not including, the first
+    s_waitcnt lgkmcnt behind it.  What sits there issues while the operands are in flight.  For the lean forward kernel: the window at
+    the top of the step (laid out behind the refill block's barrier), behind barrier A, behind barrier B."""
+    ins = instructions(loop['lines'])
+    bars = [i for i, x in enumerate(ins) if x.startswith('s_barrier')]
+    out = []
+    for b in bars[:-1]:
+        i = next(k for k in range(b, len(ins)) if ins[k].startswith(('ds_read_b128', 'ds_read_b64')))
+        k = next(k for k in range(i, len(ins)) if ins[k].startswith('s_waitcnt') and 'lgkmcnt' in ins[k])
+        out.append(ins[i:k])
+    return out
+
+
+def closing_stretch(loop):
+    """The instructions between the last LDS store in front of the step loop's last s_barrier in layout order (the lean forward kernel's
+    y store and closing barrier; the cold blocks behind the back edge hold no barrier) and that barrier."""
+    ins = instructions(loop['lines'])
+    last = max(i for i, x in enumerate(ins) if x.startswith('s_barrier'))
+    store = max(i for i in range(last) if ins[i].startswith('ds_write'))
+    return ins[store + 1:last]
+
+
 def main():
     path, key = sys.argv[1], sys.argv[2]
     lines = open(path).read().split('\n')
@@ -196,6 +220,11 @@ def main():
     print(f"  step loop {lp['header']} depth {lp['depth']}: instrs {sum(sc.values())} {dict(sc)}")
     print(f"  left on: {left_on(fn, lp)} ({', '.join(op + ' .L' + t for op, t in ex)}); scalar loads from the first barrier on: "
           f"{len(smem_after_first_barrier(lp))}; {kernel_resources(lines, key)}")
+    for name, w in zip(('top', 'after A', 'after B'), operand_windows(lp)):
+        c = mix(w)
+        trans = [x.split()[0] for x in w if x.startswith(('v_exp_f32', 'v_rcp_f32'))]
+        print(f"  window {name}: {c['ds']} LDS reads, {c['valu']} VALU ({', '.join(trans) or 'no transcendental'}), {c['vmem']} VMEM, {c['mfma']} MFMA")
+    print(f"  y store -> closing barrier: {', '.join(x.split()[0] for x in closing_stretch(lp))}")
 
 
 if __name__ == '__main__':
