@@ -60,8 +60,8 @@ def _series_coeffs(times, x):
     """times (L,), x (S, L) with NaN = missing  ->  a, b, two_c, three_d each (S, L-1).
 
     Per series: impute the first/last observation at the ends (interpolate.py:100-114), fit the natural
-    spline through the observed knots only, then re-express every observed-interval cubic on each
-    original sub-interval (interpolate.py:131-150).
+    spline through the observed knots only (two knots: the straight line, interpolate.py:16-20), then re-express
+    every observed-interval cubic on each original sub-interval (interpolate.py:131-150).
     """
     S, L = x.shape
     dt, dev = x.dtype, x.device
@@ -113,6 +113,14 @@ def _series_coeffs(times, x):
     b_c = kd[:, :-1]
     two_c = (6 * dx * rec - 4 * kd[:, :-1] - 2 * kd[:, 1:]) * rec
     three_d = (-6 * dx * rec + 3 * (kd[:, :-1] + kd[:, 1:])) * rec * rec
+    # two knots: the straight line (interpolate.py:16-20), slope = one subtraction and one division, curvature exactly 0.  The
+    # Thomas branch that torch.where discards for these series is finite (h[:, 0] > 0: interval 0 is always real), so autograd
+    # carries no NaN out of it.
+    two = (m == 2)[:, None]
+    z = torch.zeros((), dtype=dt, device=dev)
+    b_c = torch.where(two, (dx[:, 0] / h[:, 0])[:, None], b_c)
+    two_c = torch.where(two, z, two_c)
+    three_d = torch.where(two, z, three_d)
     # expand: original interval j lies in observed interval p = pos[j]
     p = pos[:, :-1]
     off = torch.gather(tc, 1, p) - times[None, :-1]      # prev observed time - time_j  (<= 0)
@@ -123,7 +131,6 @@ def _series_coeffs(times, x):
     b = gb + (gd * off - gc) * off
     c2 = gc - 2 * gd * off
     zero = ~any_obs[:, None]
-    z = torch.zeros((), dtype=dt, device=dev)
     return (torch.where(zero, z, a), torch.where(zero, z, b), torch.where(zero, z, c2), torch.where(zero, z, gd))
 
 
