@@ -717,6 +717,51 @@ SNSDE_API int snsde_ensemble_stats_backward(const float* grad_mean, const float*
                                             int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
                                             float* grad_ys, void* hip_stream);
 
+/* ---- scores of sample paths against an observation ---------------------------------------------
+ * ys viewed as (outer, members, groups, samples, width) = (outer, M, G, S, W) as above (a sampled solve: members = 1, its T B
+ * (time, row) pairs fold into groups).  The members axis is addressing only (member stride G S W): the pooled sample set of an
+ * output element (o, g, w) is x_n, n = m S + s, N = M S of them - the predictive mixture whose variance snsde_ensemble_stats
+ * splits - and a pooled call gives the bits of the members = 1 call on the permuted (outer G, M S, W) tensor.
+ * target y is (outer, groups, width).  With d_n = x_n - y, the strict counts c_n = #{j : x_j < x_n} - #{j : x_j > x_n} (ties
+ * contribute 0, sum_n c_n = 0) and D = N - 1 (fair != 0: the unbiased estimator; N < 2 is then SNSDE_ERR_DIMS) or D = N,
+ *     crps = (sum_n |d_n|) / N - (sum_n c_n d_n) / (N D)            = mean |x - y| - sum_ij |x_i - x_j| / (2 N D)
+ *     rank = #{n : x_n < y},  ties = #{n : x_n == y}                (outer, groups, width) as float; each optional, NULL = not wanted
+ * One workgroup of four waves stages the (N, 64-column) slab of a group in LDS (N * 256 bytes: N > 256 is SNSDE_ERR_DIMS) and
+ * each lane walks its own column; wave k owns the quarter n in [k N / 4, (k + 1) N / 4).  Summation order: the two sums run n
+ * ascending inside a quarter (sum += |d_n|; sum = fmaf(c_n, d_n, sum)), the four quarter sums are added k ascending, then one
+ * division each and the subtraction.  No atomics, no dependence on the grid: the same bits on every launch.  Enqueue-only, no
+ * workspace, capturable.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target or crps NULL.  SNSDE_ERR_DIMS:
+ * a non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits. */
+SNSDE_API int snsde_sample_crps(const float* ys, const float* target, int64_t outer, int32_t members, int64_t groups, int32_t samples,
+                                int32_t width, int32_t fair, float* crps, float* rank, float* ties, void* hip_stream);
+
+/* Adjoint of snsde_sample_crps: with grad_crps (outer, groups, width) = g, and sign(0) = 0 (what |.| differentiates to),
+ *     grad_ys[o, m, g, s, w] = g * (sign(d_n) / N - c_n / (N D))
+ *     grad_target[o, g, w]   = -(g * sum_n sign(d_n)) / N                 (optional, NULL = not wanted)
+ * which is autograd of the pairwise statement, ties included.  The counts are formed again from ys (no rank plane is saved);
+ * every element of grad_ys is written; rank and ties carry no gradient.  The same ownership, errors and guarantees. */
+SNSDE_API int snsde_sample_crps_backward(const float* grad_crps, const float* ys, const float* target, int64_t outer, int32_t members,
+                                         int64_t groups, int32_t samples, int32_t width, int32_t fair, float* grad_ys, float* grad_target,
+                                         void* hip_stream);
+
+/* Quantiles of the pooled sample set by linear interpolation of order statistics (torch.quantile's 'linear' rule).  x_(k) is the
+ * sample whose permutation rank r_n = #{j : x_j < x_n} + #{j < n : x_j == x_n} (ties broken by index) equals k.  For each of
+ * the n_q requested levels the caller gives, from pos = q (N - 1) in double, k[i] = floor(pos) and frac[i] = (float)(pos - k[i]):
+ *     out[i, o, g, w] = x_(k[i])                                                   where frac[i] == 0
+ *                     = fmaf(frac[i], x_(k[i] + 1) - x_(k[i]), x_(k[i]))           otherwise
+ * out is (n_q, outer, groups, width).  k and frac are HOST arrays of n_q entries, copied into the kernel's argument struct: no
+ * device allocation, capturable.  SNSDE_ERR_DIMS also for n_q outside 1 .. 8, k[i] outside [0, N - 1], frac[i] outside [0, 1),
+ * and k[i] == N - 1 with frac[i] != 0.  SNSDE_ERR_NULL: ys, k, frac or out NULL. */
+SNSDE_API int snsde_sample_quantiles(const float* ys, int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
+                                     int32_t n_q, const int32_t* k, const float* frac, float* out, void* hip_stream);
+
+/* Adjoint of snsde_sample_quantiles: grad_out (n_q, outer, groups, width) = g_i; the ranks are formed again from ys,
+ *     grad_ys[n] = sum_i ( g_i (1 - frac[i]) [r_n == k[i]] + g_i frac[i] [r_n == k[i] + 1, frac[i] != 0] ),   i ascending
+ * and exact zeros everywhere else; every element of grad_ys is written. */
+SNSDE_API int snsde_sample_quantiles_backward(const float* grad_out, const float* ys, int64_t outer, int32_t members, int64_t groups,
+                                              int32_t samples, int32_t width, int32_t n_q, const int32_t* k, const float* frac,
+                                              float* grad_ys, void* hip_stream);
+
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /
  * snsde_backward / snsde_head); SNSDE_ERR_ABI otherwise.  A size of 0 means "this binding does not declare that struct"

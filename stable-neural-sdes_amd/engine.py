@@ -1253,6 +1253,231 @@ class _EnsembleStats(torch.autograd.Function):
         return ensemble_stats_backward(gm, gw, gb, ys, ctx.M, ctx.S), None, None, None, None
 
 
+SCORE_MAX_POOLED = 256      # pooled samples N = members * samples the score kernels stage in LDS (csrc/snsde_scores.hip: MAX_N)
+SCORE_MAX_QUANTILES = 8     # quantile levels per launch (they travel in the kernel's argument struct)
+
+
+def _score_dims(ys, samples, members):
+    """(S, M, lead, G, W) of a result scored over its sample paths: ys (..., B S, W) for members = 1, (..., M, B S, W) otherwise."""
+    S = check_samples(samples)
+    if isinstance(members, bool) or not isinstance(members, int) or members < 1:
+        raise ValueError(f'members must be an integer >= 1 (models of the ensemble), got {members!r}')
+    M = members
+    if M == 1:
+        if ys.dim() < 2 or ys.shape[-2] % S:
+            raise ValueError(f'ys has shape {tuple(ys.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
+        lead = tuple(ys.shape[:-2])
+    else:
+        if ys.dim() < 3 or ys.shape[-3] != M or ys.shape[-2] % S:
+            raise ValueError(f'ys has shape {tuple(ys.shape)}: expected (..., members, rows, width) with members = {M} and a whole '
+                             f'number of groups of {S} paths per member')
+        lead = tuple(ys.shape[:-3])
+    return S, M, lead, ys.shape[-2] // S, ys.shape[-1]
+
+
+def _pooled(ys, S, M, lead, G, W):
+    """The pooled sample sets as a tensor (..., G, N, W), n = m S + s (a view where members = 1)."""
+    if M == 1:
+        return ys.reshape(lead + (G, S, W))
+    return ys.reshape(lead + (M, G, S, W)).movedim(-4, -3).reshape(lead + (G, M * S, W))
+
+
+def _score_native(ys, N, *others):
+    return (ys.is_cuda and ys.dtype == torch.float32 and ys.numel() > 0 and N <= SCORE_MAX_POOLED
+            and all(o.is_cuda and o.dtype == torch.float32 and o.device == ys.device for o in others))
+
+
+def _outer(lead):
+    n = 1
+    for e in lead:
+        n *= e
+    return n
+
+
+def sample_crps(ys, samples, target, fair=True, members=1, rank=False):
+    """Continuous ranked probability score of the sample paths of a solve against an observation.  ys is (..., B S, W) - a
+    sampled solve's result, path index b S + s - or, with members = M > 1, (..., M, B S, W): the paths of all members are pooled
+    into one sample set x_n, n = m S + s, N = M S (the predictive mixture whose variance `ensemble_stats` splits).  target y is
+    (..., B, W).  With d_n = x_n - y, the strict counts c_n = #{x_j < x_n} - #{x_j > x_n} and D = N - 1 (fair: the unbiased
+    estimator, N >= 2) or D = N,
+        crps = sum |d_n| / N - sum c_n d_n / (N D)        (= mean |x - y| - sum_ij |x_i - x_j| / (2 N D))
+    of shape (..., B, W); with rank=True returns (crps, rank, ties), rank = #{x_n < y} and ties = #{x_n == y} as float32 (for the
+    PIT / rank histogram; no gradient).  Differentiable in ys and target, sign(0) = 0.
+    CUDA float32 inputs with N <= 256: one launch of snsde_sample_crps (the (N, 64-column) slab of a group staged in LDS, no
+    (.., S, S, ..) intermediate, deterministic, capturable) - inside an autograd node whose backward is snsde_sample_crps_backward
+    when an input requires grad.  Other tensors: the same definitions in tensor ops, the counts from a sort."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N, out_shape = M * S, lead + (G, W)
+    if tuple(target.shape) != out_shape:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {out_shape} (one observation per input row and column)')
+    if fair and N < 2:
+        raise ValueError('the fair (unbiased) score needs at least 2 pooled samples')
+    fair, rank = bool(fair), bool(rank)
+    if _score_native(ys, N, target):
+        if (ys.requires_grad or target.requires_grad) and torch.is_grad_enabled():
+            crps, rk, ti = _SampleCRPS.apply(ys, target, S, M, fair, rank)
+        else:
+            crps, rk, ti = _sample_crps_launch(ys.contiguous(), target.contiguous(), S, M, fair, rank)
+        return (crps, rk, ti) if rank else crps
+    return sample_crps_tensor_ops(ys, S, target, fair, M, rank)
+
+
+def sample_crps_tensor_ops(ys, samples, target, fair=True, members=1, rank=False):
+    """`sample_crps` stated in tensor ops (any device and dtype; autograd differentiates it): the strict counts c_n come from a
+    sort of each column, so there is no (.., N, N, ..) intermediate.  What `sample_crps` runs off the kernels' domain."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    x = _pooled(ys, S, M, lead, G, W)
+    D = N - 1 if fair else N
+    d = x - target.unsqueeze(-2)
+    with torch.no_grad():      # (integers: no gradient)
+        xt = x.transpose(-1, -2).contiguous()
+        xs = torch.sort(xt, dim=-1).values
+        c = (torch.searchsorted(xs, xt, right=False) + torch.searchsorted(xs, xt, right=True) - N).transpose(-1, -2).to(d.dtype)
+    crps = d.abs().sum(dim=-2) / N - (c * d).sum(dim=-2) / (N * D)
+    if not rank:
+        return crps
+    with torch.no_grad():
+        return crps, (d < 0).sum(dim=-2).to(torch.float32), (d == 0).sum(dim=-2).to(torch.float32)
+
+
+def _sample_crps_launch(ys, target, S, M, fair, rank):
+    G, W = ys.shape[-2] // S, ys.shape[-1]
+    crps = torch.empty_like(target)
+    rk = torch.empty_like(target) if rank else None
+    ti = torch.empty_like(target) if rank else None
+    _lib.check(_lib.lib().snsde_sample_crps(_ptr(ys), _ptr(target), ys.numel() // (M * G * S * W), M, G, S, W, int(fair), _ptr(crps),
+                                            _ptr(rk), _ptr(ti), C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_crps')
+    return crps, rk, ti
+
+
+def sample_crps_backward(grad_crps, ys, target, samples, fair=True, members=1, grad_target=True):
+    """(dL/d ys, dL/d target) of `sample_crps` from dL/d crps: one launch of snsde_sample_crps_backward (dL/d target None when
+    grad_target=False).  Contiguous float32 CUDA tensors, ys (..., B S, W) or (..., M, B S, W), the others (..., B, W)."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    _check_f32('ys', ys)
+    _check_f32('target', target, lead + (G, W))
+    _check_f32('grad_crps', grad_crps, lead + (G, W))
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    _lib.check(_lib.lib().snsde_sample_crps_backward(_ptr(grad_crps), _ptr(ys), _ptr(target), _outer(lead), M, G, S, W, int(bool(fair)),
+                                                     _ptr(gys), _ptr(gt), C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_crps_backward')
+    return gys, gt
+
+
+class _SampleCRPS(torch.autograd.Function):
+    """sample_crps of CUDA float32 tensors of which one requires grad: the forward kernel, and snsde_sample_crps_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ys, target, S, M, fair, rank):
+        ysc, tc = ys.detach().contiguous(), target.detach().contiguous()
+        crps, rk, ti = _sample_crps_launch(ysc, tc, S, M, fair, rank)
+        ctx.S, ctx.M, ctx.fair = S, M, fair
+        ctx.save_for_backward(ysc, tc)
+        if not rank:
+            rk, ti = crps.new_empty(0), crps.new_empty(0)
+        ctx.mark_non_differentiable(rk, ti)
+        return crps, rk, ti
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_crps, grad_rank, grad_ties):
+        ys, target = ctx.saved_tensors
+        g = torch.zeros_like(target) if grad_crps is None else grad_crps.to(torch.float32).contiguous()
+        gys, gt = sample_crps_backward(g, ys, target, ctx.S, ctx.fair, ctx.M, grad_target=ctx.needs_input_grad[1])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None
+
+
+def quantile_positions(q, N):
+    """Order-statistic positions of the levels q among N samples, torch.quantile's 'linear' rule: pos = q (N - 1) in float64,
+    k = floor(pos), frac = float32(pos - k).  Returns (k, frac) as lists; ValueError for a level outside [0, 1] or no level."""
+    try:
+        qs = [float(v) for v in (q.tolist() if isinstance(q, (torch.Tensor, np.ndarray)) else q)]
+    except TypeError:
+        qs = [float(q)]
+    if not qs or any(not 0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f'q must hold at least one level, each in [0, 1], got {q!r}')
+    ks, fracs = [], []
+    for v in qs:
+        pos = v * (N - 1)
+        k = int(np.floor(pos))
+        frac = float(np.float32(pos - k))
+        if frac >= 1.0:      # (pos - k rounds to 1 in float32: the next order statistic itself)
+            k, frac = k + 1, 0.0
+        ks.append(k)
+        fracs.append(frac)
+    return ks, fracs
+
+
+def _quantile_args(ks, fracs):
+    n = len(ks)
+    return n, (C.c_int32 * n)(*ks), (C.c_float * n)(*fracs)
+
+
+def sample_quantiles(ys, samples, q, members=1):
+    """Quantiles of the sample paths of a solve at the levels q (a sequence of numbers in [0, 1]): ys as for `sample_crps`, the
+    result (len(q), ..., B, W).  Linear interpolation between order statistics (torch.quantile's 'linear' rule): with
+    pos = q (N - 1), k = floor(pos) and frac = float32(pos - k), the value is x_(k), or fma(frac, x_(k+1) - x_(k), x_(k)) where
+    frac != 0; ties are ordered by index.  Differentiable in ys: the gradient goes to the one or two samples that set the value.
+    CUDA float32 input with N <= 256 and at most 8 levels: one launch of snsde_sample_quantiles (backward:
+    snsde_sample_quantiles_backward); other tensors: a stable sort in tensor ops."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    ks, fracs = quantile_positions(q, N)
+    if _score_native(ys, N) and len(ks) <= SCORE_MAX_QUANTILES:
+        if ys.requires_grad and torch.is_grad_enabled():
+            return _SampleQuantiles.apply(ys, S, M, tuple(ks), tuple(fracs))
+        return _sample_quantiles_launch(ys.contiguous(), S, M, ks, fracs)
+    xs = torch.sort(_pooled(ys, S, M, lead, G, W), dim=-2, stable=True).values
+    out = []
+    for k, frac in zip(ks, fracs):
+        lo = xs[..., k, :]
+        out.append(lo if frac == 0.0 else lo + frac * (xs[..., k + 1, :] - lo))
+    return torch.stack(out)
+
+
+def _sample_quantiles_launch(ys, S, M, ks, fracs):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    n_q, k, frac = _quantile_args(ks, fracs)
+    out = torch.empty((n_q,) + lead + (G, W), device=ys.device, dtype=torch.float32)
+    _lib.check(_lib.lib().snsde_sample_quantiles(_ptr(ys), _outer(lead), M, G, S, W, n_q, k, frac, _ptr(out),
+                                                 C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_sample_quantiles')
+    return out
+
+
+def sample_quantiles_backward(grad_out, ys, samples, ks, fracs, members=1):
+    """dL/d ys of `sample_quantiles` from dL/d out (len(ks), ..., B, W) at the positions (ks, fracs) of `quantile_positions`: one
+    launch of snsde_sample_quantiles_backward.  Contiguous float32 CUDA tensors."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    n_q, k, frac = _quantile_args(ks, fracs)
+    _check_f32('ys', ys)
+    _check_f32('grad_out', grad_out, (n_q,) + lead + (G, W))
+    gys = torch.empty_like(ys)
+    _lib.check(_lib.lib().snsde_sample_quantiles_backward(_ptr(grad_out), _ptr(ys), _outer(lead), M, G, S, W, n_q, k, frac, _ptr(gys),
+                                                          C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_quantiles_backward')
+    return gys
+
+
+class _SampleQuantiles(torch.autograd.Function):
+    """sample_quantiles of a CUDA float32 tensor that requires grad: the forward kernel, and snsde_sample_quantiles_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ys, S, M, ks, fracs):
+        ysc = ys.detach().contiguous()
+        ctx.S, ctx.M, ctx.ks, ctx.fracs = S, M, ks, fracs
+        ctx.save_for_backward(ysc)
+        return _sample_quantiles_launch(ysc, S, M, ks, fracs)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ys, = ctx.saved_tensors
+        return sample_quantiles_backward(grad_out.to(torch.float32).contiguous(), ys, ctx.S, ctx.ks, ctx.fracs, ctx.M), None, None, None, None
+
+
 def spline_grad_native():
     """False under SNSDE_SPLINE_GRAD=torch: the spline constructors then differentiate their tensor-op statement with autograd
     (the in-repo cross-check of the HIP adjoint, and the route that supports double backward).  Read at every call."""

@@ -57,6 +57,27 @@ def add_weight_regularisation(loss_fn, regularise_parameters, scaling=0.01, mode
     return new_loss_fn
 
 
+def crps_loss(samples, fair=True, members=1):
+    """loss_fn(pred, true) for `train_loop` / `GraphedStep` / `evaluate_metrics`: the mean continuous ranked probability score
+    (engine.sample_crps) of a model solved with options={'samples': S}.  pred has one row per path, as the wrappers return it in
+    both modes - (B S, ...), or (M, B S, ...) from an `Ensemble` of `members` = M models, whose paths are pooled; true is
+    (B, ...).  Trailing axes are flattened to the width; the result is the mean over the elements of true."""
+    from . import engine
+    S = engine.check_samples(samples)
+
+    lead = 1 if members > 1 else 0      # (an Ensemble's leading member axis)
+
+    def loss_fn(pred_y, true_y):
+        want = ((members,) if lead else ()) + (S * true_y.shape[0],) if true_y.dim() else None
+        if want is None or tuple(pred_y.shape[:lead + 1]) != want:
+            raise ValueError(f'crps_loss(samples={S}, members={members}): pred has shape {tuple(pred_y.shape)} for a target of shape '
+                             f'{tuple(true_y.shape)}: expected {"(members, " if lead else "("}samples x target rows, ...)')
+        pred = pred_y.reshape(want + (-1,))
+        true = true_y.reshape(true_y.shape[0], -1).to(pred.dtype)
+        return engine.sample_crps(pred, S, true, fair=fair, members=members).mean()
+    return loss_fn
+
+
 class SqueezeEnd(torch.nn.Module):
     def __init__(self, model):
         super().__init__()
@@ -341,14 +362,16 @@ def make_model(name, input_channels, output_channels, hidden_channels, hidden_hi
 
 def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloader, device, make_model, num_classes,
          max_epochs, lr, kwargs, step_mode, pos_weight=torch.tensor(1), results_dir=None, log=print, regularise='l2',
-         graph_steps=None, shard_invariant=False):
+         graph_steps=None, shard_invariant=False, loss=None):
     """common_sde.main (common_sde.py:248-298): build, train, evaluate; `num_classes=None` trains a regression model with
     the mean-squared error (the forecasting benchmark).  Results are written only when `name` and `results_dir` are set.
     graph_steps: replay the training step from a CUDA/HIP graph (GraphedStep) - the step of these models is bound by the host
     (whole-model neurallnsde step: 1.43 ms eager, 0.88 ms replayed, 0.61 ms for its solve).  None (default) = wherever it is eligible:
     one process, CUDA device; False = eager steps; True = required where eligible (still eager under DDP / on the CPU).
     shard_invariant (default off): every solve passes options={'global_rows': 'world'} - under a process group the kernels are
-    planned for world_size x the local batch, so each rank's rows evolve as they would in the unsharded batch on one device."""
+    planned for world_size x the local batch, so each rank's rows evolve as they would in the unsharded batch on one device.
+    loss: a callable loss(pred, true) that replaces the default base loss (e.g. `crps_loss(S)` for a model solved with
+    options={'samples': S}); the weight regulariser is added to it as to the default."""
     device = torch.device(device)
     if shard_invariant:
         kwargs = dict(kwargs, options=dict(kwargs.get('options') or {}, global_rows='world'))
@@ -366,6 +389,8 @@ def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloa
         base_loss = torch.nn.functional.mse_loss
     else:
         base_loss = torch.nn.functional.cross_entropy
+    if loss is not None:
+        base_loss = loss
     loss_fn = add_weight_regularisation(base_loss, regularise_parameters, mode=regularise)
     model.to(device)
     dist = _world()
