@@ -693,29 +693,23 @@ int snsde_eval_fg(const snsde_solve* s, const float* step_row, const float* y, f
 int snsde_act_slots(const snsde_model* m) {
     int rc = validate_model(m);
     if (rc) return rc;
-    const int nn = snsde_noise_net_layers(m->noise_option);   // + the diffusion net's activations (hidden for 18/19, output)
-    // smooth activations (tutorial fields): the pre-activations of the NL activated layers as well (their derivative)
-    // (+ the hidden pre-activation of a two-layer diffusion net, the last slot)
-    return m->num_hidden_layers + 1 + nn + (m->activation != SNSDE_ACT_RELU ? m->num_hidden_layers + (nn == 2 ? 1 : 0) : 0);
+    // (the per-step count of a one-pass method: snsde_save_layout adds what SRK saves for its fourth evaluation)
+    return snsde_save::nsave(m->num_hidden_layers - 1, snsde_noise_net_layers(m->noise_option), SNSDE_EULER, m->activation != SNSDE_ACT_RELU);
 }
 
 int snsde_save_layout(const snsde_solve* s, int32_t* act_slots, int32_t* stage_planes, int32_t* delta_slots) {
     if (!s) return SNSDE_ERR_NULL;
     if (s->struct_size != sizeof(snsde_solve)) return SNSDE_ERR_ABI;
-    int slots = snsde_act_slots(&s->model);
-    if (slots < 0) return slots;
+    int rc = validate_model(&s->model);
+    if (rc) return rc;
     if (!global_rows_ok(s)) return SNSDE_ERR_DIMS;
-    const int nn = snsde_noise_net_layers(s->model.noise_option);
-    int planes = 1;
-    if (s->method == SNSDE_SRK && nn > 0) {
-        slots += nn; planes = 3;
-        if (nn == 2 && s->model.activation != SNSDE_ACT_RELU) slots += 1;      // (+ the fourth evaluation's hidden pre-activation)
-    }
+    const int nhid = s->model.num_hidden_layers - 1, nn = snsde_noise_net_layers(s->model.noise_option);
+    const bool smooth = s->model.activation != SNSDE_ACT_RELU;
+    const int slots = snsde_save::nsave(nhid, nn, s->method, smooth), planes = snsde_save::stage_planes(nn, s->method);
     if (act_slots) *act_slots = slots;
     if (stage_planes) *stage_planes = planes;
-    // Milstein through a diffusion net: the adjoint also leaves the tangent pass's factors (second-order parameter terms)
     if (delta_slots) {
-        *delta_slots = slots + ((s->method == SNSDE_MILSTEIN && nn > 0) ? (nn == 2 ? 3 : 1) : 0);
+        *delta_slots = slots + snsde_save::milstein_slots(nn, s->method);      // (act_save's count + Milstein's factors: snsde_save_layout.h)
         // 0: the adjoint of this solve accumulates the weight gradients itself (wave-pair adjoint, snsde_w4_kernel.h): no delta planes
         SnsdeNet net;
         if (nn > 0 && s->batch > 0 && s->n_steps > 0 && snsde_build_net(s->model, s->n_steps, &net) == SNSDE_OK) {

@@ -1,7 +1,7 @@
 // Gradient of the fused solve with respect to the control path (include/snsde.h: snsde_coeff_gradients), gfx950.
 //
 // X(t) enters the drift's first layer only, and linearly: with delta_p (B, H) = dL/d(pre-activation of the first rectified layer)
-// at drift pass p (delta_save slot nhid + 1, the slot the weight-gradient pass reads for the folded first layer) and
+// at drift pass p (delta_save slot snsde_save::delta_first, the one the weight-gradient pass reads for the folded first layer) and
 //     M (H, C) = emb.weight[:, H:] . initial_network.weight   (input_option 2 / 4 / 6),   initial_network.weight   (input_option 0)
 // the cotangent of X(t_p) is v_p = delta_p . M (B, C), and the spline a + (b + (two_c / 2 + three_d r / 3) r) r spreads it over
 // the four coefficient blocks of the pass's interval k_p with the weights phi(r_p) = (1, r, r^2 / 2, r^3 / 3):
@@ -268,7 +268,7 @@ int snsde_cgrad_launch(const snsde_backward* b, const SnsdeNet& net, int delta_s
     const bool emb = io == 2 || io == 4 || io == 6;
     const int nhid = s.model.num_hidden_layers - 1;
     if (!snsde_cgrad_reads_x(s.model) || !net.init.present || (emb && !net.emb.present)) return SNSDE_ERR_UNSUPPORTED;
-    if (H % 4 != 0 || nhid + 1 >= delta_slots) return SNSDE_ERR_UNSUPPORTED;
+    if (H % 4 != 0 || snsde_save::delta_first(nhid) >= delta_slots) return SNSDE_ERR_UNSUPPORTED;
     const int CC = chunk_channels(H, C);
     if (CC < 1) return SNSDE_ERR_LDS;
     CArgs a{};
@@ -276,7 +276,7 @@ int snsde_cgrad_launch(const snsde_backward* b, const SnsdeNet& net, int delta_s
     a.M = ws; a.v = ws + m_floats(s); a.grad = grad_coeffs;
     a.srk = s.method == SNSDE_SRK ? 1 : 0;
     a.P = s.n_steps * (a.srk ? 3 : 1);
-    a.B = s.batch; a.H = H; a.C = C; a.Lm1 = s.knots - 1; a.NG = delta_slots; a.slot = nhid + 1;
+    a.B = s.batch; a.H = H; a.C = C; a.Lm1 = s.knots - 1; a.NG = delta_slots; a.slot = snsde_save::delta_first(nhid);
     a.S = snsde_samples(&s);
     if (a.B % a.S != 0) return SNSDE_ERR_DIMS;
     if (a.S > 1 && C > WNT) return SNSDE_ERR_UNSUPPORTED;      // (walk_groups: a lane per channel of a row; the MFMA paths stop at C = 80)

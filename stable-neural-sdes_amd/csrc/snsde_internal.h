@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "snsde.h"
+#include "snsde_save_layout.h"
 
 #define SNSDE_MAX_HIDDEN 8  // NL-1 <= 8 (`linears`, neuralsde.py:156-157; the reference sweeps NL 1..4)
 

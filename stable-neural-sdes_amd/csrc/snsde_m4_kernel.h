@@ -49,9 +49,9 @@ struct CfgL {
     static constexpr int LDX = ld_for(16 * (KUXT > 0 ? KUXT : 1), 16);
     static constexpr int LDA = LDY;
     static constexpr int NLAYER = NHID + 2;                   // bias rows: first, hidden.., out
-    static constexpr int NSAVE = NHID + 2 + (SWISH ? NHID + 1 : 0);   // outputs: first, hidden.., pre-tanh drift [, the pre-activations]
-    static constexpr int ZSLOT = NHID + 1;
-    static constexpr int PRE0 = NHID + 2;                     // SWISH: slot of the first layer's pre-activation (then hidden..)
+    static constexpr int NSAVE = snsde_save::nsave(NHID, 0, SNSDE_EULER, SWISH);      // act_save slots per step (snsde_save_layout.h)
+    static constexpr int ZSLOT = snsde_save::act_z(NHID);
+    static constexpr int PRE0 = snsde_save::act_pre(NHID, 0, SNSDE_EULER, 0);      // SWISH: slot of the first layer's pre-activation (then hidden..)
     static constexpr int ZB = 4;                              // Philox calls generated together per element
     static constexpr int ZSTASH = 4 * ZB * 64;                // floats per wave
     static constexpr int ROWCH = 128;
@@ -948,7 +948,7 @@ __global__ void __launch_bounds__(CF::NT, lean_spec<CF>::value ? LEAN_SPEC_WPS :
         vm_wait(dw_nxt, gt_nxt);      // this step's prefetches (issued one to three phases ago)
         float z = m4_reduce_scatter(c + d);
         if constexpr (SAVE) {      // the saved pre-tanh drift carries the step's relu signs in its low NHID + 1 bits (the adjoint's masks)
-            if (a.act_save && row_ok) lean_gstore(CF::SWISH ? z : snsde_pack_signs(z, sgn, NHID + 1), goff4, act_n + uoff(0, 0, CF::ZSLOT, (uint32_t)BH));
+            if (a.act_save && row_ok) lean_gstore(CF::SWISH ? z : snsde_pack_signs(z, sgn, snsde_save::drift_sign_bits(NHID)), goff4, act_n + uoff(0, 0, CF::ZSLOT, (uint32_t)BH));
         }
         if (__builtin_expect(geo, 0)) z *= fast_tanh(yv);
         float f;

@@ -123,9 +123,9 @@ struct CfgN {
     static constexpr int LDY = ld_for(16 * KUY, PAD), LDX = EMB ? ld_for(16 * KUX, PAD) : 0, LDA = ld_for(16 * KUH, PAD);
     static constexpr int NLAYER = NHID + 2 + NN;                      // bias rows: first, hidden.., out, net..
     static constexpr int XI = EMB ? (M * 16 * KUX + NT - 1) / NT : 1;
-    static constexpr int ZSLOT = NHID + 1;                            // act_save slot of the pre-tanh drift
-    static constexpr int NSAVE = NHID + 2 + (SRK ? 2 * NN : NN);      // + net hidden / output (SRK: and the tail evaluation's)
-    static constexpr int NPLANE = SRK ? 3 : 1;                        // stage_save planes per pass: H0 | H1 | H1_3
+    static constexpr int ZSLOT = snsde_save::act_z(NHID);             // act_save slot of the pre-tanh drift (snsde_save_layout.h)
+    static constexpr int NSAVE = snsde_save::act_slots(NHID, NN, METHOD);
+    static constexpr int NPLANE = snsde_save::stage_planes(NN, METHOD);                   // stage_save planes per pass: H0 | H1 | H1_3
     static constexpr int ROWCH = 48;                                  // step-table rows staged in LDS (multiple of 3)
     static constexpr int NNET = m4n_net_count(NN, METHOD);
     static constexpr int NMAT = m4n_nmat(KUX, NHID, NN, METHOD);
@@ -324,14 +324,13 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
         if (__builtin_expect(g_raw, 0)) return raw;
         return fast_tanh(sig_theta * snsde_nan_to_num(raw));
     };
-    // smooth activations (field variants): the NL drift pre-activations and the net's hidden pre-activation follow the regular slots
-    // (snsde_act_slots); SRK: per pass, + the hidden pre-activation of the step's fourth evaluation (pass 3n + 2) in one more slot
-    const int nsave_rt = act_fn != 0 ? NSAVE + NHID + 1 + (NN == 2 ? (SRK ? 2 : 1) : 0) : NSAVE;
+    // smooth activations (field variants): the pre-activations follow the regular slots
+    const int nsave_rt = act_fn != 0 ? snsde_save::nsave(NHID, NN, CF::METHOD, true) : NSAVE;
     auto save_act = [&](int pass, int slot, float v) {
         if (a.act_save && row_ok) (a.act_save + uoff(pass, (uint32_t)nsave_rt * (uint32_t)BH, slot, (uint32_t)BH))[(uint32_t)(row * H + fcol)] = v;
     };
-    auto save_pre = [&](int pass, int idx, float v) {      // idx: drift layer 0 .. NHID, NHID + 1 = the net's hidden layer (SRK: + 2 = the tail's)
-        if (act_fn != 0) save_act(pass, NSAVE + idx, v);
+    auto save_pre = [&](int pass, int idx, float v) {      // idx: drift layer 0 .. NHID, pre_net = the net's hidden layer (SRK: pre_tail = the tail's)
+        if (act_fn != 0) save_act(pass, snsde_save::act_pre(NHID, NN, CF::METHOD, idx), v);
     };
     // one net evaluation's layer 1 (reads gyrow): NN == 2 -> relu'd hidden into nbuf (returned); NN == 1 -> the output q
     auto net_l1 = [&](int pass, int slot0, float& q) {
@@ -342,7 +341,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
         if constexpr (NN == 2) {
             o = actf(o);
             nbuf[r * LDA + fcol] = o;
-            save_pre(pass, slot0 == CF::ZSLOT + 1 ? NHID + 1 : NHID + 2, pre);
+            save_pre(pass, slot0 == snsde_save::act_net(NHID, 0) ? snsde_save::pre_net(NHID) : snsde_save::pre_tail(NHID), pre);
         } else {
             q = o;
         }
@@ -397,11 +396,11 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
             save_pre(n, 0, pre);
             sgn = o > 0.0f ? 1u : 0u;      // relu signs of this lane's element (Euler: folded into the saved z, snsde_pack_signs)
         }
-        const float nhid_own = net_l1(n, CF::ZSLOT + 1, q);      // (NN == 2: this lane's hidden pre-activation of the net)
-        if constexpr ((SRK || MIL) && NN == 2) sgn |= (nhid_own > 0.0f ? 1u : 0u) << (NHID + 1);      // SRK / Milstein: the net's hidden sign rides in z as well
+        const float nhid_own = net_l1(n, snsde_save::act_net(NHID, 0), q);      // (NN == 2: this lane's hidden pre-activation of the net)
+        if constexpr ((SRK || MIL) && NN == 2) sgn |= (nhid_own > 0.0f ? 1u : 0u) << snsde_save::net_sign_bit(NHID);      // SRK / Milstein: the net's hidden sign rides in z as well
         __syncthreads();
         // ---- phase 1: net output; increments; next pass's control values / time features ----
-        if constexpr (NN == 2) net_l2(n, CF::ZSLOT + 2, q);
+        if constexpr (NN == 2) net_l2(n, snsde_save::act_net(NHID, 1), q);
         if constexpr (SRK) {
             if (stage == 0) {
                 if (phx) {
@@ -507,11 +506,9 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
         }
         // Euler on these kernels is differentiated by snsde_mfma_reverse_kernel, which takes the relu masks of the drift chain from z.
         // SRK (snsde_m4n_rev_kernel.h): every pass's z carries the pass's drift signs, the hidden sign of the net evaluation beside it
-        // (bit NHID + 1) and - pass 3n + 2 - of the step's fourth evaluation (bit NHID + 2, known after the tail: stored there)
-        constexpr int SRK_BITS = NHID + 1 + (NN == 2 ? 2 : 0);
-        if (CF::METHOD == SNSDE_EULER) save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, NHID + 1) : z);
-        else if (MIL) save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, NHID + 1 + (NN == 2 ? 1 : 0)) : z);      // (snsde_m4n_mil_rev_kernel.h)
-        else if (stage != 2) save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, SRK_BITS) : z);
+        // and - pass 3n + 2 - of the step's fourth evaluation (known after the tail: stored there).  Milstein: snsde_m4n_mil_rev_kernel.h
+        constexpr int Z_BITS = snsde_save::sign_bits(NHID, NN, CF::METHOD);
+        if (!SRK || stage != 2) save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, Z_BITS) : z);
 
         // ---- f, g and the update (own element) ----
         const float yin = SRK ? sk_y : yv;         // (the drift pass's input state is yv)
@@ -574,11 +571,11 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_kernel(MfmaArgs a) 
                 __syncthreads();
                 // ---- tail: G3 = g(t0 + h/4, H1_3) ----
                 float q3 = 0.0f;
-                const float nh3 = net_l1(n, CF::ZSLOT + NN + 1, q3);
-                if constexpr (NN == 2) sgn |= (nh3 > 0.0f ? 1u : 0u) << (NHID + 2);
-                save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, SRK_BITS) : z);
+                const float nh3 = net_l1(n, snsde_save::act_tail(NHID, NN, 0), q3);
+                if constexpr (NN == 2) sgn |= (nh3 > 0.0f ? 1u : 0u) << snsde_save::tail_sign_bit(NHID);
+                save_act(n, CF::ZSLOT, act_fn == 0 ? snsde_pack_signs(z, sgn, Z_BITS) : z);
                 __syncthreads();
-                if constexpr (NN == 2) net_l2(n, CF::ZSLOT + NN + 2, q3);
+                if constexpr (NN == 2) net_l2(n, snsde_save::act_tail(NHID, NN, 1), q3);
                 if (tid < M) { gybuf[tid * LDY + H] = nxt.nsn; gybuf[tid * LDY + H + 1] = nxt.ncs; }
                 const float g3 = gfun(q3, h1n);
                 const float f1 = sk_f1, g1 = sk_g1, g2 = sk_g2, ik = sk_dw, ik0 = sk_du;

@@ -40,10 +40,9 @@ struct CfgNM {
     static constexpr int NW = H / 16, NT = NW * 64, WPS = NW >= 8 ? NW / 4 : 2, M = 4;
     static constexpr int KUH = H / 16, LDA = ld_for(16 * KUH, 16);
     static constexpr int ND = NHID + 2, NMAT = m4nm_nmat(NHID, NN);
-    static constexpr int NSAVE = NHID + 2 + NN;                       // act_save slots per step
-    static constexpr int NEXTRA = NN == 2 ? 3 : 1;                    // eps2, eps1, hdot | eps
-    static constexpr int NDELTA = NSAVE + NEXTRA;                     // delta_save slots per step
-    static constexpr int ZSLOT = NHID + 1, NB0 = NHID + 2;
+    static constexpr int NSAVE = snsde_save::act_slots(NHID, NN, SNSDE_MILSTEIN);       // act_save slots per step (snsde_save_layout.h)
+    static constexpr int NDELTA = snsde_save::delta_slots(NHID, NN, SNSDE_MILSTEIN);    // delta_save slots per step
+    static constexpr int ZSLOT = snsde_save::act_z(NHID), NB0 = snsde_save::delta_net(NHID, 0);
     static constexpr int NLDS = m4nm_nlds(H, NHID, NN);
     static constexpr bool FITS = NLDS >= 0;
     static constexpr bool in_lds(int i) { return i >= 0 && i < NMAT && i >= NMAT - NLDS; }
@@ -133,20 +132,20 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_mil_reverse_kernel(
     // (round 4: the relu masks - drift chain, the net's hidden layer - are sign bits in the low mantissa bits of the saved z)
     struct StepIn { float y, z, dw, q; float h; int nout, kfirst; };
     struct PreIn { float dpre[NHID + 1], npre; };      // VAR, smooth activations: pre-activations of the drift layers / the net's hidden layer
-    constexpr int MIL_BITS = NHID + 1 + (NN == 2 ? 1 : 0);
+    constexpr int MIL_BITS = snsde_save::sign_bits(NHID, NN, SNSDE_MILSTEIN);
     auto fetch = [&](int n, StepIn& p, PreIn& pp) {
         const size_t so = uoff(n, BH32) + goff;
         const float* ap = a.act + uoff(n, ASL) + goff;
         if constexpr (VAR) {
             if (smooth) {      // (wave-uniform)
 #pragma unroll
-                for (int k = 0; k <= NHID; ++k) pp.dpre[k] = ap[(size_t)(NSAVE + k) * BH];
-                pp.npre = NN == 2 ? ap[(size_t)(NSAVE + NHID + 1) * BH] : 0.0f;
+                for (int k = 0; k <= NHID; ++k) pp.dpre[k] = ap[(size_t)snsde_save::act_pre(NHID, NN, SNSDE_MILSTEIN, k) * BH];
+                pp.npre = NN == 2 ? ap[(size_t)snsde_save::act_pre(NHID, NN, SNSDE_MILSTEIN, snsde_save::pre_net(NHID)) * BH] : 0.0f;
             }
         }
         p.y = a.traj[so]; p.dw = a.dW[so];
         p.z = ap[(size_t)ZSLOT * BH];
-        p.q = ap[(size_t)(ZSLOT + NN) * BH];
+        p.q = ap[(size_t)snsde_save::act_net_out(NHID, NN) * BH];
         const float* stp = a.step_tab + uoff(n, SNSDE_STEP_STRIDE);
         p.h = stp[1]; p.nout = __float_as_int(stp[8]); p.kfirst = __float_as_int(stp[9]);
     };
@@ -169,7 +168,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_mil_reverse_kernel(
         const float av = adj, y = cur.y, dw = cur.dw, q = cur.q;
         const uint32_t zb = __builtin_bit_cast(uint32_t, cur.z);
         const float zc = smooth ? cur.z : __builtin_bit_cast(float, zb & ~((1u << MIL_BITS) - 1u));      // z with its sign bits cleared (smooth: saved as it is)
-        const bool h1pos = NN == 2 && ((zb >> (NHID + 1)) & 1u) != 0;                       // [h1 > 0]: the net's hidden mask
+        const bool h1pos = NN == 2 && ((zb >> snsde_save::net_sign_bit(NHID)) & 1u) != 0;                       // [h1 > 0]: the net's hidden mask
         // VAR, smooth: act' of the drift layers, act' and act'' of the net's hidden layer (x sigma(x) family: act'' = c s (1 - s)(2 + x (1 - 2 s)))
         float dfac[NHID + 1], nf1 = 0.0f, nf2 = 0.0f;
 #pragma unroll
@@ -240,7 +239,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_mil_reverse_kernel(
             if constexpr (NN == 2) { if (!net_lin) { cq = q > 0.0f ? cq : 0.0f; cqd = q > 0.0f ? cqd : 0.0f; } }      // (VAR: the net may end in its linear layer)
             bRA[lrow] = cq;
             put_delta(n, NB0, cq);
-            put_delta(n, NSAVE, cqd);                 // eps2 (NN = 2) / eps (NN = 1): left factor of the second-order term
+            put_delta(n, snsde_save::delta_eps2(NHID, NN), cqd);                 // eps2 (NN = 2) / eps (NN = 1): left factor of the second-order term
             if constexpr (NN == 2) bRB[lrow] = cqd;
         };
         if constexpr (NN == 2) {
@@ -254,7 +253,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_mil_reverse_kernel(
                 float hd = h1pos ? hd_all : 0.0f;
                 if constexpr (VAR) { if (smooth) hd = nf1 * hd_all; }
                 bTB[lrow] = hd;
-                put_delta(n, NSAVE + 2, hd);
+                put_delta(n, snsde_save::delta_hdot(NHID, NN), hd);
             }
             __syncthreads();
             // phase 2: drift 1 || qdot = [q > 0] W2 hdot, then the cotangents
@@ -284,8 +283,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_mil_reverse_kernel(
                     }
                 }
                 bRC[lrow] = d1;
-                put_delta(n, NB0 + 1, d1);
-                put_delta(n, NSAVE + 1, e1);
+                put_delta(n, snsde_save::delta_net(NHID, 1), d1);
+                put_delta(n, snsde_save::delta_eps1(NHID, NN), e1);
             }
             __syncthreads();
             // phase 4: drift 3 || dy = W1_y^T delta1

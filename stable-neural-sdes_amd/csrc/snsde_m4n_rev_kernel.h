@@ -8,9 +8,8 @@
 // out^T -> [relu] -> hid^T .. -> first_y^T on pass 3n + s.  A net chain and the drift chain written beside it are
 // independent (SRID2's stage dependencies, see the comments in the step loop) and share their barriers.  F_s, G_e, H0_s,
 // H1_e are recomputed per lane from y_n, the saved pre-tanh drifts / net outputs and (I_k, I_k0); relu masks come from the
-// forward's act_save.  Left for snsde_param_gradients: the per-layer deltas of every pass (delta_save: drift slots 0 ..
-// NHID + 1, net slots NHID + 2 .., the step's fourth evaluation in a second set of net slots at pass 3n + 2) and the
-// per-workgroup sums of dL/d sigmoid(theta).
+// forward's act_save.  Left for snsde_param_gradients: the per-layer deltas of every pass (delta_save, slots as in
+// snsde_save_layout.h) and the per-workgroup sums of dL/d sigmoid(theta).
 // Weights as in the forward: what does not fit the register budget is parked in the wave's private LDS slice.
 #pragma once
 #include "snsde_m4n_kernel.h"
@@ -38,8 +37,9 @@ struct CfgNR {
     static constexpr int NW = H / 16, NT = NW * 64, WPS = NW >= 8 ? NW / 4 : 2, M = 4;
     static constexpr int KUH = H / 16, LDA = ld_for(16 * KUH, 16);
     static constexpr int ND = NHID + 2, NMAT = ND + NN;
-    static constexpr int NSLOT = NHID + 2 + 2 * NN;       // act_save / delta_save slots per pass
-    static constexpr int ZSLOT = NHID + 1, NB0 = NHID + 2;
+    static constexpr int NSLOT = snsde_save::act_slots(NHID, NN, SNSDE_SRK);       // act_save / delta_save slots per pass
+    static_assert(NSLOT == snsde_save::delta_slots(NHID, NN, SNSDE_SRK), "one stride for both planes");
+    static constexpr int ZSLOT = snsde_save::act_z(NHID), NB0 = snsde_save::delta_net(NHID, 0);
     static constexpr int NLDS = m4nr_nlds(H, NHID, NN);
     static constexpr bool FITS = NLDS >= 0;
     static constexpr bool in_lds(int i) { return i >= 0 && i < NMAT && i >= NMAT - NLDS; }
@@ -126,7 +126,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_srk_reverse_kernel(
     // VAR, smooth activations: pre-activations of the drift passes / the net's hidden layers (their own struct: members a flavour never
     // touches would travel through scratch with every cur = nxt, see snsde_mfma_reverse_kernel)
     struct PreIn { float dpre[3][NHID + 1], npre[4]; };
-    constexpr int SRK_BITS = NHID + 1 + (NN == 2 ? 2 : 0);
+    constexpr int SRK_BITS = snsde_save::sign_bits(NHID, NN, SNSDE_SRK);
     auto fetch = [&](int n, StepIn& p, PreIn& pp) {
         const size_t so = uoff(n, BH32) + goff;
         p.y = a.traj[so]; p.ik = a.dW[so]; p.ik0 = a.dU[so];
@@ -134,15 +134,15 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_srk_reverse_kernel(
         for (int st = 0; st < 3; ++st) {
             const float* ap = a.act + uoff(3 * n + st, ASL) + goff;
             p.z[st] = ap[(size_t)ZSLOT * BH];
-            p.q[st] = ap[(size_t)(ZSLOT + NN) * BH];
-            if (st == 2) p.q[3] = ap[(size_t)(ZSLOT + 2 * NN) * BH];
+            p.q[st] = ap[(size_t)snsde_save::act_net_out(NHID, NN) * BH];
+            if (st == 2) p.q[3] = ap[(size_t)snsde_save::act_tail_out(NHID, NN) * BH];
             if constexpr (VAR) {
                 if (smooth) {      // (wave-uniform)
 #pragma unroll
-                    for (int k = 0; k <= NHID; ++k) pp.dpre[st][k] = ap[(size_t)(NSLOT + k) * BH];
+                    for (int k = 0; k <= NHID; ++k) pp.dpre[st][k] = ap[(size_t)snsde_save::act_pre(NHID, NN, SNSDE_SRK, k) * BH];
                     if constexpr (NN == 2) {
-                        pp.npre[st] = ap[(size_t)(NSLOT + NHID + 1) * BH];
-                        if (st == 2) pp.npre[3] = ap[(size_t)(NSLOT + NHID + 2) * BH];
+                        pp.npre[st] = ap[(size_t)snsde_save::act_pre(NHID, NN, SNSDE_SRK, snsde_save::pre_net(NHID)) * BH];
+                        if (st == 2) pp.npre[3] = ap[(size_t)snsde_save::act_pre(NHID, NN, SNSDE_SRK, snsde_save::pre_tail(NHID)) * BH];
                     }
                 }
             }
@@ -306,14 +306,14 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_srk_reverse_kernel(
 
         // ---- G3 = g(t0 + h/4, H1_3): the tail evaluation (second set of net slots of pass 3n + 2) ----
         float qb = net_in(gb3, om3, rc3, fi3, cur.q[3], h13, nd);
-        chains(false, 0, 0.0f, zb[2], true, 3 * n + 2, NB0 + NN, qb, ((zb[2] >> (NHID + 2)) & 1u) != 0, dres, nres, nullptr, nf[3]);
+        chains(false, 0, 0.0f, zb[2], true, 3 * n + 2, snsde_save::delta_tail(NHID, NN, 0), qb, ((zb[2] >> snsde_save::tail_sign_bit(NHID)) & 1u) != 0, dres, nres, nullptr, nf[3]);
         float hb = nres + nd;
         yb += hb; fb2 = fmaf(0.25f * h, hb, fb2);
         gb0 = fmaf(SRK_B1_30 * rdt, hb, gb0); gb1 = fmaf(SRK_B1_31 * rdt, hb, gb1); gb2 = fmaf(SRK_B1_32 * rdt, hb, gb2);
         // ---- G2 = g(t0 + h, H1_2) beside the drift at (t0 + h/2, H0_2) ----
         qb = net_in(gb2, om2, rc2, fi2, cur.q[2], h12, nd);
         float dz = drift_in(fb2, f2, zc[2], h02, dd);
-        chains(true, 3 * n + 2, dz, zb[2], true, 3 * n + 2, NB0, qb, ((zb[2] >> (NHID + 1)) & 1u) != 0, dres, nres, df[VAR ? 2 : 0], nf[2]);
+        chains(true, 3 * n + 2, dz, zb[2], true, 3 * n + 2, NB0, qb, ((zb[2] >> snsde_save::net_sign_bit(NHID)) & 1u) != 0, dres, nres, df[VAR ? 2 : 0], nf[2]);
         hb = nres + nd;
         float d = dres + dd;
         yb += hb; fb0 = fmaf(h, hb, fb0); gb0 = fmaf(SRK_B1_20 * rdt, hb, gb0);
@@ -323,7 +323,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_srk_reverse_kernel(
         // ---- G1 = g(t0 + h/4, H1_1) beside the drift at (t0 + h, H0_1) ----
         qb = net_in(gb1, om1, rc1, fi1, cur.q[1], h11, nd);
         dz = drift_in(fb1, f1, zc[1], h01, dd);
-        chains(true, 3 * n + 1, dz, zb[1], true, 3 * n + 1, NB0, qb, ((zb[1] >> (NHID + 1)) & 1u) != 0, dres, nres, df[VAR ? 1 : 0], nf[1]);
+        chains(true, 3 * n + 1, dz, zb[1], true, 3 * n + 1, NB0, qb, ((zb[1] >> snsde_save::net_sign_bit(NHID)) & 1u) != 0, dres, nres, df[VAR ? 1 : 0], nf[1]);
         hb = nres + nd;
         d = dres + dd;
         yb += hb; fb0 = fmaf(0.25f * h, hb, fb0); gb0 = fmaf(SRK_B1_10 * rdt, hb, gb0);
@@ -331,7 +331,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_m4n_srk_reverse_kernel(
         // ---- G0 and F0, both at (t0, y) ----
         qb = net_in(gb0, om0, rc0, fi0, cur.q[0], y, nd);
         dz = drift_in(fb0, f0, zc[0], y, dd);
-        chains(true, 3 * n, dz, zb[0], true, 3 * n, NB0, qb, ((zb[0] >> (NHID + 1)) & 1u) != 0, dres, nres, df[0], nf[0]);
+        chains(true, 3 * n, dz, zb[0], true, 3 * n, NB0, qb, ((zb[0] >> snsde_save::net_sign_bit(NHID)) & 1u) != 0, dres, nres, df[0], nf[0]);
         adj = yb + (nres + nd) + (dres + dd);
         cur = nxt;
         if constexpr (VAR) { if (smooth) curp = nxtp; }

@@ -29,7 +29,7 @@ struct CfgS2 {
     static constexpr int LDY = ld_for(16 * KUH, 16);
     static constexpr int LDX = ld_for(16 * (KUXT > 0 ? KUXT : 1), 16);
     static constexpr int LDA = LDY;
-    static constexpr int NLAYER = NHID + 2, NSAVE = NHID + 2, ZSLOT = NHID + 1;
+    static constexpr int NLAYER = NHID + 2, NSAVE = snsde_save::act_slots(NHID, 0, SNSDE_EULER), ZSLOT = snsde_save::act_z(NHID);
     static constexpr int ROWCH = 128, RS = 8;
     static constexpr int RK = 4;                              // resident k-blocks per streamed layer and tile
     static constexpr int NS = KUH - RK;                       // streamed k-blocks per layer and tile
@@ -455,7 +455,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_kernel(MfmaArgs a) {
             float z = m4_reduce_scatter(c[j] + d[j]) + lbias[(NHID + 1) * H + fo[j]];
             if constexpr (SAVE) {      // the saved pre-tanh drift carries the step's relu signs in its low NHID + 1 bits (the adjoint's masks)
                 if (a.act_save && row_ok)
-                    lean_gstore(snsde_pack_signs(z, sgn[j], NHID + 1), goff4[j], a.act_save + ((size_t)n * CF::NSAVE + CF::ZSLOT) * BH);
+                    lean_gstore(snsde_pack_signs(z, sgn[j], snsde_save::drift_sign_bits(NHID)), goff4[j], a.act_save + ((size_t)n * CF::NSAVE + CF::ZSLOT) * BH);
             }
             if (__builtin_expect(geo, 0)) z *= fast_tanh(yv[j]);
             float f;

@@ -20,7 +20,7 @@ struct CfgS2R {
     static constexpr bool GEO = GEO_ != 0;
     static constexpr int NW = 8, NT = 512, KUH = 16, TPW = 2, M = 4;
     static constexpr int LDA = ld_for(16 * KUH, 16);
-    static constexpr int ND = NHID + 2, NG = ND, NBUF = NHID + 2, NSAVE = NHID + 2, ZSLOT = NHID + 1;
+    static constexpr int ND = NHID + 2, NG = ND, NBUF = snsde_save::delta_slots(NHID, 0, SNSDE_EULER), NSAVE = snsde_save::act_slots(NHID, 0, SNSDE_EULER), ZSLOT = snsde_save::act_z(NHID);
     static constexpr int ROWCH = 128;
     static constexpr int RK = 4, NS = KUH - RK, R = 6;
     static constexpr int RING0 = NBUF * M * LDA + (ROWCH + 1) * SNSDE_STEP_STRIDE;      // multiple of 4 floats
@@ -159,7 +159,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_reverse_kernel(RevArgs a
         // ---- elementwise: d(f h + g dW)/d(zout, y) applied to the adjoint (the general kernel's reference-field branch) ----------------
         float ay[2], dz[2], dsv[2];
         uint32_t zb[2];
-        const uint32_t zclear = ~((1u << (NHID + 1)) - 1u);
+        const uint32_t zclear = ~((1u << snsde_save::drift_sign_bits(NHID)) - 1u);
 #pragma unroll
         for (int j = 0; j < 2; ++j) {
             dsv[j] = 0.0f;

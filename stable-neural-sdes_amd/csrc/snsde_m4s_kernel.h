@@ -34,7 +34,7 @@ struct CfgS {
     static constexpr int LDY = ld_for(16 * KUH, 16);
     static constexpr int LDX = ld_for(16 * (KUXT > 0 ? KUXT : 1), 16);
     static constexpr int LDA = LDY;
-    static constexpr int NLAYER = NHID + 2, NSAVE = NHID + 2, ZSLOT = NHID + 1;
+    static constexpr int NLAYER = NHID + 2, NSAVE = snsde_save::act_slots(NHID, 0, SNSDE_EULER), ZSLOT = snsde_save::act_z(NHID);
     static constexpr int ROWCH = 128, RS = 8;
     static constexpr int XI = 1;                              // 4 rows x (<= 48 columns) spread over 1024 lanes
     static constexpr int R = 8, CH = 2;                       // ring slots per wave; k-blocks consumed (and refilled) together
@@ -307,7 +307,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s_kernel(MfmaArgs a) {
         if constexpr (SAVE) {      // the saved pre-tanh drift carries the step's relu signs in its low NHID + 1 bits (the adjoint's masks)
             if (a.act_save && row_ok) {
                 if constexpr (!CF::SWISH && NHID == 1) sgn = (*aown > 0.0f ? 1u : 0u) | (*bown > 0.0f ? 2u : 0u);
-                lean_gstore(CF::SWISH ? z : snsde_pack_signs(z, sgn, NHID + 1), goff4, a.act_save + ((size_t)n * CF::NSAVE + CF::ZSLOT) * BH);
+                lean_gstore(CF::SWISH ? z : snsde_pack_signs(z, sgn, snsde_save::drift_sign_bits(NHID)), goff4, a.act_save + ((size_t)n * CF::NSAVE + CF::ZSLOT) * BH);
             }
         }
         if (__builtin_expect(geo, 0)) z *= fast_tanh(yv);

@@ -23,7 +23,7 @@ struct CfgT {
     static constexpr int LDY = ld_for(16 * KUH, 16);
     static constexpr int LDX = ld_for(16 * (KUXT > 0 ? KUXT : 1), 16);
     static constexpr int LDA = LDY;
-    static constexpr int NLAYER = NHID + 2, NSAVE = NHID + 2, ZSLOT = NHID + 1;
+    static constexpr int NLAYER = NHID + 2, NSAVE = snsde_save::act_slots(NHID, 0, SNSDE_EULER), ZSLOT = snsde_save::act_z(NHID);
     static constexpr int ROWCH = 128, RS = 8;
     static constexpr int ZB = 4;                              // Philox calls generated together per element
     static constexpr int ZSTASH = 2 * 4 * ZB * 64;            // floats per wave: two tiles
@@ -408,7 +408,7 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4t_kernel(MfmaArgs a) {
         for (int j = 0; j < 2; ++j) {
             float z = m4_reduce_scatter(c[j] + d[j]);
             if constexpr (SAVE) {
-                if (a.act_save && row_ok) lean_gstore(snsde_pack_signs(z, sgn[j], NHID + 1), goff4[j], act_n + uoff(0, 0, CF::ZSLOT, (uint32_t)BH));
+                if (a.act_save && row_ok) lean_gstore(snsde_pack_signs(z, sgn[j], snsde_save::drift_sign_bits(NHID)), goff4[j], act_n + uoff(0, 0, CF::ZSLOT, (uint32_t)BH));
             }
             if (__builtin_expect(geo, 0)) z *= fast_tanh(yv[j]);
             float f;

@@ -835,9 +835,7 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     a.params = s->params; a.ws = ws;
     a.gt = s->noise_table ? s->noise_table : (fp.gt_off >= 0 ? static_cast<const float*>(s->workspace) + fp.gt_off : nullptr);
     a.act_fn = s->model.activation; a.f_out = s->model.drift_output; a.g_out = s->model.diffusion_output;
-    a.nsave = s->model.num_hidden_layers + 1 + fp.NN + (s->model.activation != SNSDE_ACT_RELU ? s->model.num_hidden_layers + (fp.NN == 2 ? 1 : 0) : 0);
-    if (s->method == SNSDE_SRK && fp.NN > 0)      // (snsde_save_layout: the fourth evaluation's net slots, smooth: + its hidden pre-activation)
-        a.nsave += fp.NN + ((fp.NN == 2 && s->model.activation != SNSDE_ACT_RELU) ? 1 : 0);
+    a.nsave = snsde_save::nsave(s->model.num_hidden_layers - 1, fp.NN, s->method, s->model.activation != SNSDE_ACT_RELU);
     a.step_tab = s->step_tab; a.out_w = s->out_w; a.traj = s->traj; a.act = s->act_save;
     // increments: the ones the forward wrote out, else the supplied ones, else (Philox, host key) regenerated by the kernel
     a.dW = s->dW_out ? s->dW_out : s->dW;

@@ -191,10 +191,9 @@ __device__ __forceinline__ float fast_tanh(float x) {
 
 // Relu signs inside the saved pre-tanh drift (round 4).  The MFMA adjoint needs [activation > 0] of every rectified layer output of a
 // step; it used to re-read the saved activation planes for that - two of the seven (N, B, H) planes a K2 adjoint step moves.  A lane
-// owns the SAME (row, feature) element of every layer's output and of the drift output z, so the Euler / Milstein forward kernels fold
-// the signs of that element's NHID + 1 rectified outputs (act_save slots 0 .. NHID) into the low NHID + 1 mantissa bits of the z they
-// save (slot NHID + 1; bit k = [slot k > 0]) and the adjoint takes its masks from the z it loads anyway: no extra store, load or
-// buffer.  The saved z is used for tanh'(z) only (its low <= 4 bits are noise of <= 1e-6 relative; the forward itself computes with
+// owns the SAME (row, feature) element of every layer's output and of the drift output z, so the forward kernels fold the signs of that
+// element's rectified outputs into the low mantissa bits of the z they save (snsde_save_layout.h: sign_bits) and the adjoint takes its
+// masks from the z it loads anyway: no extra store, load or buffer.  The saved z is used for tanh'(z) only (its low <= 4 bits are noise of <= 1e-6 relative; the forward itself computes with
 // the exact register value, so states are bit-identical); models with a smooth activation keep their pre-activation planes.
 __device__ __forceinline__ float snsde_pack_signs(float z, uint32_t signs, int nbits) {
     const uint32_t m = (1u << nbits) - 1u;
@@ -396,8 +395,8 @@ struct Cfg {
     static constexpr int NLAYER = (EMB && !FOLD ? 3 : 1) + NHID + 1 + NN;   // bias rows: [init, in, emb] | [first], hid.., out, noise..
     static constexpr int XI = (M * 16 * KUX + NT - 1) / NT;           // spline items per thread
     static constexpr int EPT = FL ? 1 : 4;                            // owned state elements per lane per tile
-    static constexpr int NSAVE = NHID + 2 + NN;                       // saved activations per step: z0, hidden.., zout, [noise-net hidden], [noise-net output]
-    static constexpr int ZSLOT = NHID + 1;                            // slot of the pre-tanh drift
+    static constexpr int NSAVE = snsde_save::act_slots(NHID, NN, SRK ? SNSDE_SRK : SNSDE_EULER);      // act_save slots per pass (snsde_save_layout.h)
+    static constexpr int ZSLOT = snsde_save::act_z(NHID);
     static constexpr int ZB = (FL && !STREAM && !SRK) ? 4 : 1;                     // Philox calls generated together per element
     static constexpr int ROWCH = 128;                                 // step-table rows staged in LDS per chunk
     static constexpr int ZSTASH = !SRK ? 4 * ZB * 64 * EPT : 0;  // floats per wave (Philox normals of 4*ZB steps)
@@ -560,8 +559,8 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
     // (slot + 8 i) for fragment element i on 16-row tiles; folded into the saved z and cleared at the end of the step / SRK pass
     [[maybe_unused]] uint32_t sgn = 0;
     const bool pack_signs = a.act == 0 && a.act_save != nullptr;      // (SRK: every pass's z carries the pass's signs)
-    // field variants with a smooth activation (4-row tiles): the NHID + 1 pre-activations follow the regular slots (snsde_act_slots)
-    const int nsave_rt = (FL && a.act != 0) ? CF::NSAVE + NHID + 1 : CF::NSAVE;
+    // field variants with a smooth activation (4-row tiles; with a diffusion net they run snsde_m4n_kernel.h): + the pre-activations
+    const int nsave_rt = (FL && a.act != 0) ? CF::NSAVE + snsde_save::pre_slots(NHID, 0, SNSDE_EULER, true) : CF::NSAVE;
     // M4: the layer's bias is added after the k-slot reduction, from a register (one value per lane and layer)
     float bias_own[CF::NLAYER];
 #pragma unroll
@@ -773,15 +772,15 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
                 init_acc(NROW);
                 gemm<FL, (CF::NN > 0) ? CF::KUN : 1, TPW>(wn0, yrow, acc, acc2);
                 sum_acc();
-                if constexpr (CF::NN == 2) store_frag(nbuf, LDA, wave * 16, acc[0], true, CF::ZSLOT + 1, NROW);
+                if constexpr (CF::NN == 2) store_frag(nbuf, LDA, wave * 16, acc[0], true, snsde_save::act_net(NHID, 0), NROW);
                 else {
                     gnv = acc[0];
                     if constexpr (FL) {
                         gnv[0] = finish(NROW, gnv);
                         if (a.act_save && row_ok)
-                            a.act_save[(((size_t)n * CF::NSAVE + CF::ZSLOT + 1) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
+                            a.act_save[(((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 0)) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
                     } else if (a.act_save && row_ok)
-                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + CF::ZSLOT + 1) * B + row) * H + wave * 16 + fsub) = gnv;
+                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 0)) * B + row) * H + wave * 16 + fsub) = gnv;
                 }
             }
             TRACE(3)
@@ -795,12 +794,12 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
                 if constexpr (FL) {
                     gnv[0] = fmaxf(finish(CF::NLAYER - 1, gnv), 0.0f);
                     if (a.act_save && row_ok)
-                        a.act_save[(((size_t)n * CF::NSAVE + CF::ZSLOT + 2) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
+                        a.act_save[(((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 1)) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) gnv[i] = fmaxf(gnv[i], 0.0f);
                     if (a.act_save && row_ok)
-                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + CF::ZSLOT + 2) * B + row) * H + wave * 16 + fsub) = gnv;
+                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 1)) * B + row) * H + wave * 16 + fsub) = gnv;
                 }
             }
             cur = arow;
@@ -825,15 +824,15 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
                 init_acc(NROW);
                 gemm<FL, (CF::NN > 0) ? CF::KUN : 1, TPW>(wn0, yrow, acc, acc2);
                 sum_acc();
-                if constexpr (CF::NN == 2) store_frag(nbuf, LDA, wave * 16, acc[0], true, CF::ZSLOT + 1, NROW);
+                if constexpr (CF::NN == 2) store_frag(nbuf, LDA, wave * 16, acc[0], true, snsde_save::act_net(NHID, 0), NROW);
                 else {
                     gnv = acc[0];
                     if constexpr (FL) {
                         gnv[0] = finish(NROW, gnv);
                         if (a.act_save && row_ok)
-                            a.act_save[(((size_t)n * CF::NSAVE + CF::ZSLOT + 1) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
+                            a.act_save[(((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 0)) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
                     } else if (a.act_save && row_ok)
-                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + CF::ZSLOT + 1) * B + row) * H + wave * 16 + fsub) = gnv;
+                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 0)) * B + row) * H + wave * 16 + fsub) = gnv;
                 }
             }
             __syncthreads();
@@ -845,12 +844,12 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
                 if constexpr (FL) {
                     gnv[0] = fmaxf(finish(CF::NLAYER - 1, gnv), 0.0f);
                     if (a.act_save && row_ok)
-                        a.act_save[(((size_t)n * CF::NSAVE + CF::ZSLOT + 2) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
+                        a.act_save[(((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 1)) * B + row) * H + wave * 16 + fsub + s] = gnv[0];
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) gnv[i] = fmaxf(gnv[i], 0.0f);
                     if (a.act_save && row_ok)
-                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + CF::ZSLOT + 2) * B + row) * H + wave * 16 + fsub) = gnv;
+                        *reinterpret_cast<f32x4*>(a.act_save + (((size_t)n * CF::NSAVE + snsde_save::act_net(NHID, 1)) * B + row) * H + wave * 16 + fsub) = gnv;
                 }
             }
             cur = crow;
@@ -982,7 +981,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_kernel(MfmaArgs a)
                 float* zp = a.act_save + uoff(n, (uint32_t)nsave_rt * (uint32_t)(B * H), CF::ZSLOT, (uint32_t)(B * H)) + goff;
                 if (pack_signs) {
 #pragma unroll
-                    for (int e = 0; e < EPT; ++e) zsave[e] = snsde_pack_signs(zsave[e], sgn >> (8 * e), NHID + 1);
+                    for (int e = 0; e < EPT; ++e) zsave[e] = snsde_pack_signs(zsave[e], sgn >> (8 * e), snsde_save::drift_sign_bits(NHID));
                 }
                 if constexpr (FL) zp[0] = zsave[0];
                 else *reinterpret_cast<f32x4*>(zp) = f32x4{zsave[0], zsave[1], zsave[2], zsave[3]};
@@ -1070,9 +1069,9 @@ struct CfgR {
     static constexpr int LDA = ld_for(16 * KUH, PAD);
     static constexpr int ND = NHID + (IO0 ? 1 : 2);   // transposed GEMMs of the drift chain
     static constexpr int NG = ND + NN;           // + the diffusion net's
-    static constexpr int NBUF = NHID + 2 + NN;   // LDS buffers = delta slots
-    static constexpr int NSAVE = NHID + 2 + NN;
-    static constexpr int ZSLOT = NHID + 1;
+    static constexpr int NBUF = snsde_save::delta_slots(NHID, NN, SNSDE_EULER);   // LDS buffers = delta slots (snsde_save_layout.h)
+    static constexpr int NSAVE = snsde_save::act_slots(NHID, NN, SNSDE_EULER);
+    static constexpr int ZSLOT = snsde_save::act_z(NHID);
     static constexpr int EPT = FL ? 1 : 4;
     static constexpr int ROWCH = 128;
     static constexpr bool STREAM = H > 128;
@@ -1135,7 +1134,7 @@ template <class CF>
 __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(RevArgs a) {
     constexpr int H = CF::H, TPW = 1, FL = CF::FL, M = CF::M, NT = CF::NT, NHID = CF::NHID, NG = CF::NG;
     constexpr int NS = CF::NBUF;                 // LDS buffers = delta slots: z_out, hidden.., first layer, [diffusion net]
-    constexpr int NB0 = NHID + 2;                // first buffer / slot of the diffusion net's chain
+    constexpr int NB0 = snsde_save::delta_net(NHID, 0);      // first buffer / slot of the diffusion net's chain
     constexpr bool IO0 = CF::IO0;
     constexpr int NM = IO0 ? CF::ND : CF::ND - 1;   // relu masks of the drift chain
     constexpr int KUH = CF::KUH, EPT = CF::EPT, LDA = CF::LDA, ND = CF::ND, NN = CF::NN;
@@ -1227,7 +1226,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     int zblk_id = -1;
     const uint32_t grow = (uint32_t)(a.row_offset + row);
     const uint32_t BH32 = (uint32_t)BH, SBH = (uint32_t)NSAVE * BH32, NSBH = (uint32_t)NS * BH32;     // uniform strides (see uoff)
-    const uint32_t pre0 = a.act_fn != 0 ? (uint32_t)(NHID + 2 + NN) : 0u;      // smooth activations: first PRE-activation slot
+    const uint32_t pre0 = a.act_fn != 0 ? (uint32_t)snsde_save::act_pre(NHID, NN, SNSDE_EULER, 0) : 0u;      // smooth activations: first PRE-activation slot
     auto prefetch = [&](int n, StepIn& p) {
         if (!a.dW) {                    // (wave-uniform)
             if ((n >> 2) != zblk_id) {
@@ -1246,7 +1245,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
             p.y[e] = (a.traj + uoff(n, BH32))[goff + e];
             p.z[e] = (a.act + uoff(n, SBH, CF::ZSLOT, BH32))[goff + e];
             if (a.dW) p.dw[e] = (a.dW + uoff(n, BH32))[goff + e];
-            if constexpr (NN > 0) p.gq[e] = (a.act + uoff(n, SBH, CF::ZSLOT + NN, BH32))[goff + e];   // diffusion-net output
+            if constexpr (NN > 0) p.gq[e] = (a.act + uoff(n, SBH, snsde_save::act_net_out(NHID, NN), BH32))[goff + e];   // diffusion-net output
             else p.gq[e] = a.gt ? (a.gt + uoff(n, H, blockIdx.y, a.gt_stride))[fcol + e] : 0.0f;      // (row n of the member's table)
         }
         if constexpr (FL) {
@@ -1256,11 +1255,11 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
                 p.mask[g] = (a.act + uoff(n, SBH, (uint32_t)(NHID - g) + pre0, BH32))[goff];
             }
             if constexpr (NN == 2)               // hidden activation of the diffusion net (smooth: its pre-activation, the last slot)
-                p.nmask[0] = (a.act + uoff(n, SBH, a.act_fn != 0 ? (uint32_t)NSAVE - 1u : (uint32_t)(CF::ZSLOT + 1), BH32))[goff];
+                p.nmask[0] = (a.act + uoff(n, SBH, a.act_fn != 0 ? (uint32_t)NSAVE - 1u : (uint32_t)snsde_save::act_net(NHID, 0), BH32))[goff];
         } else if (writer) {      // (16-row tiles: relu only - the drift chain's masks come out of z)
             if constexpr (NN == 2)
                 p.nmask = *reinterpret_cast<const f32x4*>(
-                    a.act + uoff(n, SBH, CF::ZSLOT + 1, BH32) + (uint32_t)(rowc * H + wave * 16 + fsub));
+                    a.act + uoff(n, SBH, snsde_save::act_net(NHID, 0), BH32) + (uint32_t)(rowc * H + wave * 16 + fsub));
         }
     };
     constexpr bool AHEAD = !CF::STREAM || CF::RING;   // (the M16 streamed-weight variant has no registers to spare for it)
@@ -1315,7 +1314,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
         }
         // ---- elementwise: d(f h + g dW)/d(zout, y) applied to the adjoint ----
         float ay[EPT], dz[EPT], dsv[EPT], dq[EPT];
-        const uint32_t zclear = a.act_fn == 0 ? ~((1u << (NHID + 1)) - 1u) : ~0u;
+        const uint32_t zclear = a.act_fn == 0 ? ~((1u << snsde_save::drift_sign_bits(NHID)) - 1u) : ~0u;
         uint32_t zb[EPT];      // bit pattern of the saved z: its low NHID + 1 bits are the relu signs of the step (snsde_pack_signs)
 #pragma unroll
         for (int e = 0; e < EPT; ++e) {
@@ -1636,7 +1635,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
         if (writer) {
 #pragma unroll
             for (int g = 0; g < NG - 1; ++g)
-                dst[g] = *reinterpret_cast<const f32x4*>(a.act + uoff(p, SBH, (uint32_t)(NHID - g) + (a.act_fn != 0 ? (uint32_t)(NHID + 2) : 0u), BH32) +
+                dst[g] = *reinterpret_cast<const f32x4*>(a.act + uoff(p, SBH, (uint32_t)(NHID - g) + (a.act_fn != 0 ? (uint32_t)snsde_save::act_pre(NHID, 0, SNSDE_SRK, 0) : 0u), BH32) +
                                                          (uint32_t)(rowc * H + wave * 16 + fsub));     // (smooth activations: the PRE-activation slots)
         }
     };
@@ -1743,7 +1742,7 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_srk_reverse_kernel
         if (row_ok && !a.adj0_only) (a.adj + uoff(n + 1, BH32))[goff] = adj;
         // ---- recompute the stage values of the step for the own element ----
         const float y = cur.y, ik = cur.ik, ik0 = cur.ik0;
-        const uint32_t zclear = a.act_fn == 0 ? ~((1u << (NHID + 1)) - 1u) : ~0u;      // (the sign bits are cleared before z is used)
+        const uint32_t zclear = a.act_fn == 0 ? ~((1u << snsde_save::drift_sign_bits(NHID)) - 1u) : ~0u;      // (the sign bits are cleared before z is used)
         const uint32_t zb0 = __builtin_bit_cast(uint32_t, cur.z0), zb1 = __builtin_bit_cast(uint32_t, cur.z1), zb2 = __builtin_bit_cast(uint32_t, cur.z2);
         const float z0 = __builtin_bit_cast(float, zb0 & zclear), z1 = __builtin_bit_cast(float, zb1 & zclear), z2 = __builtin_bit_cast(float, zb2 & zclear);
         const float t0v = cur.t0v, t1v = cur.t1v, t3v = cur.t3v;

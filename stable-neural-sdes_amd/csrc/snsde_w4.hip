@@ -104,7 +104,7 @@ static int srk_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* d
     a.dW = ik; a.dU = ik0; a.grad_ys = b->grad_ys; a.adj = b->adj; a.dth_part = dth_part; a.gpart = gpart; a.row_out = s->row_out;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
     const int nn = (m.noise_option >= 18) ? 2 : 1;
-    a.nsave = snsde_act_slots(&m) + nn;      // (snsde_save_layout: the fourth evaluation's net slots)
+    a.nsave = snsde_save::nsave(m.num_hidden_layers - 1, nn, SNSDE_SRK, m.activation != SNSDE_ACT_RELU);
     a.adj0_only = (b->flags & SNSDE_BWD_ADJ0_ONLY) ? 1 : 0; a.off_theta = net.off_theta;
     a.w_in = net.in.src_w; a.k_in = net.in.K; a.t_in = net.in.tshift;
     const int nhid = m.num_hidden_layers - 1;
@@ -138,7 +138,7 @@ int snsde_w4_launch(const snsde_solve* s, const SnsdeNet& net, hipStream_t strea
     a.dW_out = s->dW_out; a.act_save = s->act_save; a.row_out = s->row_out; a.row_offset = s->row_offset; a.seed = s->seed;
     a.seed_dev = s->seed_dev; a.step_offset = step_offset;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
-    a.nsave = snsde_act_slots(&m);
+    a.nsave = snsde_save::nsave(m.num_hidden_layers - 1, snsde_noise_net_layers(m.noise_option), s->method, m.activation != SNSDE_ACT_RELU);
     if (const int members = snsde_members(s); members > 1) {
         // (SNSDE_FLAG_ENSEMBLE_NETS: make_plan; training planes only where the ensemble has the pair adjoints to read them, all three
         //  flags: route_forward refuses the others, and so does this launcher)
@@ -196,7 +196,8 @@ int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth
     a.delta = gpart ? nullptr : b->delta_save;      // fused weight gradients: no delta planes are written
     a.seed = s->seed; a.row_offset = s->row_offset;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
-    a.nsave = snsde_act_slots(&m); a.nslots = a.nsave;
+    a.nsave = snsde_save::nsave(m.num_hidden_layers - 1, snsde_noise_net_layers(m.noise_option), SNSDE_EULER, m.activation != SNSDE_ACT_RELU);
+    a.nslots = snsde_save::delta_slots(m.num_hidden_layers - 1, snsde_noise_net_layers(m.noise_option), SNSDE_EULER);
     a.adj0_only = (b->flags & SNSDE_BWD_ADJ0_ONLY) ? 1 : 0; a.off_theta = net.off_theta;
     a.w_in = net.in.src_w; a.k_in = net.in.K; a.t_in = net.in.tshift;
     const int nhid = m.num_hidden_layers - 1;
@@ -227,7 +228,7 @@ int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, fl
     using namespace snsde_w4;
     const snsde_solve* s = &b->fwd;
     const snsde_model& m = s->model;
-    const int nhid = m.num_hidden_layers - 1, nn = m.noise_option >= 18 ? 2 : 1, nd = nhid + 2;
+    const int nhid = m.num_hidden_layers - 1, nn = m.noise_option >= 18 ? 2 : 1;
     if (members < 1) members = 1;
     if (members > 1 && (!member_strides_ok(s, members, ws_stride) || n_params != snsde_param_numel(&m))) return SNSDE_ERR_UNSUPPORTED;
     W4GReduce r{};
@@ -239,7 +240,7 @@ int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, fl
     auto tcols = [&](int src, const SnsdeLayer& L) { r.seg[n++] = W4GSeg{src, L.src_w, L.K, 0, 2}; r.seg[n++] = W4GSeg{src + 64, L.src_w, L.K, 1, 2}; };
     weight(0, net.out, 0);
     for (int g = 1; g <= nhid; ++g) weight(g * w4g_layer_floats(), net.hid[nhid - g], 0);
-    weight((nd - 1) * w4g_layer_floats(), net.in, net.in.tshift);
+    weight(snsde_save::delta_first(nhid) * w4g_layer_floats(), net.in, net.in.tshift);
     if (net.in.tshift == 2) tcols(w4g_d_time(nhid), net.in);
     if (nn == 2) { weight(w4g_n_off(nhid, 0), net.ny1, 0); weight(w4g_n_off(nhid, 1), net.ny0, 2); }
     else weight(w4g_n_off(nhid, 0), net.ny0, 2);

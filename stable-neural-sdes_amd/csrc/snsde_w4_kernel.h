@@ -161,7 +161,7 @@ struct CfgW {
     static constexpr int NHID = NHID_, NN = NN_;
     static constexpr bool TIME = TIME_, SAVE = SAVE_;       // SAVE: training mode (act_save planes, relu signs in the saved z)
     static constexpr int H = 64, KIN = TIME ? 66 : 64;
-    static constexpr int ZSLOT = NHID + 1;
+    static constexpr int ZSLOT = snsde_save::act_z(NHID);      // (act_save slots: snsde_save_layout.h)
 };
 
 // -DW4_TRACE (tools/w4_trace.py): s_memtime stamps at the phase boundaries of a step, summed per wave of workgroup 0 and left in the
@@ -352,7 +352,7 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
             if constexpr (CF::SAVE) {
                 float zs[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) zs[i] = snsde_pack_signs(z[i], sgn[i], NHID + 1);
+                for (int i = 0; i < 4; ++i) zs[i] = snsde_pack_signs(z[i], sgn[i], snsde_save::sign_bits(NHID, NN, SNSDE_EULER));
                 save(n, CF::ZSLOT, zs);
             }
             pair_barrier();
@@ -434,11 +434,11 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
                 d = mfma_bk<0>(cur.cs, wn0[65], d);
                 if constexpr (NN == 2) {
                     relu_hand_off(c, d, v, vt);
-                    if constexpr (CF::SAVE) save_x(n, CF::ZSLOT + 1, vt);
+                    if constexpr (CF::SAVE) save_x(n, snsde_save::act_net(NHID, 0), vt);
                 } else {
 #pragma unroll
                     for (int i = 0; i < 4; ++i) q[i] = c[i] + d[i];
-                    if constexpr (CF::SAVE) save(n, CF::ZSLOT + 1, q);
+                    if constexpr (CF::SAVE) save(n, snsde_save::act_net(NHID, 0), q);
                 }
             }
             W4_T(2)
@@ -447,7 +447,7 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
                 gemm64(vt, wn1, c, d, Seq{});
 #pragma unroll
                 for (int i = 0; i < 4; ++i) q[i] = fmaxf(c[i] + d[i], 0.0f);
-                if constexpr (CF::SAVE) save(n, CF::ZSLOT + 2, q);
+                if constexpr (CF::SAVE) save(n, snsde_save::act_net(NHID, 1), q);
             }
             W4_T(3)
             float g[4];
@@ -484,10 +484,8 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_euler_kernel(W4Args a) {
 // and the step's result and publishes it.  Five exchanges per step, each behind one s_barrier:
 //     B1: F0 ->, <- G0, I_k0     B2: F1 ->, <- G1     B3: F2 ->     (the net wave: G2 beside F2, then G3 alone)     B4: <- y'
 // (H0_1 needs F0 only; H0_2 needs F0, F1, G0, G1, I_k0; H1_2 needs F0, G0 only, so G1 and G2 do not wait for the drift wave.)
-// Training-mode saves = snsde_m4n_kernel's (act_save per pass 3n + s with 2 NN + NHID + 2 slots, the pass's drift signs and the hidden
-// signs of the net evaluation beside it / of the fourth evaluation in the low bits of the saved z, stage_save planes H0 | H1 | H1_3):
-// snsde_m4n_rev_kernel.h + the weight-gradient pass read them unchanged; the wave-group adjoint below (snsde_w4_srk_reverse_kernel)
-// reads the same planes.
+// Training-mode saves = snsde_m4n_kernel's (snsde_save_layout.h; stage_save planes H0 | H1 | H1_3): snsde_m4n_rev_kernel.h + the
+// weight-gradient pass read them unchanged; the wave-group adjoint below (snsde_w4_srk_reverse_kernel) reads the same planes.
 // =====================================================================================================================================
 template <int NHID, bool SAVE> __host__ __device__ constexpr int w4srk_fwd_lds_floats() { return 2 * 12 * 256 + 2 * 4096 + ((SAVE && NHID >= 1) ? 2 * 4096 : 0); }
 
@@ -495,8 +493,7 @@ template <class CF, bool ENS = false>      // (ENS: see snsde_w4_euler_kernel)
 __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
     constexpr int H = 64, NHID = CF::NHID, NN = CF::NN;
     constexpr bool TIME = CF::TIME, SAVE = CF::SAVE;
-    constexpr int NSAVE = NHID + 2 + 2 * NN, ZSLOT = NHID + 1, NP = 3;
-    constexpr int SRK_BITS = NHID + 1 + (NN == 2 ? 2 : 0);
+    constexpr int NSAVE = snsde_save::act_slots(NHID, NN, SNSDE_SRK), ZSLOT = snsde_save::act_z(NHID), NP = snsde_save::stage_planes(NN, SNSDE_SRK), SRK_BITS = snsde_save::sign_bits(NHID, NN, SNSDE_SRK);
     using Seq = std::make_integer_sequence<int, 16>;
     // exchange planes of a pair: F0 F1 F2 | G0 G1 | I_k0 | y' | hidden-sign words of G0..G3 (training)
     enum { XF0 = 0, XF1, XF2, XG0, XG1, XDU, XY, XS0, XS1, XS2, XS3, XN };
@@ -623,8 +620,8 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
             for (int i = 0; i < 4; ++i) {
                 uint32_t sg = sgn[i];
                 if constexpr (NN == 2) {
-                    sg |= __float_as_uint(xchg[plane_a][i][lane]) << (NHID + 1);
-                    if (plane_b >= 0) sg |= __float_as_uint(xchg[plane_b][i][lane]) << (NHID + 2);
+                    sg |= __float_as_uint(xchg[plane_a][i][lane]) << snsde_save::net_sign_bit(NHID);
+                    if (plane_b >= 0) sg |= __float_as_uint(xchg[plane_b][i][lane]) << snsde_save::tail_sign_bit(NHID);
                 }
                 zs[i] = snsde_pack_signs(z[i], sg, SRK_BITS);
             }
@@ -723,7 +720,7 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
             float xt[4], v[4], vt[4], q[4];
             quad_transpose(x, xt);
             if constexpr (SAVE) {      // H1 of the evaluation (plane 1; the fourth evaluation of a step: plane 2 of pass 3n + 2)
-                if (a.stage_save) store4x(a.stage_save + uoff(pass, NP * BH, slot0 == ZSLOT + 1 ? 1u : 2u, BH), xt);
+                if (a.stage_save) store4x(a.stage_save + uoff(pass, NP * BH, slot0 == snsde_save::act_net(NHID, 0) ? 1u : 2u, BH), xt);
             }
             {
                 f32x4 c = {b0, b0, b0, b0}, d = {0.f, 0.f, 0.f, 0.f};
@@ -783,21 +780,21 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
             }
             float g0[4], g1[4], g2[4], g3[4], f0[4], f1[4], f2[4], x[4];
             // ---- G0 at (t0, y) ----
-            net(y, s0, c0, 3 * n, ZSLOT + 1, XS0, g0);
+            net(y, s0, c0, 3 * n, snsde_save::act_net(NHID, 0), XS0, g0);
             put(XG0, g0); put(XDU, ik0);
             pair_barrier();                                   // B1
             get(XF0, f0);
 #pragma unroll
             for (int i = 0; i < 4; ++i) x[i] = y[i] + 0.25f * f0[i] * h + SRK_B1_10 * g0[i] * sqh;      // H1_1
             // ---- G1 at (t0 + h/4, H1_1) ----
-            net(x, sq, cq, 3 * n + 1, ZSLOT + 1, XS1, g1);
+            net(x, sq, cq, 3 * n + 1, snsde_save::act_net(NHID, 0), XS1, g1);
             put(XG1, g1);
             pair_barrier();                                   // B2
             get(XF1, f1);
 #pragma unroll
             for (int i = 0; i < 4; ++i) x[i] = y[i] + f0[i] * h + SRK_B1_20 * g0[i] * sqh;                     // H1_2
             // ---- G2 at (t0 + h, H1_2) ----
-            net(x, s1, c1, 3 * n + 2, ZSLOT + 1, XS2, g2);
+            net(x, s1, c1, 3 * n + 2, snsde_save::act_net(NHID, 0), XS2, g2);
             // everything of the step's result that does not need F2 / G3, while the drift wave finishes F2 (same association as the
             // other kernels' `y + (f0 + f1) h/6 + f2 2h/3;  += w0 g0 + w1 g1 + w2 g2 + a4 g3`)
             float pa[4], ps[4], a4v[4];
@@ -818,7 +815,7 @@ __global__ void __launch_bounds__(256, 2) snsde_w4_srk_kernel(W4Args a) {
 #pragma unroll
             for (int i = 0; i < 4; ++i) x[i] = y[i] + 0.25f * f2[i] * h + (SRK_B1_30 * g0[i] + SRK_B1_31 * g1[i] + SRK_B1_32 * g2[i]) * sqh;   // H1_3
             // ---- G3 at (t0 + h/4, H1_3), then the step ----
-            net(x, sq, cq, 3 * n + 2, ZSLOT + NN + 1, XS3, g3);
+            net(x, sq, cq, 3 * n + 2, snsde_save::act_tail(NHID, NN, 0), XS3, g3);
             float yn[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -925,7 +922,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
     long long tr_last = __builtin_readcyclecounter();
 #endif
     constexpr int H = 64, NHID = CF::NHID, NN = CF::NN;
-    constexpr int ZSLOT = NHID + 1, NB0 = NHID + 2, ND = NHID + 2;
+    constexpr int ZSLOT = snsde_save::act_z(NHID), NB0 = snsde_save::delta_net(NHID, 0), ND = NHID + 2;
     constexpr int WPT = FUSED ? 4 : 2;                 // waves per tile
     using Seq = std::make_integer_sequence<int, 16>;
     enum { XA = 0, XN, XCNT };
@@ -1072,7 +1069,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 zb[i] = __float_as_uint(z[i]);
-                zc[i] = __uint_as_float(zb[i] & ~((1u << (NHID + 1)) - 1u));
+                zc[i] = __uint_as_float(zb[i] & ~((1u << snsde_save::sign_bits(NHID, NN, SNSDE_EULER)) - 1u));
                 f[i] = zc[i];
             }
             if (geo) {
@@ -1156,8 +1153,8 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
         float y[4], q[4], hm[4], dw[4], yn[4], qn[4], hmn[4], dwn[4];
         auto fetch = [&](int n, float (&yy)[4], float (&qq)[4], float (&hh)[4], float (&ww)[4]) {
             load4(a.traj + uoff(n, BH), yy);
-            load4(a.act + uoff(n, SBH, ZSLOT + NN, BH), qq);
-            if constexpr (NN == 2) load4(a.act + uoff(n, SBH, ZSLOT + 1, BH), hh);
+            load4(a.act + uoff(n, SBH, snsde_save::act_net_out(NHID, NN), BH), qq);
+            if constexpr (NN == 2) load4(a.act + uoff(n, SBH, snsde_save::act_net(NHID, 0), BH), hh);
             if (!phx) load4(a.dW + uoff(n, BH), ww);
             else {
                 if ((n >> 2) != zblk_id) {
@@ -1205,7 +1202,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
                 gemm64(vt, w1t, c, d, Seq{});
 #pragma unroll
                 for (int i = 0; i < 4; ++i) v[i] = hm[i] > 0.0f ? c[i] + d[i] : 0.0f;
-                if (a.delta) store4(a.delta + uoff(n, DBH, NB0 + 1, BH), v);
+                if (a.delta) store4(a.delta + uoff(n, DBH, snsde_save::delta_net(NHID, 1), BH), v);
                 publish(n, ND + 1, v);
                 quad_transpose(v, vt);
             }
@@ -1242,7 +1239,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
             for (int q = 0; q < 16; ++q) acc[g][q] = f32x4{0.f, 0.f, 0.f, 0.f};
         }
         // layer inputs of step n in the D layout: drift wave layer g reads act slot NHID - g (g <= NHID), the first layer the state y_n;
-        // net: layer 0 of a two-layer net reads its hidden activation (slot ZSLOT + 1), the layer on [tau, y] the state
+        // net: layer 0 of a two-layer net reads its hidden activation (act_net 0), the layer on [tau, y] the state
         float in_cur[NLG][4];
         const int nl = dside ? ND : NN, p0 = dside ? 0 : ND;
         auto fetch_in = [&](int n, auto gc) {
@@ -1251,7 +1248,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
                 if constexpr (g <= NHID) load4(a.act + uoff(n, SBH, (uint32_t)(NHID - g), BH), in_cur[g]);
                 else if constexpr (g < ND) load4(a.traj + uoff(n, BH), in_cur[g]);
             } else if constexpr (g < NN) {
-                if constexpr (NN == 2 && g == 0) load4(a.act + uoff(n, SBH, ZSLOT + 1, BH), in_cur[0]);
+                if constexpr (NN == 2 && g == 0) load4(a.act + uoff(n, SBH, snsde_save::act_net(NHID, 0), BH), in_cur[0]);
                 else load4(a.traj + uoff(n, BH), in_cur[NN - 1]);
             }
         };
@@ -1360,8 +1357,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
 #endif
     constexpr int H = 64, NHID = CF::NHID, NN = CF::NN;
     constexpr bool geo = CF::GEO, mul_y = CF::MULY;
-    constexpr int ZSLOT = NHID + 1, ND = NHID + 2, NP = 3;
-    constexpr int SRK_BITS = NHID + 1 + (NN == 2 ? 2 : 0);
+    constexpr int ZSLOT = snsde_save::act_z(NHID), ND = NHID + 2, NP = snsde_save::stage_planes(NN, SNSDE_SRK), SRK_BITS = snsde_save::sign_bits(NHID, NN, SNSDE_SRK);
     constexpr bool PARK = NHID >= 1;
     using Seq = std::make_integer_sequence<int, 16>;
     // dynamic LDS, per tile: exchange planes | delta planes [step parity][3 ND + 4 NN] | the drift wave's parked W_in,y^T
@@ -1517,7 +1513,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
                     uint32_t m = 0;
                     if constexpr (NN == 2) {
                         const uint32_t b0 = __float_as_uint(z[0][i]), b1 = __float_as_uint(z[1][i]), b2 = __float_as_uint(z[2][i]);
-                        m = ((b0 >> (NHID + 1)) & 1u) | (((b1 >> (NHID + 1)) & 1u) << 1) | (((b2 >> (NHID + 1)) & 3u) << 2);
+                        m = ((b0 >> snsde_save::net_sign_bit(NHID)) & 1u) | (((b1 >> snsde_save::net_sign_bit(NHID)) & 1u) << 1) | (((b2 >> snsde_save::net_sign_bit(NHID)) & 3u) << 2);      // (b2: + the tail's bit)
                     }
                     msk[i] = __uint_as_float(m);
                 }
@@ -1647,7 +1643,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
         auto fetch = [&](int n, auto ec) {
             constexpr int e = decltype(ec)::value;
             const int p = 3 * n + (e < 3 ? e : 2);
-            load4(a.act + uoff(p, SBH, (uint32_t)(e < 3 ? ZSLOT + NN : ZSLOT + 2 * NN), BH), q[e]);
+            load4(a.act + uoff(p, SBH, (uint32_t)(e < 3 ? snsde_save::act_net_out(NHID, NN) : snsde_save::act_tail_out(NHID, NN)), BH), q[e]);
             if constexpr (mul_y) load4(a.stage + uoff(p, PBH, e < 3 ? 1u : 2u, BH), h1[e]);
         };
 #pragma unroll
@@ -1792,7 +1788,7 @@ __global__ void __launch_bounds__(512, 2) snsde_w4_srk_reverse_kernel(W4SrkRevAr
                 else if constexpr (g < ND) load4x(a.stage + uoff(3 * m + u, PBH), in_cur[g]);
             } else if constexpr (g < NN) {
                 const int p = 3 * m + (u < 3 ? u : 2);
-                if constexpr (NN == 2 && g == 0) load4x(a.act + uoff(p, SBH, (uint32_t)(u < 3 ? ZSLOT + 1 : ZSLOT + NN + 1), BH), in_cur[0]);
+                if constexpr (NN == 2 && g == 0) load4x(a.act + uoff(p, SBH, (uint32_t)(u < 3 ? snsde_save::act_net(NHID, 0) : snsde_save::act_tail(NHID, NN, 0)), BH), in_cur[0]);
                 else load4x(a.stage + uoff(p, PBH, u < 3 ? 1u : 2u, BH), in_cur[NN - 1]);
             }
         };

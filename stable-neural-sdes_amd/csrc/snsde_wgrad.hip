@@ -726,7 +726,7 @@ struct WPlan {
     int ntiles, max_split, naux, ldx, n_pass, n_trow;
     size_t part_floats, sums_floats, ds_off, dth_off, dz1_off, dz2_off, a1_off, xaux_off, total_floats;
     bool tnoise, has_dth;
-    int nact, ndelta, xt, t_col0, x_col0, x_cols, n_col0, NP;
+    int xt, t_col0, x_col0, x_cols, n_col0, NP;
     AArgs aa;
     WTile tile[MAX_TILES];
 };
@@ -747,7 +747,7 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     const bool tau_last = usex && !timef && nn > 0;
     const int t_col0 = tau_last ? ((C + 3) & ~3) : 0, x_col0 = tau_last ? 0 : xt;
     const int naux = tau_last ? t_col0 + 2 : xt + (usex ? C : 0);
-    const int nd = nhid + 2;                           // delta slots of the drift chain
+    namespace sv = snsde_save;                         // (the slots of act_save / delta_save a tile reads: snsde_save_layout.h)
     const bool srk = s.method == SNSDE_SRK;
     const int n_pass = s.n_steps * (srk ? 3 : 1);      // drift passes (one per step, three for SRK): rows of act / delta
     const int n_trow = s.n_steps * (srk ? 4 : 1);      // rows of the time-only diffusion table
@@ -776,18 +776,18 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     };
     auto alloc = [&](size_t n) { const int o = (int)off; off += n; return o; };
     aa.o_out = alloc((size_t)H * H); aa.b_out = alloc(H);
-    bool ok = add_tiles(0, 0, nhid, H, aa.o_out, H, aa.b_out, 1 << 30, 0);
+    bool ok = add_tiles(sv::delta_out(), 0, sv::act_layer(nhid), H, aa.o_out, H, aa.b_out, 1 << 30, 0);
     for (int l = 0; l < nhid && ok; ++l) {
         aa.o_hid[l] = alloc((size_t)H * H); aa.b_hid[l] = alloc(H);
-        ok = add_tiles(nhid - l, 0, l, H, aa.o_hid[l], H, aa.b_hid[l], 1 << 30, 0);
+        ok = add_tiles(sv::delta_hidden(nhid, l), 0, sv::act_layer(l), H, aa.o_hid[l], H, aa.b_hid[l], 1 << 30, 0);
     }
     // first layer: dense sums in linear_in's column order followed by the control channels: [sin t, cos t | y | X(t)]
     // (the y-free drift of input_option 0 has the control channels only: the matrix is initial_network.weight's)
     aa.ld_first = ts + (io0 ? 0 : H) + (usex ? C : 0);
     aa.o_first = alloc((size_t)H * aa.ld_first); aa.b_first = alloc(H);
-    if (!io0) ok = ok && add_tiles(nhid + 1, 1, 0, H, aa.o_first + ts, aa.ld_first, aa.b_first, 1 << 30, 0);
+    if (!io0) ok = ok && add_tiles(sv::delta_first(nhid), 1, 0, H, aa.o_first + ts, aa.ld_first, aa.b_first, 1 << 30, 0);
     if (ok && ts + (usex ? C : 0) > 0)
-        ok = add_tiles(nhid + 1, 2, 0, ts + (usex ? C : 0), aa.o_first, aa.ld_first, io0 ? aa.b_first : -1, ts, io0 ? 0 : H, 0);
+        ok = add_tiles(sv::delta_first(nhid), 2, 0, ts + (usex ? C : 0), aa.o_first, aa.ld_first, io0 ? aa.b_first : -1, ts, io0 ? 0 : H, 0);
     aa.nn = nn;
     // SRK through a diffusion net (snsde_m4n_rev_kernel.h): the net's inputs are the H1 states (plane 1 of the stage buffer)
     // at the diffusion stage times (xaux columns n_col0 ..), and the step's fourth evaluation adds a second set of sums over
@@ -796,37 +796,37 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     const bool milnet = s.method == SNSDE_MILSTEIN && nn > 0;
     const int n_col0 = srknet ? ((naux + 3) & ~3) : -1;
     aa.tail = srknet ? 1 : 0;
-    if (ok && nn > 0) {     // diffusion net: first layer on [sin t, cos t | y] (delta slot nd + nn - 1), output layer on its hidden
-        const int d0n = nd + nn - 1;
+    if (ok && nn > 0) {     // diffusion net: first layer on [sin t, cos t | y], output layer on its hidden
+        const int d0n = sv::delta_net_in(nhid, nn);
         aa.o_ny0 = alloc((size_t)H * (H + 2)); aa.b_ny0 = alloc(H);
         cur_plane = srknet ? 1 : 0;
         ok = add_tiles(d0n, 1, 0, H, aa.o_ny0 + 2, H + 2, aa.b_ny0, 1 << 30, 0)
              && add_tiles(d0n, 2, 0, 2, aa.o_ny0, H + 2, -1, 1 << 30, 0, srknet ? n_col0 : t_col0);
         if (ok && nn == 2) {
             aa.o_ny1 = alloc((size_t)H * H); aa.b_ny1 = alloc(H);
-            ok = add_tiles(nd, 0, nhid + 2, H, aa.o_ny1, H, aa.b_ny1, 1 << 30, 0);
+            ok = add_tiles(sv::delta_net(nhid, 0), 0, sv::act_net(nhid, 0), H, aa.o_ny1, H, aa.b_ny1, 1 << 30, 0);
         }
         if (ok && srknet) {
             cur_pstride = 3; cur_poff = 2; cur_plane = 2;
             aa.o_ny0b = alloc((size_t)H * (H + 2)); aa.b_ny0b = alloc(H);
-            ok = add_tiles(d0n + nn, 1, 0, H, aa.o_ny0b + 2, H + 2, aa.b_ny0b, 1 << 30, 0)
-                 && add_tiles(d0n + nn, 2, 0, 2, aa.o_ny0b, H + 2, -1, 1 << 30, 0, n_col0 + 4);
+            ok = add_tiles(sv::delta_tail_in(nhid, nn), 1, 0, H, aa.o_ny0b + 2, H + 2, aa.b_ny0b, 1 << 30, 0)
+                 && add_tiles(sv::delta_tail_in(nhid, nn), 2, 0, 2, aa.o_ny0b, H + 2, -1, 1 << 30, 0, n_col0 + 4);
             if (ok && nn == 2) {
                 aa.o_ny1b = alloc((size_t)H * H); aa.b_ny1b = alloc(H);
-                ok = add_tiles(nd + nn, 0, nhid + 2 + nn, H, aa.o_ny1b, H, aa.b_ny1b, 1 << 30, 0);
+                ok = add_tiles(sv::delta_tail(nhid, nn, 0), 0, sv::act_tail(nhid, nn, 0), H, aa.o_ny1b, H, aa.b_ny1b, 1 << 30, 0);
             }
             cur_pstride = 1; cur_poff = 0;
         }
         cur_plane = 0;
         if (ok && milnet) {
             // Milstein through the net (snsde_m4n_mil_rev_kernel.h): the tangent p = J_g a depends on W1_y and W2 too:
-            //   d W2 += sum eps2 hdot^T (delta slots nact, nact + 2),  d W1_y += sum eps1 a_{n+1}^T (slot nact + 1 | nact for one layer)
+            //   d W2 += sum eps2 hdot^T,  d W1_y += sum eps1 a_{n+1}^T (one layer: eps)
             aa.tail = 2;
             aa.o_ny0b = alloc((size_t)H * (H + 2));
-            ok = add_tiles(nhid + 2 + nn + (nn == 2 ? 1 : 0), 4, 0, H, aa.o_ny0b + 2, H + 2, -1, 1 << 30, 0);
+            ok = add_tiles(sv::delta_eps_y(nhid, nn), 4, 0, H, aa.o_ny0b + 2, H + 2, -1, 1 << 30, 0);
             if (ok && nn == 2) {
                 aa.o_ny1b = alloc((size_t)H * H);
-                ok = add_tiles(nhid + 2 + nn, 3, nhid + 2 + nn + 2, H, aa.o_ny1b, H, -1, 1 << 30, 0);
+                ok = add_tiles(sv::delta_eps2(nhid, nn), 3, sv::delta_hdot(nhid, nn), H, aa.o_ny1b, H, -1, 1 << 30, 0);
             }
         }
     }
@@ -880,8 +880,6 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
     w->ds_off = o; o += w->tnoise ? NH : 0;
     w->has_dth = w->tnoise || nn > 0 || snsde_y_noise(no);
     w->t_col0 = t_col0; w->x_col0 = x_col0; w->x_cols = usex ? C : 0;
-    w->nact = nhid + 2 + nn + (srknet ? nn : 0);      // act_save slots per pass (snsde_save_layout)
-    w->ndelta = w->nact + (milnet ? (nn == 2 ? 3 : 1) : 0);      // delta_save slots per pass
     w->xt = xt;
     w->dth_off = o; o += 4;
     w->dz1_off = o; o += two ? NH : 0;
@@ -901,7 +899,7 @@ bool make_wplan(const snsde_backward* b, const SnsdeNet& net, WPlan* w) {
                     "pstride %d poff %d rows %d xplane %d\n", i, t.d_slot, t.h0, t.x_kind, t.x_slot, t.k0, t.kd, t.ncols, t.out, t.ldo, t.bias,
                     t.nsplit, t.rows_per_split, t.part, t.cls, t.pstride, t.poff, t.rows, t.xplane);
         }
-        fprintf(stderr, "nact %d ldx %d naux %d n_col0 %d NP %d sums %zu part %zu xaux_off %zu total %zu\n", w->nact, w->ldx, w->naux, w->n_col0,
+        fprintf(stderr, "ldx %d naux %d n_col0 %d NP %d sums %zu part %zu xaux_off %zu total %zu\n", w->ldx, w->naux, w->n_col0,
                 w->NP, w->sums_floats, w->part_floats, w->xaux_off, w->total_floats);
     }
 #endif
@@ -976,10 +974,10 @@ int snsde_wgrad_launch(const snsde_backward* b, const SnsdeNet& net, const snsde
         pass_tab = static_cast<const float*>(s.workspace) + fp.srk_tab_off;      // (3N, SNSDE_STEP_STRIDE): the forward's expanded table
         a.traj = s.stage_save;                     // first-layer inputs = the stage states
     }
-    const bool smooth = s.model.activation != SNSDE_ACT_RELU;      // act_save then also holds the NL pre-activations per step
-    a.B = s.batch; a.H = H; a.N = wp->n_pass; a.NG = wp->ndelta;
+    a.B = s.batch; a.H = H; a.N = wp->n_pass;
     a.Br = Bm; a.mrows = members > 1 ? Bm : 0; a.ms = ms;
-    a.NSAVE = wp->nact + (smooth ? s.model.num_hidden_layers + (snsde_noise_net_layers(no) == 2 ? (srk ? 2 : 1) : 0) : 0);      // (SRK: + the fourth evaluation's)
+    const int nhid = s.model.num_hidden_layers - 1, nn = snsde_noise_net_layers(no);      // (slots per pass of act_save and of delta_save)
+    a.NSAVE = snsde_save::nsave(nhid, nn, s.method, s.model.activation != SNSDE_ACT_RELU); a.NG = snsde_save::delta_slots(nhid, nn, s.method);
     a.adj = b->adj;
     a.R = wp->n_pass * Bm; a.ntiles = wp->ntiles; a.NP = wp->NP;
     const bool xq = fp.kernel == snsde_mfma::FwdKernel::lean_bf16;      // (mode 1 after a bf16-operand forward: SNSDE_FLAG_BF16_GRAD)
