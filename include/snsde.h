@@ -762,6 +762,44 @@ SNSDE_API int snsde_sample_quantiles_backward(const float* grad_out, const float
                                               int32_t samples, int32_t width, int32_t n_q, const int32_t* k, const float* frac,
                                               float* grad_ys, void* hip_stream);
 
+/* Energy score: the multivariate generalisation of the CRPS, ES = E||X - y|| - E||X - X'|| / 2.  ys viewed as (outer, M, G, S, W)
+ * exactly as for snsde_sample_crps (members axis: addressing only, member stride G S W; pooled set of group g: x_n, n = m S + s,
+ * N = M S).  Two vector modes:
+ *   path == 0: the vector is the last axis, x_n in R^W, V = W; one score per (o, g): energy is (outer, groups);
+ *   path != 0: the outer axis joins the vector, component v = o W + w, V = outer W; one score per g: energy is (groups) - the
+ *              score of the WHOLE path, all output times by all channels as one vector, addressed in place (no permuted copy).
+ * target y is (outer, groups, width) in both modes.  With r_n = ||x_n - y||_2, r_nj = ||x_n - x_j||_2 and D = N - 1 (fair != 0:
+ * the unbiased estimator; N < 2 is then SNSDE_ERR_DIMS) or D = N,
+ *     energy = (sum_n r_n) / N - (sum_{n<j} r_nj) / (N D)                       (the CRPS at V = 1)
+ * Every squared distance is formed from differences, sum_v (x_nv - x_jv)^2, never from a Gram matrix or norms: samples that
+ * nearly coincide do not cancel.  One workgroup per score; the N + 1 rows (row N: the observation) are paired in 4 x 4
+ * micro-tiles of row blocks, dealt to the lanes, which keep their squared distances in registers while the columns pass through
+ * LDS in chunks of 16 (lanes past V stage zeros and store nothing); N > 256 is SNSDE_ERR_DIMS.  Summation order, a function of
+ * (N, V, fair) only: a squared distance is one fmaf(d, d, .) chain over v ascending; after one sqrtf each, the 16 terms of a
+ * tile (tile t = bj (bj + 1) / 2 + bi of row blocks bi <= bj, masked pairs as +0) are added as a balanced binary tree, the tiles
+ * of a lane (t = lane + k THREADS) k ascending, the lanes of a wave by a butterfly (xor 1, 2, .., 32), the waves in order - the
+ * pairs with the observation and the pairs among samples separately - then one division each and the subtraction.  THREADS = 64
+ * for N <= 39, else 256.  No atomics, no dependence on the grid, the pointer alignment or `members`: the same bits on every
+ * launch, and a pooled call gives the bits of the members = 1 call on the permuted (outer, G, M S, W) tensor.  Enqueue-only, no
+ * workspace, capturable.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target or energy NULL.  SNSDE_ERR_DIMS: a
+ * non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits. */
+SNSDE_API int snsde_sample_energy(const float* ys, const float* target, int64_t outer, int32_t members, int64_t groups, int32_t samples,
+                                  int32_t width, int32_t fair, int32_t path, float* energy, void* hip_stream);
+
+/* Adjoint of snsde_sample_energy: with grad_energy = g ((outer, groups), or (groups) under path), u(d) = d / ||d|| and u(0) = 0
+ * (what the norm differentiates to in torch.linalg.vector_norm and torch.cdist: coincident samples and a sample on the
+ * observation give finite gradients),
+ *     grad_ys[n]  = g * ( u(x_n - y) / N - sum_{j != n} u(x_n - x_j) / (N D) )
+ *     grad_target = -g * sum_n u(x_n - y) / N                                   (optional, NULL = not wanted)
+ * The distances are formed again as in the forward; each pair leaves w = (1 / r, or 0 where r == 0) * (1 / N with the
+ * observation, -1 / (N D) among samples) in an LDS plane of the lower triangle's 4 x 4 blocks (137 KB at N = 256: no workspace),
+ * and a second pass over the columns writes g * sum_j w_nj (x_nv - x_jv), j ascending over the N + 1 rows, one fmaf each, for
+ * every row n of every column (row N: grad_target).  Every element of grad_ys is written.  The same errors and guarantees;
+ * SNSDE_ERR_NULL: grad_energy, ys, target or grad_ys NULL. */
+SNSDE_API int snsde_sample_energy_backward(const float* grad_energy, const float* ys, const float* target, int64_t outer, int32_t members,
+                                           int64_t groups, int32_t samples, int32_t width, int32_t fair, int32_t path, float* grad_ys,
+                                           float* grad_target, void* hip_stream);
+
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /
  * snsde_backward / snsde_head); SNSDE_ERR_ABI otherwise.  A size of 0 means "this binding does not declare that struct"

@@ -110,7 +110,7 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward',
            'snsde_solve_forward_at', 'snsde_sample_crps', 'snsde_sample_crps_backward', 'snsde_sample_quantiles',
-           'snsde_sample_quantiles_backward')
+           'snsde_sample_quantiles_backward', 'snsde_sample_energy', 'snsde_sample_energy_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -198,6 +198,10 @@ def lib():
     quant = [C.c_int32, C.POINTER(C.c_int32), C.POINTER(C.c_float)]     # (n_q, k, frac): host arrays
     L.snsde_sample_quantiles.argtypes = [C.c_void_p] + dims + quant + [C.c_void_p, C.c_void_p]
     L.snsde_sample_quantiles_backward.argtypes = [C.c_void_p, C.c_void_p] + dims + quant + [C.c_void_p, C.c_void_p]
+    # (ys, target, dims, fair, path, energy, stream) / (grad_energy, ys, target, dims, fair, path, grad_ys, grad_target, stream)
+    L.snsde_sample_energy.argtypes = [C.c_void_p, C.c_void_p] + dims + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
+    L.snsde_sample_energy_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + dims + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
+                                                                                             C.c_void_p]
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

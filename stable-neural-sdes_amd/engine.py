@@ -1390,6 +1390,109 @@ class _SampleCRPS(torch.autograd.Function):
         return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None
 
 
+_CDIST_MAX_PLANE = 2 ** 23     # distances per torch.cdist call of `sample_energy_tensor_ops`
+
+
+def _energy_dims(ys, samples, target, fair, members, path):
+    """(S, M, lead, G, W, N, result shape) of an energy score; the shape errors of `sample_energy`."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    if tuple(target.shape) != lead + (G, W):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {lead + (G, W)} (one observed vector per input row)')
+    if fair and N < 2:
+        raise ValueError('the fair (unbiased) score needs at least 2 pooled samples')
+    return S, M, lead, G, W, N, ((G,) if path else lead + (G,))
+
+
+def sample_energy(ys, samples, target, fair=True, members=1, path=False):
+    """Energy score of the sample paths of a solve against an observation: the multivariate generalisation of the CRPS, which
+    also sees the dependence between the components of the vector.  ys, samples, members and target (..., B, W) as for
+    `sample_crps`; the pooled samples x_n of an input row are vectors: of the W components of the last axis (path=False: the
+    result is (..., B)), or of ALL leading axes by W (path=True: the whole path as one vector, the result is (B,); ys is
+    addressed in place, never permuted).  With D = N - 1 (fair: the unbiased estimator, N >= 2) or D = N,
+        energy = sum_n ||x_n - y|| / N - sum_{n<j} ||x_n - x_j|| / (N D)
+    every distance from differences (never a Gram matrix).  Differentiable in ys and target, d||d|| = d / ||d|| and 0 at d = 0.
+    CUDA float32 inputs with N <= 256: one launch of snsde_sample_energy (no (.., N, N) intermediate, deterministic, capturable)
+    - inside an autograd node whose backward is snsde_sample_energy_backward when an input requires grad.  Other tensors:
+    `sample_energy_tensor_ops`."""
+    fair, path = bool(fair), bool(path)
+    S, M, lead, G, W, N, out_shape = _energy_dims(ys, samples, target, fair, members, path)
+    if _score_native(ys, N, target):
+        if (ys.requires_grad or target.requires_grad) and torch.is_grad_enabled():
+            return _SampleEnergy.apply(ys, target, S, M, fair, path)
+        return _sample_energy_launch(ys.contiguous(), target.contiguous(), S, M, fair, path)
+    return sample_energy_tensor_ops(ys, S, target, fair, M, path)
+
+
+def sample_energy_tensor_ops(ys, samples, target, fair=True, members=1, path=False):
+    """`sample_energy` stated in tensor ops (any device and dtype; autograd differentiates it): torch.linalg.vector_norm of the
+    differences to the observation and torch.cdist in its direct-difference mode - an (.., N, N) plane, no (.., N, N, V) tensor.
+    What `sample_energy` runs off the kernels' domain, and the baseline the kernels are timed against."""
+    fair, path = bool(fair), bool(path)
+    S, M, lead, G, W, N, out_shape = _energy_dims(ys, samples, target, fair, members, path)
+    if ys.numel() == 0:
+        return ys.new_zeros(out_shape)
+    x, y = _pooled(ys, S, M, lead, G, W), target                        # (..., G, N, W), (..., G, W)
+    if path:      # every leading axis joins the vector: (G, N, outer W)
+        O = _outer(lead)
+        x = x.reshape(O, G, N, W).permute(1, 2, 0, 3).reshape(G, N, O * W)
+        y = y.reshape(O, G, W).permute(1, 0, 2).reshape(G, O * W)
+    D = N - 1 if fair else N
+    a = torch.linalg.vector_norm(x - y.unsqueeze(-2), dim=-1).sum(dim=-1) / N
+    # torch.cdist's direct kernel launches one 256-thread block per distance and HIP bounds a grid at 2^32 threads: 2^23
+    # distances per call (the groups are independent, so the slices change no value)
+    flat = x.reshape((-1, N, x.shape[-1]))
+    step = max(1, _CDIST_MAX_PLANE // (N * N))
+    sums = [torch.cdist(flat[i:i + step], flat[i:i + step], compute_mode='donot_use_mm_for_euclid_dist').sum(dim=(-2, -1))
+            for i in range(0, flat.shape[0], step)]
+    b = (sums[0] if len(sums) == 1 else torch.cat(sums)).reshape(a.shape) / (2 * N * D)
+    return a - b
+
+
+def _sample_energy_launch(ys, target, S, M, fair, path):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    energy = torch.empty((G,) if path else lead + (G,), device=ys.device, dtype=torch.float32)
+    _lib.check(_lib.lib().snsde_sample_energy(_ptr(ys), _ptr(target), _outer(lead), M, G, S, W, int(fair), int(path), _ptr(energy),
+                                              C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_sample_energy')
+    return energy
+
+
+def sample_energy_backward(grad_energy, ys, target, samples, fair=True, members=1, path=False, grad_target=True):
+    """(dL/d ys, dL/d target) of `sample_energy` from dL/d energy: one launch of snsde_sample_energy_backward (dL/d target None
+    when grad_target=False).  Contiguous float32 CUDA tensors, ys (..., B S, W) or (..., M, B S, W), target (..., B, W), grad_energy
+    (..., B) or, under path, (B,)."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    _check_f32('ys', ys)
+    _check_f32('target', target, lead + (G, W))
+    _check_f32('grad_energy', grad_energy, (G,) if path else lead + (G,))
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    _lib.check(_lib.lib().snsde_sample_energy_backward(_ptr(grad_energy), _ptr(ys), _ptr(target), _outer(lead), M, G, S, W, int(bool(fair)),
+                                                       int(bool(path)), _ptr(gys), _ptr(gt),
+                                                       C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_energy_backward')
+    return gys, gt
+
+
+class _SampleEnergy(torch.autograd.Function):
+    """sample_energy of CUDA float32 tensors of which one requires grad: the forward kernel, and snsde_sample_energy_backward as its backward."""
+
+    @staticmethod
+    def forward(ctx, ys, target, S, M, fair, path):
+        ysc, tc = ys.detach().contiguous(), target.detach().contiguous()
+        ctx.S, ctx.M, ctx.fair, ctx.path = S, M, fair, path
+        ctx.save_for_backward(ysc, tc)
+        return _sample_energy_launch(ysc, tc, S, M, fair, path)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_energy):
+        ys, target = ctx.saved_tensors
+        gys, gt = sample_energy_backward(grad_energy.to(torch.float32).contiguous(), ys, target, ctx.S, ctx.fair, ctx.M, ctx.path,
+                                         grad_target=ctx.needs_input_grad[1])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None
+
+
 def quantile_positions(q, N):
     """Order-statistic positions of the levels q among N samples, torch.quantile's 'linear' rule: pos = q (N - 1) in float64,
     k = floor(pos), frac = float32(pos - k).  Returns (k, frac) as lists; ValueError for a level outside [0, 1] or no level."""

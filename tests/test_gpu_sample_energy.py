@@ -1,0 +1,347 @@
+"""snsde_sample_energy and its adjoint on the GPU, through sample_energy / energy_loss.
+
+Shapes (groups, N, V): (1, 2, 1) - the smallest fair score, one pair, one column; (3, 5, 3) - odd sizes; (2, 64, 65) - a chunk
+boundary with one live tail column; (2, 65, 130) - N + 1 rows one past a block of four; (1, 256, 4) - the cap (nine tiles per
+lane, the 137 KB plane of the backward); (9000, 3, 2) - more scores than the 8192-block cap: the grid stride; (2, 4, 16) and
+(2, 3, 17) - N + 1 on either side of one row block, exactly one chunk and one column more; and N on either side of each bucket
+edge of the kernels: 39 | 40 (one wave | four waves), 87 | 88 (one | three tiles per lane), 151 | 152 (three | nine).
+u = 2^-24 throughout.  The float64 references are computed once per shape from the float32 inputs and shared.
+
+The value bound (V / 2 + 2 N + 8) u (A + B'): a squared distance is a chain of V fmaf over non-negative terms of once-rounded
+differences (within (V + 2) u relative; sqrtf halves it and rounds once); the kernel's documented order then adds the terms of
+each of the two sums through a 4-level tree inside a tile, at most 9 tiles of a lane, 6 butterfly levels and 3 waves - masked
+pairs enter as exact zeros, so the chain is never deeper than min(#terms - 1, 22) <= 2 N for every N (N = 2: 1 and 0 additions,
+N = 3: 2 and 2) - one division each and the subtraction: inside the 2 N + 8 the bound allows."""
+import copy
+import functools
+
+import numpy as np
+import pytest
+import torch
+
+import stable_neural_sdes_amd as S
+from stable_neural_sdes_amd import engine, train
+from tests.helpers import make_problem
+
+DEV = 'cuda:0'
+pytestmark = pytest.mark.gpu
+
+SHAPES = [(1, 2, 1), (3, 5, 3), (2, 64, 65), (2, 65, 130), (1, 256, 4), (9000, 3, 2), (2, 4, 16), (2, 3, 17),
+          (2, 39, 5), (2, 40, 18), (1, 87, 3), (1, 88, 17), (1, 151, 2), (1, 152, 33)]
+U = 2.0 ** -24
+
+
+@functools.lru_cache(maxsize=None)
+def _case(shape):
+    """Inputs with planted ties - in every group sample 1 duplicates sample 0 and, where N > 2, the observation equals sample 2 -
+    and everything the float64 formulas give for them.  Never modified."""
+    G, N, V = shape
+    rng = np.random.default_rng(G + N + V)
+    x = (2.0 * rng.standard_normal((G, N, V)) + 0.5).astype(np.float32)
+    x[:, 1] = x[:, 0]
+    y = rng.standard_normal((G, V)).astype(np.float32)
+    if N > 2:
+        y[:] = x[:, 2]
+    g = rng.standard_normal(G).astype(np.float32)
+    x64, y64, g64 = x.astype(np.float64), y.astype(np.float64), g.astype(np.float64)
+    d = x64 - y64[:, None]                                # (G, N, V)
+    rn = np.sqrt((d * d).sum(-1))                         # (G, N)
+    diff = x64[:, :, None] - x64[:, None, :]              # (G, N, N, V)
+    rnj = np.sqrt((diff * diff).sum(-1))                  # (G, N, N)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        un = np.where(rn[..., None] > 0, d / rn[..., None], 0.0)
+        unj = np.where(rnj[..., None] > 0, diff / rnj[..., None], 0.0)
+    out = dict(x=x, y=y, g=g, rn=rn)
+    for fair in (True, False):
+        D = N - 1 if fair else N
+        A, B = rn.sum(1) / N, rnj.sum((1, 2)) / (2 * N * D)      # (the full plane counts every pair twice)
+        out[fair] = dict(energy=A - B, scale=A + B,
+                         gx=g64[:, None, None] * (un / N - unj.sum(2) / (N * D)),
+                         gx_scale=np.abs(g64) * (1.0 / N + (N - 1) / (N * D)),
+                         gy=-g64[:, None] * un.sum(1) / N)
+    return out
+
+
+def _dev(a):
+    return torch.from_numpy(a).to(DEV)
+
+
+@pytest.mark.parametrize('fair', [True, False])
+@pytest.mark.parametrize('shape', SHAPES)
+def test_energy_against_float64(shape, fair):
+    """|err| <= (V / 2 + 2 N + 8) u (A + B'), A = sum r_n / N and B' = sum_{n<j} r_nj / (N D) in float64 (the module docstring
+    derives it from the kernel's summation order).  Two launches give the same bits."""
+    G, N, V = shape
+    c = _case(shape)
+    xd, yd = _dev(c['x']).reshape(G * N, V), _dev(c['y'])
+    e = S.sample_energy(xd, N, yd, fair=fair)
+    assert tuple(e.shape) == (G,) and e.dtype == torch.float32
+    err = np.abs(e.double().cpu().numpy() - c[fair]['energy'])
+    bound = (V / 2 + 2 * N + 8) * U * c[fair]['scale']
+    print(f'sample_energy {shape} fair={fair}: err / bound max {np.max(err / bound):.3f}')
+    assert (err <= bound).all()
+    assert torch.equal(S.sample_energy(xd, N, yd, fair=fair), e)
+    if N > 2:
+        assert float(c['rn'][:, 2].max()) == 0      # (the planted sample on the observation)
+
+
+@pytest.mark.parametrize('fair', [True, False])
+@pytest.mark.parametrize('shape', SHAPES)
+def test_gradients_against_the_float64_formula_with_planted_ties(shape, fair):
+    """Every component of grad_ys within (V / 2 + N + 8) u |g| (1 / N + (N - 1) / (N D)), of grad_target within
+    (V / 2 + N + 8) u |g|: 1 / r carries the (V / 2 + 2) u of the distance and one division, its weight 1 / N or 1 / (N D) two
+    more roundings, each term one rounded difference, the N terms of a row one fmaf each, and the product with g.  Finite at the
+    duplicate and at the sample on the observation."""
+    G, N, V = shape
+    c = _case(shape)
+    xd, yd = _dev(c['x']).reshape(G * N, V).requires_grad_(True), _dev(c['y']).requires_grad_(True)
+    e = S.sample_energy(xd, N, yd, fair=fair)
+    assert type(e.grad_fn).__name__.startswith('_SampleEnergy')
+    gx, gy = torch.autograd.grad(e, (xd, yd), _dev(c['g']))
+    gx2, gy2 = torch.autograd.grad(S.sample_energy(xd, N, yd, fair=fair), (xd, yd), _dev(c['g']))
+    assert torch.equal(gx, gx2) and torch.equal(gy, gy2)
+    assert bool(torch.isfinite(gx).all()) and bool(torch.isfinite(gy).all())
+    r = c[fair]
+    gxn, gyn = gx.double().cpu().numpy().reshape(G, N, V), gy.double().cpu().numpy()
+    bx = (V / 2 + N + 8) * U * r['gx_scale'][:, None, None]
+    by = (V / 2 + N + 8) * U * np.abs(c['g'].astype(np.float64))[:, None]
+    ex, ey = np.abs(gxn - r['gx']), np.abs(gyn - r['gy'])
+    print(f'sample_energy backward {shape} fair={fair}: grad_ys err / bound max {np.max(ex / bx):.3f}, grad_target {np.max(ey / by):.3f}')
+    assert (ex <= bx).all() and (ey <= by).all()
+    # only one input requires grad: grad_target = NULL, or grad_ys dropped
+    x2 = xd.detach().requires_grad_(True)
+    assert torch.equal(torch.autograd.grad(S.sample_energy(x2, N, yd.detach(), fair=fair), x2, _dev(c['g']))[0], gx)
+    y2 = yd.detach().requires_grad_(True)
+    assert torch.equal(torch.autograd.grad(S.sample_energy(xd.detach(), N, y2, fair=fair), y2, _dev(c['g']))[0], gy)
+    # engine.sample_energy_backward: the same launch without autograd
+    hx, hy = engine.sample_energy_backward(_dev(c['g']), xd.detach(), yd.detach(), N, fair)
+    assert torch.equal(hx, gx) and torch.equal(hy, gy)
+
+
+def test_exact_zeros_where_every_direction_is_u_of_zero():
+    x = torch.tensor([[1.5, -2.0, 0.25]] * 4, device=DEV).requires_grad_(True)      # two groups of two coincident samples
+    y = torch.tensor([[1.5, -2.0, 0.25]] * 2, device=DEV).requires_grad_(True)      # ... on their observation
+    e = S.sample_energy(x, 2, y)
+    gx, gy = torch.autograd.grad(e.sum(), (x, y))
+    assert float(e.detach().abs().max()) == 0 and float(gx.abs().max()) == 0 and float(gy.abs().max()) == 0
+    e1 = S.sample_energy(x[:2], 1, y, fair=False)                                    # N = 1: no pair
+    assert float(e1.detach().abs().max()) == 0 and float(torch.autograd.grad(e1.sum(), x)[0].abs().max()) == 0
+    # the hand answers of the CPU test: exact in float32 (a 3-4-5 triangle)
+    assert S.sample_energy(torch.tensor([[0., 0.], [3., 4.]], device=DEV), 2, torch.tensor([[3., 0.]], device=DEV)).item() == 1.0
+    assert S.sample_energy(torch.tensor([[0., 0.], [3., 4.]], device=DEV), 2, torch.tensor([[3., 0.]], device=DEV), fair=False).item() == 2.25
+
+
+def test_pooled_ensemble_layout_gives_the_bits_of_the_permuted_single_member_call():
+    O, M, G, Sn, W = 2, 3, 5, 4, 70
+    gen = torch.Generator().manual_seed(3)
+    x = torch.randn(O, M, G * Sn, W, generator=gen)
+    x[:, 1, 3] = x[:, 0, 2]      # coincident samples across members
+    y, g = torch.randn(O, G, W, generator=gen), torch.randn(O, G, generator=gen)
+    flat = x.reshape(O, M, G, Sn, W).permute(0, 2, 1, 3, 4).reshape(O, G * M * Sn, W).contiguous()
+    for path in (False, True):
+        gg = (g[0] if path else g).contiguous().to(DEV)
+        xa, xb, ya, yb = (t.to(DEV).requires_grad_(True) for t in (x, flat, y, y))
+        a, b = S.sample_energy(xa, Sn, ya, members=M, path=path), S.sample_energy(xb, M * Sn, yb, path=path)
+        assert tuple(a.shape) == ((G,) if path else (O, G)) and torch.equal(a, b)
+        ga, gb = torch.autograd.grad(a, (xa, ya), gg), torch.autograd.grad(b, (xb, yb), gg)
+        assert torch.equal(ga[0].reshape(O, M, G, Sn, W).permute(0, 2, 1, 3, 4).reshape(O, G * M * Sn, W), gb[0]) and torch.equal(ga[1], gb[1])
+    N = M * Sn
+    x64 = flat.double().reshape(O, G, N, W)      # float64 of the pooled set
+    A, B = (x64 - y.double().unsqueeze(-2)).norm(dim=-1).sum(-1) / N, torch.cdist(x64, x64).sum((-2, -1)) / (2 * N * (N - 1))
+    a = S.sample_energy(x.to(DEV), Sn, y.to(DEV), members=M)
+    assert ((a.double().cpu() - (A - B)).abs() <= (W / 2 + 2 * N + 8) * U * (A + B)).all()
+
+
+def test_unaligned_and_non_contiguous_inputs_give_the_bits_of_their_clones():
+    G, N, W = 4, 6, 37
+    buf = torch.randn(G * N * W + 1, device=DEV)
+    tb = torch.randn(G * W + 1, device=DEV)
+    xu, tu = buf[1:].reshape(G * N, W).requires_grad_(True), tb[1:].reshape(G, W).requires_grad_(True)      # 4 bytes off a 16-byte boundary
+    xc, tc = buf[1:].clone().reshape(G * N, W).requires_grad_(True), tb[1:].clone().reshape(G, W).requires_grad_(True)
+    g = torch.randn(G, device=DEV)
+    a, b = S.sample_energy(xu, N, tu), S.sample_energy(xc, N, tc)
+    assert torch.equal(a, b)
+    ga, gb = torch.autograd.grad(a, (xu, tu), g), torch.autograd.grad(b, (xc, tc), g)
+    assert torch.equal(ga[0], gb[0]) and torch.equal(ga[1], gb[1])
+    wide = torch.randn(G * N, 2 * W, device=DEV).requires_grad_(True)
+    tw = torch.randn(G, 2 * W, device=DEV).requires_grad_(True)
+    xs, ts = wide[:, ::2], tw[:, ::2]                                                     # non-contiguous views
+    xk, tk = xs.detach().clone().requires_grad_(True), ts.detach().clone().requires_grad_(True)
+    assert not xs.is_contiguous()
+    c1, c2 = S.sample_energy(xs, N, ts), S.sample_energy(xk, N, tk)
+    assert torch.equal(c1, c2)
+    g1, g2 = torch.autograd.grad(c1, (wide, tw), g), torch.autograd.grad(c2, (xk, tk), g)
+    assert torch.equal(g1[0][:, ::2], g2[0]) and torch.equal(g1[1][:, ::2], g2[1]) and float(g1[0][:, 1::2].abs().max()) == 0
+
+
+def test_path_mode_agrees_with_the_permuted_copy_where_chunks_straddle_the_outer_axis():
+    """outer = 3, W = 33: V = 99, the chunks of 16 columns cross o at 33 and 66.  Against the path=False call on the permuted
+    (G N, outer W) copy within the sum of the two value bounds, and against float64."""
+    O, G, N, W = 3, 4, 6, 33
+    V = O * W
+    gen = torch.Generator().manual_seed(8)
+    x = torch.randn(O, G * N, W, generator=gen)
+    x[:, 1::N] = x[:, 0::N]
+    y, g = torch.randn(O, G, W, generator=gen), torch.randn(G, generator=gen)
+    px, py = x.movedim(0, -2).reshape(G * N, V).contiguous(), y.movedim(0, -2).reshape(G, V).contiguous()
+    ref = S.sample_energy(px.double().requires_grad_(True), N, py.double().requires_grad_(True))
+    x64 = px.double().reshape(G, N, V)
+    scale = ((x64 - py.double()[:, None]).norm(dim=-1).sum(1) / N + torch.cdist(x64, x64).sum((1, 2)) / (2 * N * (N - 1))).numpy()
+    bound = (V / 2 + 2 * N + 8) * U * scale
+    xa, ya = x.to(DEV).requires_grad_(True), y.to(DEV).requires_grad_(True)
+    xb, yb = px.to(DEV).requires_grad_(True), py.to(DEV).requires_grad_(True)
+    a, b = S.sample_energy(xa, N, ya, path=True), S.sample_energy(xb, N, yb)
+    assert tuple(a.shape) == (G,)
+    assert (np.abs((a - b).detach().double().cpu().numpy()) <= 2 * bound).all()
+    assert (np.abs(a.detach().double().cpu().numpy() - ref.detach().numpy()) <= bound).all()
+    ga, gb = torch.autograd.grad(a, (xa, ya), g.to(DEV)), torch.autograd.grad(b, (xb, yb), g.to(DEV))
+    gbound = (V / 2 + N + 8) * U * g.abs().double().numpy() * (2.0 / N)
+    da = (ga[0].movedim(0, -2).reshape(G, N, V) - gb[0].reshape(G, N, V)).abs().double().cpu().numpy()
+    assert (da <= 2 * gbound[:, None, None]).all()
+    assert ((ga[1].movedim(0, -2).reshape(G, V) - gb[1]).abs().double().cpu().numpy() <= 2 * (V / 2 + N + 8) * U * g.abs().double().numpy()[:, None]).all()
+    assert float(ga[0].abs().max()) > 0 and float(ga[1].abs().max()) > 0
+
+
+def test_width_one_agrees_with_the_crps_kernel():
+    """V = 1: within the sum of the two scores' bounds, (1 / 2 + 2 N + 8) u (A + B') and (2 N + 4) u (A + B'_crps)."""
+    G, N = 7, 12
+    gen = torch.Generator().manual_seed(9)
+    x = torch.randn(G * N, 1, generator=gen)
+    x[1::N] = x[0::N]
+    y = torch.randn(G, 1, generator=gen)
+    x64, y64 = x.double().reshape(G, N), y.double()
+    d = x64 - y64
+    A = d.abs().sum(1) / N
+    Bp = (x64[:, :, None] - x64[:, None, :]).abs().sum((1, 2)) / (2 * N * (N - 1))
+    c = ((x64[:, None, :] < x64[:, :, None]).sum(2) - (x64[:, None, :] > x64[:, :, None]).sum(2)).double()
+    Bc = (c.abs() * d.abs()).sum(1) / (N * (N - 1))
+    e, cr = S.sample_energy(x.to(DEV), N, y.to(DEV)), S.sample_crps(x.to(DEV), N, y.to(DEV))[..., 0]
+    bound = (0.5 + 2 * N + 8) * U * (A + Bp) + (2 * N + 4) * U * (A + Bc)
+    assert ((e - cr).abs().double().cpu() <= bound).all()
+    assert ((e.double().cpu() - (A - Bp)).abs() <= (0.5 + 2 * N + 8) * U * (A + Bp)).all()
+
+
+def test_more_than_256_pooled_samples_take_the_tensor_op_route():
+    """N = 257: tensor ops in float32 on the device - distances from differences, then torch's own sums: within the same
+    (V / 2 + 2 N + 8) u (A + B') of float64 (a tree sum is no deeper than the 2 N levels the bound allows)."""
+    G, N, W = 2, 257, 3
+    gen = torch.Generator().manual_seed(5)
+    x, y = torch.randn(G * N, W, generator=gen), torch.randn(G, W, generator=gen)
+    xd = x.to(DEV).requires_grad_(True)
+    e = S.sample_energy(xd, N, y.to(DEV))
+    assert e.grad_fn is not None and not type(e.grad_fn).__name__.startswith('_SampleEnergy')
+    x64 = x.double().reshape(G, N, W)
+    A, B = (x64 - y.double()[:, None]).norm(dim=-1).sum(1) / N, torch.cdist(x64, x64).sum((1, 2)) / (2 * N * (N - 1))
+    assert ((e.detach().double().cpu() - (A - B)).abs() <= (W / 2 + 2 * N + 8) * U * (A + B)).all()
+    gx, = torch.autograd.grad(e.sum(), xd)
+    assert bool(torch.isfinite(gx).all()) and float(gx.abs().max()) > 0
+
+
+def test_forward_and_backward_replay_from_one_graph_on_new_values():
+    G, N, W = 7, 12, 50
+    gen = torch.Generator().manual_seed(6)
+    first = [torch.randn(G * N, W, generator=gen).to(DEV), torch.randn(G, W, generator=gen).to(DEV), torch.randn(G, generator=gen).to(DEV)]
+    second = [torch.randn(G * N, W, generator=gen).to(DEV), torch.randn(G, W, generator=gen).to(DEV), torch.randn(G, generator=gen).to(DEV)]
+    second[0][1] = second[0][0]
+    sx, sy, sg = (t.clone() for t in first)
+    sx.requires_grad_(True)
+    sy.requires_grad_(True)
+
+    def step(x, y, g):
+        e = S.sample_energy(x, N, y)
+        gx, gy = torch.autograd.grad(e, (x, y), g)
+        return e.detach(), gx, gy
+
+    side = torch.cuda.Stream()      # (warm-up outside the capture, on a side stream as capture asks)
+    side.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(side):
+        step(sx, sy, sg)
+    torch.cuda.current_stream().wait_stream(side)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        static = step(sx, sy, sg)
+    with torch.no_grad():
+        for dst, src in zip((sx, sy, sg), second):
+            dst.copy_(src)
+    graph.replay()
+    torch.cuda.synchronize()
+    eager = step(second[0].clone().requires_grad_(True), second[1].clone().requires_grad_(True), second[2])
+    for name, a, b in zip(('energy', 'grad_ys', 'grad_target'), static, eager):
+        assert torch.equal(a, b), name
+    assert float(static[0].abs().max()) > 0 and float(static[1].abs().max()) > 0
+
+
+TIMES = np.array([0., 1., 2., 3., 4., 5.], np.float32)
+
+
+def _solve_and_score(pr, target, B, Sn, H):
+    m = S.Diffusion_model(3, H, H, 2, input_option=4, noise_option=17)
+    m.load_state_dict({k: torch.from_numpy(v.copy()) for k, v in pr['params'].items()})
+    m = m.to(DEV)
+    coeffs = torch.from_numpy(pr['coeffs']).to(DEV).requires_grad_(True)
+    m.set_X(coeffs, torch.from_numpy(TIMES).to(DEV))
+    y0 = torch.from_numpy(pr['y0']).to(DEV).repeat_interleave(Sn, 0).requires_grad_(True)
+    ys = S.sdeint(m, y0, torch.tensor([0., 2., 5.], device=DEV), method='euler', dt=1.0, options={'samples': Sn, 'sample_grad': True, 'seed': 17})
+    assert tuple(ys.shape) == (3, B * Sn, H)
+    score = S.sample_energy(ys[1:], Sn, target, path=True)      # the two solved times by H channels: one vector per path
+    assert tuple(score.shape) == (B,)
+    score.mean().backward()
+    return m, coeffs, y0, score
+
+
+def test_a_sampled_solve_trains_through_the_path_score():
+    B, Sn, H = 5, 4, 64
+    pr = make_problem(23, 4, 17, 2, B, H, 3, len(TIMES), times=TIMES)
+    target = torch.from_numpy(np.random.default_rng(2).standard_normal((2, B, H)).astype(np.float32)).to(DEV)
+    m, coeffs, y0, score = _solve_and_score(pr, target, B, Sn, H)
+    grads = {n: p.grad for n, p in m.named_parameters()}
+    grads.update(y0=y0.grad, coeffs=coeffs.grad)
+    for n, gr in grads.items():
+        assert gr is not None and bool(torch.isfinite(gr).all()) and float(gr.abs().max()) > 0, n
+    m2, coeffs2, y02, score2 = _solve_and_score(pr, target, B, Sn, H)
+    assert torch.equal(score, score2) and torch.equal(y0.grad, y02.grad) and torch.equal(coeffs.grad, coeffs2.grad)
+    for (n, p), (_, p2) in zip(m.named_parameters(), m2.named_parameters()):
+        assert torch.equal(p.grad, p2.grad), n
+
+
+def test_ensemble_trains_on_energy_loss_through_a_graphed_step():
+    M, Sn, B, H, Cn, out_time = 2, 2, 4, 64, 3, 2
+    pr = make_problem(31, 4, 17, 2, B, H, Cn, len(TIMES), times=TIMES)
+    models = []
+    for mi in range(M):
+        torch.manual_seed(700 + mi)
+        func = S.Diffusion_model(Cn, H, H, 2, input_option=4, noise_option=17)
+        models.append(S.NeuralSDE_forecasting(func, Cn, out_time, H, Cn).to(DEV))
+    ens = S.Ensemble(models).train()
+    ens2 = copy.deepcopy(ens)
+    coeffs, times = torch.from_numpy(pr['coeffs']).to(DEV), torch.from_numpy(TIMES).to(DEV)
+    true = torch.from_numpy(np.random.default_rng(4).standard_normal((B, out_time, Cn)).astype(np.float32)).to(DEV)
+    lengths = torch.full((B,), len(TIMES) - 1, device=DEV)
+    kwargs = {'method': 'euler', 'options': {'seed': 9, 'samples': Sn, 'ensemble_samples': True, 'ensemble_grad': True, 'sample_grad': True}}
+    base = S.energy_loss(Sn, members=M)
+    seen = []
+
+    def loss_fn(pred, y):
+        assert tuple(pred.shape) == (M, B * Sn, out_time, Cn)
+        loss = base(pred, y)
+        seen.append(loss.detach())      # (under capture: a view of the recording's loss, refreshed by every replay)
+        return loss
+
+    opt = torch.optim.Adam(ens.parameters(), lr=1e-3, capturable=True)
+    for _ in range(2):
+        loss_fn(ens(times, (coeffs,), lengths, **kwargs), true).backward()
+        opt.step()
+        opt.zero_grad(set_to_none=True)
+    eager = [t.clone() for t in seen]
+    del seen[:]
+    opt2 = torch.optim.Adam(ens2.parameters(), lr=1e-3, capturable=True)
+    graphed = train.GraphedStep(ens2, times, opt2, loss_fn, kwargs, torch.device(DEV), warmup=1)
+    graphed((coeffs,), true, lengths)      # the warm-up step of this batch shape: eager
+    graphed((coeffs,), true, lengths)      # recorded, then replayed
+    torch.cuda.synchronize()
+    assert graphed.disabled is None and graphed.replays == 1, graphed.disabled
+    assert len(seen) == 2 and torch.equal(seen[0], eager[0]) and torch.equal(seen[1], eager[1])
+    assert float(eager[1]) > 0 and not torch.equal(eager[0], eager[1])
+    for p, p2 in zip(ens.parameters(), ens2.parameters()):
+        assert torch.equal(p, p2)
