@@ -731,7 +731,10 @@ SNSDE_API int snsde_ensemble_stats_backward(const float* grad_mean, const float*
  * ascending inside a quarter (sum += |d_n|; sum = fmaf(c_n, d_n, sum)), the four quarter sums are added k ascending, then one
  * division each and the subtraction.  No atomics, no dependence on the grid: the same bits on every launch.  Enqueue-only, no
  * workspace, capturable.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target or crps NULL.  SNSDE_ERR_DIMS:
- * a non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits. */
+ * a non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits.
+ * Non-finite values (here and in the statistics and the energy score): the comparisons are IEEE - a NaN sample counts in no
+ * c_n, in neither rank nor ties - and NaN and +-Inf flow through the arithmetic of the formulas as written (an infinite
+ * |d_n| against an infinite c_n d_n is NaN), in the one output element whose set holds them and in no other. */
 SNSDE_API int snsde_sample_crps(const float* ys, const float* target, int64_t outer, int32_t members, int64_t groups, int32_t samples,
                                 int32_t width, int32_t fair, float* crps, float* rank, float* ties, void* hip_stream);
 
@@ -749,6 +752,10 @@ SNSDE_API int snsde_sample_crps_backward(const float* grad_crps, const float* ys
  * the n_q requested levels the caller gives, from pos = q (N - 1) in double, k[i] = floor(pos) and frac[i] = (float)(pos - k[i]):
  *     out[i, o, g, w] = x_(k[i])                                                   where frac[i] == 0
  *                     = fmaf(frac[i], x_(k[i] + 1) - x_(k[i]), x_(k[i]))           otherwise
+ * A sample set that holds a NaN has no order: out is NaN at every level (torch.quantile's rule; a NaN is given no rank, every wave
+ * flags the NaNs of its quarter and the epilogue reads no order statistic of a flagged column - the same bits on every launch).
+ * A set with +-Inf and no NaN follows the formula: an order statistic may be +-Inf, and interpolating (frac[i] != 0) from -Inf or
+ * between equal infinities is NaN.
  * out is (n_q, outer, groups, width).  k and frac are HOST arrays of n_q entries, copied into the kernel's argument struct: no
  * device allocation, capturable.  SNSDE_ERR_DIMS also for n_q outside 1 .. 8, k[i] outside [0, N - 1], frac[i] outside [0, 1),
  * and k[i] == N - 1 with frac[i] != 0.  SNSDE_ERR_NULL: ys, k, frac or out NULL. */
@@ -757,7 +764,9 @@ SNSDE_API int snsde_sample_quantiles(const float* ys, int64_t outer, int32_t mem
 
 /* Adjoint of snsde_sample_quantiles: grad_out (n_q, outer, groups, width) = g_i; the ranks are formed again from ys,
  *     grad_ys[n] = sum_i ( g_i (1 - frac[i]) [r_n == k[i]] + g_i frac[i] [r_n == k[i] + 1, frac[i] != 0] ),   i ascending
- * and exact zeros everywhere else; every element of grad_ys is written. */
+ * and exact zeros everywhere else; every element of grad_ys is written.  In a set that holds a NaN (out is NaN there and has no
+ * derivative) the result is still a function of the inputs alone: a NaN sample has no rank and gets an exact zero, the F finite
+ * samples rank 0 .. F-1 among themselves and get the terms of the ranks they hold, and the terms of ranks >= F go nowhere. */
 SNSDE_API int snsde_sample_quantiles_backward(const float* grad_out, const float* ys, int64_t outer, int32_t members, int64_t groups,
                                               int32_t samples, int32_t width, int32_t n_q, const int32_t* k, const float* frac,
                                               float* grad_ys, void* hip_stream);

@@ -23,7 +23,8 @@ constexpr int WAVES = ST / LANES;   // waves sharing a tile
 constexpr int RB = 4;               // x_n held in registers per walk over the slab
 constexpr int MAX_N = 256;          // pooled samples: MAX_N * 256 B = 64 KB of LDS
 constexpr int MAX_Q = 8;            // quantiles per call (their k / frac travel in the kernel's argument struct)
-constexpr int MIN_ROWS = 16;        // slab rows allocated at least: the exchange area (MAX_Q * 2 * 64 floats) aliases the slab
+constexpr int XROWS = MAX_Q * 2;    // rows of the exchange area (MAX_Q * 2 * 64 floats), which aliases the slab
+constexpr int MIN_ROWS = XROWS + WAVES;   // slab rows allocated at least: the exchange area and one row of NaN flags per wave
 
 struct Dims {
     int64_t outer, G, mstride, wtiles, tiles;      // mstride = G S W; tiles = outer G wtiles, wtiles = ceil(W / 64)
@@ -80,7 +81,8 @@ __device__ __forceinline__ void strict_counts(const float* col, int N, const flo
     }
 }
 
-// permutation ranks, ties broken by index: rk[r] = #{j : x_j < xn[r]} + #{j < n[r] : x_j == xn[r]}
+// permutation ranks, ties broken by index: rk[r] = #{j : x_j < xn[r]} + #{j < n[r] : x_j == xn[r]}; a NaN has no rank: -1, which
+// no level asks for (both comparisons are false for it and nothing counts it: the finite samples rank among themselves)
 __device__ __forceinline__ void perm_ranks(const float* col, int N, const float (&xn)[RB], const int (&n)[RB], int (&rk)[RB]) {
 #pragma unroll
     for (int r = 0; r < RB; ++r) rk[r] = 0;
@@ -90,6 +92,8 @@ __device__ __forceinline__ void perm_ranks(const float* col, int N, const float 
 #pragma unroll
         for (int r = 0; r < RB; ++r) rk[r] += (xj < xn[r] || (xj == xn[r] && j < n[r])) ? 1 : 0;
     }
+#pragma unroll
+    for (int r = 0; r < RB; ++r) rk[r] = xn[r] != xn[r] ? -1 : rk[r];
 }
 
 __device__ __forceinline__ float sign0(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
@@ -192,7 +196,9 @@ __global__ void __launch_bounds__(ST) snsde_sample_crps_backward_kernel(const fl
     }
 }
 
-// out[q] = x_(k_q), or fmaf(frac_q, x_(k_q + 1) - x_(k_q), x_(k_q)) where frac_q != 0
+// out[q] = x_(k_q), or fmaf(frac_q, x_(k_q + 1) - x_(k_q), x_(k_q)) where frac_q != 0; NaN at every level where the column holds a
+// NaN.  Such a column has fewer ranked samples than levels may ask for, so some exchange rows are never written: every wave flags
+// the NaNs of its own quarter, and the epilogue reads no exchange row of a flagged column.
 __global__ void __launch_bounds__(ST) snsde_sample_quantiles_kernel(const float* __restrict__ ys, Dims d, QArgs qa, float* __restrict__ outq) {
     extern __shared__ float slab[];
     const int lane = threadIdx.x & (LANES - 1), wave = __builtin_amdgcn_readfirstlane(threadIdx.x / LANES);
@@ -204,7 +210,8 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_kernel(const float*
         stage(ys, tl, d, slab, wave, lane);
         __syncthreads();
         float lo[MAX_Q], hi[MAX_Q];
-        unsigned found_lo = 0, found_hi = 0;      // (a rank is held by exactly one sample: one wave finds each order statistic)
+        unsigned found_lo = 0, found_hi = 0;      // (a rank is held by at most one sample: one wave finds each order statistic)
+        float has_nan = 0.0f;
 #pragma unroll
         for (int q = 0; q < MAX_Q; ++q) lo[q] = hi[q] = 0.0f;
         for (int nb = n0; nb < n1; nb += RB) {
@@ -219,6 +226,7 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_kernel(const float*
 #pragma unroll
             for (int r = 0; r < RB; ++r) {
                 if (nb + r < n1) {
+                    has_nan = rk[r] < 0 ? 1.0f : has_nan;
 #pragma unroll
                     for (int q = 0; q < MAX_Q; ++q) {
                         if (q < qa.n_q && rk[r] == qa.k[q]) { lo[q] = xn[r]; found_lo |= 1u << q; }
@@ -233,15 +241,22 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_kernel(const float*
             if (found_lo & (1u << q)) slab[(q * 2 + 0) * LANES + lane] = lo[q];
             if (found_hi & (1u << q)) slab[(q * 2 + 1) * LANES + lane] = hi[q];
         }
+        slab[(XROWS + wave) * LANES + lane] = has_nan;
         __syncthreads();
         if (wave == 0 && tl.live) {
-                const int64_t plane = d.outer * d.G * d.W;
+            const int64_t plane = d.outer * d.G * d.W;
+            bool bad = false;
+#pragma unroll
+            for (int k = 0; k < WAVES; ++k) bad |= slab[(XROWS + k) * LANES + lane] != 0.0f;
 #pragma unroll
             for (int q = 0; q < MAX_Q; ++q) {
                 if (q < qa.n_q) {
-                    const float a = slab[(q * 2 + 0) * LANES + lane];
-                    float v = a;
-                    if (qa.frac[q] != 0.0f) v = fmaf(qa.frac[q], slab[(q * 2 + 1) * LANES + lane] - a, a);
+                    float v = __builtin_nanf("");
+                    if (!bad) {
+                        const float a = slab[(q * 2 + 0) * LANES + lane];
+                        v = a;
+                        if (qa.frac[q] != 0.0f) v = fmaf(qa.frac[q], slab[(q * 2 + 1) * LANES + lane] - a, a);
+                    }
                     outq[q * plane + tl.out] = v;
                 }
             }
@@ -249,7 +264,9 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_kernel(const float*
     }
 }
 
-// grad_ys[n] = sum_q g_q (1 - frac_q) [rank_n == k_q] + g_q frac_q [rank_n == k_q + 1], q ascending; exact zeros elsewhere
+// grad_ys[n] = sum_q g_q (1 - frac_q) [rank_n == k_q] + g_q frac_q [rank_n == k_q + 1], q ascending; exact zeros elsewhere.  In a
+// column that holds a NaN (forward: NaN) a NaN sample has no rank and gets an exact zero; the finite samples get the terms of the
+// ranks they hold among themselves, and the terms of ranks nobody holds go nowhere: still a function of the inputs alone.
 __global__ void __launch_bounds__(ST) snsde_sample_quantiles_backward_kernel(const float* __restrict__ gout, const float* __restrict__ ys, Dims d,
                                                                              QArgs qa, float* __restrict__ gys) {
     extern __shared__ float slab[];

@@ -1302,7 +1302,9 @@ def sample_crps(ys, samples, target, fair=True, members=1, rank=False):
     estimator, N >= 2) or D = N,
         crps = sum |d_n| / N - sum c_n d_n / (N D)        (= mean |x - y| - sum_ij |x_i - x_j| / (2 N D))
     of shape (..., B, W); with rank=True returns (crps, rank, ties), rank = #{x_n < y} and ties = #{x_n == y} as float32 (for the
-    PIT / rank histogram; no gradient).  Differentiable in ys and target, sign(0) = 0.
+    PIT / rank histogram; no gradient).  Differentiable in ys and target, sign(0) = 0.  The comparisons are IEEE (a NaN sample
+    counts in no c_n, in neither rank nor ties) and NaN / +-Inf flow through the formula as written, in the one element whose
+    set holds them: a diverged path turns its own score into NaN and no other.
     CUDA float32 inputs with N <= 256: one launch of snsde_sample_crps (the (N, 64-column) slab of a group staged in LDS, no
     (.., S, S, ..) intermediate, deterministic, capturable) - inside an autograd node whose backward is snsde_sample_crps_backward
     when an input requires grad.  Other tensors: the same definitions in tensor ops, the counts from a sort."""
@@ -1524,6 +1526,11 @@ def sample_quantiles(ys, samples, q, members=1):
     result (len(q), ..., B, W).  Linear interpolation between order statistics (torch.quantile's 'linear' rule): with
     pos = q (N - 1), k = floor(pos) and frac = float32(pos - k), the value is x_(k), or fma(frac, x_(k+1) - x_(k), x_(k)) where
     frac != 0; ties are ordered by index.  Differentiable in ys: the gradient goes to the one or two samples that set the value.
+    A sample set that holds a NaN has no order: NaN at every level (torch.quantile's rule), on every route.  A set with +-Inf
+    and no NaN follows the formula: an order statistic may be +-Inf, and interpolating (frac != 0) from -Inf or between equal
+    infinities is NaN.  The gradient of a set whose value is NaN is a derivative of nothing but a function of the inputs alone:
+    the kernel gives a NaN sample an exact zero and the finite samples, ranked among themselves, the terms of the ranks they
+    hold; the tensor-op route gives the whole set zeros.
     CUDA float32 input with N <= 256 and at most 8 levels: one launch of snsde_sample_quantiles (backward:
     snsde_sample_quantiles_backward); other tensors: a stable sort in tensor ops."""
     S, M, lead, G, W = _score_dims(ys, samples, members)
@@ -1533,12 +1540,15 @@ def sample_quantiles(ys, samples, q, members=1):
         if ys.requires_grad and torch.is_grad_enabled():
             return _SampleQuantiles.apply(ys, S, M, tuple(ks), tuple(fracs))
         return _sample_quantiles_launch(ys.contiguous(), S, M, ks, fracs)
-    xs = torch.sort(_pooled(ys, S, M, lead, G, W), dim=-2, stable=True).values
+    x = _pooled(ys, S, M, lead, G, W)
+    xs = torch.sort(x, dim=-2, stable=True).values
     out = []
     for k, frac in zip(ks, fracs):
         lo = xs[..., k, :]
         out.append(lo if frac == 0.0 else lo + frac * (xs[..., k + 1, :] - lo))
-    return torch.stack(out)
+    out = torch.stack(out)
+    # a set that holds a NaN has no order: NaN at every level (the sort puts a NaN last, which would leave the low levels finite)
+    return torch.where(torch.isnan(x).any(dim=-2), torch.full_like(out[:1], float('nan')), out)
 
 
 def _sample_quantiles_launch(ys, S, M, ks, fracs):
