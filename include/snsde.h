@@ -809,6 +809,57 @@ SNSDE_API int snsde_sample_energy_backward(const float* grad_energy, const float
                                            int64_t groups, int32_t samples, int32_t width, int32_t fair, int32_t path, float* grad_ys,
                                            float* grad_target, void* hip_stream);
 
+/* Masked Gaussian log-likelihood of sample paths and its importance-weighted (IWAE) bound: the training objective for data with
+ * missing entries.  ys viewed as (outer, M, G, S, W) exactly as for snsde_sample_energy with path != 0: pooled sample
+ * n = m S + s, N = M S; vector component v = o W + w, V = outer W; addressed in place (no permuted copy).  target y and mask m
+ * are (outer, groups, width); an element is observed where m_v != 0.  The observation noise is one scalar std > 0: the caller
+ * computes logvar = 2 log(std) and inv_var = exp(-logvar) in double and passes both as float.
+ *     logpx[g, n] = sum_{v observed} m_v (-1/2) (log 2 pi + logvar + (y_v - x_nv)^2 inv_var)                 (groups, N)
+ *     count[g]    = sum_{v observed} m_v                                                                     (groups)
+ *     norm != 0:    logpx[g, .] is divided by count[g] where count[g] > 0 and stays 0 where count[g] == 0 (a deliberate
+ *                   difference from dividing 0 by 0)
+ *     bound[g]    = logsumexp_n(logpx[g, n] + logw[g, n]) - log N                                            (groups)
+ *     sqerr[g]    = sum_{v observed} m_v (y_v - xbar_v)^2,  xbar_v = (sum_n x_nv) / N                        (groups)
+ * logw (groups, N) is an optional log importance weight (-kl_coef * kl, the per-path KL column of a latent solve); NULL = 0.
+ * sqerr is the numerator of the masked mean squared error of the sample mean (the caller divides by count): a metric.
+ * Select, never multiply: an element with m_v == 0 enters no sum (exact +0; its samples are not loaded) and receives an exact-zero
+ * gradient, whatever target or ys hold there (NaN-marked missing data is accepted as it is).  Fractional mask values weigh.
+ * A NaN in an observed element of path n makes logpx[g, n], bound[g] and sqerr[g] NaN and touches no other group; the
+ * logsumexp subtracts the maximum (all -Inf gives -Inf, a NaN gives NaN).
+ * One workgroup of 256 threads per group (grid stride beyond 8192 groups).  L = min(32, largest power of two <= 256 / N) lanes
+ * share a sample; the group's N x V slab passes once from memory, coalesced along w, through LDS in chunks of CW = 64 L columns
+ * as the residuals d_nv = y_v - x_nv (row stride CW + L mod 32 words: the transposed read of the per-sample sums is free of
+ * bank conflicts); the thread that stages a column adds its residuals as they arrive.  Summation order, a function of (N, V) only:
+ *   q_n = sum_v m_v d_nv^2: sub-lane l a chain q = fmaf(m_v d, d, q) over v = l (mod L) ascending, the L chains by a butterfly
+ *   (xor 1, .., L / 2); count likewise with additions; logpx = -0.5f fmaf(inv_var, q, ((float)log 2 pi + logvar) count), then
+ *   the division under norm;
+ *   s_v = sum_n d_nv: n ascending inside each of RS = max(1, 4 / L) contiguous parts [k N / RS, (k + 1) N / RS), the parts in
+ *   order; e_v = s_v / N; thread t a chain fmaf(m_v e_v, e_v, .) over v = t (mod min(CW, 256)) ascending; the 64 lanes of a
+ *   wave by a butterfly (xor 1, .., 32), the four waves in order;
+ *   bound: max_n a_n, a_n = logpx_n + logw_n; lane i a chain of expf(a_n - max) over n = i (mod 64) ascending, the lanes by a
+ *   butterfly; max + logf(sum) - logf((float)N).
+ * No atomics, no workspace, no dependence on the grid, the pointer alignment or `members`: the same bits on every launch, and a
+ * pooled call gives the bits of the members = 1 call on the permuted tensor.  Enqueue-only, capturable.  All pointers device,
+ * fp32, contiguous.  SNSDE_ERR_NULL: ys, target, mask, logpx, count, bound or sqerr NULL.  SNSDE_ERR_DIMS: a non-positive
+ * extent, N > 256, logvar or inv_var not finite or inv_var <= 0 (a non-finite or non-positive std), an element count beyond 63 bits. */
+SNSDE_API int snsde_sample_loglik(const float* ys, const float* target, const float* mask, const float* logw, int64_t outer,
+                                  int32_t members, int64_t groups, int32_t samples, int32_t width, float logvar, float inv_var,
+                                  int32_t norm, float* logpx, float* count, float* bound, float* sqerr, void* hip_stream);
+
+/* Adjoint of snsde_sample_loglik: grad_logpx (groups, N) and grad_bound (groups), either may be NULL (none).  With logpx and
+ * count as the forward left them, p_n = softmax_n(logpx[g, n] + logw[g, n]) (formed again in the kernel's prologue: <= 256
+ * terms per group) and c[g, n] = (grad_logpx[g, n] + grad_bound[g] p_n) / (count[g] under norm, else 1; 0 where count == 0),
+ *     grad_ys[n, v]   = c_n m_v (y_v - x_nv) inv_var                     (as ys; every element is written)
+ *     grad_target[v]  = -sum_n grad_ys[n, v], n ascending in the lane that owns the column   (optional, NULL = not wanted)
+ *     grad_logw[g, n] = grad_bound[g] p_n                                                    (optional, NULL = not wanted)
+ * computed as ((c_n inv_var) m_v) (y_v - x_nv).  Unobserved elements of grad_ys and grad_target are exact +0.  sqerr, mask and
+ * the variance carry no gradient.  Elementwise over the slab: a workgroup per (group, 256 adjacent columns).  The same errors
+ * and guarantees; SNSDE_ERR_NULL: ys, target, mask, logpx, count or grad_ys NULL. */
+SNSDE_API int snsde_sample_loglik_backward(const float* grad_logpx, const float* grad_bound, const float* ys, const float* target,
+                                           const float* mask, const float* logw, const float* logpx, const float* count, int64_t outer,
+                                           int32_t members, int64_t groups, int32_t samples, int32_t width, float logvar, float inv_var,
+                                           int32_t norm, float* grad_ys, float* grad_target, float* grad_logw, void* hip_stream);
+
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /
  * snsde_backward / snsde_head); SNSDE_ERR_ABI otherwise.  A size of 0 means "this binding does not declare that struct"

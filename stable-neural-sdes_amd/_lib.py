@@ -110,7 +110,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward',
            'snsde_solve_forward_at', 'snsde_sample_crps', 'snsde_sample_crps_backward', 'snsde_sample_quantiles',
-           'snsde_sample_quantiles_backward', 'snsde_sample_energy', 'snsde_sample_energy_backward')
+           'snsde_sample_quantiles_backward', 'snsde_sample_energy', 'snsde_sample_energy_backward', 'snsde_sample_loglik',
+           'snsde_sample_loglik_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -202,6 +203,11 @@ def lib():
     L.snsde_sample_energy.argtypes = [C.c_void_p, C.c_void_p] + dims + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
     L.snsde_sample_energy_backward.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p] + dims + [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p,
                                                                                              C.c_void_p]
+    # (ys, target, mask, logw, dims, logvar, inv_var, norm, logpx, count, bound, sqerr, stream) /
+    # (grad_logpx, grad_bound, ys, target, mask, logw, logpx, count, dims, logvar, inv_var, norm, grad_ys, grad_target, grad_logw, stream)
+    var = [C.c_float, C.c_float, C.c_int32]
+    L.snsde_sample_loglik.argtypes = [C.c_void_p] * 4 + dims + var + [C.c_void_p] * 5
+    L.snsde_sample_loglik_backward.argtypes = [C.c_void_p] * 8 + dims + var + [C.c_void_p] * 4
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

@@ -7,6 +7,7 @@ import os
 import ctypes as C
 import collections
 import functools
+import math
 import struct
 from collections import OrderedDict
 
@@ -1493,6 +1494,162 @@ class _SampleEnergy(torch.autograd.Function):
         gys, gt = sample_energy_backward(grad_energy.to(torch.float32).contiguous(), ys, target, ctx.S, ctx.fair, ctx.M, ctx.path,
                                          grad_target=ctx.needs_input_grad[1])
         return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None
+
+
+def _loglik_args(ys, samples, target, mask, std, members, log_weight):
+    """(S, M, lead, G, W, N, mask, logvar, inv_var) of a masked likelihood; the argument errors of `sample_loglik`.  mask=None is
+    ~isnan(target) as float32; a bool mask becomes float32.  logvar = 2 log(std) and inv_var = exp(-logvar) in double."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    if tuple(target.shape) != lead + (G, W):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {lead + (G, W)} (one observed vector per input row)')
+    if mask is None:
+        mask = (~torch.isnan(target)).to(torch.float32)
+    elif tuple(mask.shape) != lead + (G, W):
+        raise ValueError(f'mask has shape {tuple(mask.shape)}, expected {lead + (G, W)} (the shape of target)')
+    elif not mask.dtype.is_floating_point:
+        mask = mask.to(torch.float32)
+    if isinstance(std, bool) or not isinstance(std, (int, float, np.integer, np.floating)) or not math.isfinite(std) or std <= 0:
+        raise ValueError(f'std must be a finite number > 0 (the standard deviation of the observation noise), got {std!r}')
+    if log_weight is not None and tuple(log_weight.shape) != (G, N):
+        raise ValueError(f'log_weight has shape {tuple(log_weight.shape)}, expected {(G, N)} (one log importance weight per input '
+                         f'row and pooled sample)')
+    logvar = 2.0 * math.log(float(std))
+    return S, M, lead, G, W, N, mask, logvar, math.exp(-logvar)
+
+
+def sample_loglik(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False):
+    """Masked Gaussian log-likelihood of the sample paths of a solve against a partially observed target, and its
+    importance-weighted (IWAE) bound: the objective that trains options={'samples': S} on data with gaps.  ys is
+    (..., B S, W) or (..., M, B S, W) as for `sample_energy(path=True)`: the pooled samples x_n (n = m S + s, N = M S) of an
+    input row are vectors of ALL leading axes by W, component v, addressed in place.  target y and mask m are (..., B, W); an
+    element is observed where m_v != 0, and mask=None means ~isnan(target) as float32.  std > 0 is the scalar standard deviation
+    of the observation noise, logvar = 2 log(std) (in double).
+        logpx[b, n] = sum_{v observed} m_v (-1/2) (log 2 pi + logvar + (y_v - x_nv)^2 / var)                  (B, N)
+        count[b]    = sum_{v observed} m_v                                                                    (B,)
+        norm=True:    logpx[b, .] / count[b] where count[b] > 0, and 0 where count[b] == 0 (the reference's args.norm would give
+                      0 / 0 there: a deliberate difference)
+        bound[b]    = logsumexp_n(logpx[b, n] + log_weight[b, n]) - log N                                     (B,)
+        sqerr[b]    = sum_{v observed} m_v (y_v - mean_n x_nv)^2      (the numerator of the masked MSE of the sample mean: divide
+                      by count; a metric, no gradient - like rank in `sample_crps`)
+    log_weight (B, N) is an optional log importance weight: -kl_coef * kl of the reference's objective, or the per-path KL
+    column of the latent route; None is 0.  Returns bound, or (bound, logpx, count, sqerr) with stats=True.
+    Select, never multiply: an element with m_v == 0 is never read into a sum - it contributes an exact +0 and receives an
+    exact-zero gradient, whatever target or ys hold there.  NaN-marked targets (the convention of torchcde and of
+    natural_cubic_spline_coeffs) are accepted as they are; the reference multiplies by the mask and needs them zero-filled.
+    Fractional mask values act as weights.  A NaN in an observed element of path n makes logpx[b, n], bound[b] and sqerr[b] NaN
+    and touches no other row.  Differentiable in ys, target and log_weight; not in mask or std.
+    CUDA float32 inputs with N <= 256: one launch of snsde_sample_loglik (the slab read once, no intermediate, deterministic,
+    capturable) - inside an autograd node whose backward is snsde_sample_loglik_backward when an input requires grad.  Other
+    tensors: `sample_loglik_tensor_ops`."""
+    norm, stats = bool(norm), bool(stats)
+    S, M, lead, G, W, N, mask, logvar, inv_var = _loglik_args(ys, samples, target, mask, std, members, log_weight)
+    others = (target, mask) if log_weight is None else (target, mask, log_weight)
+    if _score_native(ys, N, *others):
+        if any(t.requires_grad for t in (ys,) + others) and torch.is_grad_enabled():
+            out = _SampleLoglik.apply(ys, target, mask, log_weight, S, M, logvar, inv_var, norm)
+        else:
+            out = _sample_loglik_launch(ys.contiguous(), target.contiguous(), mask.contiguous(),
+                                        None if log_weight is None else log_weight.contiguous(), S, M, logvar, inv_var, norm)
+        return out if stats else out[0]
+    return sample_loglik_tensor_ops(ys, S, target, mask, std, M, log_weight, norm, stats)
+
+
+def sample_loglik_tensor_ops(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False):
+    """`sample_loglik` stated in tensor ops (any device and dtype; autograd differentiates it): torch.where on the mask selects
+    the observed residuals - never a product with the mask - so NaN and Inf at unobserved positions reach neither a value nor a
+    gradient.  What `sample_loglik` runs off the kernels' domain, and the baseline the kernels are timed against."""
+    norm, stats = bool(norm), bool(stats)
+    S, M, lead, G, W, N, mask, logvar, inv_var = _loglik_args(ys, samples, target, mask, std, members, log_weight)
+    O = _outer(lead)
+    x = _pooled(ys, S, M, lead, G, W).reshape(O, G, N, W).permute(1, 2, 0, 3).reshape(G, N, O * W)      # (G, N, V)
+    y = target.to(x.dtype).reshape(O, G, W).permute(1, 0, 2).reshape(G, 1, O * W)
+    m = mask.detach().to(x.dtype).reshape(O, G, W).permute(1, 0, 2).reshape(G, 1, O * W)
+    obs = m != 0
+    d = torch.where(obs, y - x, x.new_zeros(()))                                  # (G, N, V): exact zeros where unobserved
+    logpx = (-0.5 * m * ((math.log(2.0 * math.pi) + logvar) + d * d * inv_var)).sum(dim=-1)
+    count = m.sum(dim=-1)                                                         # (G, 1)
+    if norm:
+        some = count > 0
+        logpx = torch.where(some, logpx / torch.where(some, count, torch.ones_like(count)), logpx.new_zeros(()))
+    a = logpx if log_weight is None else logpx + log_weight.to(x.dtype)
+    bound = torch.logsumexp(a, dim=-1) - math.log(N)
+    if not stats:
+        return bound
+    with torch.no_grad():      # (a metric)
+        e = d.mean(dim=1)
+        sqerr = (m[:, 0] * e * e).sum(dim=-1)
+    return bound, logpx, count[:, 0], sqerr
+
+
+def _sample_loglik_launch(ys, target, mask, logw, S, M, logvar, inv_var, norm):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    N = M * S
+    logpx = torch.empty((G, N), device=ys.device, dtype=torch.float32)
+    count, bound, sqerr = (torch.empty((G,), device=ys.device, dtype=torch.float32) for _ in range(3))
+    _lib.check(_lib.lib().snsde_sample_loglik(_ptr(ys), _ptr(target), _ptr(mask), _ptr(logw), _outer(lead), M, G, S, W, logvar, inv_var,
+                                              int(norm), _ptr(logpx), _ptr(count), _ptr(bound), _ptr(sqerr),
+                                              C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)), 'snsde_sample_loglik')
+    return bound, logpx, count, sqerr
+
+
+def sample_loglik_backward(grad_logpx, grad_bound, ys, target, mask, logpx, count, samples, std=0.1, members=1, log_weight=None,
+                           norm=False, grad_target=True, grad_log_weight=True):
+    """(dL/d ys, dL/d target, dL/d log_weight) of `sample_loglik` from dL/d logpx (B, N) and dL/d bound (B,) - either may be None -
+    and the forward's logpx and count: one launch of snsde_sample_loglik_backward.  dL/d target is None when grad_target=False,
+    dL/d log_weight when grad_log_weight=False.  Contiguous float32 CUDA tensors, shapes as for `sample_loglik`."""
+    S, M, lead, G, W, N, mask, logvar, inv_var = _loglik_args(ys, samples, target, mask, std, members, log_weight)
+    _check_f32('ys', ys)
+    _check_f32('target', target)
+    _check_f32('mask', mask)
+    _check_f32('logpx', logpx, (G, N))
+    _check_f32('count', count, (G,))
+    for name, t, shape in (('grad_logpx', grad_logpx, (G, N)), ('grad_bound', grad_bound, (G,)), ('log_weight', log_weight, (G, N))):
+        if t is not None:
+            _check_f32(name, t, shape)
+    return _sample_loglik_backward_launch(grad_logpx, grad_bound, ys, target, mask, log_weight, logpx, count, S, M, logvar, inv_var,
+                                          bool(norm), grad_target, grad_log_weight)
+
+
+def _sample_loglik_backward_launch(grad_logpx, grad_bound, ys, target, mask, logw, logpx, count, S, M, logvar, inv_var, norm,
+                                   grad_target, grad_logw):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    glw = torch.empty_like(logpx) if grad_logw else None
+    _lib.check(_lib.lib().snsde_sample_loglik_backward(_ptr(grad_logpx), _ptr(grad_bound), _ptr(ys), _ptr(target), _ptr(mask), _ptr(logw),
+                                                       _ptr(logpx), _ptr(count), _outer(lead), M, G, S, W, logvar, inv_var, int(norm),
+                                                       _ptr(gys), _ptr(gt), _ptr(glw),
+                                                       C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_loglik_backward')
+    return gys, gt, glw
+
+
+class _SampleLoglik(torch.autograd.Function):
+    """sample_loglik of CUDA float32 tensors of which one requires grad: the forward kernel, and snsde_sample_loglik_backward as its
+    backward (from the saved logpx and count).  count and sqerr carry no gradient; mask receives none."""
+
+    @staticmethod
+    def forward(ctx, ys, target, mask, logw, S, M, logvar, inv_var, norm):
+        ysc, tc, mc = ys.detach().contiguous(), target.detach().contiguous(), mask.detach().contiguous()
+        lw = None if logw is None else logw.detach().contiguous()
+        bound, logpx, count, sqerr = _sample_loglik_launch(ysc, tc, mc, lw, S, M, logvar, inv_var, norm)
+        ctx.S, ctx.M, ctx.logvar, ctx.inv_var, ctx.norm, ctx.has_logw = S, M, logvar, inv_var, norm, lw is not None
+        ctx.save_for_backward(ysc, tc, mc, logpx, count, *(() if lw is None else (lw,)))
+        ctx.mark_non_differentiable(count, sqerr)
+        ctx.set_materialize_grads(False)
+        return bound, logpx, count, sqerr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_bound, grad_logpx, grad_count, grad_sqerr):
+        ys, target, mask, logpx, count = ctx.saved_tensors[:5]
+        lw = ctx.saved_tensors[5] if ctx.has_logw else None
+        gb = None if grad_bound is None else grad_bound.to(torch.float32).contiguous()
+        gl = None if grad_logpx is None else grad_logpx.to(torch.float32).contiguous()
+        gys, gt, glw = _sample_loglik_backward_launch(gl, gb, ys, target, mask, lw, logpx, count, ctx.S, ctx.M, ctx.logvar, ctx.inv_var,
+                                                      ctx.norm, ctx.needs_input_grad[1], ctx.has_logw and ctx.needs_input_grad[3])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, glw, None, None, None, None, None
 
 
 def quantile_positions(q, N):

@@ -100,6 +100,33 @@ def energy_loss(samples, fair=True, members=1):
     return loss_fn
 
 
+def iwae_loss(samples, std=0.1, members=1, norm=False):
+    """loss_fn(pred, true) for `train_loop` / `GraphedStep` / `evaluate_metrics`: minus the mean importance-weighted bound
+    (engine.sample_loglik) of a model solved with options={'samples': S} against a partially observed target - the multi-sample
+    ELBO / IWAE objective on data with gaps.  pred and true as for `energy_loss`: (B S, ...) or (M, B S, ...), and (B, ...);
+    trailing axes are flattened into the vector.  A NaN in true marks a missing entry (the mask is ~isnan(true)); data that
+    carries its own mask is passed as true = (values, mask).  std is the standard deviation of the observation noise; norm
+    divides each row's likelihood by its number of observed entries."""
+    from . import engine
+    S = engine.check_samples(samples)
+
+    lead = 1 if members > 1 else 0      # (an Ensemble's leading member axis)
+
+    def loss_fn(pred_y, true_y):
+        true_y, mask = true_y if isinstance(true_y, (tuple, list)) else (true_y, None)
+        want = ((members,) if lead else ()) + (S * true_y.shape[0],) if true_y.dim() else None
+        if want is None or tuple(pred_y.shape[:lead + 1]) != want:
+            raise ValueError(f'iwae_loss(samples={S}, members={members}): pred has shape {tuple(pred_y.shape)} for a target of shape '
+                             f'{tuple(true_y.shape)}: expected {"(members, " if lead else "("}samples x target rows, ...)')
+        if mask is not None and tuple(mask.shape) != tuple(true_y.shape):
+            raise ValueError(f'iwae_loss: the mask has shape {tuple(mask.shape)} for a target of shape {tuple(true_y.shape)}')
+        pred = pred_y.reshape(want + (-1,))
+        true = true_y.reshape(true_y.shape[0], -1).to(pred.dtype)
+        mask = None if mask is None else mask.reshape(true.shape).to(pred.dtype)
+        return -engine.sample_loglik(pred, S, true, mask=mask, std=std, members=members, norm=norm).mean()
+    return loss_fn
+
+
 class SqueezeEnd(torch.nn.Module):
     def __init__(self, model):
         super().__init__()
