@@ -860,6 +860,62 @@ SNSDE_API int snsde_sample_loglik_backward(const float* grad_logpx, const float*
                                            int32_t members, int64_t groups, int32_t samples, int32_t width, float logvar, float inv_var,
                                            int32_t norm, float* grad_ys, float* grad_target, float* grad_logw, void* hip_stream);
 
+/* Classification with sample paths: the predictive (model-average) negative log-likelihood of a label, the expected
+ * cross-entropy, the predictive distribution and the split of its entropy.  logits viewed as (outer, M, G, S, C) exactly as ys
+ * for snsde_sample_crps: pooled path n = m S + s, N = M S <= 256; one result per (o, g).  labels are int32 (outer, groups) or
+ * NULL; logw (outer, groups, N) is an optional log importance weight as for snsde_sample_loglik (NULL = 0); class_weight (C
+ * classes; two for binary) is optional (NULL = 1).  binary != 0: the stored width is 1 and the two class logits of a path
+ * are (0, z) (a logit for BCE-with-logits; class_weight = (1, pos_weight) gives BCEWithLogitsLoss(pos_weight)).
+ * With lp_n[c] = z_n[c] - logsumexp_c z_n, a_n = lp_n[y], w = class_weight[y]:
+ *     logp[g, n]  = a_n                                                                              (outer, groups, N)
+ *     nll[g]      = -w (logsumexp_n(a_n + logw_n) - log N)          the predictive negative log-likelihood
+ *     xent[g]     = -w (1 / N) sum_n a_n                            the expected cross-entropy (>= nll where logw = 0)
+ *     probs[g, c] = (1 / N) sum_n exp(lp_n[c])                      (outer, groups, C); binary: (outer, groups, 1), class 1
+ *     entropy[g]  = -sum_c pbar_c log pbar_c   (0 log 0 = 0)        total uncertainty
+ *     expent[g]   = -(1 / N) sum_n sum_c p_nc lp_nc   (p = 0: 0)    expected entropy; entropy - expent is the mutual information
+ * Every logsumexp subtracts its maximum, and lp is formed as (z - max) - log sum exp(z - max): logits of magnitude 1e4 neither
+ * overflow nor lose the answer.  A -Inf logit is a class of probability zero (exact zeros).  label < 0 (or labels == NULL): the
+ * row is unlabelled, logp, nll and xent are exact +0 and probs, entropy, expent are computed all the same.  label >= the number
+ * of classes: NaN in logp, nll and xent.  The label only selects among values already read, by comparison with the column index:
+ * it forms no address.  A NaN logit in path n makes logp[g, n] and the group's nll, xent, probs, entropy and expent NaN and
+ * touches no other group.
+ * A workgroup of 256 threads per pack of GP adjacent groups (grid stride beyond 4096 packs).  L = min(64, least power of two
+ * >= C) lanes share a row, R = 256 / L rows at a time; GP = 1 for C > 64, else the largest power of two <= max(1, R / N).
+ * The pack's slab goes once from memory into LDS, coalesced along c, where GP N C <= 24576 floats, and everything else reads
+ * LDS; a larger one is read from memory by the row sums and a second time (from L2) for probs.  Summation order, a function of (N, C) only:
+ *   row: lane l the online pair (m, s) over c = l (mod L) ascending - z > m: s = s expf(m - z) + 1, m = z; else s += expf(z - m)
+ *   (shift 0 while m = -Inf) - then the row's maximum m' by a butterfly over the L lanes, each lane's s scaled once,
+ *   s expf(m - m'), and the L products added by a butterfly (xor 1, .., L / 2); ls = logf(s); lp_c = (z_c - m') - ls.
+ *   binary: m = max(0, z), s = expf(0 - m) + expf(z - m).
+ *   probs: C <= 64: thread (group, part k, column c) adds p_nc = expf(lp_nc) over n ascending in its part
+ *   [k N / RS, (k + 1) N / RS), RS = min(16, R / GP), then the parts k ascending; C > 64: thread t the columns c = t (mod 256),
+ *   n ascending; then / N.  The same thread adds p lp as it goes (C > 64: columns outer, rows inner), then the parts in order;
+ *   entropy adds -pbar logf(pbar) (C > 64: c ascending per thread); both then over the min(C', 64) column lanes (C' = L, or 256
+ *   for C > 64) by a butterfly (xor 1, ..) and for C > 64 over the four waves in order.  binary: pbar_0 is summed like pbar_1.
+ *   nll, xent: a'_n = a_n + logw_n; TN = min(64, 256 / GP) lanes per group; max over n; lane i the chains sum += expf(a'_n - max)
+ *   and sum += a_n over n = i (mod TN) ascending, the lanes by a butterfly; nll = -w (max + logf(sum) - logf((float)N)), xent =
+ *   -w (sum / N).  A NaN a'_n gives NaN, an infinite maximum max - logf(N).
+ * No atomics, no workspace, no dependence on the grid, the pointer alignment or `members`: the same bits on every launch, and a
+ * pooled call gives the bits of the members = 1 call on the permuted tensor.  Enqueue-only, capturable.  All pointers device,
+ * contiguous; fp32 but labels.  SNSDE_ERR_NULL: logits or an output NULL.  SNSDE_ERR_DIMS: a non-positive extent, N > 256,
+ * binary with width != 1, an element count beyond 63 bits. */
+SNSDE_API int snsde_sample_class(const float* logits, const int32_t* labels, const float* logw, const float* class_weight,
+                                 int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t binary,
+                                 float* logp, float* nll, float* xent, float* probs, float* entropy, float* expent, void* hip_stream);
+
+/* Adjoint of snsde_sample_class: grad_nll (outer, groups), grad_xent (outer, groups) and grad_logp (outer, groups, N), each may
+ * be NULL (none).  The row statistics are formed again as in the forward; with r_n = softmax_n(a_n + logw_n) (expf(a'_n - max) /
+ * sum, the forward's max and sum; the slab staged as in the forward) and k_n = w (grad_nll r_n + grad_xent / N) - grad_logp_n,
+ *     grad_logits[n, c] = k_n (p_nc - [c == y])                  (as logits; every element is written)
+ *     grad_logw[g, n]   = -w grad_nll[g] r_n                      (optional, NULL = not wanted)
+ * binary: the gradient of z is the class-1 column.  An unlabelled group's slab and grad_logw row are exact +0; a label >= the
+ * number of classes gives NaN in that group's rows.  probs, entropy, expent and class_weight carry no gradient.  The same
+ * errors and guarantees; SNSDE_ERR_NULL: logits or grad_logits NULL. */
+SNSDE_API int snsde_sample_class_backward(const float* grad_nll, const float* grad_xent, const float* grad_logp, const float* logits,
+                                          const int32_t* labels, const float* logw, const float* class_weight, int64_t outer,
+                                          int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t binary,
+                                          float* grad_logits, float* grad_logw, void* hip_stream);
+
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /
  * snsde_backward / snsde_head); SNSDE_ERR_ABI otherwise.  A size of 0 means "this binding does not declare that struct"

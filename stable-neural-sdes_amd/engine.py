@@ -1652,6 +1652,177 @@ class _SampleLoglik(torch.autograd.Function):
         return (gys if ctx.needs_input_grad[0] else None), gt, None, glw, None, None, None, None, None
 
 
+SampleClass = collections.namedtuple('SampleClass', 'nll xent logp probs entropy expected_entropy mutual_information')
+
+
+def _class_args(logits, samples, labels, members, binary, class_weight, log_weight):
+    """(S, M, lead, G, W, N, classes, labels) of a classification over sample paths; the argument errors of `sample_class`.
+    labels come back as int32 (values beyond its range saturate, which keeps them out of range), or None."""
+    S, M, lead, G, W = _score_dims(logits, samples, members)
+    N = M * S
+    if not logits.dtype.is_floating_point:
+        raise ValueError(f'logits must be a floating-point tensor, got {logits.dtype}')
+    if binary and W != 1:
+        raise ValueError(f'binary=True takes one logit per path (a last axis of 1), got a last axis of {W}')
+    classes = 2 if binary else W
+    if labels is not None:
+        if labels.dtype.is_floating_point or labels.dtype.is_complex or labels.dtype == torch.bool:
+            raise ValueError(f'labels must be an integer tensor of class indices (< 0: unlabelled), got {labels.dtype}')
+        if tuple(labels.shape) != lead + (G,):
+            raise ValueError(f'labels has shape {tuple(labels.shape)}, expected {lead + (G,)} (one label per input row)')
+        if labels.dtype != torch.int32:
+            labels = (labels.clamp(-1, 2 ** 31 - 1) if labels.dtype == torch.int64 else labels).to(torch.int32)
+    if class_weight is not None and tuple(class_weight.shape) != (classes,):
+        raise ValueError(f'class_weight has shape {tuple(class_weight.shape)}, expected {(classes,)} (one weight per class)')
+    if log_weight is not None and tuple(log_weight.shape) != lead + (G, N):
+        raise ValueError(f'log_weight has shape {tuple(log_weight.shape)}, expected {lead + (G, N)} (one log importance weight per '
+                         f'input row and pooled path)')
+    return S, M, lead, G, W, N, classes, labels
+
+
+def sample_class(logits, samples, labels=None, members=1, binary=False, class_weight=None, log_weight=None, stats=False):
+    """Classify with the sample paths of a solve: the predictive (Bayesian model average) negative log-likelihood of the labels,
+    and the predictive distribution with its uncertainty split.  logits is (..., B S, C) - one row of class logits per path, path
+    index b S + s - or, with members = M > 1, (..., M, B S, C): the N = M S paths of an input row are pooled, n = m S + s.
+    binary=True: the last axis is 1 and the two class logits of a path are (0, z) (the BCE-with-logits layout).  labels is an
+    integer tensor (..., B) (any integer dtype, converted once), < 0 marks an unlabelled row; None: no row is labelled (pure
+    prediction).  With lp_n = log_softmax(z_n), a_n = lp_n[y], w = class_weight[y] (None: 1):
+        nll[b]      = -w (logsumexp_n(a_n + log_weight[b, n]) - log N)    the loss whose mean trains the model average
+        xent[b]     = -w mean_n a_n                                       the expected cross-entropy (the Jensen bound, >= nll)
+        logp[b, n]  = a_n                                                 (..., B, N)
+        probs[b, c] = mean_n softmax(z_n)[c]                              (..., B, C); binary: (..., B, 1), the class-1 probability
+        entropy     = H[probs]                                            total uncertainty
+        expected_entropy   = mean_n H[softmax(z_n)]                       the aleatoric part
+        mutual_information = max(entropy - expected_entropy, 0)           the epistemic part (BALD)
+    Returns nll, or the named tuple SampleClass(nll, xent, logp, probs, entropy, expected_entropy, mutual_information) with
+    stats=True.  class_weight = (1, pos_weight) with binary=True reproduces BCEWithLogitsLoss(pos_weight) at S = 1.
+    log_weight (..., B, N) is an optional log importance weight, as in `sample_loglik`.
+    Every logsumexp subtracts its maximum; a -Inf logit is a class of probability zero with a zero gradient; an unlabelled row
+    has nll = xent = logp = 0 and an exactly zero gradient while its probs and entropies are computed all the same; a label >= C
+    gives NaN in that row's nll, xent, logp and gradient; a NaN logit poisons its own row only.
+    Differentiable in logits and log_weight through nll, xent and logp.  probs, entropy, expected_entropy and
+    mutual_information are returned detached (no gradient), and class_weight receives none.
+    CUDA float32 inputs with N <= 256: one launch of snsde_sample_class (the slab read once and staged in LDS, deterministic,
+    capturable) - inside an autograd node whose backward is snsde_sample_class_backward when an input requires grad.  Other
+    tensors: `sample_class_tensor_ops`."""
+    binary, stats = bool(binary), bool(stats)
+    S, M, lead, G, W, N, classes, lab = _class_args(logits, samples, labels, members, binary, class_weight, log_weight)
+    floats = tuple(t for t in (class_weight, log_weight) if t is not None)
+    if _score_native(logits, N, *floats) and (lab is None or (lab.is_cuda and lab.device == logits.device)):
+        if (logits.requires_grad or (log_weight is not None and log_weight.requires_grad)) and torch.is_grad_enabled():
+            out = _SampleClass.apply(logits, lab, log_weight, class_weight, S, M, binary)
+        else:
+            out = _sample_class_launch(logits.contiguous(), None if lab is None else lab.contiguous(),
+                                       None if log_weight is None else log_weight.contiguous(),
+                                       None if class_weight is None else class_weight.contiguous(), S, M, binary)
+        if not stats:
+            return out[0]
+        return SampleClass(*out, (out[4] - out[5]).clamp_min(0))
+    return sample_class_tensor_ops(logits, S, lab, M, binary, class_weight, log_weight, stats)
+
+
+def sample_class_tensor_ops(logits, samples, labels=None, members=1, binary=False, class_weight=None, log_weight=None, stats=False):
+    """`sample_class` stated in tensor ops (any device and floating dtype; autograd differentiates it): log_softmax over the
+    classes, logsumexp over the paths, torch.where for unlabelled rows.  What `sample_class` runs off the kernels' domain, and
+    the baseline the kernels are timed against."""
+    binary, stats = bool(binary), bool(stats)
+    S, M, lead, G, W, N, classes, lab = _class_args(logits, samples, labels, members, binary, class_weight, log_weight)
+    x = _pooled(logits, S, M, lead, G, W)                                          # (..., G, N, W)
+    if binary:
+        x = torch.cat([torch.zeros_like(x), x], dim=-1)
+    lp = torch.log_softmax(x, dim=-1)                                              # (..., G, N, classes)
+    zero = lp.new_zeros(())
+    lab = torch.full(lead + (G,), -1, device=lp.device) if lab is None else lab.to(torch.int64)
+    unlabelled, beyond = lab < 0, lab >= classes
+    pick = lab.clamp(0, classes - 1)                                               # (selects; never out of range)
+    a = lp.gather(-1, pick[..., None, None].expand(lead + (G, N, 1))).squeeze(-1)
+    a = torch.where(beyond[..., None], lp.new_full((), float('nan')), a)
+    logp = torch.where(unlabelled[..., None], zero, a)
+    w = 1.0 if class_weight is None else class_weight.detach().to(lp.dtype)[pick]
+    at = logp if log_weight is None else logp + log_weight.to(lp.dtype)
+    nll = torch.where(unlabelled, zero, -w * (torch.logsumexp(at, dim=-1) - math.log(N)))
+    xent = torch.where(unlabelled, zero, -w * logp.mean(dim=-1))
+    if not stats:
+        return nll
+    with torch.no_grad():      # (metrics: no gradient)
+        p = lp.exp()
+        pbar = p.mean(dim=-2)
+        entropy = -torch.special.xlogy(pbar, pbar).sum(dim=-1)
+        expent = -torch.where(p == 0, zero, p * lp).sum(dim=-1).mean(dim=-1)
+        probs = pbar[..., 1:] if binary else pbar
+    return SampleClass(nll, xent, logp, probs, entropy, expent, (entropy - expent).clamp_min(0))
+
+
+def _sample_class_launch(logits, labels, logw, cw, S, M, binary):
+    S_, M_, lead, G, W = _score_dims(logits, S, M)
+    N = M * S
+    new = lambda *shape: torch.empty(lead + shape, device=logits.device, dtype=torch.float32)
+    nll, xent, entropy, expent, logp, probs = new(G), new(G), new(G), new(G), new(G, N), new(G, W)
+    _lib.check(_lib.lib().snsde_sample_class(_ptr(logits), _ptr(labels), _ptr(logw), _ptr(cw), _outer(lead), M, G, S, W, int(binary),
+                                             _ptr(logp), _ptr(nll), _ptr(xent), _ptr(probs), _ptr(entropy), _ptr(expent),
+                                             C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)), 'snsde_sample_class')
+    return nll, xent, logp, probs, entropy, expent
+
+
+def sample_class_backward(grad_nll, grad_xent, grad_logp, logits, samples, labels=None, members=1, binary=False, class_weight=None,
+                          log_weight=None, grad_log_weight=True):
+    """(dL/d logits, dL/d log_weight) of `sample_class` from dL/d nll (..., B), dL/d xent (..., B) and dL/d logp (..., B, N) - each
+    may be None: one launch of snsde_sample_class_backward.  dL/d log_weight is None when grad_log_weight=False.  Contiguous
+    float32 CUDA tensors (labels: a contiguous integer CUDA tensor), shapes as for `sample_class`."""
+    S, M, lead, G, W, N, classes, lab = _class_args(logits, samples, labels, members, bool(binary), class_weight, log_weight)
+    _check_f32('logits', logits)
+    for name, t, shape in (('grad_nll', grad_nll, lead + (G,)), ('grad_xent', grad_xent, lead + (G,)), ('grad_logp', grad_logp, lead + (G, N)),
+                           ('log_weight', log_weight, lead + (G, N)), ('class_weight', class_weight, (classes,))):
+        if t is not None:
+            _check_f32(name, t, shape)
+    if lab is not None and not (lab.is_cuda and lab.is_contiguous()):
+        raise ValueError('labels must be a contiguous integer CUDA tensor')
+    return _sample_class_backward_launch(grad_nll, grad_xent, grad_logp, logits, lab, log_weight, class_weight, S, M, bool(binary),
+                                         grad_log_weight)
+
+
+def _sample_class_backward_launch(grad_nll, grad_xent, grad_logp, logits, labels, logw, cw, S, M, binary, grad_logw):
+    S_, M_, lead, G, W = _score_dims(logits, S, M)
+    gz = torch.empty_like(logits)
+    glw = torch.empty(lead + (G, M * S), device=logits.device, dtype=torch.float32) if grad_logw else None
+    _lib.check(_lib.lib().snsde_sample_class_backward(_ptr(grad_nll), _ptr(grad_xent), _ptr(grad_logp), _ptr(logits), _ptr(labels),
+                                                      _ptr(logw), _ptr(cw), _outer(lead), M, G, S, W, int(binary), _ptr(gz), _ptr(glw),
+                                                      C.c_void_p(torch.cuda.current_stream(logits.device).cuda_stream)),
+               'snsde_sample_class_backward')
+    return gz, glw
+
+
+class _SampleClass(torch.autograd.Function):
+    """sample_class of CUDA float32 tensors of which one requires grad: the forward kernel, and snsde_sample_class_backward as its
+    backward (the row statistics are formed again from the saved logits).  probs, entropy and expent carry no gradient; labels and
+    class_weight receive none."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, logw, cw, S, M, binary):
+        zc = logits.detach().contiguous()
+        lab = None if labels is None else labels.contiguous()
+        lw = None if logw is None else logw.detach().contiguous()
+        cwc = None if cw is None else cw.detach().contiguous()
+        out = _sample_class_launch(zc, lab, lw, cwc, S, M, binary)
+        ctx.S, ctx.M, ctx.binary = S, M, binary
+        ctx.has = (lab is not None, lw is not None, cwc is not None)
+        ctx.save_for_backward(zc, *(t for t in (lab, lw, cwc) if t is not None))
+        ctx.mark_non_differentiable(*out[3:])
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_nll, grad_xent, grad_logp, *unused):
+        saved = list(ctx.saved_tensors)
+        zc = saved.pop(0)
+        lab, lw, cwc = (saved.pop(0) if h else None for h in ctx.has)
+        f = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        gz, glw = _sample_class_backward_launch(f(grad_nll), f(grad_xent), f(grad_logp), zc, lab, lw, cwc, ctx.S, ctx.M, ctx.binary,
+                                                lw is not None and ctx.needs_input_grad[2])
+        return (gz if ctx.needs_input_grad[0] else None), None, glw, None, None, None, None
+
+
 def quantile_positions(q, N):
     """Order-statistic positions of the levels q among N samples, torch.quantile's 'linear' rule: pos = q (N - 1) in float64,
     k = floor(pos), frac = float32(pos - k).  Returns (k, frac) as lists; ValueError for a level outside [0, 1] or no level."""

@@ -127,6 +127,51 @@ def iwae_loss(samples, std=0.1, members=1, norm=False):
     return loss_fn
 
 
+def mc_class_loss(samples, members=1, binary=False, pos_weight=None, class_weight=None, objective='predictive'):
+    """loss_fn(pred, true) for `train_loop` / `GraphedStep` / `evaluate_metrics`: classification with a model solved with
+    options={'samples': S} (engine.sample_class).  pred has one row of logits per path - (B S, C), or (M, B S, C) from an
+    `Ensemble` of `members` = M models, whose paths are pooled; binary=True: one logit per path, (B S,) or (B S, 1) (the
+    `SqueezeEnd` / BCEWithLogitsLoss layout).  true is (B,): integer class indices, or 0 / 1 of any dtype for binary; a label
+    < 0 marks an unlabelled row, which adds 0.  objective='predictive' is the negative log-likelihood of the model average,
+    -log((1 / N) sum_n softmax(z_n)[y]); 'expected' is the mean cross-entropy of the paths (what replicating the labels S times
+    gives: the looser Jensen bound).  class_weight (C,) weighs the rows by the weight of their class; pos_weight (binary only)
+    is class_weight = (1, pos_weight).  The reduction is the mean over the rows of true - BCEWithLogitsLoss's convention, NOT
+    cross_entropy(weight=)'s division by the summed weights."""
+    from . import engine
+    S = engine.check_samples(samples)
+    if objective not in ('predictive', 'expected'):
+        raise ValueError(f"objective must be 'predictive' or 'expected', got {objective!r}")
+    if pos_weight is not None and (not binary or class_weight is not None):
+        raise ValueError('pos_weight belongs to binary=True and replaces class_weight: give one of the two')
+    lead = 1 if members > 1 else 0      # (an Ensemble's leading member axis)
+    weights = {}
+
+    def weight(like):      # (per device and dtype, formed once: nothing is allocated inside a recorded step after the first)
+        key = (like.device, like.dtype)
+        if key not in weights:
+            if pos_weight is not None:
+                w = torch.cat([torch.ones(1), torch.as_tensor(pos_weight, dtype=torch.float32).detach().reshape(1).cpu()])
+            else:
+                w = torch.as_tensor(class_weight, dtype=torch.float32).detach()
+            weights[key] = w.to(device=like.device, dtype=like.dtype)
+        return weights[key]
+
+    def loss_fn(pred_y, true_y):
+        want = ((members,) if lead else ()) + (S * true_y.shape[0],) if true_y.dim() == 1 else None
+        tail = tuple(pred_y.shape[lead + 1:])
+        if want is None or tuple(pred_y.shape[:lead + 1]) != want or (tail not in ((), (1,)) if binary else len(tail) != 1):
+            raise ValueError(f'mc_class_loss(samples={S}, members={members}, binary={bool(binary)}): pred has shape '
+                             f'{tuple(pred_y.shape)} for labels of shape {tuple(true_y.shape)}: expected '
+                             f'{"(members, " if lead else "("}samples x labels{")" if binary else ", classes)"}')
+        pred = pred_y.reshape(want + (1,)) if binary else pred_y
+        labels = true_y if not (true_y.dtype.is_floating_point or true_y.dtype == torch.bool) else true_y.to(torch.int32)
+        w = None if pos_weight is None and class_weight is None else weight(pred)
+        if objective == 'predictive':
+            return engine.sample_class(pred, S, labels, members=members, binary=binary, class_weight=w).mean()
+        return engine.sample_class(pred, S, labels, members=members, binary=binary, class_weight=w, stats=True).xent.mean()
+    return loss_fn
+
+
 class SqueezeEnd(torch.nn.Module):
     def __init__(self, model):
         super().__init__()
@@ -170,13 +215,20 @@ def _world():
     return None
 
 
-def evaluate_metrics(dataloader, model, times, loss_fn, num_classes, device, kwargs):
+def evaluate_metrics(dataloader, model, times, loss_fn, num_classes, device, kwargs, samples=1, members=1):
     """One pass over `dataloader` (batches = (*coeffs, true_y, lengths)): loss, accuracy, confusion matrix and, for two
-    classes, AUROC / average precision.  num_classes=None: regression (loss only).  One host synchronisation."""
+    classes, AUROC / average precision.  num_classes=None: regression (loss only).  One host synchronisation.
+    samples=S, members=M with N = M S > 1: the model returns one row of logits per path ((B S, C), (M, B S, C); two classes:
+    one logit per path); the guess is the argmax of the averaged probabilities (engine.sample_class; two classes: pbar(1) >
+    0.5), the AUROC / AP scores are pbar(1), and the metrics gain `predictive_nll` and `mutual_information` (means over the
+    rows)."""
+    from . import engine
+    pooled = num_classes is not None and engine.check_samples(samples) * members > 1
     dist = _world()
     with torch.no_grad():
         loss_sum = torch.zeros((), device=device, dtype=torch.float64)
         correct = torch.zeros((), device=device, dtype=torch.float64)
+        extra = torch.zeros(2, device=device, dtype=torch.float64)      # (sums of predictive_nll, mutual_information)
         size = 0
         confusion = None if num_classes is None else torch.zeros(num_classes * num_classes, device=device, dtype=torch.int64)
         scores, labels = [], []
@@ -189,8 +241,16 @@ def evaluate_metrics(dataloader, model, times, loss_fn, num_classes, device, kwa
             loss_sum += loss_fn(pred_y, true_y).double() * bs
             if num_classes is None:
                 continue
-            guess = (pred_y > 0).to(torch.int64) if num_classes == 2 else torch.argmax(pred_y, dim=1)
             truth = true_y.to(torch.int64)
+            if pooled:
+                binary = num_classes == 2
+                logits = pred_y.reshape(tuple(pred_y.shape[:2 if members > 1 else 1]) + (1,)) if binary else pred_y
+                st = engine.sample_class(logits, samples, truth, members=members, binary=binary, stats=True)
+                extra += torch.stack([st.nll.sum(), st.mutual_information.sum()]).double()
+                guess = (st.probs[:, 0] > 0.5).to(torch.int64) if binary else torch.argmax(st.probs, dim=1)
+                pred_y = st.probs[:, 0]      # (the score of the ranking metrics)
+            else:
+                guess = (pred_y > 0).to(torch.int64) if num_classes == 2 else torch.argmax(pred_y, dim=1)
             correct += (guess == truth).sum()
             confusion += torch.bincount(truth.reshape(-1) * num_classes + guess.reshape(-1), minlength=num_classes * num_classes)
             if num_classes == 2:
@@ -204,6 +264,10 @@ def evaluate_metrics(dataloader, model, times, loss_fn, num_classes, device, kwa
         metrics = AttrDict(dataset_size=int(sums[2].item()))
         total = max(metrics.dataset_size, 1)
         metrics.loss = float(sums[0]) / total            # assumes 'mean' reduction in the loss function
+        if pooled:
+            if dist is not None:
+                dist.all_reduce(extra)
+            metrics.predictive_nll, metrics.mutual_information = float(extra[0]) / total, float(extra[1]) / total
         if num_classes is not None:
             metrics.accuracy = float(sums[1]) / total
             metrics.confusion = confusion.reshape(num_classes, num_classes).cpu().numpy().astype(np.float64)
@@ -302,10 +366,11 @@ class GraphedStep:
 
 
 def train_loop(train_dataloader, val_dataloader, model, times, optimizer, loss_fn, max_epochs, num_classes, device, kwargs,
-               step_mode, log=None, plateau_terminate=None, graph_steps=False):
+               step_mode, log=None, plateau_terminate=None, graph_steps=False, samples=1, members=1):
     """The reference's epoch loop (common_sde.py:107-216).  Returns the history; `model` ends with the best parameters
     (validation accuracy for classification, validation loss for regression).  graph_steps=True replays the training step
-    from a CUDA/HIP graph (GraphedStep; one process, CUDA, optimizer with capturable=True)."""
+    from a CUDA/HIP graph (GraphedStep; one process, CUDA, optimizer with capturable=True).  samples, members: the sample
+    paths per row and ensemble members behind the model's logits, for `evaluate_metrics`."""
     modes = {'trainloss': 'min', 'valloss': 'min', 'valaccuracy': 'max', 'valauc': 'max', 'none': None}
     if step_mode not in modes:
         raise ValueError(f'step_mode must be one of {sorted(modes)}')
@@ -342,8 +407,8 @@ def train_loop(train_dataloader, val_dataloader, model, times, optimizer, loss_f
                 log('Caught AssertionError: ' + str(exc))
                 optimizer.zero_grad(set_to_none=True)
         model.eval()
-        train_metrics = evaluate_metrics(train_dataloader, model, times, loss_fn, num_classes, device, kwargs)
-        val_metrics = evaluate_metrics(val_dataloader, model, times, loss_fn, num_classes, device, kwargs)
+        train_metrics = evaluate_metrics(train_dataloader, model, times, loss_fn, num_classes, device, kwargs, samples, members)
+        val_metrics = evaluate_metrics(val_dataloader, model, times, loss_fn, num_classes, device, kwargs, samples, members)
         model.train()
         if train_metrics.loss * 1.0001 < best_train_loss:
             best_train_loss, best_train_loss_epoch = train_metrics.loss, epoch
@@ -411,7 +476,7 @@ def make_model(name, input_channels, output_channels, hidden_channels, hidden_hi
 
 def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloader, device, make_model, num_classes,
          max_epochs, lr, kwargs, step_mode, pos_weight=torch.tensor(1), results_dir=None, log=print, regularise='l2',
-         graph_steps=None, shard_invariant=False, loss=None):
+         graph_steps=None, shard_invariant=False, loss=None, samples=1, members=1):
     """common_sde.main (common_sde.py:248-298): build, train, evaluate; `num_classes=None` trains a regression model with
     the mean-squared error (the forecasting benchmark).  Results are written only when `name` and `results_dir` are set.
     graph_steps: replay the training step from a CUDA/HIP graph (GraphedStep) - the step of these models is bound by the host
@@ -420,7 +485,9 @@ def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloa
     shard_invariant (default off): every solve passes options={'global_rows': 'world'} - under a process group the kernels are
     planned for world_size x the local batch, so each rank's rows evolve as they would in the unsharded batch on one device.
     loss: a callable loss(pred, true) that replaces the default base loss (e.g. `crps_loss(S)` for a model solved with
-    options={'samples': S}); the weight regulariser is added to it as to the default."""
+    options={'samples': S}); the weight regulariser is added to it as to the default.
+    samples, members: what `evaluate_metrics` needs to read a classifier's logits when they come one row per sample path
+    (`main(..., loss=mc_class_loss(S), samples=S)` with kwargs options={'samples': S, 'sample_grad': True})."""
     device = torch.device(device)
     if shard_invariant:
         kwargs = dict(kwargs, options=dict(kwargs.get('options') or {}, global_rows='world'))
@@ -452,11 +519,12 @@ def main(name, model_name, times, train_dataloader, val_dataloader, test_dataloa
     optimizer = torch.optim.Adam(net.parameters(), lr=lr, weight_decay=lr * 0.01, fused=True if on_gpu else None,
                                  capturable=graph_steps)
     history = train_loop(train_dataloader, val_dataloader, net, times, optimizer, loss_fn, max_epochs, num_classes, device,
-                         kwargs, step_mode, log=log if (dist is None or dist.get_rank() == 0) else None, graph_steps=graph_steps)
+                         kwargs, step_mode, log=log if (dist is None or dist.get_rank() == 0) else None, graph_steps=graph_steps,
+                         samples=samples, members=members)
     net.eval()
-    train_metrics = evaluate_metrics(train_dataloader, net, times, loss_fn, num_classes, device, kwargs)
-    val_metrics = evaluate_metrics(val_dataloader, net, times, loss_fn, num_classes, device, kwargs)
-    test_metrics = evaluate_metrics(test_dataloader, net, times, loss_fn, num_classes, device, kwargs)
+    train_metrics = evaluate_metrics(train_dataloader, net, times, loss_fn, num_classes, device, kwargs, samples, members)
+    val_metrics = evaluate_metrics(val_dataloader, net, times, loss_fn, num_classes, device, kwargs, samples, members)
+    test_metrics = evaluate_metrics(test_dataloader, net, times, loss_fn, num_classes, device, kwargs, samples, members)
     memory_usage = torch.cuda.max_memory_allocated(device) - baseline_memory if on_gpu else None
     result = AttrDict(name=name, model_name=model_name, times=times, memory_usage=memory_usage,
                       baseline_memory=baseline_memory, num_classes=num_classes, train_dataloader=train_dataloader,
