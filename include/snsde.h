@@ -540,14 +540,19 @@ SNSDE_API int    snsde_coeff_gradients(const snsde_backward* b, float* grad_coef
 /* ---- cubic spline evaluation (A10) -----------------------------------------------------------
  * out[b, c] = a + (b + (0.5*two_c + three_d*frac/3)*frac)*frac   on interval `index`
  * (derivative != 0: b + (two_c + three_d*frac)*frac), operation order as
- * controldiffeq/interpolate.py:270-283 (bit-exact with the CPU reference).                      */
+ * controldiffeq/interpolate.py:270-283 (bit-exact with the CPU reference).  Every element of out
+ * (batch, channels) is written and nothing else; coeffs is only read; no workspace, no alignment
+ * beyond that of a float.                                                                       */
 SNSDE_API int snsde_spline_evaluate(const float* coeffs, int32_t batch, int32_t knots, int32_t channels,
                           int32_t index, float frac, int32_t derivative, float* out, void* hip_stream);
 
 /* ---- spline coefficient construction (A11 / A12; offline preprocessing in the reference) ------------
  * natural: controldiffeq.natural_cubic_spline_coeffs (interpolate.py:161-228) incl. its missing-value handling;
  * hermite: torchcde.hermite_cubic_coefficients_with_backward_differences (datasets/common.py:82-84).
- * times (L) and X (B, L, C) device float32, NaN = missing; coeffs (B, L-1, 4C) = cat[a, b, two_c, three_d] out. */
+ * times (L) and X (B, L, C) device float32, NaN = missing; coeffs (B, L-1, 4C) = cat[a, b, two_c, three_d] out.
+ * Every element of coeffs is written - a series without an observation included - and no byte outside it but the workspace of
+ * the natural construction, which is written before it is read (its contents on entry do not matter).  times and X are only read.
+ * The pointers need the alignment of a float and no more. */
 SNSDE_API size_t snsde_spline_workspace_bytes(int32_t batch, int32_t knots, int32_t channels);
 SNSDE_API int snsde_natural_cubic_coeffs(const float* times, const float* X, int32_t batch, int32_t knots, int32_t channels,
                                float* coeffs, void* workspace, size_t workspace_bytes, void* hip_stream);
@@ -643,7 +648,7 @@ typedef struct snsde_head {
     const float* bn_bias;    /* (hidden) or NULL                                      */
     const float* w2;         /* (out_features, hidden)                                */
     const float* b2;         /* (out_features) or NULL                                */
-    float*       out;        /* (rows, out_features)                                  */
+    float*       out;        /* (rows, out_features): every element is written, nothing else is; no workspace */
 } snsde_head;
 SNSDE_API int snsde_readout_head(const snsde_head* h, void* hip_stream);
 
@@ -658,7 +663,11 @@ SNSDE_API int snsde_readout_head(const snsde_head* h, void* hip_stream);
  * zero_col >= 0 inserts a zero column at that index of W' (the field's [t, y] columns -> the block's [t, 0, y]).
  * dst_w / dst_b: float offsets into `dst` (snsde_param_info); the caller zero-fills what no job writes.
  * The backward reads grad_dst at the same offsets and writes dL/d(each source tensor) at g_* float offsets of `grad_src`
- * (-1: not wanted).  All pointers device, fp32, row-major contiguous; at most SNSDE_MAX_AFFINE_JOBS jobs per call. */
+ * (-1: not wanted).  All pointers device, fp32, row-major contiguous; at most SNSDE_MAX_AFFINE_JOBS jobs per call.
+ * What a call writes: the forward, per job, the R x (Cin + 1 with a zero column, else Cin) floats at dst_w and the R floats at dst_b,
+ * and no other float of dst; the backward, per job and wanted offset, g_w_outer: R K, g_b_outer: R, g_w_inner: K Cin, g_b_inner: K
+ * floats (a copy job: g_w_inner: R Cin, g_b_inner: R) and no other float of grad_src - the caller zero-fills that one too.  No
+ * workspace; the sources and grad_dst are only read. */
 #define SNSDE_MAX_AFFINE_JOBS 12
 typedef struct snsde_affine_job {
     const float* w_outer;    /* (R, K) or NULL                                  */
@@ -677,7 +686,8 @@ SNSDE_API int snsde_affine_compose_backward(const snsde_affine_job* jobs, int32_
 /* ---- statistics over sample paths ------------------------------------------------------------
  * ys viewed as (groups, samples, width) - the T leading planes of a (T, B S, H) result of a solve with `samples` = S fold
  * into groups = T B - reduced over the sample axis: mean (groups, width) and, where var != NULL, the unbiased variance
- * (groups, width; / (S - 1), samples < 2 is then SNSDE_ERR_DIMS).  Enqueue-only, no workspace, capturable.  Deterministic:
+ * (groups, width; / (S - 1), samples < 2 is then SNSDE_ERR_DIMS).  Every element of mean and (where given) var is written and
+ * nothing else; ys is only read.  Enqueue-only, no workspace, capturable.  Deterministic:
  * one lane per output element walks s = 0 .. S-1 in order, twice (the sum, then the squared deviations from the mean).
  * All pointers device, fp32, contiguous. */
 SNSDE_API int snsde_sample_stats(const float* ys, int64_t groups, int32_t samples, int32_t width, float* mean, float* var,
@@ -704,6 +714,7 @@ SNSDE_API int snsde_sample_stats_backward(const float* grad_mean, const float* g
  * within + between is the law-of-total-variance estimate of the predictive variance.  `within` with samples < 2 or `between`
  * with members < 2 is SNSDE_ERR_DIMS.  One lane per output element (four adjacent ones with 16-byte accesses where width % 4
  * == 0 and the pointers are 16-byte aligned); no atomics, no dependence on the grid: the same bits on every launch.
+ * Every element of each output given is written and nothing else; ys is only read.
  * Enqueue-only, no workspace, capturable.  All pointers device, fp32, contiguous. */
 SNSDE_API int snsde_ensemble_stats(const float* ys, int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
                                    float* mean, float* within, float* between, void* hip_stream);
@@ -732,6 +743,8 @@ SNSDE_API int snsde_ensemble_stats_backward(const float* grad_mean, const float*
  * division each and the subtraction.  No atomics, no dependence on the grid: the same bits on every launch.  Enqueue-only, no
  * workspace, capturable.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target or crps NULL.  SNSDE_ERR_DIMS:
  * a non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits.
+ * What the score calls write (snsde_sample_crps, _quantiles, _energy and their adjoints): every element of every output given -
+ * crps, rank, ties; out; energy; grad_ys, grad_target - whatever it held, and no other byte; the inputs are only read.
  * Non-finite values (here and in the statistics and the energy score): the comparisons are IEEE - a NaN sample counts in no
  * c_n, in neither rank nor ties - and NaN and +-Inf flow through the arithmetic of the formulas as written (an infinite
  * |d_n| against an infinite c_n d_n is NaN), in the one output element whose set holds them and in no other. */
@@ -839,7 +852,8 @@ SNSDE_API int snsde_sample_energy_backward(const float* grad_energy, const float
  *   bound: max_n a_n, a_n = logpx_n + logw_n; lane i a chain of expf(a_n - max) over n = i (mod 64) ascending, the lanes by a
  *   butterfly; max + logf(sum) - logf((float)N).
  * No atomics, no workspace, no dependence on the grid, the pointer alignment or `members`: the same bits on every launch, and a
- * pooled call gives the bits of the members = 1 call on the permuted tensor.  Enqueue-only, capturable.  All pointers device,
+ * pooled call gives the bits of the members = 1 call on the permuted tensor.  Every element of logpx, count, bound and sqerr is
+ * written (a fully masked group included) and no other byte; the inputs are only read.  Enqueue-only, capturable.  All pointers device,
  * fp32, contiguous.  SNSDE_ERR_NULL: ys, target, mask, logpx, count, bound or sqerr NULL.  SNSDE_ERR_DIMS: a non-positive
  * extent, N > 256, logvar or inv_var not finite or inv_var <= 0 (a non-finite or non-positive std), an element count beyond 63 bits. */
 SNSDE_API int snsde_sample_loglik(const float* ys, const float* target, const float* mask, const float* logw, int64_t outer,
@@ -853,7 +867,8 @@ SNSDE_API int snsde_sample_loglik(const float* ys, const float* target, const fl
  *     grad_target[v]  = -sum_n grad_ys[n, v], n ascending in the lane that owns the column   (optional, NULL = not wanted)
  *     grad_logw[g, n] = grad_bound[g] p_n                                                    (optional, NULL = not wanted)
  * computed as ((c_n inv_var) m_v) (y_v - x_nv).  Unobserved elements of grad_ys and grad_target are exact +0.  sqerr, mask and
- * the variance carry no gradient.  Elementwise over the slab: a workgroup per (group, 256 adjacent columns).  The same errors
+ * the variance carry no gradient.  Every element of grad_target and grad_logw, where given, is written too, and no other byte.
+ * Elementwise over the slab: a workgroup per (group, 256 adjacent columns).  The same errors
  * and guarantees; SNSDE_ERR_NULL: ys, target, mask, logpx, count or grad_ys NULL. */
 SNSDE_API int snsde_sample_loglik_backward(const float* grad_logpx, const float* grad_bound, const float* ys, const float* target,
                                            const float* mask, const float* logw, const float* logpx, const float* count, int64_t outer,
@@ -896,7 +911,8 @@ SNSDE_API int snsde_sample_loglik_backward(const float* grad_logpx, const float*
  *   and sum += a_n over n = i (mod TN) ascending, the lanes by a butterfly; nll = -w (max + logf(sum) - logf((float)N)), xent =
  *   -w (sum / N).  A NaN a'_n gives NaN, an infinite maximum max - logf(N).
  * No atomics, no workspace, no dependence on the grid, the pointer alignment or `members`: the same bits on every launch, and a
- * pooled call gives the bits of the members = 1 call on the permuted tensor.  Enqueue-only, capturable.  All pointers device,
+ * pooled call gives the bits of the members = 1 call on the permuted tensor.  Every element of the six outputs is written (an
+ * unlabelled group included) and no other byte; the inputs are only read.  Enqueue-only, capturable.  All pointers device,
  * contiguous; fp32 but labels.  SNSDE_ERR_NULL: logits or an output NULL.  SNSDE_ERR_DIMS: a non-positive extent, N > 256,
  * binary with width != 1, an element count beyond 63 bits. */
 SNSDE_API int snsde_sample_class(const float* logits, const int32_t* labels, const float* logw, const float* class_weight,
@@ -909,7 +925,8 @@ SNSDE_API int snsde_sample_class(const float* logits, const int32_t* labels, con
  *     grad_logits[n, c] = k_n (p_nc - [c == y])                  (as logits; every element is written)
  *     grad_logw[g, n]   = -w grad_nll[g] r_n                      (optional, NULL = not wanted)
  * binary: the gradient of z is the class-1 column.  An unlabelled group's slab and grad_logw row are exact +0; a label >= the
- * number of classes gives NaN in that group's rows.  probs, entropy, expent and class_weight carry no gradient.  The same
+ * number of classes gives NaN in that group's rows.  Every element of grad_logw, where given, is written too, and no other byte.
+ * probs, entropy, expent and class_weight carry no gradient.  The same
  * errors and guarantees; SNSDE_ERR_NULL: logits or grad_logits NULL. */
 SNSDE_API int snsde_sample_class_backward(const float* grad_nll, const float* grad_xent, const float* grad_logp, const float* logits,
                                           const int32_t* labels, const float* logw, const float* class_weight, int64_t outer,

@@ -4,7 +4,8 @@ Plain data, importable without a GPU.  The GPU tests (tests/test_gpu_parity.py, 
 parametrise over these tables and assert the kernels on the descriptor they launched (engine.forward_kernel / engine.backward_kernel,
 the names of _lib.FWD_KERNELS / _lib.REV_KERNELS); tests/test_kernel_census_cpu.py rebuilds every case's descriptor on the host,
 asserts that the plan names those kernels, and that the union of the cases covers every kernel and every compiled instantiation of
-the two-tile kernels.  A case whose plan moves to another kernel fails there, without a GPU.
+the two-tile kernels.  A case whose plan moves to another kernel fails there, without a GPU.  STEP_OFFSET_CASES and
+POISONED_TRAINING_CASES (tests/test_gpu_step_offset.py, tests/test_gpu_poisoned_allocations.py) are held to their kernels there too.
 
 `fwd` / `rev`: the kernel names; rev = None for a case that runs no backward.  The case tuples of the tests that existed before this
 module were moved here unchanged."""
@@ -66,6 +67,16 @@ def descriptor(c):
         if c.train:
             s.dU_out = s.stage_save = p
     return s
+
+
+def delta_slots(c):
+    """Delta planes per pass the adjoint of a training Launch leaves (snsde_save_layout, host-only): 0 where the adjoint sums the
+    weight gradients itself or the solve has no MFMA adjoint - no coefficient gradient comes from such a solve's planes."""
+    from stable_neural_sdes_amd import _lib
+    s = descriptor(c)
+    a, p, d = C.c_int32(-1), C.c_int32(-1), C.c_int32(-1)
+    rc = _lib.lib().snsde_save_layout(C.byref(s), C.byref(a), C.byref(p), C.byref(d))
+    return d.value if rc == 0 else 0
 
 
 # The instantiation lists of the two-tile kernels, written out once.  (NHID, KUXT, SAVE): hidden layers between the first layer and
@@ -297,6 +308,56 @@ EDGE_LAUNCHES = [
     launch('generic backward euler', 4, 17, 2, 11, 24, 5, 9, [0, 3, 8], 1.0, kernel='generic', train=True, fwd='generic', rev='generic'),
     launch('generic backward srk', 4, 17, 2, 11, 24, 5, 9, [0, 3.5, 8], 1.0, 'srk', kernel='generic', train=True, fwd='generic_srk', rev='generic'),
 ]
+
+# ---- resumable solves (tests/test_gpu_step_offset.py), moved here unchanged: every forward kernel once, Philox-driven, inference ----
+# 37 steps of dt = 0.25 over knots 0 .. 10; outputs 1 and 2 are interpolated inside steps 10 and 24
+STEP_OFFSET_TS, STEP_OFFSET_DT, STEP_OFFSET_L = [0.0, 2.6, 6.1, 9.25], 0.25, 11
+# One Philox-driven inference launch per forward kernel at its smallest shapes: test, io, no, NL, B, H, C, L, ts, dt, method, kernel
+STEP_OFFSET_CASES = [
+    launch('lean specialised', 4, 17, 2, 8, 128, 21, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, supplied=False, fwd='lean'),
+    launch('lean general', 4, 17, 2, 8, 32, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma4', supplied=False, fwd='lean'),
+    launch('lean general milstein', 6, 16, 2, 8, 32, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'milstein', 'mfma4', supplied=False, fwd='lean'),
+    launch('lean bf16', 4, 17, 2, 8, 64, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, supplied=False, bf16=True, fwd='lean_bf16'),
+    launch('two tiles h128', 4, 17, 2, 8, 128, 21, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma4', two_tile=True, supplied=False, fwd='lean_two_tile_h128'),
+    launch('two tiles h256', 4, 17, 2, 8, 256, 14, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma4', supplied=False, fwd='lean_two_tile_h256'),
+    launch('streamed h256', 4, 17, 2, 8, 256, 14, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma4', stream_all=True, supplied=False, fwd='lean_streamed_h256'),
+    launch('general m4 euler', 4, 17, 2, 8, 32, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma4', exact=True, supplied=False, fwd='general_m4'),
+    launch('general m4 srk', 6, 17, 2, 8, 32, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'srk', 'mfma4', supplied=False, fwd='general_m4'),
+    launch('general m16 euler', 4, 17, 2, 32, 32, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='mfma16', supplied=False, fwd='general_m16'),
+    launch('m4n srk', 1, 18, 2, 8, 16, 3, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'srk', 'mfma4', supplied=False, fwd='m4n'),
+    launch('m4n milstein', 1, 18, 2, 8, 32, 3, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'milstein', supplied=False, fwd='m4n'),
+    launch('m4n euler', 4, 18, 2, 8, 32, 40, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, supplied=False, fwd='m4n'),
+    launch('w4 euler', 3, 18, 2, 8, 64, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='w4', supplied=False, fwd='w4'),
+    launch('w4 srk', 3, 18, 2, 8, 64, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'srk', 'w4', supplied=False, fwd='w4'),
+    launch('generic euler', 4, 17, 2, 8, 24, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, kernel='generic', supplied=False, fwd='generic'),
+    launch('generic milstein net', 3, 18, 2, 8, 24, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'milstein', 'generic', supplied=False, fwd='generic'),
+    launch('generic srk', 4, 17, 2, 8, 24, 5, STEP_OFFSET_L, STEP_OFFSET_TS, STEP_OFFSET_DT, 'srk', 'generic', supplied=False, fwd='generic_srk'),
+]
+
+# ---- the solve chain under poisoned allocations (tests/test_gpu_poisoned_allocations.py) ---------------------------------------------
+# Forward, inference: STEP_OFFSET_CASES above (every forward kernel once).  Training: one Philox-driven case per adjoint kernel - of
+# each family above the row with the fewest B x H among those with an explicit output grid, every M4S2_REV_MODELS entry at B = 3, the
+# generic rows of EDGE_LAUNCHES and one lean / general row (the long-solve model of LONG_CASES at H = 32 on the small grid).
+# tests/test_kernel_census_cpu.py holds every row to the kernels it names and the table to every adjoint kernel.
+def _poisoned_training():
+    out = []
+
+    def add(test, *a, **k):
+        out.append(launch(test, *a, train=True, supplied=False, **k))
+
+    io, no, NL, B, C_, L, ts, dt = W4_BWD[1]
+    add('w4 fused', io, no, NL, B, 64, C_, L, ts, dt, 'euler', 'w4', fwd='w4', rev='w4_fused')
+    add('general srk', *SRK_BWD_CASES[9], 'srk', 'mfma4', fwd='general_m4', rev='general_srk')
+    add('m4n srk', *SRK_BWD_CASES[SRK_BWD_FIRST_NET], 'srk', 'mfma4', fwd='m4n', rev='m4n_srk')
+    add('m4n milstein', *MIL_NET_BWD_CASES[0], 'milstein', 'auto', fwd=MIL_NET_KERNELS[0], rev=MIL_NET_KERNELS[1])
+    for (nhid, geo), (io, no, NL, C_, method, fwd) in M4S2_REV_MODELS.items():
+        add(f'two tile h256 {(nhid, geo)}', io, no, NL, CENSUS_B[0], 256, C_, 9, TS8, DT8, method, 'mfma4', fwd=fwd, rev='two_tile_h256')
+    out.extend(c._replace(supplied=False) for c in EDGE_LAUNCHES if c.rev == 'generic')
+    add('lean / general', 4, 17, 2, 9, 32, 5, 9, TS8, DT8, 'euler', 'mfma4', fwd='lean', rev='general')
+    return out
+
+
+POISONED_TRAINING_CASES = _poisoned_training()
 
 
 def census():

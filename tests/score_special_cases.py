@@ -31,6 +31,13 @@ SHAPES = [(1, 2, 3), (2, 5, 70), (2, 17, 5), (1, 256, 4), (8200, 3, 2)]      # (
 ENERGY_SHAPES = SHAPES + [(2, 5, 17)]                                         # one column past a chunk of 16
 ENSEMBLE = (2, 3, 2, 4, 6)                                                    # (outer, M, G, S, W)
 BIG_GROUPS = (5, 6)                                                           # the slots of a shape with more than 8 groups
+# The shape tables of the float64 GPU tests of the same kernels, moved here unchanged so that other tests can share them; each test
+# module says why its shapes are there.
+SCORE_SHAPES = [(1, 2, 1), (3, 5, 33), (2, 64, 130), (1, 256, 4), (9000, 3, 2)]      # tests/test_gpu_sample_scores.py: (G, N, W)
+ENSEMBLE_STATS_SHAPES = [(2, 3, 5, 4, 64), (1, 2, 3, 2, 7), (1, 4, 1, 3, 1)]         # tests/test_gpu_ensemble_stats.py: (outer, M, G, S, W)
+LOGLIK_SHAPES = [(1, 1, 1, 1), (3, 5, 2, 3), (2, 8, 1, 64), (2, 8, 1, 65), (2, 7, 3, 130), (1, 256, 1, 4), (9000, 2, 1, 2),
+                 (2, 8, 1, 2048), (1, 2, 1, 2049), (1, 9, 1, 1025), (2, 16, 2, 40), (2, 17, 1, 70), (2, 32, 1, 513), (2, 33, 1, 257),
+                 (2, 64, 1, 256), (2, 65, 1, 129), (1, 128, 1, 128), (1, 129, 1, 65)]  # tests/test_gpu_sample_loglik.py: (G, N, outer, W)
 FINITE, POS_INF, NEG_INF, NAN = 0, 1, 2, 3
 
 

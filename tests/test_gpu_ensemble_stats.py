@@ -9,11 +9,12 @@ import torch
 
 import stable_neural_sdes_amd as S
 from stable_neural_sdes_amd import engine
+from tests.score_special_cases import ENSEMBLE_STATS_SHAPES
 
 DEV = 'cuda:0'
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(2, 3, 5, 4, 64), (1, 2, 3, 2, 7), (1, 4, 1, 3, 1)]
+SHAPES = ENSEMBLE_STATS_SHAPES
 U = 2.0 ** -24
 
 

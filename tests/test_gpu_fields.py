@@ -10,7 +10,7 @@ from stable_neural_sdes_amd import fields
 from tests.helpers import grad_close, make_problem
 
 GRAD_TOL = 1e-4      # measured <= 2.3e-5 over 887 tensors (profiles/r05_grad_margins_small.txt); it was 2e-3
-from tests.tutorial_fields import TutorialField
+from tests.tutorial_fields import COMPOSITION_CASES, TutorialField
 
 pytestmark = pytest.mark.gpu
 
@@ -415,7 +415,7 @@ def test_field_training_step_at_the_timed_size_vs_fp64_autograd(kind, method):
         close(p.grad, gr, name)
 
 
-@pytest.mark.parametrize('kind,H,layers', [('lnsde', 64, 2), ('gsde', 128, 1), ('nsde', 32, 1), ('lnsde_additive', 32, 3), ('lsde', 32, 1), ('lsde', 64, 2)])
+@pytest.mark.parametrize('kind,H,layers', COMPOSITION_CASES)
 def test_native_block_composition_matches_the_torch_composition(kind, H, layers):
     """snsde_affine_compose / _backward (one launch each; round 6) against the torch formulation of ComposedField._flat they replace in
     training: the same parameter block to float32 round-off, and the same gradients for a random cotangent of the block."""

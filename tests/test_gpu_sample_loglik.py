@@ -45,13 +45,12 @@ import torch
 import stable_neural_sdes_amd as S
 from stable_neural_sdes_amd import engine, train
 from tests.helpers import make_problem
+from tests.score_special_cases import LOGLIK_SHAPES
 
 DEV = 'cuda:0'
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 1, 1, 1), (3, 5, 2, 3), (2, 8, 1, 64), (2, 8, 1, 65), (2, 7, 3, 130), (1, 256, 1, 4), (9000, 2, 1, 2),
-          (2, 8, 1, 2048), (1, 2, 1, 2049), (1, 9, 1, 1025), (2, 16, 2, 40), (2, 17, 1, 70), (2, 32, 1, 513), (2, 33, 1, 257),
-          (2, 64, 1, 256), (2, 65, 1, 129), (1, 128, 1, 128), (1, 129, 1, 65)]
+SHAPES = LOGLIK_SHAPES
 U = 2.0 ** -24
 TINY = 2.0 ** -126      # the smallest normal float32
 STD = 0.3

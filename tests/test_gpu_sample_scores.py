@@ -14,11 +14,12 @@ import torch
 import stable_neural_sdes_amd as S
 from stable_neural_sdes_amd import engine, train
 from tests.helpers import make_problem
+from tests.score_special_cases import SCORE_SHAPES
 
 DEV = 'cuda:0'
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(1, 2, 1), (3, 5, 33), (2, 64, 130), (1, 256, 4), (9000, 3, 2)]
+SHAPES = SCORE_SHAPES
 U = 2.0 ** -24
 QS = (0.0, 0.1, 0.5, 0.9, 1.0)
 

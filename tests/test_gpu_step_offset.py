@@ -11,38 +11,16 @@ import stable_neural_sdes_amd as S
 from oracle import sde_oracle as O
 from stable_neural_sdes_amd import _lib, engine
 from tests.helpers import assert_kernels, launched_kernels, make_problem, param_spec
-from tests.kernel_cases import launch
+from tests.kernel_cases import STEP_OFFSET_CASES, STEP_OFFSET_DT, STEP_OFFSET_L, STEP_OFFSET_TS
 
 DEV = 'cuda:0'
 pytestmark = pytest.mark.gpu
 
-# 37 steps of dt = 0.25 over knots 0 .. 10; outputs 1 and 2 are interpolated inside steps 10 and 24
-TS, DT, L = [0.0, 2.6, 6.1, 9.25], 0.25, 11
+TS, DT, L, CASES = STEP_OFFSET_TS, STEP_OFFSET_DT, STEP_OFFSET_L, STEP_OFFSET_CASES      # (tests/kernel_cases.py)
 CUTS = (0, 3, 9, 16, 22, 37)      # offsets of phase 3, 1, 0, 2 modulo 4; a first piece shorter than a Philox block; cuts inside, on and
                                   # beyond the lean kernel's first 16-step batch
 SEED = 0x0123_4567_89AB_CDEF
 
-# One Philox-driven inference launch per forward kernel at its smallest shapes: test, io, no, NL, B, H, C, L, ts, dt, method, kernel
-CASES = [
-    launch('lean specialised', 4, 17, 2, 8, 128, 21, L, TS, DT, supplied=False, fwd='lean'),
-    launch('lean general', 4, 17, 2, 8, 32, 5, L, TS, DT, kernel='mfma4', supplied=False, fwd='lean'),
-    launch('lean general milstein', 6, 16, 2, 8, 32, 5, L, TS, DT, 'milstein', 'mfma4', supplied=False, fwd='lean'),
-    launch('lean bf16', 4, 17, 2, 8, 64, 5, L, TS, DT, supplied=False, bf16=True, fwd='lean_bf16'),
-    launch('two tiles h128', 4, 17, 2, 8, 128, 21, L, TS, DT, kernel='mfma4', two_tile=True, supplied=False, fwd='lean_two_tile_h128'),
-    launch('two tiles h256', 4, 17, 2, 8, 256, 14, L, TS, DT, kernel='mfma4', supplied=False, fwd='lean_two_tile_h256'),
-    launch('streamed h256', 4, 17, 2, 8, 256, 14, L, TS, DT, kernel='mfma4', stream_all=True, supplied=False, fwd='lean_streamed_h256'),
-    launch('general m4 euler', 4, 17, 2, 8, 32, 5, L, TS, DT, kernel='mfma4', exact=True, supplied=False, fwd='general_m4'),
-    launch('general m4 srk', 6, 17, 2, 8, 32, 5, L, TS, DT, 'srk', 'mfma4', supplied=False, fwd='general_m4'),
-    launch('general m16 euler', 4, 17, 2, 32, 32, 5, L, TS, DT, kernel='mfma16', supplied=False, fwd='general_m16'),
-    launch('m4n srk', 1, 18, 2, 8, 16, 3, L, TS, DT, 'srk', 'mfma4', supplied=False, fwd='m4n'),
-    launch('m4n milstein', 1, 18, 2, 8, 32, 3, L, TS, DT, 'milstein', supplied=False, fwd='m4n'),
-    launch('m4n euler', 4, 18, 2, 8, 32, 40, L, TS, DT, supplied=False, fwd='m4n'),
-    launch('w4 euler', 3, 18, 2, 8, 64, 5, L, TS, DT, kernel='w4', supplied=False, fwd='w4'),
-    launch('w4 srk', 3, 18, 2, 8, 64, 5, L, TS, DT, 'srk', 'w4', supplied=False, fwd='w4'),
-    launch('generic euler', 4, 17, 2, 8, 24, 5, L, TS, DT, kernel='generic', supplied=False, fwd='generic'),
-    launch('generic milstein net', 3, 18, 2, 8, 24, 5, L, TS, DT, 'milstein', 'generic', supplied=False, fwd='generic'),
-    launch('generic srk', 4, 17, 2, 8, 24, 5, L, TS, DT, 'srk', 'generic', supplied=False, fwd='generic_srk'),
-]
 LEAN_VARIANT = {'lean specialised': 'specialised', 'lean general': 'general', 'lean general milstein': 'general'}
 
 

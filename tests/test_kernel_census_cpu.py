@@ -177,3 +177,19 @@ def test_helpers_take_a_call_or_a_descriptor():
     lib = _lib.lib()
     assert lib.snsde_forward_kernel(C.byref(s), None, None) == _lib.FWD_KERNELS.index('lean_two_tile_h256')      # (NULL out-pointers)
     assert lib.snsde_forward_kernel(None, None, None) == 0 and lib.snsde_backward_kernel(None) == 0
+
+
+def test_the_poisoned_allocation_tables_name_every_forward_and_every_adjoint_kernel():
+    """tests/test_gpu_poisoned_allocations.py runs STEP_OFFSET_CASES (inference) and POISONED_TRAINING_CASES (training): every row
+    plans the kernels it names, the first table covers every forward kernel, the second every adjoint kernel, and only the
+    wave-pair adjoint - which sums the weight gradients itself - leaves no delta planes for a coefficient gradient."""
+    for c in K.STEP_OFFSET_CASES + K.POISONED_TRAINING_CASES:
+        s = K.descriptor(c)
+        assert engine.forward_kernel(s) == c.fwd, (c.test, engine.forward_kernel(s, keys=True))
+        if c.train:
+            assert engine.backward_kernel(s) == c.rev, (c.test, engine.backward_kernel(s))
+            assert (K.delta_slots(c) == 0) == (c.rev == 'w4_fused'), (c.test, K.delta_slots(c))      # (w4_fused: no planes, no dL/d coeffs)
+    assert not any(c.train or c.supplied for c in K.STEP_OFFSET_CASES) and all(c.train and not c.supplied for c in K.POISONED_TRAINING_CASES)
+    assert {c.fwd for c in K.STEP_OFFSET_CASES} == set(_lib.FWD_KERNELS) - {'none'}
+    assert {c.rev for c in K.POISONED_TRAINING_CASES} == set(_lib.REV_KERNELS) - {'none'}
+    assert len({c.test for c in K.POISONED_TRAINING_CASES}) == len(K.POISONED_TRAINING_CASES)

@@ -13,6 +13,9 @@ class LipSwish(nn.Module):
 
 
 ACTS = {'lipswish': LipSwish, 'relu': nn.ReLU, 'silu': nn.SiLU}
+# (kind, hidden size, layers): the six fields whose composed parameter block tests/test_gpu_fields.py builds natively
+# (snsde_affine_compose) and compares with the torch composition
+COMPOSITION_CASES = [('lnsde', 64, 2), ('gsde', 128, 1), ('nsde', 32, 1), ('lnsde_additive', 32, 3), ('lsde', 32, 1), ('lsde', 64, 2)]
 
 
 class MLP(nn.Module):
