@@ -933,6 +933,50 @@ SNSDE_API int snsde_sample_class_backward(const float* grad_nll, const float* gr
                                           int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t binary,
                                           float* grad_logits, float* grad_logw, void* hip_stream);
 
+/* ---- particle filtering on sample paths -------------------------------------------------------
+ * One step of the bootstrap particle filter: weigh the S paths of every group by the newest observation and resample them.
+ * state viewed as (groups, samples, width) = (G, S, W): the (B S, H) last state of a sampled solve, path b S + s; an ensemble
+ * result folds its members into the groups (members are never pooled: a particle does not change model).  logw (G, S) is the
+ * carried log-weight, loginc (G, S) the optional log-likelihood increment (NULL = 0), u the uniforms in [0, 1) the caller drew:
+ * (G) for systematic resampling, (G, S) where stratified != 0.  Per group, n and j in 0 .. S-1:
+ *     a_n  = logw_n + loginc_n                  mx = max_n a_n                  e_n = expf(a_n - mx)
+ *     P_n  = e_0 + .. + e_n
+ *     logz = mx + logf(P_{S-1}) - logf((float)S)                                 logsumexp(a) - log S            (G)
+ *     ess  = P_{S-1}^2 / sum_n e_n^2                                             the effective sample size      (G)
+ * The group is resampled where threshold >= 1, or where ess < threshold S; threshold <= 0 never resamples.  Where resampled:
+ *     t_j = ((j + u_j) / S) P_{S-1},  u_j = u[g] (stratified: u[g, j])
+ *     ancestor[j]     = #{n < S-1 : P_n <= t_j}                                                                  (G, S) int32
+ *     state_out[j, :] = state[ancestor[j], :]                                                                    (G, S, W)
+ *     logw_out[j]     = logz                                                                                     (G, S)
+ * and where not: ancestor[j] = j, state_out a copy of state, logw_out = a.  resampled[g] is 1 or 0 (int32).  Either way
+ * logsumexp(logw_out) - log S = logz: the evidence is carried in the weights, and logw_out handed to snsde_sample_loglik as
+ * logw makes its bound the running log marginal likelihood.
+ * Special values.  A particle with e_n == 0 (a -Inf weight, or one so far below the maximum that expf gives 0) is never an
+ * ancestor: P_n == P_{n-1} exactly, so nothing counts into it, and a t_j that rounds up to P_{S-1} behind dead trailing
+ * particles (u the largest float below 1) is clamped to the last particle with e_n > 0 instead of S - 1.  (A u outside [0, 1)
+ * or NaN is clamped into the first .. last such particle likewise.)  A group whose a are all -Inf is not resampled: ancestor
+ * is the identity, state_out a copy, logw_out = a, ess = 0, logz = -Inf, resampled = 0.  A group that holds a NaN or a +Inf
+ * in a is not resampled either: identity, copies, logw_out = a, ess = logz = NaN, resampled = 0; no other group is touched.
+ * state is only moved, in 32-bit or 128-bit words: NaN, Inf and every other bit pattern arrive bit for bit.  S = 1 is legal:
+ * the identity, ess = 1.
+ * A workgroup of 256 threads per pack of GP adjacent groups (grid stride beyond 2048 packs), GP the largest power of two
+ * <= max(1, min(256 / S, 4096 / (S W))); thread gp S + n is particle n of the pack's group gp.  Rows are gathered with 16-byte
+ * accesses where W % 4 == 0 and state and state_out are 16-byte aligned, one float at a time otherwise: the same bits.
+ * Summation order, a function of S only:
+ *   a_n one rounded addition; mx by fmaxf over n ascending; e_n = expf(a_n - mx), the difference rounded once;
+ *   P_n = P_{n-1} + e_n and q = fmaf(e_n, e_n, q): two sequential chains over n ascending in one thread (so P is non-decreasing
+ *   whatever the rounding); ess = (P_{S-1} P_{S-1}) / q; logz = (mx + logf(P_{S-1})) - logf((float)S);
+ *   t_j = (((float)j + u_j) / (float)S) P_{S-1}, every operation rounded once; the count by a binary search over P_0 .. P_{S-2}.
+ * No atomics, no workspace, no dependence on the grid or the pointer alignment: the same bits on every launch.  Every element
+ * of the six outputs is written and no other byte; the inputs are only read.  Enqueue-only, capturable.  All pointers device,
+ * contiguous; fp32 but ancestor and resampled (int32).  Errors are returned before any launch.  SNSDE_ERR_NULL: state, logw,
+ * u or an output NULL.  SNSDE_ERR_DIMS: a non-positive extent, S > 256, a NaN threshold, an element count beyond 63 bits,
+ * state_out overlapping state. */
+SNSDE_API int snsde_sample_resample(const float* state, const float* logw, const float* loginc, const float* u,
+                                    int64_t groups, int32_t samples, int32_t width, int32_t stratified, float threshold,
+                                    float* state_out, float* logw_out, int32_t* ancestor, float* ess, float* logz,
+                                    int32_t* resampled, void* hip_stream);
+
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /
  * snsde_backward / snsde_head); SNSDE_ERR_ABI otherwise.  A size of 0 means "this binding does not declare that struct"

@@ -1823,6 +1823,136 @@ class _SampleClass(torch.autograd.Function):
         return (gz if ctx.needs_input_grad[0] else None), None, glw, None, None, None, None
 
 
+SampleResample = collections.namedtuple('SampleResample', 'state log_weight ancestor ess logz resampled')
+
+
+def _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified):
+    """(S, lead, B, W, threshold) of a resampling step; the argument errors of `sample_resample`.  u=None is not checked."""
+    S = check_samples(samples)
+    if state.dim() < 2 or state.shape[-2] % S:
+        raise ValueError(f'state has shape {tuple(state.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
+    lead, B, W = tuple(state.shape[:-2]), state.shape[-2] // S, state.shape[-1]
+    if not state.dtype.is_floating_point or not log_weight.dtype.is_floating_point:
+        raise ValueError(f'state and log_weight must be floating-point tensors, got {state.dtype} and {log_weight.dtype}')
+    if tuple(log_weight.shape) != lead + (B, S):
+        raise ValueError(f'log_weight has shape {tuple(log_weight.shape)}, expected {lead + (B, S)} (one carried log-weight per path)')
+    if log_increment is not None and tuple(log_increment.shape) != lead + (B, S):
+        raise ValueError(f'log_increment has shape {tuple(log_increment.shape)}, expected {lead + (B, S)} (the shape of log_weight)')
+    want = lead + ((B, S) if stratified else (B,))
+    if u is not None and tuple(u.shape) != want:
+        raise ValueError(f'u has shape {tuple(u.shape)}, expected {want} (one uniform per ' + ('path' if stratified else 'group') +
+                         f' with stratified={stratified})')
+    if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or math.isnan(threshold):
+        raise ValueError(f'threshold must be a number (resample where ess < threshold * samples; <= 0 never, >= 1 always), got {threshold!r}')
+    tensors = [t for t in (state, log_weight, log_increment) if t is not None]
+    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+        raise ValueError('sample_resample is inference only: state, log_weight or log_increment requires grad (use torch.no_grad() or '
+                         'detach()); resampling has no backward')
+    return S, lead, B, W, float(threshold)
+
+
+def sample_resample(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None):
+    """One step of the bootstrap particle filter on the sample paths of a solve: weigh the S paths of every input row by the
+    newest observation and resample them.  state is (..., B S, W) - the last state of a solve with options={'samples': S}, path
+    b S + s; the leading axes (the members of an ensemble) fold into the groups, members are never pooled - log_weight (..., B, S)
+    the carried log-weight and log_increment (..., B, S) the log-likelihood of the newest observation per path (None: 0; for
+    example `sample_loglik(..., stats=True)`'s logpx of a readout).  With a = log_weight + log_increment, e_n = exp(a_n - max a)
+    and P_n = e_0 + .. + e_n:
+        logz[b] = logsumexp_n a_n - log S                                 ess[b] = P_{S-1}^2 / sum_n e_n^2
+    A row is resampled where threshold >= 1, or where ess < threshold S (threshold <= 0: never):
+        ancestor[b, j] = #{n < S-1 : P_n <= ((j + u_j) / S) P_{S-1}}      systematic: u_j = u[b]; stratified=True: u[b, j]
+        state[b S + j] = state[b S + ancestor[b, j]]                       log_weight[b, j] = logz[b]
+    and elsewhere ancestor is the identity, state a copy and log_weight = a.  Either way logsumexp(log_weight) - log S = logz: the
+    returned weights carry the evidence, and handed to `sample_loglik` as log_weight they make its bound the running log marginal
+    likelihood log p(y_1..k).  u (..., B) - stratified: (..., B, S) - holds uniforms in [0, 1); None draws torch.rand on the
+    state's device with `generator`.  Returns SampleResample(state, log_weight, ancestor (int32), ess, logz, resampled (int32)).
+    A path with e_n == 0 (a -Inf weight) is never an ancestor; a row whose a are all -Inf is left as it is with ess = 0 and
+    logz = -Inf; a row with a NaN or +Inf in a is left as it is with ess = logz = NaN and touches no other row; state is only
+    moved, NaN and Inf included.  Inference only: an input that requires grad under enabled autograd is a ValueError.
+    CUDA float32 inputs with S <= 256: one launch of snsde_sample_resample (deterministic for a given u, capturable with u a
+    device tensor).  Other tensors: `sample_resample_tensor_ops`."""
+    stratified = bool(stratified)
+    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified)
+    if u is None:
+        u = torch.rand(lead + ((B, S) if stratified else (B,)), device=state.device, dtype=log_weight.dtype, generator=generator)
+    others = tuple(t for t in (log_weight, log_increment, u) if t is not None)
+    if _score_native(state, S, *others):
+        return _sample_resample_launch(state.contiguous(), log_weight.contiguous(), None if log_increment is None else log_increment.contiguous(),
+                                       u.contiguous(), S, threshold, stratified)
+    return sample_resample_tensor_ops(state, S, log_weight, log_increment, u, threshold, stratified)
+
+
+def sample_resample_tensor_ops(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None):
+    """`sample_resample` stated in tensor ops (any device and floating dtype): logsumexp, cumsum, searchsorted, gather and where.
+    What `sample_resample` runs off the kernel's domain, and the baseline the kernel is timed against."""
+    stratified = bool(stratified)
+    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified)
+    if u is None:
+        u = torch.rand(lead + ((B, S) if stratified else (B,)), device=state.device, dtype=log_weight.dtype, generator=generator)
+    G = _outer(lead) * B
+    a = log_weight if log_increment is None else log_weight + log_increment.to(log_weight.dtype)
+    a = a.detach().reshape(G, S)
+    x = state.detach().reshape(G, S, W)
+    uu = u.detach().to(a.dtype).reshape(G, S if stratified else 1)
+    nan, inf = a.new_full((), float('nan')), float('inf')
+    mx = a.max(dim=-1, keepdim=True).values
+    bad = (torch.isnan(a) | (a == inf)).any(dim=-1)                   # a NaN or +Inf: the row is left as it is
+    dead = ~bad & (mx[:, 0] == -inf)                                  # all -Inf
+    kept = bad | dead
+    e = torch.exp(a - torch.where(kept[:, None], torch.zeros_like(mx), mx))
+    e = torch.where(kept[:, None], torch.ones_like(e), e)             # (a stand-in that keeps the arithmetic below finite)
+    P = torch.cumsum(e, dim=-1)
+    total = P[:, -1:]
+    logz = torch.where(bad, nan, torch.logsumexp(torch.where(bad[:, None], torch.zeros_like(a), a), dim=-1) - math.log(S))
+    ess = torch.where(bad, nan, torch.where(dead, torch.zeros_like(logz), total[:, 0] ** 2 / (e * e).sum(dim=-1)))
+    res = ~kept & (ess < threshold * S if 0 < threshold < 1 else torch.full_like(kept, threshold >= 1))
+    j = torch.arange(S, device=a.device)
+    t = ((j.to(a.dtype) + uu) / S) * total                            # (G, S)
+    count = torch.searchsorted(P[:, :S - 1].contiguous(), t.contiguous(), right=True) if S > 1 else torch.zeros_like(t, dtype=torch.int64)
+    alive = e > 0                                                     # a path with e_n == 0 is never an ancestor
+    first = alive.to(torch.int8).argmax(dim=-1, keepdim=True)
+    last = S - 1 - alive.flip(-1).to(torch.int8).argmax(dim=-1, keepdim=True)
+    anc = torch.where(res[:, None], torch.minimum(torch.maximum(count, first), last), j.expand(G, S))
+    out = x.gather(1, anc[:, :, None].expand(G, S, W))
+    logw = torch.where(res[:, None], logz[:, None], a)
+    return SampleResample(out.reshape(state.shape), logw.reshape(lead + (B, S)), anc.to(torch.int32).reshape(lead + (B, S)),
+                          ess.reshape(lead + (B,)), logz.reshape(lead + (B,)), res.to(torch.int32).reshape(lead + (B,)))
+
+
+def _sample_resample_launch(state, logw, loginc, u, S, threshold, stratified):
+    lead, B, W = tuple(state.shape[:-2]), state.shape[-2] // S, state.shape[-1]
+    G = _outer(lead) * B
+    new = lambda shape, dtype: torch.empty(lead + shape, device=state.device, dtype=dtype)
+    out, logw_out, anc = torch.empty_like(state), new((B, S), torch.float32), new((B, S), torch.int32)
+    ess, logz, res = new((B,), torch.float32), new((B,), torch.float32), new((B,), torch.int32)
+    _lib.check(_lib.lib().snsde_sample_resample(_ptr(state), _ptr(logw), _ptr(loginc), _ptr(u), G, S, W, int(stratified), threshold,
+                                                _ptr(out), _ptr(logw_out), _ptr(anc), _ptr(ess), _ptr(logz), _ptr(res),
+                                                C.c_void_p(torch.cuda.current_stream(state.device).cuda_stream)), 'snsde_sample_resample')
+    return SampleResample(out, logw_out, anc, ess, logz, res)
+
+
+def filter_paths(ys, ancestors, samples):
+    """The surviving trajectories of a particle filter.  ys (T, B S, H) holds the states BEFORE each resampling and ancestors
+    (T, B, S) the resampling of each step (`sdeint_filter`'s ys and ancestor): slot p of ys[k + 1] continues slot
+    ancestors[k][p] of ys[k].  Traced back from the last step - i_{T-1}[p] = p, i_k = ancestors[k][i_{k+1}] - the result
+    (T, B S, H) holds ys[k][i_k[p]] in slot p: its last entry is ys[-1], and ancestors[-1] (the resampling after the last state)
+    is not used.  Tensor ops: the index composition is T B S ints."""
+    S = check_samples(samples)
+    if ys.dim() != 3 or ys.shape[1] % S:
+        raise ValueError(f'ys has shape {tuple(ys.shape)}, expected (T, B S, H) with a whole number of groups of {S} paths')
+    T, B, H = ys.shape[0], ys.shape[1] // S, ys.shape[2]
+    if tuple(ancestors.shape) != (T, B, S) or ancestors.dtype.is_floating_point or ancestors.dtype == torch.bool:
+        raise ValueError(f'ancestors must be an integer tensor of shape {(T, B, S)}, got {ancestors.dtype} {tuple(ancestors.shape)}')
+    anc = ancestors.to(device=ys.device, dtype=torch.int64)
+    idx = torch.arange(S, device=ys.device).expand(B, S)
+    picks = [idx]
+    for k in range(T - 2, -1, -1):
+        idx = anc[k].gather(1, idx)
+        picks.append(idx)
+    picks = torch.stack(picks[::-1])                                   # (T, B, S)
+    return ys.reshape(T, B, S, H).gather(2, picks[..., None].expand(T, B, S, H)).reshape(T, B * S, H)
+
+
 def quantile_positions(q, N):
     """Order-statistic positions of the levels q among N samples, torch.quantile's 'linear' rule: pos = q (N - 1) in float64,
     k = floor(pos), frac = float32(pos - k).  Returns (k, frac) as lists; ValueError for a level outside [0, 1] or no level."""

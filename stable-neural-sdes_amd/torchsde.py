@@ -765,6 +765,75 @@ def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoi
     return sdeint(sde, y0, ts, bm=bm, method=method, names=names, **kwargs)
 
 
+# the resampling step and the genealogy trace under this module's name too (what a `import torchsde` user of sdeint_filter reaches for)
+sample_resample, filter_paths = engine.sample_resample, engine.filter_paths
+
+FilterResult = collections.namedtuple('FilterResult', 'ys log_weight ancestor ess logz')
+
+
+def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, options=None, threshold=0.5, stratified=False,
+                  generator=None):
+    """Bootstrap particle filter of an SDE state-space model on the sample paths of a solve: options={'samples': S} (required)
+    paths per input row are advanced from one observation time to the next, weighed by the observation and resampled.  For
+    k = 1 .. T-1:
+      1. ``sdeint`` over [ts[k-1], ts[k]]: the first piece with ``extra=True``, the later ones with ``extra_solver_state`` - the
+         SAME Brownian streams at the global step count, so slot p keeps slot p's stream and two children of one ancestor
+         diverge on independent noise;
+      2. ``inc = log_likelihood(k, y_k)``: y_k (B S, H) is the state at ts[k], inc (B, S) the log-likelihood of observation k per
+         path (for example ``sample_loglik(readout(y_k), S, obs[k], stats=True)[1]``);
+      3. ``engine.sample_resample(y_k, S, log_weight, inc, None, threshold, stratified, generator)``;
+      4. the resampled state is the next piece's ``y0``.
+    Returns FilterResult(ys (T, B S, H): the states BEFORE each resampling; log_weight (T, B, S): the carried weights after each
+    step; ancestor (T, B, S) int32; ess (T, B); logz (T, B)).  Entry 0 is the start: zero weights, the identity, ess = S,
+    logz = 0.  logsumexp(log_weight[k]) - log S = logz[k] = log p(y_1..k) (the running estimate of the log marginal likelihood);
+    ``engine.filter_paths(ys, ancestor, S)`` traces the surviving trajectories; the particles after the last resampling are
+    ys[-1] gathered by ancestor[-1].  dt=None reads options['dt'], else sdeint's default.  Inference only; a route that cannot
+    continue a Brownian path raises in ``sdeint`` (its docstring), and ensembles are not driven here (``sample_resample`` itself
+    serves them)."""
+    options = dict(options or {})
+    if 'samples' not in options:
+        raise ValueError("sdeint_filter needs options={'samples': S}: the particles per input row")
+    S = engine.check_samples(options['samples'])
+    if not callable(log_likelihood):
+        raise ValueError("log_likelihood must be callable: log_likelihood(k, y_k) -> (B, S) log-likelihood of observation k per path")
+    if not torch.is_tensor(y0) or y0.dim() != 2:
+        raise ValueError("`y0` must be a 2-dimensional tensor of shape (batch, channels).")
+    ts = _as_ts(ts, y0)
+    if dt is None:
+        dt = options.get('dt', 1e-3)
+    coeffs = getattr(sde, 'coeffs', None)
+    control = torch.is_tensor(coeffs) and coeffs.dim() == 3 and hasattr(sde, 'set_X')
+    T = int(ts.numel())
+    ys, state, y, logw = [], None, y0, None
+    weights, ancestors, esss, logzs = [], [], [], []
+    with torch.no_grad():
+        for k in range(1, T):
+            # (without a control path nothing tells an expanded y0 from a batch of B S rows: the later pieces hand their rows over as they are)
+            opts = options if k == 1 or control else {o: v for o, v in options.items() if o != 'samples'}
+            piece, state = sdeint(sde, y, ts[k - 1:k + 1], bm=bm, method=method, dt=dt, options=opts, extra=True, extra_solver_state=state)
+            if k == 1:
+                B = int(piece.shape[1]) // S
+                logw = torch.zeros((B, S), device=piece.device, dtype=piece.dtype)
+                ys.append(piece[0])
+                weights.append(logw)
+                ancestors.append(torch.arange(S, device=piece.device, dtype=torch.int32).expand(B, S).contiguous())
+                esss.append(torch.full((B,), float(S), device=piece.device, dtype=piece.dtype))
+                logzs.append(torch.zeros((B,), device=piece.device, dtype=piece.dtype))
+            yk = piece[1]
+            inc = log_likelihood(k, yk)
+            if not torch.is_tensor(inc) or tuple(inc.shape) != (B, S):
+                raise ValueError(f"log_likelihood({k}, y_k) must return a tensor of shape {(B, S)} (one log-likelihood per input row and "
+                                 f"path), got {tuple(inc.shape) if torch.is_tensor(inc) else type(inc).__name__}")
+            r = engine.sample_resample(yk, S, logw, inc.detach().to(device=logw.device, dtype=logw.dtype), None, threshold, stratified, generator)
+            ys.append(yk)
+            weights.append(r.log_weight)
+            ancestors.append(r.ancestor)
+            esss.append(r.ess)
+            logzs.append(r.logz)
+            y, logw = r.state, r.log_weight
+    return FilterResult(torch.stack(ys), torch.stack(weights), torch.stack(ancestors), torch.stack(esss), torch.stack(logzs))
+
+
 def _materialise_z0(sde, y0, ts, lin):
     """lin = options['z0_linear'] = the wrapper's `initial_network`: y0 is a placeholder and the solve starts from
     initial_network(X(ts[0])) (NeuralSDE._prepare_initial_state, neuralsde.py:63-69).  Evaluated here with tensor ops for
