@@ -291,8 +291,14 @@ typedef struct snsde_solve {
                            /* field variants, kernel = generic / 4-row / 16-row tiles, z0_weight, noise_table, kl_column1.  */
                            /* Never another kernel, no mode 2.                                                              */
     int64_t  row_offset;  /* global index of local row 0 (batch shards keep the global Philox   */
-                           /* stream: counter = (row_offset + row, step, col/4, 0)); the planner */
-                           /* sees the local batch unless `global_rows` (below) is set           */
+                           /* stream: counter = (row_offset + row, step >> 2, col, stream),      */
+                           /* output element step & 3); the planner sees the local batch unless  */
+                           /* `global_rows` (below) is set.  Range: 0 <= row_offset and          */
+                           /* row_offset + batch <= 2^32, with or without global_rows:           */
+                           /* SNSDE_ERR_DIMS otherwise, from every entry point that validates    */
+                           /* the descriptor.  The first counter word is the global row itself,  */
+                           /* never the global row modulo 2^32: a call whose rows would reach    */
+                           /* 2^32 is refused, it does not re-draw the paths of rows 0 ..        */
     uint64_t seed;         /* Philox key                                                         */
     const float*   params;    /* device, snsde_param_numel floats (members = M > 1: M such blocks) */
     const float*   coeffs;    /* device (B, L-1, 4C) = cat[a, b, two_c, three_d] (members: (B / M, ..)) */
@@ -359,7 +365,7 @@ typedef struct snsde_solve {
     /* Monte-Carlo sample paths: S = samples > 1 Brownian paths per input row in one solve (0 or 1: one path per row, today's
      * behaviour).  `batch` is then the number of PATHS of this call; path p (local row p) integrates against input row p / S:
      * coeffs is (batch / S, L-1, 4C), while y0, ys, dW, dU and row_out stay per path, (batch, ...).  The Philox counter stays
-     * (row_offset + p, step, col/4, 0), so the solve equals, bit for bit, the same descriptor with samples = 0 and every row
+     * (row_offset + p, step >> 2, col, stream), so the solve equals, bit for bit, the same descriptor with samples = 0 and every row
      * of coeffs repeated S times - without the S copies in memory.  batch, row_offset (and global_rows where set) must be
      * multiples of S, S >= 0: SNSDE_ERR_DIMS otherwise.  Inference only: act_save, stage_save, traj, dW_out, dU_out or
      * z0_weight (the host materialises y0) is SNSDE_ERR_UNSUPPORTED, as are snsde_eval_fg and every backward entry point

@@ -144,6 +144,12 @@ static bool global_rows_ok(const snsde_solve* s) {
     return s->global_rows == 0 || (s->global_rows > 0 && s->row_offset >= 0 && s->global_rows - s->row_offset >= (int64_t)s->batch);
 }
 
+// row_offset (snsde.h): the first Philox counter word is the global row as a uint32 - every row of the call lies in [0, 2^32),
+// with or without global_rows (a row beyond it would silently draw the Brownian path of row - 2^32)
+static bool row_range_ok(const snsde_solve* s) {
+    return s->row_offset >= 0 && s->row_offset <= ((int64_t)1 << 32) - (int64_t)s->batch;
+}
+
 // samples (snsde.h): S paths per input row - whole groups of S paths per call, shard and problem
 static bool samples_ok(const snsde_solve* s) {
     if (s->samples < 0 || s->reserved3 != 0) return false;
@@ -524,7 +530,7 @@ static int validate_solve(const snsde_solve* s, bool eval) {
     int rc = validate_model(&s->model);
     if (rc) return rc;
     if (s->batch <= 0 || s->knots < 2) return SNSDE_ERR_DIMS;
-    if (!global_rows_ok(s) || !samples_ok(s) || !members_ok(s)) return SNSDE_ERR_DIMS;
+    if (!row_range_ok(s) || !global_rows_ok(s) || !samples_ok(s) || !members_ok(s)) return SNSDE_ERR_DIMS;
     if (!s->params || !s->coeffs || !s->workspace) return SNSDE_ERR_NULL;
     if (!eval) {
         if (s->n_steps <= 0 || s->n_out < 2) return SNSDE_ERR_DIMS;

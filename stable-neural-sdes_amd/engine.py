@@ -636,6 +636,17 @@ def check_step_offset(step_offset, n_steps=0):
     return int(step_offset)
 
 
+def check_row_offset(row_offset, batch):
+    """`row_offset` of a solve of `batch` rows as an int with 0 <= row_offset and row_offset + batch <= 2**32 (the first Philox counter
+    word is the global row, 32 bits: the library refuses rows beyond it instead of re-drawing the paths of rows 0 ..); ValueError
+    otherwise.  Independent of global_rows."""
+    r = int(row_offset)
+    if r < 0 or r + int(batch) > 2 ** 32:
+        raise ValueError(f'row_offset={row_offset!r}: the global rows row_offset .. row_offset + batch - 1 = {r} .. {r + int(batch) - 1} of a '
+                         'solve must lie in [0, 2**32) (the Philox counter holds the global row in 32 bits)')
+    return r
+
+
 class SolveCall:
     """A fully prepared solve: owns references to every device buffer named in the descriptor so the
     launch itself is one C call that only enqueues kernels (hipGraph-capturable).
@@ -681,6 +692,7 @@ class SolveCall:
         # step_offset = n0 (resumable solves, snsde_solve_forward_at): local step i draws the normals of global step n0 + i.  A stream
         # coordinate like row_offset and seed - kept on the call, not in SolveConfig: no plan and no size query reads it
         self.step_offset = check_step_offset(step_offset, grid.N)
+        row_offset = check_row_offset(row_offset, B)
         if self.step_offset and (save_act or z0_linear is not None):
             raise ValueError('step_offset != 0 is inference only: a continued solve has no backward (no saved activations) and starts '
                              'from the caller\'s state (no fused initial network)')

@@ -183,10 +183,10 @@ def _row_offset(options, rows):
     Brownian paths, and shard r of equal-sized shards starts at row r * rows; else 0.  Always an int."""
     given = options.get('row_offset')
     if given is not None:
-        return int(given)
+        return engine.check_row_offset(given, rows)      # rows row_offset .. row_offset + rows - 1 inside [0, 2**32): ValueError otherwise
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-        return dist.get_rank() * int(rows)
+        return engine.check_row_offset(dist.get_rank() * int(rows), rows)
     return 0
 
 
@@ -333,6 +333,10 @@ def _sdeint(sde, y0, ts, bm, method, dt, options, names):
     bf16_grad = engine.check_bf16_grad(options['bf16_grad']) if 'bf16_grad' in options else False
     if bf16_grad:
         _bf16_grad_conflicts(sde, y0, options, backend, samples)
+    # options={'row_offset': r}: the global row of this call's first row (of its first path under `samples`).  The Philox counter holds the
+    # global row in 32 bits: rows outside [0, 2**32) are a ValueError, for every backend (engine.check_row_offset, include/snsde.h)
+    if options.get('row_offset') is not None:
+        engine.check_row_offset(options['row_offset'], y0.shape[0] * samples)
     if samples > 1:
         return _sdeint_samples(sde, y0, ts, bm, method, float(dt), options, names, samples, sample_grad)
     if backend != 'torch':      # (the tensor-op loop has no tiles to plan: it accepts the option and ignores it)
