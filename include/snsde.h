@@ -790,6 +790,96 @@ SNSDE_API int snsde_sample_quantiles_backward(const float* grad_out, const float
                                               int32_t samples, int32_t width, int32_t n_q, const int32_t* k, const float* frac,
                                               float* grad_ys, void* hip_stream);
 
+/* ---- weighted sample sets: statistics, CRPS and quantiles of sample paths that carry log-weights ---------------------------
+ * The six calls below are the weighted forms of snsde_sample_stats, snsde_sample_crps, snsde_sample_quantiles and their adjoints
+ * (csrc/snsde_weighted.hip); the unweighted calls keep their kernels and their bits.  ys is viewed as above, and logw is
+ * (outer, groups, N): one log-weight a_n per pooled path n = m S + s of an input row (N = M S; the statistics take members = 1,
+ * N = S and outer folded into groups), shared by the `width` columns of the group - a particle filter's (T, B, S) log-weights
+ * against its (T, B S, H) states.  N > 256 is SNSDE_ERR_DIMS in all six.
+ * Normalisation, per group, by one wave before any sample is read (lane l holds a_n for n = l, 64 + l, 128 + l, 192 + l):
+ *     mx  = fmaxf over all a_n (fmaxf skips a NaN)
+ *     e_n = expf(a_n - mx), the difference rounded once
+ *     P   = ((T_0 + T_1) + T_2) + T_3,  T_i = the sum of e_(64 i + l) over the 64 lanes l by the butterfly
+ *           v_l <- v_l + v_(l xor s), s = 32, 16, 8, 4, 2, 1, with zeros in the places past N: a 256-leaf tree whose shape is a
+ *           function of N alone (not of the grid, the width or the tile); nine additions deep
+ *     w_n = e_n / P
+ *     D'  = sum_n t_n over the same tree, t_n = w_n * (1 - w_n), each operation rounded once: the weighted (N - 1) / N, summed
+ *           from non-negative terms (no cancellation near collapse)
+ * Dead samples: a sample with e_n == 0 (a -Inf weight, or expf underflowed) in a group whose P is a number is dead.  It is
+ * selected out, never multiplied: its value - NaN and +-Inf included - reaches no output and no gradient, its own gradient is an
+ * exact zero, and the quantiles rank the live samples only.
+ * Unusable weight sets: a group whose weights are all -Inf (mx = -Inf, e_n = expf(NaN)), or that holds a NaN or a +Inf weight,
+ * has P = NaN and with it every w_n = NaN, 0 / NaN included: nothing is selected out and NaN reaches every output and gradient
+ * element of the group by the arithmetic (the quantile calls, whose value is a selection, write NaN where P is NaN).  No other
+ * group is affected.  A live sample that is NaN or +-Inf flows through the formulas as written.
+ * The weights carry no gradient: the adjoints below are those with the weights fixed.
+ * All six: enqueue-only, no workspace, no atomics, capturable; the same bits on every launch, whatever the grid and the alignment
+ * of the pointers; every element of every output given is written and no other byte; the inputs are only read.  All pointers
+ * device, fp32, contiguous.  Every check happens before the launch. */
+
+/* Weighted mean and reliability-weights unbiased variance.  ys (groups, samples, width), logw (groups, samples); a wave owns one
+ * (group, 64 adjacent columns) item, a lane one column, walked n ascending over the live samples, twice:
+ *     mean = sum_n fmaf(w_n, x_n, .)
+ *     var  = (sum_n fmaf(w_n, d_n * d_n, .)) / D',  d_n = x_n - mean         (optional, NULL = not wanted)
+ * At equal weights D' = (S - 1) / S and var is the / (S - 1) estimator; with a single live sample var = 0 / 0 = NaN by the formula
+ * (mean is that sample).  SNSDE_ERR_NULL: ys, logw or mean NULL.  SNSDE_ERR_DIMS: a non-positive extent, samples > 256, var with
+ * samples < 2, an element count beyond 63 bits. */
+SNSDE_API int snsde_sample_stats_weighted(const float* ys, const float* logw, int64_t groups, int32_t samples, int32_t width,
+                                          float* mean, float* var, void* hip_stream);
+
+/* Adjoint of snsde_sample_stats_weighted with the weights fixed: with c = (2 grad_var) / D',
+ *     grad_ys[g, n, w] = w_n * fmaf(c, x_n - mean, grad_mean)       (grad_var NULL: w_n * grad_mean; ys and mean are then not read)
+ * and an exact zero for a dead sample.  The weights are normalised again from logw.  The same ownership, errors and guarantees. */
+SNSDE_API int snsde_sample_stats_weighted_backward(const float* grad_mean, const float* grad_var, const float* ys, const float* logw,
+                                                   const float* mean, int64_t groups, int32_t samples, int32_t width, float* grad_ys,
+                                                   void* hip_stream);
+
+/* Weighted CRPS.  ys (outer, M, G, S, W), target (outer, G, W), logw (outer, G, N); tiles and quarters as snsde_sample_crps.  With
+ * d_n = x_n - y and, over j ascending (IEEE comparisons; a dead j adds an exact zero),
+ *     L_n = sum_j w_j [x_j < x_n],   U_n = sum_j w_j [x_j > x_n],   C_n = L_n - U_n
+ *     crps = sum_n w_n |d_n| - (sum_n (w_n C_n) d_n) / D            D = D' (fair != 0) or 1
+ *          = E_w |X - y| - sum_ij w_i w_j |x_i - x_j| / (2 D)
+ *     rank = sum_n w_n [x_n < y],  ties = sum_n w_n [x_n == y]      the weighted PIT pieces, in [0, 1]; each optional, NULL = not wanted
+ * over the live n.  Summation order: inside a quarter, n ascending, A = fmaf(w_n, |d_n|, A), B = fmaf(w_n * C_n, d_n, B), rank and
+ * ties by fmaf(w_n, 0 or 1, .); the four quarter sums are added k ascending; then crps = A - B / D.  Fair with one live sample is
+ * 0 / 0 = NaN by the formula.  SNSDE_ERR_NULL: ys, target, logw or crps NULL.  SNSDE_ERR_DIMS: a non-positive extent, N > 256, fair
+ * with N < 2, an element count beyond 63 bits.  SNSDE_ERR_LDS: the device refuses the slab (N * 256 bytes) plus the weight rows. */
+SNSDE_API int snsde_sample_crps_weighted(const float* ys, const float* target, const float* logw, int64_t outer, int32_t members,
+                                         int64_t groups, int32_t samples, int32_t width, int32_t fair, float* crps, float* rank,
+                                         float* ties, void* hip_stream);
+
+/* Adjoint of snsde_sample_crps_weighted with the weights fixed, sign(0) = 0:
+ *     grad_ys[n]  = g * (w_n * (sign(d_n) - C_n / D))                       an exact zero for a dead sample
+ *     grad_target = -(g * sum_n fmaf(w_n, sign(d_n), .))                    quarters as above (optional, NULL = not wanted)
+ * The C_n are formed again from ys and the weights; no plane is saved.  The same ownership, errors and guarantees. */
+SNSDE_API int snsde_sample_crps_weighted_backward(const float* grad_crps, const float* ys, const float* target, const float* logw,
+                                                  int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width,
+                                                  int32_t fair, float* grad_ys, float* grad_target, void* hip_stream);
+
+/* Weighted quantiles at the n_q levels q[i] in [0, 1] (a HOST array, copied into the kernel's argument struct); out is
+ * (n_q, outer, groups, width).  Only the F live samples are ranked: r_n = #{live j : x_j < x_n} + #{live j < n : x_j == x_n},
+ * A_n = the sum of w_j over the live j ranked before n, added j ascending, and the node of sample n is
+ *     p_n = A_n / (1 - w_n);     by definition p = 0 for rank 0 and p = 1 for rank F - 1 (rank 0 first)
+ * - the C = 1 member of the weighted-percentile family, r / (N - 1) at equal weights (torch.quantile's linear rule).  For a level q:
+ * lo = the sample of largest rank with p <= q, hi = the sample of rank r_lo + 1 (picked by the integer ranks, whatever the rounding
+ * of p), frac = clamp((q - p_lo) / (p_hi - p_lo), 0, 1) and
+ *     out = x_lo                                     where r_lo == F - 1 or frac == 0
+ *         = fmaf(frac, x_hi - x_lo, x_lo)            otherwise
+ * A live NaN sample makes every level of its column NaN; +-Inf follows the formula.  SNSDE_ERR_NULL: ys, logw, q or out NULL.
+ * SNSDE_ERR_DIMS: as above, n_q outside 1 .. 8, a level outside [0, 1].  SNSDE_ERR_LDS: the device refuses the slab, the nodes
+ * (N * 256 bytes each), the rank table (N * 64 bytes) and the weight rows. */
+SNSDE_API int snsde_sample_quantiles_weighted(const float* ys, const float* logw, int64_t outer, int32_t members, int64_t groups,
+                                              int32_t samples, int32_t width, int32_t n_q, const float* q, float* out, void* hip_stream);
+
+/* Adjoint of snsde_sample_quantiles_weighted with the weights fixed: grad_out (n_q, outer, groups, width) = g_i; the brackets are
+ * formed again,
+ *     grad_ys[lo_i] += g_i * (1 - frac_i),   grad_ys[hi_i] += g_i * frac_i (where the value interpolates),   i ascending
+ * and exact zeros elsewhere, a dead sample included.  A column that holds a live NaN (out is NaN: no derivative) gets zeros; a
+ * group with an unusable weight set NaN.  Every element of grad_ys is written. */
+SNSDE_API int snsde_sample_quantiles_weighted_backward(const float* grad_out, const float* ys, const float* logw, int64_t outer,
+                                                       int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t n_q,
+                                                       const float* q, float* grad_ys, void* hip_stream);
+
 /* Energy score: the multivariate generalisation of the CRPS, ES = E||X - y|| - E||X - X'|| / 2.  ys viewed as (outer, M, G, S, W)
  * exactly as for snsde_sample_crps (members axis: addressing only, member stride G S W; pooled set of group g: x_n, n = m S + s,
  * N = M S).  Two vector modes:

@@ -5,7 +5,7 @@ import sys as _sys
 from . import _lib, build, controldiffeq, engine, fields, modules, sharding, torchcde, torchsde, train  # noqa: F401
 from .modules import (Diffusion_model, Ensemble, IstsNeuralSDE, NeuralSDE, NeuralSDE_forecasting,  # noqa: F401
                       make_sde_model, prepare_sde_solver_kwargs)
-from .engine import (ensemble_stats, filter_paths, sample_class, sample_crps, sample_energy, sample_loglik,  # noqa: F401
+from .engine import (ensemble_stats, filter_particles, filter_paths, sample_class, sample_crps, sample_energy, sample_loglik,  # noqa: F401
                      sample_quantiles, sample_resample, sample_stats)
 from .train import crps_loss, energy_loss, iwae_loss, mc_class_loss  # noqa: F401
 from .torchsde import sdeint, sdeint_ensemble, sdeint_filter  # noqa: F401

@@ -111,7 +111,9 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward',
            'snsde_solve_forward_at', 'snsde_sample_crps', 'snsde_sample_crps_backward', 'snsde_sample_quantiles',
            'snsde_sample_quantiles_backward', 'snsde_sample_energy', 'snsde_sample_energy_backward', 'snsde_sample_loglik',
-           'snsde_sample_loglik_backward', 'snsde_sample_class', 'snsde_sample_class_backward', 'snsde_sample_resample')
+           'snsde_sample_loglik_backward', 'snsde_sample_class', 'snsde_sample_class_backward', 'snsde_sample_resample',
+           'snsde_sample_stats_weighted', 'snsde_sample_stats_weighted_backward', 'snsde_sample_crps_weighted',
+           'snsde_sample_crps_weighted_backward', 'snsde_sample_quantiles_weighted', 'snsde_sample_quantiles_weighted_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -214,6 +216,15 @@ def lib():
     L.snsde_sample_class_backward.argtypes = [C.c_void_p] * 7 + dims + [C.c_int32] + [C.c_void_p] * 3
     # (state, logw, loginc, u, groups, samples, width, stratified, threshold, state_out, logw_out, ancestor, ess, logz, resampled, stream)
     L.snsde_sample_resample.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 7
+    # weighted sample sets: the siblings' arguments with logw after the last input tensor; the quantile levels as a host float array
+    gsw = [C.c_int64, C.c_int32, C.c_int32]
+    L.snsde_sample_stats_weighted.argtypes = [C.c_void_p] * 2 + gsw + [C.c_void_p] * 3
+    L.snsde_sample_stats_weighted_backward.argtypes = [C.c_void_p] * 5 + gsw + [C.c_void_p] * 2
+    L.snsde_sample_crps_weighted.argtypes = [C.c_void_p] * 3 + dims + [C.c_int32] + [C.c_void_p] * 4
+    L.snsde_sample_crps_weighted_backward.argtypes = [C.c_void_p] * 4 + dims + [C.c_int32] + [C.c_void_p] * 3
+    levels = [C.c_int32, C.POINTER(C.c_float)]
+    L.snsde_sample_quantiles_weighted.argtypes = [C.c_void_p] * 2 + dims + levels + [C.c_void_p] * 2
+    L.snsde_sample_quantiles_weighted_backward.argtypes = [C.c_void_p] * 3 + dims + levels + [C.c_void_p] * 2
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

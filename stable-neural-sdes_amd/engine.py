@@ -1105,12 +1105,18 @@ def readout_head(x, layers, stream=None):
     return out.reshape(*lead, lin2.out_features)
 
 
-def sample_stats(ys, samples, var=True):
+def sample_stats(ys, samples, var=True, log_weight=None):
     """Mean and unbiased variance over the sample axis of a sampled solve's result (sdeint options={'samples': S}): ys is
     (..., B S, H) with path index b S + s; returns (mean, var), each (..., B, H) (var None when var=False).  CUDA float32 input:
     one launch of snsde_sample_stats (one lane per output element walks its S samples in order, twice: deterministic) - inside an
     autograd node whose backward is snsde_sample_stats_backward when the input requires grad; other tensors: the same two passes
-    in torch, which autograd differentiates."""
+    in torch, which autograd differentiates.
+    log_weight (..., B, S) - a particle filter's log-weights, `FilterResult.log_weight` against `filter_particles` of its states -
+    makes them the weighted mean sum w_n x_n and the reliability-weights unbiased variance sum w_n (x_n - mean)^2 / D',
+    D' = sum w_n (1 - w_n), w = softmax(log_weight): see `sample_stats_weighted_tensor_ops` for the definitions (dead samples,
+    unusable weight sets; a single live sample gives var = 0 / 0 = NaN).  The weights carry no gradient."""
+    if log_weight is not None:
+        return _sample_stats_weighted(ys, samples, var, log_weight)
     S = check_samples(samples)
     if ys.dim() < 2 or ys.shape[-2] % S:
         raise ValueError(f'ys has shape {tuple(ys.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
@@ -1307,7 +1313,7 @@ def _outer(lead):
     return n
 
 
-def sample_crps(ys, samples, target, fair=True, members=1, rank=False):
+def sample_crps(ys, samples, target, fair=True, members=1, rank=False, log_weight=None):
     """Continuous ranked probability score of the sample paths of a solve against an observation.  ys is (..., B S, W) - a
     sampled solve's result, path index b S + s - or, with members = M > 1, (..., M, B S, W): the paths of all members are pooled
     into one sample set x_n, n = m S + s, N = M S (the predictive mixture whose variance `ensemble_stats` splits).  target y is
@@ -1320,7 +1326,14 @@ def sample_crps(ys, samples, target, fair=True, members=1, rank=False):
     set holds them: a diverged path turns its own score into NaN and no other.
     CUDA float32 inputs with N <= 256: one launch of snsde_sample_crps (the (N, 64-column) slab of a group staged in LDS, no
     (.., S, S, ..) intermediate, deterministic, capturable) - inside an autograd node whose backward is snsde_sample_crps_backward
-    when an input requires grad.  Other tensors: the same definitions in tensor ops, the counts from a sort."""
+    when an input requires grad.  Other tensors: the same definitions in tensor ops, the counts from a sort.
+    log_weight (..., B, N), one log-weight per pooled path n = m S + s, scores the weighted sample set: with w = softmax(log_weight),
+    C_n = sum_j w_j [x_j < x_n] - sum_j w_j [x_j > x_n] and D = D' = sum w_n (1 - w_n) (fair) or 1,
+        crps = sum w_n |d_n| - sum w_n C_n d_n / D        (= E_w |X - y| - sum_ij w_i w_j |x_i - x_j| / (2 D))
+    and rank / ties become the weighted PIT pieces sum w_n [x_n < y], sum w_n [x_n == y] in [0, 1]: see
+    `sample_crps_weighted_tensor_ops`.  The weights carry no gradient."""
+    if log_weight is not None:
+        return _sample_crps_weighted(ys, samples, target, fair, members, rank, log_weight)
     S, M, lead, G, W = _score_dims(ys, samples, members)
     N, out_shape = M * S, lead + (G, W)
     if tuple(target.shape) != out_shape:
@@ -1991,7 +2004,7 @@ def _quantile_args(ks, fracs):
     return n, (C.c_int32 * n)(*ks), (C.c_float * n)(*fracs)
 
 
-def sample_quantiles(ys, samples, q, members=1):
+def sample_quantiles(ys, samples, q, members=1, log_weight=None):
     """Quantiles of the sample paths of a solve at the levels q (a sequence of numbers in [0, 1]): ys as for `sample_crps`, the
     result (len(q), ..., B, W).  Linear interpolation between order statistics (torch.quantile's 'linear' rule): with
     pos = q (N - 1), k = floor(pos) and frac = float32(pos - k), the value is x_(k), or fma(frac, x_(k+1) - x_(k), x_(k)) where
@@ -2002,7 +2015,13 @@ def sample_quantiles(ys, samples, q, members=1):
     the kernel gives a NaN sample an exact zero and the finite samples, ranked among themselves, the terms of the ranks they
     hold; the tensor-op route gives the whole set zeros.
     CUDA float32 input with N <= 256 and at most 8 levels: one launch of snsde_sample_quantiles (backward:
-    snsde_sample_quantiles_backward); other tensors: a stable sort in tensor ops."""
+    snsde_sample_quantiles_backward); other tensors: a stable sort in tensor ops.
+    log_weight (..., B, N) gives the weighted quantiles: the live samples are ranked, the node of a sample is
+    p_n = A_n / (1 - w_n) with A_n the weight ranked before it (0 and 1 at the two ends), and a level interpolates linearly between
+    the two nodes around it - r / (N - 1) at equal weights, the rule above: see `sample_quantiles_weighted_tensor_ops`.  The
+    weights carry no gradient."""
+    if log_weight is not None:
+        return _sample_quantiles_weighted(ys, samples, q, members, log_weight)
     S, M, lead, G, W = _score_dims(ys, samples, members)
     N = M * S
     ks, fracs = quantile_positions(q, N)
@@ -2059,6 +2078,364 @@ class _SampleQuantiles(torch.autograd.Function):
     def backward(ctx, grad_out):
         ys, = ctx.saved_tensors
         return sample_quantiles_backward(grad_out.to(torch.float32).contiguous(), ys, ctx.S, ctx.ks, ctx.fracs, ctx.M), None, None, None, None
+
+
+# ---- weighted sample sets (csrc/snsde_weighted.hip): log_weight= of sample_stats, sample_crps and sample_quantiles ------------
+
+def _check_log_weight(log_weight, ys, shape):
+    """The argument errors of a log_weight (..., B, N) that goes with ys."""
+    if not isinstance(log_weight, torch.Tensor) or not log_weight.dtype.is_floating_point:
+        raise ValueError(f'log_weight must be a floating-point tensor, got {getattr(log_weight, "dtype", type(log_weight))}')
+    if tuple(log_weight.shape) != tuple(shape):
+        raise ValueError(f'log_weight has shape {tuple(log_weight.shape)}, expected {tuple(shape)} (one log-weight per pooled path of an '
+                         f'input row, the leading axes of ys)')
+    if log_weight.device != ys.device:
+        raise ValueError(f'log_weight is on {log_weight.device}, ys on {ys.device}')
+    if log_weight.requires_grad and torch.is_grad_enabled():
+        raise ValueError('log_weight requires grad: the weighted statistics and scores are differentiable in ys and target only (the '
+                         'weights are fixed; detach() them)')
+
+
+def normalised_weights(log_weight, dtype=None):
+    """(w, live, D') of log-weights (..., N), the definitions every weighted function shares: mx = max a, e = exp(a - mx),
+    P = sum e, w = e / P, D' = sum w (1 - w).  live is False for a dead sample: e == 0 (a -Inf weight, or exp underflowed) in a
+    group whose P is a number; such a sample is selected out of everything by torch.where.  A group whose weights are all -Inf, or
+    that holds a NaN or +Inf weight, has P = NaN and every w = NaN: NaN in all its results, by the arithmetic.  No gradient."""
+    with torch.no_grad():
+        a = log_weight.detach() if dtype is None else log_weight.detach().to(dtype)
+        skip = torch.isnan(a)
+        mx = torch.where(skip, torch.full_like(a, float('-inf')), a).amax(dim=-1, keepdim=True)      # (fmaxf skips a NaN)
+        e = torch.exp(a - mx)
+        P = e.sum(dim=-1, keepdim=True)
+        w = e / P
+        live = ~((e == 0) & ~torch.isnan(P))
+        return w, live, (w * (1 - w)).sum(dim=-1)
+
+
+def _stats_weighted_args(ys, samples, var, log_weight):
+    S = check_samples(samples)
+    if ys.dim() < 2 or ys.shape[-2] % S:
+        raise ValueError(f'ys has shape {tuple(ys.shape)}: its second-to-last axis must hold a whole number of groups of {S} paths')
+    if var and S < 2:
+        raise ValueError('the unbiased variance needs samples >= 2')
+    lead, G, W = tuple(ys.shape[:-2]), ys.shape[-2] // S, ys.shape[-1]
+    _check_log_weight(log_weight, ys, lead + (G, S))
+    return S, lead, G, W
+
+
+def _sample_stats_weighted(ys, samples, var, log_weight):
+    S, lead, G, W = _stats_weighted_args(ys, samples, var, log_weight)
+    if _score_native(ys, S, log_weight):
+        if ys.requires_grad and torch.is_grad_enabled():
+            mean, vout = _SampleStatsWeighted.apply(ys, log_weight.detach(), S, bool(var))
+        else:
+            mean, vout = _sample_stats_weighted_launch(ys.contiguous(), log_weight.contiguous(), S, bool(var))
+        return mean, (vout if var else None)
+    return sample_stats_weighted_tensor_ops(ys, S, log_weight, var)
+
+
+def sample_stats_weighted_tensor_ops(ys, samples, log_weight, var=True):
+    """`sample_stats(..., log_weight=)` stated in tensor ops (any device and floating dtype; autograd differentiates it in ys).
+    With (w, live, D') = normalised_weights(log_weight) and the dead samples selected out,
+        mean = sum_n w_n x_n        var = sum_n w_n (x_n - mean)^2 / D'
+    - the reliability-weights unbiased estimator, / (S - 1) at equal weights; a single live sample gives var = 0 / 0 = NaN."""
+    S, lead, G, W = _stats_weighted_args(ys, samples, var, log_weight)
+    w, live, Dp = normalised_weights(log_weight, ys.dtype)
+    w, live = w.unsqueeze(-1), live.unsqueeze(-1)
+    x = torch.where(live, ys.reshape(lead + (G, S, W)), torch.zeros((), dtype=ys.dtype, device=ys.device))
+    mean = (w * x).sum(dim=-2)
+    if not var:
+        return mean, None
+    return mean, (w * (x - mean.unsqueeze(-2)).square()).sum(dim=-2) / Dp.unsqueeze(-1)
+
+
+def _sample_stats_weighted_launch(ys, logw, S, var):
+    W = ys.shape[-1]
+    out_shape = tuple(ys.shape[:-2]) + (ys.shape[-2] // S, W)
+    mean = torch.empty(out_shape, device=ys.device, dtype=torch.float32)
+    vout = torch.empty(out_shape, device=ys.device, dtype=torch.float32) if var else None
+    _lib.check(_lib.lib().snsde_sample_stats_weighted(_ptr(ys), _ptr(logw), ys.numel() // (S * W), S, W, _ptr(mean), _ptr(vout),
+                                                      C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_stats_weighted')
+    return mean, vout
+
+
+def sample_stats_weighted_backward(grad_mean, grad_var, ys, log_weight, mean, samples):
+    """dL/d ys of the weighted `sample_stats` from dL/d mean and dL/d var (None: no variance term), the weights fixed: one launch
+    of snsde_sample_stats_weighted_backward.  ys (..., B S, H), log_weight (..., B, S), the others (..., B, H): contiguous float32
+    CUDA tensors."""
+    S, W = int(samples), ys.shape[-1]
+    _check_f32('ys', ys)
+    _check_f32('log_weight', log_weight, tuple(ys.shape[:-2]) + (ys.shape[-2] // S, S))
+    _check_f32('grad_mean', grad_mean, tuple(ys.shape[:-2]) + (ys.shape[-2] // S, W))
+    if grad_var is not None:
+        _check_f32('grad_var', grad_var, tuple(grad_mean.shape))
+        _check_f32('mean', mean, tuple(grad_mean.shape))
+    out = torch.empty_like(ys)
+    _lib.check(_lib.lib().snsde_sample_stats_weighted_backward(_ptr(grad_mean), _ptr(grad_var), _ptr(ys), _ptr(log_weight),
+                                                               _ptr(mean if grad_var is not None else None), ys.numel() // (S * W), S, W,
+                                                               _ptr(out), C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_stats_weighted_backward')
+    return out
+
+
+class _SampleStatsWeighted(torch.autograd.Function):
+    """The weighted sample_stats of a CUDA float32 tensor that requires grad: snsde_sample_stats_weighted and its _backward."""
+
+    @staticmethod
+    def forward(ctx, ys, logw, S, var):
+        ysc, lw = ys.detach().contiguous(), logw.contiguous()
+        mean, vout = _sample_stats_weighted_launch(ysc, lw, S, var)
+        ctx.S, ctx.var = S, var
+        ctx.save_for_backward(ysc, lw, mean)
+        if not var:
+            vout = mean.new_empty(0)
+            ctx.mark_non_differentiable(vout)
+        return mean, vout
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mean, grad_var):
+        ys, lw, mean = ctx.saved_tensors
+        gm = torch.zeros_like(mean) if grad_mean is None else grad_mean.to(torch.float32).contiguous()
+        gv = grad_var.to(torch.float32).contiguous() if ctx.var and grad_var is not None else None
+        return sample_stats_weighted_backward(gm, gv, ys, lw, mean, ctx.S), None, None, None
+
+
+def _crps_weighted_args(ys, samples, target, fair, members, log_weight):
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    if tuple(target.shape) != lead + (G, W):
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected {lead + (G, W)} (one observation per input row and column)')
+    if fair and N < 2:
+        raise ValueError('the fair (unbiased) score needs at least 2 pooled samples')
+    _check_log_weight(log_weight, ys, lead + (G, N))
+    return S, M, lead, G, W, N
+
+
+def _sample_crps_weighted(ys, samples, target, fair, members, rank, log_weight):
+    S, M, lead, G, W, N = _crps_weighted_args(ys, samples, target, fair, members, log_weight)
+    fair, rank = bool(fair), bool(rank)
+    if _score_native(ys, N, target, log_weight):
+        if (ys.requires_grad or target.requires_grad) and torch.is_grad_enabled():
+            crps, rk, ti = _SampleCRPSWeighted.apply(ys, target, log_weight.detach(), S, M, fair, rank)
+        else:
+            crps, rk, ti = _sample_crps_weighted_launch(ys.contiguous(), target.contiguous(), log_weight.contiguous(), S, M, fair, rank)
+        return (crps, rk, ti) if rank else crps
+    return sample_crps_weighted_tensor_ops(ys, S, target, log_weight, fair, M, rank)
+
+
+def sample_crps_weighted_tensor_ops(ys, samples, target, log_weight, fair=True, members=1, rank=False):
+    """`sample_crps(..., log_weight=)` stated in tensor ops (any device and floating dtype; autograd differentiates it in ys and
+    target).  With (w, live, D') = normalised_weights(log_weight), the dead samples selected out, d_n = x_n - y and
+    C_n = sum_j w_j [x_j < x_n] - sum_j w_j [x_j > x_n] from a sort and a cumulative sum of each column (no (.., N, N, ..) term),
+        crps = sum_n w_n |d_n| - sum_n w_n C_n d_n / D,  D = D' (fair) or 1;    rank = sum_n w_n [x_n < y], ties = sum_n w_n [x_n == y]."""
+    S, M, lead, G, W, N = _crps_weighted_args(ys, samples, target, fair, members, log_weight)
+    w, live, Dp = normalised_weights(log_weight, ys.dtype)
+    w, live = w.unsqueeze(-1), live.unsqueeze(-1)
+    x = torch.where(live, _pooled(ys, S, M, lead, G, W), torch.zeros((), dtype=ys.dtype, device=ys.device))
+    d = x - target.unsqueeze(-2)
+    with torch.no_grad():      # (the weights are fixed: no gradient)
+        xt = x.transpose(-1, -2).contiguous()                                     # (..., G, W, N)
+        xs, order = torch.sort(xt, dim=-1)
+        ws = w.transpose(-1, -2).expand(xt.shape).gather(-1, order)
+        cs = torch.cat((torch.zeros_like(ws[..., :1]), torch.cumsum(ws, dim=-1)), dim=-1)
+        below = cs.gather(-1, torch.searchsorted(xs, xt, right=False))
+        above = cs[..., -1:] - cs.gather(-1, torch.searchsorted(xs, xt, right=True))
+        c = (below - above).transpose(-1, -2)
+    D = Dp.unsqueeze(-1) if fair else 1.0
+    # (sum_n w_n C_n = 0: the second sum does not depend on the observation, and is not differentiated through it - in floating
+    # point the sum is not exactly zero, and near collapse it is divided by a small D')
+    crps = (w * d.abs()).sum(dim=-2) - (w * c * (x - target.detach().unsqueeze(-2))).sum(dim=-2) / D
+    if not rank:
+        return crps
+    with torch.no_grad():
+        return crps, (w * (d < 0)).sum(dim=-2).to(torch.float32), (w * (d == 0)).sum(dim=-2).to(torch.float32)
+
+
+def _sample_crps_weighted_launch(ys, target, logw, S, M, fair, rank):
+    G, W = ys.shape[-2] // S, ys.shape[-1]
+    crps = torch.empty_like(target)
+    rk = torch.empty_like(target) if rank else None
+    ti = torch.empty_like(target) if rank else None
+    _lib.check(_lib.lib().snsde_sample_crps_weighted(_ptr(ys), _ptr(target), _ptr(logw), ys.numel() // (M * G * S * W), M, G, S, W, int(fair),
+                                                     _ptr(crps), _ptr(rk), _ptr(ti),
+                                                     C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_crps_weighted')
+    return crps, rk, ti
+
+
+def sample_crps_weighted_backward(grad_crps, ys, target, log_weight, samples, fair=True, members=1, grad_target=True):
+    """(dL/d ys, dL/d target) of the weighted `sample_crps` from dL/d crps, the weights fixed: one launch of
+    snsde_sample_crps_weighted_backward (dL/d target None when grad_target=False).  Contiguous float32 CUDA tensors."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    _check_f32('ys', ys)
+    _check_f32('target', target, lead + (G, W))
+    _check_f32('grad_crps', grad_crps, lead + (G, W))
+    _check_f32('log_weight', log_weight, lead + (G, M * S))
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    _lib.check(_lib.lib().snsde_sample_crps_weighted_backward(_ptr(grad_crps), _ptr(ys), _ptr(target), _ptr(log_weight), _outer(lead), M, G, S,
+                                                              W, int(bool(fair)), _ptr(gys), _ptr(gt),
+                                                              C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_crps_weighted_backward')
+    return gys, gt
+
+
+class _SampleCRPSWeighted(torch.autograd.Function):
+    """The weighted sample_crps of CUDA float32 tensors of which one requires grad: snsde_sample_crps_weighted and its _backward."""
+
+    @staticmethod
+    def forward(ctx, ys, target, logw, S, M, fair, rank):
+        ysc, tc, lw = ys.detach().contiguous(), target.detach().contiguous(), logw.contiguous()
+        crps, rk, ti = _sample_crps_weighted_launch(ysc, tc, lw, S, M, fair, rank)
+        ctx.S, ctx.M, ctx.fair = S, M, fair
+        ctx.save_for_backward(ysc, tc, lw)
+        if not rank:
+            rk, ti = crps.new_empty(0), crps.new_empty(0)
+        ctx.mark_non_differentiable(rk, ti)
+        return crps, rk, ti
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_crps, grad_rank, grad_ties):
+        ys, target, lw = ctx.saved_tensors
+        g = torch.zeros_like(target) if grad_crps is None else grad_crps.to(torch.float32).contiguous()
+        gys, gt = sample_crps_weighted_backward(g, ys, target, lw, ctx.S, ctx.fair, ctx.M, grad_target=ctx.needs_input_grad[1])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None, None
+
+
+def quantile_levels(q):
+    """The levels q as a list of float32-representable numbers; ValueError for a level outside [0, 1] or no level."""
+    try:
+        qs = [float(v) for v in (q.tolist() if isinstance(q, (torch.Tensor, np.ndarray)) else q)]
+    except TypeError:
+        qs = [float(q)]
+    if not qs or any(not 0.0 <= v <= 1.0 for v in qs):
+        raise ValueError(f'q must hold at least one level, each in [0, 1], got {q!r}')
+    return [float(np.float32(v)) for v in qs]
+
+
+def _sample_quantiles_weighted(ys, samples, q, members, log_weight):
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    qs = quantile_levels(q)
+    _check_log_weight(log_weight, ys, lead + (G, N))
+    if _score_native(ys, N, log_weight) and len(qs) <= SCORE_MAX_QUANTILES:
+        if ys.requires_grad and torch.is_grad_enabled():
+            return _SampleQuantilesWeighted.apply(ys, log_weight.detach(), S, M, tuple(qs))
+        return _sample_quantiles_weighted_launch(ys.contiguous(), log_weight.contiguous(), S, M, qs)
+    return sample_quantiles_weighted_tensor_ops(ys, S, q, log_weight, M)
+
+
+def sample_quantiles_weighted_tensor_ops(ys, samples, q, log_weight, members=1):
+    """`sample_quantiles(..., log_weight=)` stated in tensor ops (any device and floating dtype; autograd differentiates it in ys).
+    With (w, live, .) = normalised_weights(log_weight), only the F live samples of a group are ranked (ties by index); A_n is the
+    weight ranked before sample n and its node p_n = A_n / (1 - w_n), by definition 0 for rank 0 and 1 for rank F - 1.  For a level
+    q (rounded to float32): lo = the sample of largest rank with p <= q, hi = the next rank,
+    frac = clamp((q - p_lo) / (p_hi - p_lo), 0, 1) and the value is x_lo where lo is the last rank or frac == 0, else
+    x_lo + frac (x_hi - x_lo).  A live NaN makes every level of its column NaN (gradient: zeros); an unusable weight set NaN."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    N = M * S
+    qs = quantile_levels(q)
+    _check_log_weight(log_weight, ys, lead + (G, N))
+    w, live, _ = normalised_weights(log_weight, ys.dtype)
+    zero = torch.zeros((), dtype=ys.dtype, device=ys.device)
+    x = torch.where(live.unsqueeze(-1), _pooled(ys, S, M, lead, G, W), zero).transpose(-1, -2)      # (..., G, W, N)
+    with torch.no_grad():
+        dead = (~live).unsqueeze(-2).expand(x.shape)
+        has_nan = (torch.isnan(x) & ~dead).any(dim=-1)
+        first = torch.sort(torch.where(torch.isnan(x), zero, x), dim=-1, stable=True).indices
+        order = first.gather(-1, torch.sort(dead.gather(-1, first).to(torch.int8), dim=-1, stable=True).indices)      # the live first
+        ws = w.unsqueeze(-2).expand(x.shape).gather(-1, order)
+        F = live.sum(dim=-1)[..., None, None]                                                      # (..., G, 1, 1)
+        r = torch.arange(N, device=x.device).expand(x.shape)
+        p = torch.cat((torch.zeros_like(ws[..., :1]), torch.cumsum(ws, dim=-1)[..., :-1]), dim=-1) / (1 - ws)
+        p = torch.where(r == F - 1, torch.ones_like(p), p)
+        p = torch.where(r == 0, torch.zeros_like(p), p)
+        p = torch.where(r >= F, torch.full_like(p, float('inf')), p)
+        bad = torch.isnan(w).any(dim=-1)[..., None]                                                # (..., G, 1)
+    xs = x.gather(-1, order)
+    nan = torch.full((), float('nan'), dtype=ys.dtype, device=ys.device)
+    poison = torch.where(bad[..., None], xs, zero).sum(dim=-1) * nan      # (an unusable weight set: NaN, and a NaN gradient to every sample of the group)
+    out = []
+    for level in qs:
+        with torch.no_grad():
+            lo = torch.where(p <= level, r, torch.zeros_like(r)).amax(dim=-1, keepdim=True)
+            hi = torch.clamp(lo + 1, max=N - 1)
+            plo, phi = p.gather(-1, lo), p.gather(-1, hi)
+            frac = torch.clamp((level - plo) / (phi - plo), 0, 1)
+            flat = (lo == F - 1) | (frac == 0) | has_nan[..., None] | bad[..., None]
+            frac = torch.where(flat, torch.zeros_like(frac), frac)
+        xlo, xhi = xs.gather(-1, lo), xs.gather(-1, hi)
+        v = torch.where(flat, xlo, xlo + frac * (torch.where(flat, xlo, xhi) - xlo))[..., 0]
+        out.append(torch.where(bad, poison, torch.where(has_nan, nan, v)))
+    return torch.stack(out)
+
+
+def _level_args(qs):
+    return len(qs), (C.c_float * len(qs))(*qs)
+
+
+def _sample_quantiles_weighted_launch(ys, logw, S, M, qs):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    n_q, q = _level_args(qs)
+    out = torch.empty((n_q,) + lead + (G, W), device=ys.device, dtype=torch.float32)
+    _lib.check(_lib.lib().snsde_sample_quantiles_weighted(_ptr(ys), _ptr(logw), _outer(lead), M, G, S, W, n_q, q, _ptr(out),
+                                                          C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_quantiles_weighted')
+    return out
+
+
+def sample_quantiles_weighted_backward(grad_out, ys, log_weight, samples, q, members=1):
+    """dL/d ys of the weighted `sample_quantiles` from dL/d out (len(q), ..., B, W), the weights fixed: one launch of
+    snsde_sample_quantiles_weighted_backward.  Contiguous float32 CUDA tensors."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    n_q, qa = _level_args(quantile_levels(q))
+    _check_f32('ys', ys)
+    _check_f32('log_weight', log_weight, lead + (G, M * S))
+    _check_f32('grad_out', grad_out, (n_q,) + lead + (G, W))
+    gys = torch.empty_like(ys)
+    _lib.check(_lib.lib().snsde_sample_quantiles_weighted_backward(_ptr(grad_out), _ptr(ys), _ptr(log_weight), _outer(lead), M, G, S, W, n_q,
+                                                                   qa, _ptr(gys), C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_quantiles_weighted_backward')
+    return gys
+
+
+class _SampleQuantilesWeighted(torch.autograd.Function):
+    """The weighted sample_quantiles of a CUDA float32 tensor that requires grad: snsde_sample_quantiles_weighted and its _backward."""
+
+    @staticmethod
+    def forward(ctx, ys, logw, S, M, qs):
+        ysc, lw = ys.detach().contiguous(), logw.contiguous()
+        ctx.S, ctx.M, ctx.qs = S, M, qs
+        ctx.save_for_backward(ysc, lw)
+        return _sample_quantiles_weighted_launch(ysc, lw, S, M, list(qs))
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        ys, lw = ctx.saved_tensors
+        return sample_quantiles_weighted_backward(grad_out.to(torch.float32).contiguous(), ys, lw, ctx.S, ctx.qs, ctx.M), None, None, None, None
+
+
+def filter_particles(ys, ancestor, samples):
+    """The particle sets that a particle filter's weights belong to.  `sdeint_filter`'s ys (T, B S, H) holds the states BEFORE each
+    resampling and its log_weight (T, B, S) the weights AFTER it; this gathers every step's states through that step's own
+    resampling, out[k, b S + j] = ys[k, b S + ancestor[k, b, j]] (the identity wherever the step did not resample), so that
+    out[k] with log_weight[k] is the weighted sample set of time k:
+        sample_stats(filter_particles(r.ys, r.ancestor, S), S, log_weight=r.log_weight)
+    is the filtered mean and variance of all T times in one launch (`sample_crps` and `sample_quantiles` likewise).  Unlike
+    `filter_paths` nothing is traced back through earlier steps.  ys may carry further leading axes: (..., B S, H) against
+    ancestor (..., B, S)."""
+    S = check_samples(samples)
+    if ys.dim() < 2 or ys.shape[-2] % S:
+        raise ValueError(f'ys has shape {tuple(ys.shape)}, expected (..., B S, H) with a whole number of groups of {S} paths')
+    lead, B, H = tuple(ys.shape[:-2]), ys.shape[-2] // S, ys.shape[-1]
+    if tuple(ancestor.shape) != lead + (B, S) or ancestor.dtype.is_floating_point or ancestor.dtype == torch.bool:
+        raise ValueError(f'ancestor must be an integer tensor of shape {lead + (B, S)}, got {ancestor.dtype} {tuple(ancestor.shape)}')
+    anc = ancestor.to(device=ys.device, dtype=torch.int64)
+    return ys.reshape(lead + (B, S, H)).gather(-2, anc[..., None].expand(lead + (B, S, H))).reshape(ys.shape)
 
 
 def spline_grad_native():

@@ -770,7 +770,7 @@ def sdeint_adjoint(sde, y0, ts, bm=None, method=None, adjoint_method=None, adjoi
 
 
 # the resampling step and the genealogy trace under this module's name too (what a `import torchsde` user of sdeint_filter reaches for)
-sample_resample, filter_paths = engine.sample_resample, engine.filter_paths
+sample_resample, filter_paths, filter_particles = engine.sample_resample, engine.filter_paths, engine.filter_particles
 
 FilterResult = collections.namedtuple('FilterResult', 'ys log_weight ancestor ess logz')
 
@@ -791,7 +791,10 @@ def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, op
     step; ancestor (T, B, S) int32; ess (T, B); logz (T, B)).  Entry 0 is the start: zero weights, the identity, ess = S,
     logz = 0.  logsumexp(log_weight[k]) - log S = logz[k] = log p(y_1..k) (the running estimate of the log marginal likelihood);
     ``engine.filter_paths(ys, ancestor, S)`` traces the surviving trajectories; the particles after the last resampling are
-    ys[-1] gathered by ancestor[-1].  dt=None reads options['dt'], else sdeint's default.  Inference only; a route that cannot
+    ys[-1] gathered by ancestor[-1].  log_weight[k] belongs to the particles AFTER step k's resampling, ys[k] gathered by
+    ancestor[k]: ``engine.filter_particles(ys, ancestor, S)`` is that set for every k, and
+    ``engine.sample_stats(engine.filter_particles(r.ys, r.ancestor, S), S, log_weight=r.log_weight)`` the filtered mean and
+    variance of all T times in one launch (``sample_crps`` and ``sample_quantiles`` take ``log_weight=`` likewise).  dt=None reads options['dt'], else sdeint's default.  Inference only; a route that cannot
     continue a Brownian path raises in ``sdeint`` (its docstring), and ensembles are not driven here (``sample_resample`` itself
     serves them)."""
     options = dict(options or {})
