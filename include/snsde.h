@@ -131,7 +131,11 @@ enum {
      * or SRK; snsde_solve.members, last paragraph).  Meaningful only with members > 1 and both SNSDE_FLAG_ENSEMBLE_NETS and
      * SNSDE_FLAG_ENSEMBLE_GRAD set; each of the three keeps its own meaning.  Alone, or with only one of the other two, it changes
      * no answer. */
-    SNSDE_FLAG_ENSEMBLE_NETS_GRAD = 2048
+    SNSDE_FLAG_ENSEMBLE_NETS_GRAD = 2048,
+    /* Opt-in: a continued solve (snsde_solve_forward_at with step_offset != 0) may be differentiated.  With it the forward accepts
+     * the training planes at every offset, and the backward entry points' _at forms take the same offset (snsde_solve_forward_at,
+     * last paragraph).  No plan reads it and at step_offset == 0 it changes nothing. */
+    SNSDE_FLAG_RESUME_GRAD = 4096
 };
 
 /* Variants of the vector field beyond the benchmark Diffusion_model: the tutorial's Neural LSDE / LNSDE / GSDE fields
@@ -405,12 +409,23 @@ SNSDE_API int    snsde_solve_forward(const snsde_solve* s, void* hip_stream);
  * (and of srk_tab), step_offset = c_j, y0 = the state after step c_j - 1, and the same seed, row_offset, global_rows, samples and
  * members.  Every chunk then reproduces the states of the uncut solve bit for bit, on the same kernel.
  * snsde_solve_forward(s, st) is snsde_solve_forward_at(s, 0, st): the same launches, the same bits.
- * SNSDE_ERR_DIMS: step_offset < 0 or step_offset + n_steps > INT32_MAX.  SNSDE_ERR_UNSUPPORTED for step_offset != 0 with act_save or
- * stage_save (no adjoint regenerates offset increments: a continued solve has no backward) or with z0_weight (a continuation starts
- * from the caller's state, not from X(ts[0])).  traj, dW_out and dU_out are plain outputs, accepted wherever the offset-0 solve of
- * the same descriptor accepts them.  Every check is made before the first launch; all other validation and routing is that of
- * snsde_solve_forward.  The backward entry points take no offset: a descriptor that was run at n0 != 0 must not be handed to them.
- * Enqueue-only and capturable; the offset is a launch argument and is frozen into a recording. */
+ * SNSDE_ERR_DIMS: step_offset < 0 or step_offset + n_steps > INT32_MAX.  SNSDE_ERR_UNSUPPORTED for step_offset != 0 with z0_weight
+ * (a continuation starts from the caller's state, not from X(ts[0])), with or without SNSDE_FLAG_RESUME_GRAD.  traj, dW_out and
+ * dU_out are plain outputs, accepted wherever the offset-0 solve of the same descriptor accepts them.  Every check is made before
+ * the first launch; all other validation and routing is that of snsde_solve_forward.  Enqueue-only and capturable; the offset is
+ * a launch argument and is frozen into a recording.
+ * Training planes.  Without SNSDE_FLAG_RESUME_GRAD a continued solve is inference only: SNSDE_ERR_UNSUPPORTED for step_offset != 0
+ * with act_save or stage_save, and a descriptor that was run at n0 != 0 must not be handed to a backward entry point.  With the
+ * flag, act_save and stage_save are accepted at every offset wherever the offset-0 training forward of the same descriptor accepts
+ * them - the same training-mode kernels, which honour n0 at their Philox sites like the inference ones - and the chunk is
+ * differentiated by the _at form of a backward entry point with the chunk's own step_offset: snsde_solve_backward_at,
+ * snsde_backward_with_gradients_at.  The adjoints that regenerate Philox increments in-kernel (Euler / Milstein with a host key
+ * and neither dW_out nor a supplied dW) then draw global step n0 + n for local step n - block (n0 + n) >> 2, element (n0 + n) & 3,
+ * n0 a uniform kernel argument - bit for bit the product the forward formed; the adjoints that read dW_out or a supplied dW (SRK,
+ * the diffusion-net tiles, mode 2, a device-resident key) take the offset and need nothing from it.  snsde_param_gradients and
+ * snsde_coeff_gradients read no increments and have no _at form.  Cut a training solve as above with grad_ys of chunk j carrying,
+ * in its last output row, the chunk j + 1 adjoint adj[0]: dL/dy0 follows the adjoint recursion of the uncut solve, and the
+ * parameter and coefficient gradients of the uncut solve are the sums of the chunks'. */
 SNSDE_API int    snsde_solve_forward_at(const snsde_solve* s, int64_t step_offset, void* hip_stream);
 /* The initial state of a solve with z0_weight / z0_bias as a launch of its own: y0 (B, H, an OUTPUT as there) = z0_weight .
  * X(ts[0]) + z0_bias, through the device code the forward's prepare launch runs - the same bits.  For callers that need the state
@@ -488,6 +503,12 @@ SNSDE_API size_t snsde_backward_workspace_bytes(const snsde_backward* b);
  * SNSDE_FLAG_ENSEMBLE_NETS_GRAD): no delta planes; member m's pairs leave their theta partials and gradient blocks in block m of
  * b->workspace. */
 SNSDE_API int    snsde_solve_backward(const snsde_backward* b, void* hip_stream);
+/* The backward of a chunk that snsde_solve_forward_at ran at `step_offset` (its last paragraph): the same call, the adjoint's
+ * regenerated increments those of global steps step_offset + n.  snsde_solve_backward(b, st) is snsde_solve_backward_at(b, 0, st):
+ * the same launches, the same bits.  SNSDE_ERR_DIMS: step_offset < 0 or step_offset + fwd.n_steps > INT32_MAX.
+ * SNSDE_ERR_UNSUPPORTED: step_offset != 0 and b->fwd.flags lacks SNSDE_FLAG_RESUME_GRAD.  Both after the descriptor's own checks,
+ * before any launch. */
+SNSDE_API int    snsde_solve_backward_at(const snsde_backward* b, int64_t step_offset, void* hip_stream);
 
 /* Parameter gradients of the fused solve (mode 1 = MFMA path only): after snsde_solve_forward (traj, dW_out, act_save
  * kept; fwd.workspace untouched since) and snsde_solve_backward (adj, delta_save; b->workspace still the buffer that
@@ -513,6 +534,10 @@ SNSDE_API int    snsde_param_gradients(const snsde_backward* b, float* grad_para
  * SNSDE_FLAG_ENSEMBLE_NETS | SNSDE_FLAG_ENSEMBLE_NETS_GRAD): as the two calls.                                                    */
 SNSDE_API int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
                                             void* hip_stream);
+/* ... of a chunk run at `step_offset`: snsde_solve_backward_at followed by snsde_param_gradients (which reads no increments).  The
+ * name above is this call at offset 0; the offset's errors as for snsde_solve_backward_at. */
+SNSDE_API int snsde_backward_with_gradients_at(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
+                                               int64_t step_offset, void* hip_stream);
 
 /* Gradient of the fused solve with respect to the control path, dL/d coeffs (mode 1 = MFMA path only), from what the adjoint left
  * in HBM.  X(t) enters the drift's first layer only, and linearly: with delta_p (B, H) = dL/d(pre-activation of the drift's first
@@ -1072,6 +1097,43 @@ SNSDE_API int snsde_sample_resample(const float* state, const float* logw, const
                                     int64_t groups, int32_t samples, int32_t width, int32_t stratified, float threshold,
                                     float* state_out, float* logw_out, int32_t* ancestor, float* ess, float* logz,
                                     int32_t* resampled, void* hip_stream);
+
+/* The adjoint of snsde_sample_resample with the ancestors held fixed: ancestor, resampled (the forward's outputs, inputs here)
+ * and with them u and the threshold are constants of the backward.  This is the estimator of the filtering variational
+ * objectives (FIVO): the score-function term of the resampling decision is dropped.  Inputs: the gradients of the three
+ * differentiable outputs, grad_state_out (G, S, W), grad_logw_out (G, S) and grad_logz (G), each of which may be NULL (= zero),
+ * and the forward's logw, loginc (NULL = 0), ancestor (G, S) and resampled (G).  ess carries no gradient.  Outputs: grad_state
+ * (G, S, W) and grad_a (G, S), the gradient of a = logw + loginc and so of logw and of loginc alike.  Per group, with
+ * w_n = e_n / P_{S-1} (the softmax of a) formed again from logw and loginc:
+ *     resampled:   grad_state[n, :] = sum_{j : ancestor[j] == n} grad_state_out[j, :]
+ *                  grad_a[n]        = (grad_logz + sum_j grad_logw_out[j]) w_n            (every logw_out[j] is logz)
+ *     kept:        grad_state[n, :] = grad_state_out[n, :]
+ *                  grad_a[n]        = grad_logw_out[n] + grad_logz w_n
+ * A group counts as resampled where resampled[g] != 0 and its a are summed (next paragraph); its ancestors need not be
+ * monotone, and an ancestor outside [0, S) is the child of no particle: its row of grad_state_out is not read and no address
+ * is formed from it.
+ * Special values.  A particle with e_n == 0 receives an exact 0 from grad_logz and the weights' sum (whatever their value),
+ * and, never an ancestor, an exact +0 row of grad_state where the group is resampled.  A group whose a are all -Inf, or that
+ * holds a NaN or a +Inf, is the identity whatever resampled[g] says: grad_state = grad_state_out and grad_a = grad_logw_out bit
+ * for bit, the grad_logz term an exact zero; no other group is touched.  grad_state_out is only moved and added: a row with
+ * one child, and every kept row, arrives bit for bit, and a NaN reaches only the row of its ancestor.
+ * The forward's geometry: a workgroup of 256 threads per pack of GP adjacent groups, thread gp S + n particle n of group gp;
+ * 16-byte accesses where W % 4 == 0 and grad_state_out and grad_state are 16-byte aligned, one float at a time otherwise: the
+ * same bits.  Order of the operations, a function of S and of ancestor only:
+ *   a_n, mx, e_n and the chain P_n = P_{n-1} + e_n as the forward forms them; s = s + grad_logw_out[n] from 0, n ascending in one
+ *   thread; c = grad_logz + s (kept: grad_logz); w_n = e_n / P_{S-1}; z_n = c w_n (e_n == 0: 0); grad_a[n] = z_n (kept:
+ *   grad_logw_out[n] + z_n), every operation rounded once, no fused multiply-add;
+ *   grad_state[n, :]: the row of the least child j moved, then the rows of the further children added in ascending j, one
+ *   rounded addition each (the child lists are built per group in LDS: count, prefix, stable fill); no child: +0.
+ * No atomics, no workspace, no dependence on the grid or the pointer alignment: the same bits on every launch.  Every element
+ * of the two outputs is written and no other byte; the inputs are only read, each row of grad_state_out once at most.
+ * Enqueue-only, capturable.  All pointers device, contiguous; fp32 but ancestor and resampled (int32).  Errors are returned
+ * before any launch.  SNSDE_ERR_NULL: logw, ancestor, resampled or an output NULL.  SNSDE_ERR_DIMS: a non-positive extent,
+ * S > 256, an element count beyond 63 bits, an output overlapping an input or the other output. */
+SNSDE_API int snsde_sample_resample_backward(const float* grad_state_out, const float* grad_logw_out, const float* grad_logz,
+                                             const float* logw, const float* loginc, const int32_t* ancestor,
+                                             const int32_t* resampled, int64_t groups, int32_t samples, int32_t width,
+                                             float* grad_state, float* grad_a, void* hip_stream);
 
 SNSDE_API int         snsde_version(void);
 /* SNSDE_OK when `version` == SNSDE_VERSION and the four sizes equal the library's sizeof(snsde_model / snsde_solve /

@@ -25,6 +25,10 @@ FLAG_ENSEMBLE_GRAD = 256    # opt-in: a solve of members = M > 1 models may be d
 FLAG_ENSEMBLE_SAMPLES = 512 # opt-in: members = M > 1 together with samples = S > 1 in one solve (include/snsde.h)
 FLAG_ENSEMBLE_NETS = 1024   # opt-in: members = M > 1 on the wave-pair and diffusion-net kernels (include/snsde.h)
 FLAG_ENSEMBLE_NETS_GRAD = 2048   # opt-in: training through members = M > 1 on the wave pairs (with the two flags above it)
+# SNSDE_FLAG_RESUME_GRAD: opt-in, a continued solve (step_offset != 0) may be differentiated.  Like step_offset itself it belongs to
+# the launch, not to the plan: no planning query reads it, so it is no FLAG_* of the configuration record (engine.SolveConfig) -
+# SolveCall sets it beside the record's flags
+RESUME_GRAD = 4096
 LEAN_VARIANTS = ('none', 'general', 'specialised')      # snsde_lean_variant
 # snsde_forward_kernel / snsde_backward_kernel (SNSDE_FWD_* / SNSDE_REV_*): the names of csrc/snsde_mfma_kernels.h FwdKernel / RevKernel
 FWD_KERNELS = ('none', 'generic', 'generic_srk', 'w4', 'm4n', 'lean', 'lean_two_tile_h128', 'lean_two_tile_h256', 'lean_streamed_h256',
@@ -109,9 +113,10 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_affine_compose', 'snsde_affine_compose_backward', 'snsde_sample_stats', 'snsde_initial_state', 'snsde_coeff_gradients_workspace_bytes',
            'snsde_coeff_gradients', 'snsde_spline_backward_workspace_bytes', 'snsde_natural_cubic_coeffs_backward',
            'snsde_hermite_coeffs_backward', 'snsde_sample_stats_backward', 'snsde_ensemble_stats', 'snsde_ensemble_stats_backward',
-           'snsde_solve_forward_at', 'snsde_sample_crps', 'snsde_sample_crps_backward', 'snsde_sample_quantiles',
+           'snsde_solve_forward_at', 'snsde_solve_backward_at', 'snsde_backward_with_gradients_at', 'snsde_sample_crps', 'snsde_sample_crps_backward', 'snsde_sample_quantiles',
            'snsde_sample_quantiles_backward', 'snsde_sample_energy', 'snsde_sample_energy_backward', 'snsde_sample_loglik',
            'snsde_sample_loglik_backward', 'snsde_sample_class', 'snsde_sample_class_backward', 'snsde_sample_resample',
+           'snsde_sample_resample_backward',
            'snsde_sample_stats_weighted', 'snsde_sample_stats_weighted_backward', 'snsde_sample_crps_weighted',
            'snsde_sample_crps_weighted_backward', 'snsde_sample_quantiles_weighted', 'snsde_sample_quantiles_weighted_backward')
 
@@ -177,6 +182,9 @@ def lib():
     L.snsde_coeff_gradients_workspace_bytes.restype = C.c_size_t
     L.snsde_coeff_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
     L.snsde_backward_with_gradients.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]
+    # the backward of a continued solve (SNSDE_FLAG_RESUME_GRAD): the same calls with the chunk's step_offset in front of the stream
+    L.snsde_backward_with_gradients_at.argtypes = [C.POINTER(Backward), C.c_void_p, C.c_void_p, C.c_size_t, C.c_int64, C.c_void_p]
+    L.snsde_solve_backward_at.argtypes = [C.POINTER(Backward), C.c_int64, C.c_void_p]
     L.snsde_backward_supported.argtypes = [C.POINTER(Solve)]
     L.snsde_forward_path.argtypes = [C.POINTER(Solve)]
     L.snsde_lean_variant.argtypes = [C.POINTER(Solve)]
@@ -216,6 +224,8 @@ def lib():
     L.snsde_sample_class_backward.argtypes = [C.c_void_p] * 7 + dims + [C.c_int32] + [C.c_void_p] * 3
     # (state, logw, loginc, u, groups, samples, width, stratified, threshold, state_out, logw_out, ancestor, ess, logz, resampled, stream)
     L.snsde_sample_resample.argtypes = [C.c_void_p] * 4 + [C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_float] + [C.c_void_p] * 7
+    # (grad_state_out, grad_logw_out, grad_logz, logw, loginc, ancestor, resampled, groups, samples, width, grad_state, grad_a, stream)
+    L.snsde_sample_resample_backward.argtypes = [C.c_void_p] * 7 + [C.c_int64, C.c_int32, C.c_int32] + [C.c_void_p] * 3
     # weighted sample sets: the siblings' arguments with logw after the last input tensor; the quantile levels as a host float array
     gsw = [C.c_int64, C.c_int32, C.c_int32]
     L.snsde_sample_stats_weighted.argtypes = [C.c_void_p] * 2 + gsw + [C.c_void_p] * 3

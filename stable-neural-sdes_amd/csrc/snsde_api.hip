@@ -576,8 +576,8 @@ int snsde_solve_forward_at(const snsde_solve* s, int64_t step_offset, void* hip_
     if (rc) return rc;
     if (s->kernel < SNSDE_KERNEL_AUTO || s->kernel > SNSDE_KERNEL_MFMA_W4) return SNSDE_ERR_OPTION;
     if (step_offset < 0 || step_offset + (int64_t)s->n_steps > (int64_t)INT32_MAX) return SNSDE_ERR_DIMS;
-    // a continued solve has no backward (no adjoint regenerates offset increments) and starts from the caller's state
-    if (step_offset != 0 && (s->act_save || s->stage_save || s->z0_weight)) return SNSDE_ERR_UNSUPPORTED;
+    // a continued solve starts from the caller's state, and has a backward under SNSDE_FLAG_RESUME_GRAD only (the _at backward calls)
+    if (step_offset != 0 && (((s->act_save || s->stage_save) && !(s->flags & SNSDE_FLAG_RESUME_GRAD)) || s->z0_weight)) return SNSDE_ERR_UNSUPPORTED;
     if (s->workspace_bytes < snsde_workspace_bytes(s)) return SNSDE_ERR_WORKSPACE;
     SnsdeNet net;
     rc = snsde_build_net(s->model, s->n_steps, &net);
@@ -740,11 +740,21 @@ size_t snsde_backward_workspace_bytes(const snsde_backward* b) {
     return backward_workspace_bytes(b, net, route_backward(&b->fwd, net));
 }
 
-int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
+// The offset of a backward _at call: the forward's range, and the opt-in a continued training solve needs
+static int check_backward_offset(const snsde_solve* s, int64_t step_offset) {
+    if (step_offset < 0 || step_offset + (int64_t)s->n_steps > (int64_t)INT32_MAX) return SNSDE_ERR_DIMS;
+    if (step_offset != 0 && !(s->flags & SNSDE_FLAG_RESUME_GRAD)) return SNSDE_ERR_UNSUPPORTED;
+    return SNSDE_OK;
+}
+
+int snsde_solve_backward(const snsde_backward* b, void* hip_stream) { return snsde_solve_backward_at(b, 0, hip_stream); }
+
+int snsde_solve_backward_at(const snsde_backward* b, int64_t step_offset, void* hip_stream) {
     if (!b) return SNSDE_ERR_NULL;
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
+    if ((rc = check_backward_offset(&b->fwd, step_offset)) != SNSDE_OK) return rc;
     if ((b->fwd.flags & SNSDE_FLAG_BF16_OPERANDS) && !bf16_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (inference-only forward)
     if (snsde_samples(&b->fwd) > 1 && !sample_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (sample paths: inference only without the opt-in)
     if (snsde_members(&b->fwd) > 1 && !ensemble_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;     // (model ensembles: inference only without the opt-in)
@@ -765,7 +775,7 @@ int snsde_solve_backward(const snsde_backward* b, void* hip_stream) {
     }
     if (!b->fwd.act_save) return SNSDE_ERR_NULL;
     if (b->workspace_bytes < backward_workspace_bytes(b, net, r)) return SNSDE_ERR_WORKSPACE;
-    return snsde_mfma_backward_launch(b, net, r, static_cast<hipStream_t>(hip_stream));
+    return snsde_mfma_backward_launch(b, net, r, static_cast<hipStream_t>(hip_stream), (int)step_offset);
 }
 
 size_t snsde_param_gradients_workspace_bytes(const snsde_backward* b) {
@@ -812,10 +822,16 @@ int snsde_param_gradients(const snsde_backward* b, float* grad_params, void* wor
 
 int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
                                   void* hip_stream) {
+    return snsde_backward_with_gradients_at(b, grad_params, pg_workspace, pg_workspace_bytes, 0, hip_stream);
+}
+
+int snsde_backward_with_gradients_at(const snsde_backward* b, float* grad_params, void* pg_workspace, size_t pg_workspace_bytes,
+                                     int64_t step_offset, void* hip_stream) {
     if (!b || !grad_params || !pg_workspace) return SNSDE_ERR_NULL;
     if (b->struct_size != sizeof(snsde_backward)) return SNSDE_ERR_ABI;
     int rc = validate_solve(&b->fwd, false);
     if (rc) return rc;
+    if ((rc = check_backward_offset(&b->fwd, step_offset)) != SNSDE_OK) return rc;
     if (snsde_members(&b->fwd) > 1 && !ensemble_grad(&b->fwd)) return SNSDE_ERR_UNSUPPORTED;      // (model ensembles: inference only without the opt-in)
     if (!b->grad_ys || !b->adj || !b->workspace || !b->fwd.traj || !b->fwd.act_save || !b->fwd.workspace)
         return SNSDE_ERR_NULL;
@@ -827,7 +843,7 @@ int snsde_backward_with_gradients(const snsde_backward* b, float* grad_params, v
     rc = route_param_gradients(b, net, pg_workspace_bytes, &r);
     if (rc) return rc;
     hipStream_t st = static_cast<hipStream_t>(hip_stream);
-    rc = snsde_mfma_backward_launch(b, net, r, st);
+    rc = snsde_mfma_backward_launch(b, net, r, st, (int)step_offset);
     if (rc) return rc;
     return snsde_wgrad_launch(b, net, r, grad_params, (int32_t)snsde_param_numel(&b->fwd.model), static_cast<float*>(pg_workspace), st);
 }

@@ -112,7 +112,8 @@ size_t snsde_member_ws_stride(const snsde_solve* s, const SnsdeNet& net);
 // multiple of four floats so that every block starts 16-byte aligned (snsde.h: members, the rounding rule of the two queries)
 inline size_t snsde_member_bws_stride(size_t floats_with_tail) { return (floats_with_tail + 3) & ~(size_t)3; }
 int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const snsde_mfma::MfmaPlan& p, hipStream_t stream, int step_offset = 0);
-int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream);
+int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const snsde_mfma::BackwardRoute& r, hipStream_t stream,
+                               int step_offset = 0);
 // launchers (snsde_w4.hip): wave-owns-rows forward kernels (H = 64, diffusion nets, Euler)
 bool snsde_w4_supported(const snsde_solve* s, const SnsdeNet& net);
 bool snsde_w4_config_supported(const snsde_solve* s, const SnsdeNet& net);    // ... whatever the local batch (what a plan for the whole problem asks)
@@ -123,7 +124,7 @@ bool snsde_w4_rev_supported(const snsde_solve* s, const SnsdeNet& net);       //
 // members > 1 (SNSDE_FLAG_ENSEMBLE_NETS_GRAD): dth_part / gpart are member 0's, the members' blocks ws_stride floats apart
 // (snsde_member_bws_stride); every block is laid out and indexed as the member run alone lays it out
 int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth_part, float* gpart, hipStream_t stream, int members = 1,
-                        size_t ws_stride = 0);
+                        size_t ws_stride = 0, int step_offset = 0);
 size_t snsde_w4_grad_floats(const snsde_solve* s);
 int snsde_w4_grad_reduce_launch(const snsde_backward* b, const SnsdeNet& net, float* grad_params, int32_t n_params, float* gpart,
                                 const float* dth_part, hipStream_t stream, int members = 1, size_t ws_stride = 0);

@@ -102,13 +102,14 @@ __global__ void __launch_bounds__(CF::NT, 1) snsde_m4s2_reverse_kernel(RevArgs a
     const uint32_t BH32 = (uint32_t)BH, SBH = (uint32_t)NSAVE * BH32, NSBH = (uint32_t)NS * BH32;
     auto prefetch = [&](int n, StepIn& p) {
         if (!a.dW) {
-            if ((n >> 2) != zblk_id) {
-                zblk_id = n >> 2;
+            const int gn = a.step_offset + n;      // the global step: its block is cached while the walk stays inside it
+            if ((gn >> 2) != zblk_id) {
+                zblk_id = gn >> 2;
                 snsde_philox_normal4(a.seed, grow, (uint32_t)zblk_id, (uint32_t)fcol[0], zblk[0]);
                 snsde_philox_normal4(a.seed, grow, (uint32_t)zblk_id, (uint32_t)fcol[1], zblk[1]);
             }
             const float sqh = a.step_tab[uoff(n, SNSDE_STEP_STRIDE) + 6];
-            const bool odd = (n & 1) != 0, hi = (n & 2) != 0;
+            const bool odd = (gn & 1) != 0, hi = (gn & 2) != 0;
 #pragma unroll
             for (int j = 0; j < 2; ++j) {
                 const float lo2 = odd ? zblk[j][1] : zblk[j][0], hi2 = odd ? zblk[j][3] : zblk[j][2];

@@ -779,7 +779,7 @@ int snsde_mfma_launch(const snsde_solve* s, const SnsdeNet& net, const MfmaPlan&
 
 // ---- backward host side ---------------------------------------------------------------------------------
 
-int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const BackwardRoute& r, hipStream_t stream) {
+int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, const BackwardRoute& r, hipStream_t stream, int step_offset) {
     const snsde_solve* s = &b->fwd;
     const MfmaPlan& fp = r.fp;
     const RevPlan& p = r.rp;
@@ -800,7 +800,7 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
         // its gradient waves leave the weight-gradient sums per tile behind the plan's own workspace (RevPlan::w4_gpart_off)
         if (!(s->dW_out ? s->dW_out : s->dW) && s->seed_dev) return SNSDE_ERR_NULL;
         // (a model ensemble, SNSDE_FLAG_ENSEMBLE_NETS_GRAD: member m's pairs write into block m, ws_stride floats on)
-        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + p.w4_gpart_off, stream, members, ws_stride);
+        return snsde_w4_rev_launch(b, net, p.dth_off ? ws + p.dth_off : nullptr, ws + p.w4_gpart_off, stream, members, ws_stride, step_offset);
     }
     // first_y = emb[:, 0:H] . linear_in (all columns; the pack step picks the y columns).  A forward that ran with the folded first
     // layer left exactly this product in ITS workspace (piece `in` of snsde_prepare_kernel, same (H, K_in) layout): the pack
@@ -839,7 +839,7 @@ int snsde_mfma_backward_launch(const snsde_backward* b, const SnsdeNet& net, con
     a.step_tab = s->step_tab; a.out_w = s->out_w; a.traj = s->traj; a.act = s->act_save;
     // increments: the ones the forward wrote out, else the supplied ones, else (Philox, host key) regenerated by the kernel
     a.dW = s->dW_out ? s->dW_out : s->dW;
-    a.seed = s->seed; a.row_offset = s->row_offset;
+    a.seed = s->seed; a.row_offset = s->row_offset; a.step_offset = step_offset;
     if (!a.dW && (p.SRK || p.M4N || s->seed_dev)) return SNSDE_ERR_NULL;      // (regeneration: the Euler / Milstein kernel, host key)
     a.grad_ys = b->grad_ys; a.adj = b->adj; a.delta = b->delta_save; a.row_out = s->row_out;
     a.adj0_only = (b->flags & SNSDE_BWD_ADJ0_ONLY) ? 1 : 0;

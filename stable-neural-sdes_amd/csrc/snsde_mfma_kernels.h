@@ -1107,6 +1107,7 @@ struct RevArgs {
     // Euler / Milstein adjoint regenerates them (same call, same product z * sqrt h: bit-identical)
     uint64_t seed;
     int64_t row_offset;
+    int32_t step_offset;               // n0 of a continued solve: local step n regenerates the normals of global step n0 + n (uniform)
     int32_t acc_col;                   // path-integral accumulator column (-1: none) and its prior drift a y + b
     float acc_a, acc_b;
     // model ensembles under SNSDE_FLAG_ENSEMBLE_GRAD (snsde_solve::members = M > 1): the member is the second grid axis of the general
@@ -1229,13 +1230,14 @@ __global__ void __launch_bounds__(CF::NT, CF::WPS) snsde_mfma_reverse_kernel(Rev
     const uint32_t pre0 = a.act_fn != 0 ? (uint32_t)snsde_save::act_pre(NHID, NN, SNSDE_EULER, 0) : 0u;      // smooth activations: first PRE-activation slot
     auto prefetch = [&](int n, StepIn& p) {
         if (!a.dW) {                    // (wave-uniform)
-            if ((n >> 2) != zblk_id) {
-                zblk_id = n >> 2;
+            const int gn = a.step_offset + n;      // the global step: its block is cached while the walk stays inside it
+            if ((gn >> 2) != zblk_id) {
+                zblk_id = gn >> 2;
 #pragma unroll
                 for (int e = 0; e < EPT; ++e) snsde_philox_normal4(a.seed, grow, (uint32_t)zblk_id, (uint32_t)(fcol + e), zblk[e]);
             }
             const float sqh = a.step_tab[uoff(n, SNSDE_STEP_STRIDE) + 6];
-            const int k = n & 3;
+            const int k = gn & 3;
 #pragma unroll
             for (int e = 0; e < EPT; ++e)
                 p.dw[e] = (k == 0 ? zblk[e][0] : (k == 1 ? zblk[e][1] : (k == 2 ? zblk[e][2] : zblk[e][3]))) * sqh;

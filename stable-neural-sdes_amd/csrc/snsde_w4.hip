@@ -179,7 +179,7 @@ size_t snsde_w4_grad_floats(const snsde_solve* s) {      // per-tile gradient bl
 }
 
 int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth_part, float* gpart, hipStream_t stream, int members,
-                        size_t ws_stride) {
+                        size_t ws_stride, int step_offset) {
     using namespace snsde_w4;
     const snsde_solve* s = &b->fwd;
     if (!snsde_w4_rev_supported(s, net)) return SNSDE_ERR_UNSUPPORTED;
@@ -194,7 +194,7 @@ int snsde_w4_rev_launch(const snsde_backward* b, const SnsdeNet& net, float* dth
     a.grad_ys = b->grad_ys; a.adj = b->adj; a.dth_part = dth_part; a.row_out = s->row_out;
     a.gpart = gpart;
     a.delta = gpart ? nullptr : b->delta_save;      // fused weight gradients: no delta planes are written
-    a.seed = s->seed; a.row_offset = s->row_offset;
+    a.seed = s->seed; a.row_offset = s->row_offset; a.step_offset = step_offset;
     a.B = s->batch; a.N = s->n_steps; a.T = s->n_out; a.no = m.noise_option; a.geo = m.input_option == 5 ? 1 : 0;
     a.nsave = snsde_save::nsave(m.num_hidden_layers - 1, snsde_noise_net_layers(m.noise_option), SNSDE_EULER, m.activation != SNSDE_ACT_RELU);
     a.nslots = snsde_save::delta_slots(m.num_hidden_layers - 1, snsde_noise_net_layers(m.noise_option), SNSDE_EULER);

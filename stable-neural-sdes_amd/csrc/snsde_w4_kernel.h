@@ -875,6 +875,7 @@ struct W4RevArgs {
     const int32_t* row_out;
     uint64_t seed;
     int64_t row_offset;
+    int32_t step_offset;      // n0 of a continued solve: local step n regenerates the normals of global step n0 + n (uniform)
     int32_t B, N, T, no, geo, nsave, nslots, adj0_only, off_theta;
     int32_t w_in, k_in, t_in, w_hid[3], w_out, w_n0, w_n1;
     // model ensembles under SNSDE_FLAG_ENSEMBLE_NETS_GRAD (the ENS instantiations; one model: not read): member m = blockIdx.y owns rows
@@ -1157,8 +1158,9 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
             if constexpr (NN == 2) load4(a.act + uoff(n, SBH, snsde_save::act_net(NHID, 0), BH), hh);
             if (!phx) load4(a.dW + uoff(n, BH), ww);
             else {
-                if ((n >> 2) != zblk_id) {
-                    zblk_id = n >> 2;
+                const int gn = a.step_offset + n;      // the global step: its block is cached while the walk stays inside it
+                if ((gn >> 2) != zblk_id) {
+                    zblk_id = gn >> 2;
 #pragma unroll
                     for (int i = 0; i < 4; ++i) {      // (wave-private LDS: a register array indexed by n & 3 lands in scratch)
                         float zz[4];
@@ -1169,7 +1171,7 @@ __global__ void __launch_bounds__(FUSED ? 512 : 256, 2) snsde_w4_euler_reverse_k
                 }
                 const float sqh = (step_tab_c + (size_t)n * SNSDE_STEP_STRIDE)[6];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) ww[i] = zblk[i][n & 3][lane] * sqh;
+                for (int i = 0; i < 4; ++i) ww[i] = zblk[i][gn & 3][lane] * sqh;
             }
         };
         fetch(N - 1, y, q, hm, dw);

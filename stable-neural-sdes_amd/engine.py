@@ -201,6 +201,7 @@ def _check_bool_option(name, value, what):
 # the opt-ins as sdeint / sdeint_ensemble check them (SNSDE_FLAG_SAMPLE_GRAD, _BF16_GRAD, _ENSEMBLE_GRAD, _ENSEMBLE_SAMPLES,
 # _ENSEMBLE_NETS, _ENSEMBLE_NETS_GRAD - the last meaningful together with ensemble_nets and ensemble_grad)
 check_sample_grad = functools.partial(_check_bool_option, 'sample_grad', what='differentiate a solve of `samples` paths per input row')
+check_resume_grad = functools.partial(_check_bool_option, 'resume_grad', what='differentiate a continued solve, step_offset != 0')
 check_bf16_grad = functools.partial(_check_bool_option, 'bf16_grad', what="differentiate a precision='bf16' solve")
 check_ensemble_grad = functools.partial(_check_bool_option, 'ensemble_grad', what='differentiate a solve of `members` models')
 check_ensemble_samples = functools.partial(_check_bool_option, 'ensemble_samples',
@@ -211,7 +212,10 @@ check_ensemble_nets_grad = functools.partial(_check_bool_option, 'ensemble_nets_
 
 _METHODS = {'euler': _lib.EULER, 'milstein': _lib.MILSTEIN, 'srk': _lib.SRK}
 # The one place where an option name meets its SNSDE_FLAG_* bit (the two bf16 bits: precision_flags; SNSDE_FLAG_REUSE_PREPARED is
-# no configuration: SolveCall.launch sets it per launch)
+# no configuration: SolveCall.launch sets it per launch).  Not in the table, on purpose: SNSDE_FLAG_RESUME_GRAD (_lib.RESUME_GRAD,
+# option 'resume_grad').  Like step_offset, which it goes with, it belongs to the launch: no plan and no size query reads it, so it
+# is no field of SolveConfig (whose fields key the memos of those queries) - SolveCall(..., resume_grad=True) sets the bit beside the
+# record's flags, and it is the one descriptor flag that is neither here nor in precision_flags nor set per launch
 _FLAG_TABLE = (('exact_order', _lib.FLAG_EXACT_ORDER), ('stream_all', _lib.FLAG_STREAM_ALL), ('two_tile', _lib.FLAG_TWO_TILE),
                ('lean_general', _lib.FLAG_LEAN_GENERAL), ('sample_grad', _lib.FLAG_SAMPLE_GRAD), ('ensemble_grad', _lib.FLAG_ENSEMBLE_GRAD),
                ('ensemble_samples', _lib.FLAG_ENSEMBLE_SAMPLES), ('ensemble_nets', _lib.FLAG_ENSEMBLE_NETS),
@@ -657,7 +661,7 @@ class SolveCall:
                  kernel='auto', save_traj=False, save_dW=False, exact_order=False, save_act=False, dU=None, row_out=None,
                  noise_table=None, z0_linear=None, kl_column=None, stream_all=False, two_tile=False, precision='fp32',
                  lean_general=False, global_rows=0, samples=0, sample_grad=False, bf16_grad=False, members=0, ensemble_grad=False,
-                 ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False, step_offset=0):
+                 ensemble_samples=False, ensemble_nets=False, ensemble_nets_grad=False, step_offset=0, resume_grad=False):
         B, H = y0.shape
         C_ = model.input_channels
         L = coeffs.shape[1] + 1
@@ -693,7 +697,8 @@ class SolveCall:
         # coordinate like row_offset and seed - kept on the call, not in SolveConfig: no plan and no size query reads it
         self.step_offset = check_step_offset(step_offset, grid.N)
         row_offset = check_row_offset(row_offset, B)
-        if self.step_offset and (save_act or z0_linear is not None):
+        # resume_grad (SNSDE_FLAG_RESUME_GRAD): a continued solve may keep its training planes; the backward calls then take the offset
+        if self.step_offset and ((save_act and not resume_grad) or z0_linear is not None):
             raise ValueError('step_offset != 0 is inference only: a continued solve has no backward (no saved activations) and starts '
                              'from the caller\'s state (no fused initial network)')
         if dU is not None:
@@ -724,6 +729,8 @@ class SolveCall:
         # host-side queries of the library (save layout, workspace sizes) depend on the configuration only: memoised by the record
         self.config = self.cfg_key = cfg
         s = _describe(cfg, row_offset, planes=False)
+        if resume_grad:      # (no plan input: set beside the record's flags, after the record has keyed the memos)
+            s.flags |= _lib.RESUME_GRAD
         self.base_flags, self.members = s.flags, M
         if torch.is_tensor(seed):     # device-resident key: re-read by every launch / graph replay
             if seed.dtype != torch.int64 or not seed.is_cuda or seed.numel() != 1:
@@ -920,7 +927,11 @@ def solve_backward(call, grad_ys, stream=None, save_delta=False, adj0_only=False
     ws = torch.empty(max(nbytes, 256), device=adj.device, dtype=torch.uint8)
     b.workspace, b.workspace_bytes = _ptr(ws), ws.numel()
     stream = torch.cuda.current_stream(adj.device) if stream is None else stream
-    _lib.check(_lib.lib().snsde_solve_backward(C.byref(b), C.c_void_p(stream.cuda_stream)), 'snsde_solve_backward')
+    if call.step_offset:      # a continued solve (resume_grad): the adjoint regenerates the increments of the global steps
+        _lib.check(_lib.lib().snsde_solve_backward_at(C.byref(b), C.c_int64(call.step_offset), C.c_void_p(stream.cuda_stream)),
+                   'snsde_solve_backward_at')
+    else:
+        _lib.check(_lib.lib().snsde_solve_backward(C.byref(b), C.c_void_p(stream.cuda_stream)), 'snsde_solve_backward')
     call.keep_bwd = (ws, grad_ys)
     call.bwd_desc = b
     return (adj, delta) if save_delta else adj
@@ -968,8 +979,12 @@ def backward_with_gradients(call, grad_ys, stream=None, adj0_only=True, want_tab
     b.workspace, b.workspace_bytes = _ptr(ws), ws.numel()
     pws = torch.empty(sizes[1], device=dev, dtype=torch.uint8)
     stream = torch.cuda.current_stream(dev) if stream is None else stream
-    _lib.check(L.snsde_backward_with_gradients(C.byref(b), _ptr(grad), _ptr(pws), pws.numel(), C.c_void_p(stream.cuda_stream)),
-               'snsde_backward_with_gradients')
+    if call.step_offset:      # a continued solve (resume_grad): the adjoint regenerates the increments of the global steps
+        _lib.check(L.snsde_backward_with_gradients_at(C.byref(b), _ptr(grad), _ptr(pws), pws.numel(), C.c_int64(call.step_offset),
+                                                      C.c_void_p(stream.cuda_stream)), 'snsde_backward_with_gradients_at')
+    else:
+        _lib.check(L.snsde_backward_with_gradients(C.byref(b), _ptr(grad), _ptr(pws), pws.numel(), C.c_void_p(stream.cuda_stream)),
+                   'snsde_backward_with_gradients')
     call.keep_bwd = (ws, grad_ys)
     call.keep_pg = (pws, adj, delta, tab_grad)
     call.bwd_desc = b
@@ -1851,7 +1866,7 @@ class _SampleClass(torch.autograd.Function):
 SampleResample = collections.namedtuple('SampleResample', 'state log_weight ancestor ess logz resampled')
 
 
-def _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified):
+def _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified, differentiable=False):
     """(S, lead, B, W, threshold) of a resampling step; the argument errors of `sample_resample`.  u=None is not checked."""
     S = check_samples(samples)
     if state.dim() < 2 or state.shape[-2] % S:
@@ -1870,13 +1885,14 @@ def _resample_args(state, samples, log_weight, log_increment, u, threshold, stra
     if isinstance(threshold, bool) or not isinstance(threshold, (int, float, np.integer, np.floating)) or math.isnan(threshold):
         raise ValueError(f'threshold must be a number (resample where ess < threshold * samples; <= 0 never, >= 1 always), got {threshold!r}')
     tensors = [t for t in (state, log_weight, log_increment) if t is not None]
-    if torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
+    if not differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in tensors):
         raise ValueError('sample_resample is inference only: state, log_weight or log_increment requires grad (use torch.no_grad() or '
                          'detach()); resampling has no backward')
     return S, lead, B, W, float(threshold)
 
 
-def sample_resample(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None):
+def sample_resample(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None,
+                    differentiable=False):
     """One step of the bootstrap particle filter on the sample paths of a solve: weigh the S paths of every input row by the
     newest observation and resample them.  state is (..., B S, W) - the last state of a solve with options={'samples': S}, path
     b S + s; the leading axes (the members of an ensemble) fold into the groups, members are never pooled - log_weight (..., B, S)
@@ -1893,25 +1909,40 @@ def sample_resample(state, samples, log_weight, log_increment=None, u=None, thre
     state's device with `generator`.  Returns SampleResample(state, log_weight, ancestor (int32), ess, logz, resampled (int32)).
     A path with e_n == 0 (a -Inf weight) is never an ancestor; a row whose a are all -Inf is left as it is with ess = 0 and
     logz = -Inf; a row with a NaN or +Inf in a is left as it is with ess = logz = NaN and touches no other row; state is only
-    moved, NaN and Inf included.  Inference only: an input that requires grad under enabled autograd is a ValueError.
+    moved, NaN and Inf included.  By default inference only: an input that requires grad under enabled autograd is a ValueError.
+    differentiable=True makes state, log_weight and logz differentiable in state, log_weight and log_increment with the
+    ancestors held fixed: the ancestors, u and the threshold are constants of the backward,
+        d state[b S + n] = sum_{j : ancestor[b, j] == n} d state_out[b S + j]
+        d a[b, n]        = (d logz[b] + sum_j d log_weight_out[b, j]) softmax(a[b])_n      (not resampled: d log_weight_out[b, n] +
+                                                                                            d logz[b] softmax(a[b])_n)
+    which is the estimator of the filtering variational objectives (FIVO, Maddison et al. 2017): the score-function term of the
+    resampling decision is dropped, so the gradient of E[logz] is biased wherever a row is resampled, with a far smaller
+    variance.  A path with e_n == 0 receives exact zeros; a row left as it is for its NaN, +Inf or all -Inf weights passes its
+    gradients through unchanged.  ess, ancestor and resampled carry no gradient.
     CUDA float32 inputs with S <= 256: one launch of snsde_sample_resample (deterministic for a given u, capturable with u a
-    device tensor).  Other tensors: `sample_resample_tensor_ops`."""
-    stratified = bool(stratified)
-    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified)
+    device tensor), and one of snsde_sample_resample_backward in the backward.  Other tensors: `sample_resample_tensor_ops`."""
+    stratified, differentiable = bool(stratified), bool(differentiable)
+    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified, differentiable)
     if u is None:
         u = torch.rand(lead + ((B, S) if stratified else (B,)), device=state.device, dtype=log_weight.dtype, generator=generator)
     others = tuple(t for t in (log_weight, log_increment, u) if t is not None)
     if _score_native(state, S, *others):
-        return _sample_resample_launch(state.contiguous(), log_weight.contiguous(), None if log_increment is None else log_increment.contiguous(),
-                                       u.contiguous(), S, threshold, stratified)
-    return sample_resample_tensor_ops(state, S, log_weight, log_increment, u, threshold, stratified)
+        if differentiable and torch.is_grad_enabled() and any(t.requires_grad for t in (state, log_weight, log_increment) if t is not None):
+            return SampleResample(*_SampleResample.apply(state, log_weight, log_increment, u.detach(), S, threshold, stratified))
+        return _sample_resample_launch(state.detach().contiguous(), log_weight.detach().contiguous(),
+                                       None if log_increment is None else log_increment.detach().contiguous(), u.detach().contiguous(), S,
+                                       threshold, stratified)
+    return sample_resample_tensor_ops(state, S, log_weight, log_increment, u, threshold, stratified, differentiable=differentiable)
 
 
-def sample_resample_tensor_ops(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None):
+def sample_resample_tensor_ops(state, samples, log_weight, log_increment=None, u=None, threshold=0.5, stratified=False, generator=None,
+                               differentiable=False):
     """`sample_resample` stated in tensor ops (any device and floating dtype): logsumexp, cumsum, searchsorted, gather and where.
-    What `sample_resample` runs off the kernel's domain, and the baseline the kernel is timed against."""
-    stratified = bool(stratified)
-    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified)
+    What `sample_resample` runs off the kernel's domain, and the baseline the kernel is timed against.  differentiable=True: the
+    decision and the ancestors are formed from detached values as before, and state, log_weight and logz are then formed from the
+    inputs themselves by gather, logsumexp and where, whose autograd is the backward `sample_resample` states."""
+    stratified, differentiable = bool(stratified), bool(differentiable)
+    S, lead, B, W, threshold = _resample_args(state, samples, log_weight, log_increment, u, threshold, stratified, differentiable)
     if u is None:
         u = torch.rand(lead + ((B, S) if stratified else (B,)), device=state.device, dtype=log_weight.dtype, generator=generator)
     G = _outer(lead) * B
@@ -1938,6 +1969,14 @@ def sample_resample_tensor_ops(state, samples, log_weight, log_increment=None, u
     first = alive.to(torch.int8).argmax(dim=-1, keepdim=True)
     last = S - 1 - alive.flip(-1).to(torch.int8).argmax(dim=-1, keepdim=True)
     anc = torch.where(res[:, None], torch.minimum(torch.maximum(count, first), last), j.expand(G, S))
+    if differentiable:
+        # the three differentiable outputs again, from the inputs with their graph: the same values (a masked row contributes the
+        # constants it had above, and no gradient through logz: where() hands its unselected side an exact zero)
+        x = state.reshape(G, S, W)
+        ag = (log_weight if log_increment is None else log_weight + log_increment.to(log_weight.dtype)).reshape(G, S)
+        lse = torch.logsumexp(torch.where(kept[:, None], torch.zeros_like(a), ag), dim=-1) - math.log(S)
+        logz = torch.where(kept, logz, lse)
+        a = ag
     out = x.gather(1, anc[:, :, None].expand(G, S, W))
     logw = torch.where(res[:, None], logz[:, None], a)
     return SampleResample(out.reshape(state.shape), logw.reshape(lead + (B, S)), anc.to(torch.int32).reshape(lead + (B, S)),
@@ -1954,6 +1993,67 @@ def _sample_resample_launch(state, logw, loginc, u, S, threshold, stratified):
                                                 _ptr(out), _ptr(logw_out), _ptr(anc), _ptr(ess), _ptr(logz), _ptr(res),
                                                 C.c_void_p(torch.cuda.current_stream(state.device).cuda_stream)), 'snsde_sample_resample')
     return SampleResample(out, logw_out, anc, ess, logz, res)
+
+
+def sample_resample_backward(grad_state, grad_log_weight, grad_logz, log_weight, log_increment, ancestor, resampled, samples):
+    """(dL/d state, dL/d a) of `sample_resample(..., differentiable=True)` from dL/d of its state (..., B S, W), log_weight
+    (..., B, S) and logz (..., B) - each may be None - and the step's log_weight, log_increment (None: 0), ancestor and resampled:
+    one launch of snsde_sample_resample_backward.  dL/d a is the gradient of log_weight and of log_increment alike.  Contiguous
+    float32 (ancestor, resampled: int32) CUDA tensors; the width W is read off grad_state, which may therefore not be None here
+    unless `samples` is a pair (S, W)."""
+    S, W = samples if isinstance(samples, tuple) else (samples, None if grad_state is None else grad_state.shape[-1])
+    S = check_samples(S)
+    if W is None:
+        raise ValueError('grad_state is None: pass samples=(S, W) to state the width of the state')
+    lead, B = tuple(log_weight.shape[:-2]), log_weight.shape[-2]
+    _check_f32('log_weight', log_weight, lead + (B, S))
+    for name, t, shape in (('grad_state', grad_state, lead + (B * S, W)), ('grad_log_weight', grad_log_weight, lead + (B, S)),
+                           ('grad_logz', grad_logz, lead + (B,)), ('log_increment', log_increment, lead + (B, S))):
+        if t is not None:
+            _check_f32(name, t, shape)
+    for name, t, shape in (('ancestor', ancestor, lead + (B, S)), ('resampled', resampled, lead + (B,))):
+        if not (t.is_cuda and t.is_contiguous() and t.dtype == torch.int32 and tuple(t.shape) == shape):
+            raise ValueError(f'{name} must be a contiguous int32 CUDA tensor of shape {shape}')
+    return _sample_resample_backward_launch(grad_state, grad_log_weight, grad_logz, log_weight, log_increment, ancestor, resampled, S, W)
+
+
+def _sample_resample_backward_launch(gso, glw, glz, logw, loginc, anc, res, S, W):
+    lead, B = tuple(logw.shape[:-2]), logw.shape[-2]
+    G = _outer(lead) * B
+    gs = torch.empty(lead + (B * S, W), device=logw.device, dtype=torch.float32)
+    ga = torch.empty_like(logw)
+    _lib.check(_lib.lib().snsde_sample_resample_backward(_ptr(gso), _ptr(glw), _ptr(glz), _ptr(logw), _ptr(loginc), _ptr(anc), _ptr(res),
+                                                         G, S, W, _ptr(gs), _ptr(ga),
+                                                         C.c_void_p(torch.cuda.current_stream(logw.device).cuda_stream)),
+               'snsde_sample_resample_backward')
+    return gs, ga
+
+
+class _SampleResample(torch.autograd.Function):
+    """sample_resample(differentiable=True) of CUDA float32 tensors of which one requires grad: the forward kernel, and
+    snsde_sample_resample_backward as its backward (the weights are formed again from the saved log_weight and log_increment;
+    the ancestors are constants).  ancestor, ess and resampled carry no gradient; u receives none."""
+
+    @staticmethod
+    def forward(ctx, state, logw, loginc, u, S, threshold, stratified):
+        lw = logw.detach().contiguous()
+        inc = None if loginc is None else loginc.detach().contiguous()
+        out = _sample_resample_launch(state.detach().contiguous(), lw, inc, u.contiguous(), S, threshold, stratified)
+        ctx.S, ctx.W, ctx.has_inc = S, state.shape[-1], inc is not None
+        ctx.save_for_backward(lw, out.ancestor, out.resampled, *(() if inc is None else (inc,)))
+        ctx.mark_non_differentiable(out.ancestor, out.ess, out.resampled)
+        ctx.set_materialize_grads(False)
+        return tuple(out)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_state, grad_logw, unused_anc, unused_ess, grad_logz, unused_res):
+        lw, anc, res = ctx.saved_tensors[:3]
+        inc = ctx.saved_tensors[3] if ctx.has_inc else None
+        f = lambda g: None if g is None else g.to(torch.float32).contiguous()
+        gs, ga = _sample_resample_backward_launch(f(grad_state), f(grad_logw), f(grad_logz), lw, inc, anc, res, ctx.S, ctx.W)
+        need = ctx.needs_input_grad
+        return (gs if need[0] else None), (ga if need[1] else None), (ga if ctx.has_inc and need[2] else None), None, None, None, None
 
 
 def filter_paths(ys, ancestors, samples):

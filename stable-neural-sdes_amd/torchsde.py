@@ -258,7 +258,17 @@ def sdeint(sde, y0, ts, bm=None, method=None, dt=1e-3, adaptive=False, rtol=1e-5
     for bit exactly when every cut time is a step boundary of the single call's grid; otherwise the single call interpolates across
     the cut while the pieces land on it, as in torchsde.  Between the pieces ``sde.set_X`` may be called with a longer coefficient
     tensor and longer ``times`` (streaming: the causal Hermite path keeps the coefficients of its existing intervals).
-    Inference only: a differentiated call with step_offset != 0 is a ValueError.  A route that would draw from a torch generator
+    Inference only by default: a differentiated call with step_offset != 0 is a ValueError.  options={'resume_grad': True} opts in
+    to training through continued solves (SNSDE_FLAG_RESUME_GRAD): ``extra=True``, ``extra_solver_state`` and step_offset != 0 are
+    then legal on a differentiated call, the fused node hands the offset to the forward launch and to its backward call
+    (snsde_solve_backward_at / snsde_backward_with_gradients_at: the adjoints that regenerate Philox increments draw those of the
+    global steps), and with piece j's ``y0`` being piece j-1's ``ys[-1]`` inside the autograd graph the states equal the uncut
+    differentiable solve bit for bit, dL/dy0 follows the same adjoint recursion and the parameter and coefficient gradients are the
+    pieces' gradients summed by autograd (truncated back-propagation: detach ``y0`` between the pieces).  It goes with
+    samples + sample_grad, row_offset / global_rows, a control path that requires grad and precision='bf16' + bf16_grad; it does
+    not take recompute (the option or SNSDE_RECOMPUTE_STEPS) or z0_linear on a continued piece (ValueError), and ``sdeint_ensemble``
+    stays inference only.  The routes that are autograd through tensor ops anyway (CPU tensors, backend='torch' with a ``bm``)
+    simply stop refusing.  A route that would draw from a torch generator
     (the tensor-op loop without ``bm``, the latent route, the "no kernel covers it" fallback) raises NotImplementedError for
     step_offset != 0.  options={'step_offset': n0} is the same knob without the state (with a ``bm`` it has no effect on the
     increments).  A device-tensor seed (graph capture) with ``extra=True`` is a ValueError: the host does not know the key."""
@@ -321,9 +331,17 @@ def _sdeint(sde, y0, ts, bm, method, dt, options, names):
     # options={'step_offset': n0}: this call's first step is global step n0 of its Brownian path (a continued solve; inference).
     # Checked for every backend; from here on an int that every route finds in `options`
     step_offset = options['step_offset'] = engine.check_step_offset(options.get('step_offset') or 0)
-    if step_offset and _differentiated(sde, y0):
+    # options={'resume_grad': True}: a continued solve may be differentiated (opt-in; sdeint's docstring).  Checked for every backend
+    resume_grad = engine.check_resume_grad(options['resume_grad']) if 'resume_grad' in options else False
+    if step_offset and not resume_grad and _differentiated(sde, y0):
         raise ValueError(f"step_offset={step_offset} is inference only: y0, the control path or a parameter requires grad (use "
                          "torch.no_grad() or requires_grad_(False)); a continued solve has no backward")
+    if resume_grad and _differentiated(sde, y0):
+        for name, bad in (("recompute (options['recompute'] or SNSDE_RECOMPUTE_STEPS in the environment)", _recompute_steps(options) > 0),
+                          ('z0_linear on a continued piece (it starts from the state handed over, not from X(ts[0]))',
+                           step_offset != 0 and 'z0_linear' in options)):
+            if bad:
+                raise ValueError(f"resume_grad=True (training through continued solves) does not take {name}")
     # options={'samples': S}: S Brownian paths per input row (inference; _sdeint_samples).  Checked for every backend; 1 = no option
     # options={'sample_grad': True}: such a solve may be differentiated (opt-in: its training planes are per path).  No effect on 1
     samples = engine.check_samples(options.pop('samples')) if 'samples' in options else 1
@@ -776,7 +794,7 @@ FilterResult = collections.namedtuple('FilterResult', 'ys log_weight ancestor es
 
 
 def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, options=None, threshold=0.5, stratified=False,
-                  generator=None):
+                  generator=None, differentiable=False):
     """Bootstrap particle filter of an SDE state-space model on the sample paths of a solve: options={'samples': S} (required)
     paths per input row are advanced from one observation time to the next, weighed by the observation and resampled.  For
     k = 1 .. T-1:
@@ -794,9 +812,16 @@ def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, op
     ys[-1] gathered by ancestor[-1].  log_weight[k] belongs to the particles AFTER step k's resampling, ys[k] gathered by
     ancestor[k]: ``engine.filter_particles(ys, ancestor, S)`` is that set for every k, and
     ``engine.sample_stats(engine.filter_particles(r.ys, r.ancestor, S), S, log_weight=r.log_weight)`` the filtered mean and
-    variance of all T times in one launch (``sample_crps`` and ``sample_quantiles`` take ``log_weight=`` likewise).  dt=None reads options['dt'], else sdeint's default.  Inference only; a route that cannot
+    variance of all T times in one launch (``sample_crps`` and ``sample_quantiles`` take ``log_weight=`` likewise).  dt=None reads options['dt'], else sdeint's default.  Inference only by default (the loop runs under no_grad); a route that cannot
     continue a Brownian path raises in ``sdeint`` (its docstring), and ensembles are not driven here (``sample_resample`` itself
-    serves them)."""
+    serves them).
+    differentiable=True trains through the filter: the loop runs with autograd enabled, every piece is solved with
+    options sample_grad and resume_grad (``sdeint``'s docstring: the fused adjoint of a continued, sampled solve), ``inc`` keeps its
+    graph and the resampling is ``sample_resample(..., differentiable=True)``, whose backward holds the ancestors fixed.  logz,
+    log_weight and ys then carry gradients to the model's parameters, y0, the control path and whatever ``log_likelihood`` closes
+    over; ancestor and ess carry none.  ``-r.logz[-1].mean()`` is the FIVO loss (Maddison et al. 2017) - its gradient drops the
+    score-function term of the resampling decisions, the estimator that paper trains with.  The forward values equal those of
+    the default call bit for bit under the same seed and ``generator``."""
     options = dict(options or {})
     if 'samples' not in options:
         raise ValueError("sdeint_filter needs options={'samples': S}: the particles per input row")
@@ -813,7 +838,10 @@ def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, op
     T = int(ts.numel())
     ys, state, y, logw = [], None, y0, None
     weights, ancestors, esss, logzs = [], [], [], []
-    with torch.no_grad():
+    differentiable = bool(differentiable)
+    if differentiable:
+        options.update(sample_grad=True, resume_grad=True)
+    with torch.enable_grad() if differentiable else torch.no_grad():
         for k in range(1, T):
             # (without a control path nothing tells an expanded y0 from a batch of B S rows: the later pieces hand their rows over as they are)
             opts = options if k == 1 or control else {o: v for o, v in options.items() if o != 'samples'}
@@ -831,7 +859,8 @@ def sdeint_filter(sde, y0, ts, log_likelihood, bm=None, method=None, dt=None, op
             if not torch.is_tensor(inc) or tuple(inc.shape) != (B, S):
                 raise ValueError(f"log_likelihood({k}, y_k) must return a tensor of shape {(B, S)} (one log-likelihood per input row and "
                                  f"path), got {tuple(inc.shape) if torch.is_tensor(inc) else type(inc).__name__}")
-            r = engine.sample_resample(yk, S, logw, inc.detach().to(device=logw.device, dtype=logw.dtype), None, threshold, stratified, generator)
+            inc = (inc if differentiable else inc.detach()).to(device=logw.device, dtype=logw.dtype)
+            r = engine.sample_resample(yk, S, logw, inc, None, threshold, stratified, generator, differentiable=differentiable)
             ys.append(yk)
             weights.append(r.log_weight)
             ancestors.append(r.ancestor)
@@ -870,8 +899,9 @@ class _DrawnIncrements:
 # and the backward mode decided beside it, never the dict.  `engine`: the engine's options of the solve - the keywords the mode
 # query is asked with and SolveCall takes (method, kernel, precision, exact_order, global_rows, samples, sample_grad, bf16_grad);
 # the rest is no engine configuration, but for lean_general, which only the sampled node passes on
+# step_offset: of a differentiated solve only under options['resume_grad'] (sdeint has refused the others)
 _FusedOptions = collections.namedtuple('_FusedOptions', (
-    'engine', 'save_traj', 'strict', 'param_pass', 'recompute', 'lean_general', 'row_offset', 'row_out', 'seed'))
+    'engine', 'save_traj', 'strict', 'param_pass', 'recompute', 'lean_general', 'row_offset', 'row_out', 'seed', 'step_offset'))
 
 
 def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
@@ -899,7 +929,7 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     # (without `bm` the kernels draw Philox increments: nothing to draw here)
     dW, dU = _draw_increments(bm, grid, y0, method, dtype=torch.float32, philox=True, host_times=True)
 
-    step_offset = int(options.get('step_offset') or 0)      # (a continued solve: inference, the launch below)
+    step_offset = int(options.get('step_offset') or 0)      # (a continued solve: inference, or training under resume_grad)
 
     def loop():      # the tensor-op loop on the same device, on the increments already drawn (and on y0 as it is by then)
         if dW is None:
@@ -916,7 +946,8 @@ def _sdeint_hip(sde, rec, y0, ts, bm, method, dt, options):
     opt = _FusedOptions(
         engine=eng, seed=_philox_key(options, dev), save_traj=bool(options.get('save_traj', False)),
         strict=bool(options.get('strict', False)), param_pass=options.get('param_pass', 'hip'), recompute=_recompute_steps(options),
-        lean_general=bool(options.get('lean_general', False)), row_offset=row_offset, row_out=_device_row_out(options, dev))
+        lean_general=bool(options.get('lean_general', False)), row_offset=row_offset, row_out=_device_row_out(options, dev),
+        step_offset=step_offset)
     if precision == 'bf16':
         if needs_grad and not bf16_grad:      # (a z0_linear that requires grad was materialised above: y0 then does)
             raise ValueError("precision='bf16' is inference only: y0 or a parameter requires grad")
@@ -1044,7 +1075,7 @@ def _sdeint_composed(sde, y0, ts, bm, method, dt, options):
         flat = field.flat(dev, grad=True)
         tab = field.noise_table(tab_times, dev, grad=True) if field.tabulated else None
         return _ComposedSolve.apply(field.model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU, None,
-                                    global_rows)
+                                    global_rows, int(options.get('step_offset') or 0))      # (an offset here: sdeint's resume_grad opt-in)
     # options={'trust_versions': True}: the cached composed block / table are keyed on the parameters' addresses and version
     # counters alone (no content fingerprint = no device->host read per solve); in-place edits through `.data` are then the
     # caller's to avoid
@@ -1233,7 +1264,7 @@ def _sdeint_padded(sde, rec, pad, coeffs, grid, y0, dW, dU, method, opt, needs_g
     widen = lambda t: None if t is None else torch.nn.functional.pad(t, (0, P - H)).contiguous()
     if needs_grad:
         ys = _ComposedSolve.apply(model_p, coeffs, grid, widen(dW), method, opt.seed, opt.row_offset, opt.row_out,
-                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, opt.engine['global_rows'])
+                                  torch.nn.functional.pad(y0, (0, P - H)), flat, None, widen(dU), None, opt.engine['global_rows'], step_offset)
     else:
         call = engine.SolveCall(model_p, flat, coeffs, grid, widen(y0.detach().to(torch.float32)), dW=widen(dW), method=method,
                                 seed=opt.seed, row_offset=opt.row_offset, dU=widen(dU), row_out=opt.row_out,
@@ -1248,12 +1279,14 @@ class _ComposedSolve(torch.autograd.Function):
     gradients this node returns (dL/dy0, dL/d block, dL/d table) on to the module."""
 
     @staticmethod
-    def forward(ctx, model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU=None, kl_column=None, global_rows=0):
+    def forward(ctx, model, coeffs, grid, dW, method, seed, row_offset, row_out, y0, flat, tab, dU=None, kl_column=None, global_rows=0,
+                step_offset=0):
         y0c = y0.detach().to(torch.float32).contiguous()
         call = engine.SolveCall(model, flat.detach().contiguous(), coeffs, grid, y0c, dW=dW, method=method, seed=seed,
                                 row_offset=row_offset, row_out=row_out, dU=dU,
                                 noise_table=None if tab is None else tab.detach().contiguous(),
-                                save_traj=True, save_dW=True, save_act=True, kl_column=kl_column, global_rows=global_rows)
+                                save_traj=True, save_dW=True, save_act=True, kl_column=kl_column, global_rows=global_rows,
+                                step_offset=step_offset, resume_grad=step_offset != 0)      # (an offset: sdeint's resume_grad opt-in)
         ys = call.launch()
         ctx.call, ctx.y0_dtype, ctx.has_tab = call, y0.dtype, tab is not None
         return ys.to(y0.dtype) if y0.dtype != ys.dtype else ys.detach()
@@ -1264,7 +1297,7 @@ class _ComposedSolve(torch.autograd.Function):
         out = engine.backward_with_gradients(call, grad_ys.to(torch.float32).contiguous(), adj0_only=engine.adj0_suffices(call),
                                              want_table_grad=ctx.has_tab)
         adj, gflat, gtab = out if ctx.has_tab else (out + (None,))
-        return (None,) * 8 + (adj[0].to(ctx.y0_dtype), gflat, gtab, None, None, None)
+        return (None,) * 8 + (adj[0].to(ctx.y0_dtype), gflat, gtab, None, None, None, None)
 
 
 class _FusedSolve(torch.autograd.Function):
@@ -1306,6 +1339,7 @@ class _FusedSolve(torch.autograd.Function):
                        and os.environ.get('SNSDE_KEEP_INCREMENTS') != '1')
         call = engine.SolveCall(model, flat, coeffs, grid, y0c, dW=dW, seed=opt.seed, row_offset=opt.row_offset, save_traj=True,
                                 save_dW=keep_dw, save_act=save_act, row_out=opt.row_out, dU=dU,
+                                step_offset=opt.step_offset, resume_grad=opt.step_offset != 0,      # (a continued piece: resume_grad)
                                 lean_general=samples > 1 and opt.lean_general,      # (the sampled route's A/B switch)
                                 **dict(eng, samples=samples, sample_grad=samples > 1))   # (bf16 reaches here under bf16_grad, mode 1, only)
         ctx.coeffs_dtype = None if coeffs_src is None else coeffs_src.dtype
