@@ -943,6 +943,56 @@ SNSDE_API int snsde_sample_energy_backward(const float* grad_energy, const float
                                            int64_t groups, int32_t samples, int32_t width, int32_t fair, int32_t path, float* grad_ys,
                                            float* grad_target, void* hip_stream);
 
+/* Energy score of a WEIGHTED and / or PARTIALLY OBSERVED sample set: a sibling kernel of snsde_sample_energy
+ * (csrc/snsde_energy_weighted.hip); the unweighted, unmasked call keeps its kernels and its bits.  Layout, pooling (n = m S + s,
+ * N = M S <= 256), `path` and `fair` as for snsde_sample_energy.  Weights and mask are compile-time variants of one kernel; a call
+ * with neither runs the masked variant with every coordinate observed.
+ * Mask.  mask (NULL = none) has the shape of target, (outer, groups, width); a coordinate is observed where mask != 0 - the value
+ * is a flag, a fractional value does NOT weigh.  With mask NULL and nan_missing != 0 a coordinate is observed where target is not
+ * NaN.  Both are decided inside the kernel by the thread that stages the column: no extra launch, no mask tensor made from isnan.
+ * With O the observed coordinates of a score (under path: of all outer * width components) every distance is taken over O only,
+ *     r_n = ||(x_n - y)|_O||,   r_nj = ||(x_n - x_j)|_O||
+ * and an unobserved coordinate is selected out, never multiplied: nothing of ys or target is read there (zeros are staged for
+ * every row of the column, and fmaf(0, 0, acc) leaves each chain untouched), so NaN / Inf there reaches no value and no gradient,
+ * and grad_ys and grad_target there are exact zeros written by selection - also where grad_energy is NaN or Inf.  A score whose O
+ * is empty is 0 (NaN with an unusable weight set) with zero gradients.  A masked score has the bits of the unmasked kernel on the
+ * vectors compacted to their observed columns; a mask of all ones without weights gives the bits of snsde_sample_energy.
+ * Weights.  logw (NULL = none) is (outer, groups, N), or (groups, N) under path: one log-weight per pooled path of a score.  They
+ * are normalised exactly as for the weighted calls above - mx, e_n = expf(a_n - mx), P, w_n = e_n / P, D' = sum w_n (1 - w_n) over
+ * the same 256-leaf tree - by wave 0, once per score, while the loads of the first chunk of columns are in flight.  With D = D'
+ * (fair != 0) or 1,
+ *     energy = sum_n w_n r_n - (sum_{n<j} w_n w_j r_nj) / D
+ * which at w = 1 / N is the formula of snsde_sample_energy for both values of fair, and at integer multiplicities with fair == 0
+ * the unweighted score of the replicated set.  A dead sample (e_n == 0 where P is a number) is selected out of every pair; in a
+ * group whose P is NaN every w_n is NaN and so is every value of the group (its gradients at unobserved coordinates stay exact
+ * zeros), and no other group is touched.  One live sample under fair gives D' = 0 and 0 / 0 = NaN, as the weighted variance does.
+ * Summation order, a function of (N, V, fair) only: the squared distances, sqrtf and the tile / lane / butterfly / wave order of
+ * snsde_sample_energy; the term of a pair is fl(fl(w_i w_j) r_ij) with w = 1 for the observation, dead and masked pairs entering
+ * as +0; then energy = A - B / D' (fair) or A - B.  Without logw: A / N - B / (N D), the arithmetic of snsde_sample_energy.
+ * No atomics, no workspace, no dependence on the grid or the pointer alignment; enqueue-only, capturable; every element of energy
+ * is written and no other byte.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target or energy NULL.
+ * SNSDE_ERR_DIMS: a non-positive extent, N > 256, fair with N < 2, an element count beyond 63 bits.  SNSDE_ERR_LDS: the device
+ * refuses the chunk, the weight rows and - backward - the plane (156 160 bytes at N = 256).  Every check precedes the launch. */
+SNSDE_API int snsde_sample_energy_weighted(const float* ys, const float* target, const float* logw, const float* mask, int64_t outer,
+                                           int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t fair, int32_t path,
+                                           int32_t nan_missing, float* energy, void* hip_stream);
+
+/* Adjoint of snsde_sample_energy_weighted with the weights fixed: with grad_energy = g, u(d) = d / ||d|| over the observed
+ * coordinates and u(0) = 0,
+ *     grad_ys[n]  = g * ( w_n u(x_n - y) - sum_{j != n} w_n w_j u(x_n - x_j) / D )        live n, observed coordinates
+ *     grad_target = -g * sum_n w_n u(x_n - y)                                             (optional, NULL = not wanted)
+ * (without logw: 1 / N and 1 / (N D), the adjoint of snsde_sample_energy).  The distances are formed again; the plane entry of a
+ * pair is (1 / r, or 0 where r == 0) * c, c = fl(w_i w_j) with the observation and fl(fl(w_i w_j) * (-1 / D)) among samples, 0 where
+ * a row is dead; the second pass stages the rows of a dead sample as zeros and gives row n of a column g * sum_j c_nj (x_nv - x_jv),
+ * j ascending over the N + 1 rows, one fmaf each.  The writer selects an exact zero for every row of an unobserved column and for
+ * the whole row of a dead sample, whatever ys, target and g hold there.  One live sample under fair: NaN, the formula's 0 / 0.
+ * Every element of grad_ys (and of grad_target) is written and no other byte.  The same errors and guarantees; SNSDE_ERR_NULL:
+ * grad_energy, ys, target or grad_ys NULL. */
+SNSDE_API int snsde_sample_energy_weighted_backward(const float* grad_energy, const float* ys, const float* target, const float* logw,
+                                                    const float* mask, int64_t outer, int32_t members, int64_t groups, int32_t samples,
+                                                    int32_t width, int32_t fair, int32_t path, int32_t nan_missing, float* grad_ys,
+                                                    float* grad_target, void* hip_stream);
+
 /* Masked Gaussian log-likelihood of sample paths and its importance-weighted (IWAE) bound: the training objective for data with
  * missing entries.  ys viewed as (outer, M, G, S, W) exactly as for snsde_sample_energy with path != 0: pooled sample
  * n = m S + s, N = M S; vector component v = o W + w, V = outer W; addressed in place (no permuted copy).  target y and mask m

@@ -118,7 +118,8 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_sample_loglik_backward', 'snsde_sample_class', 'snsde_sample_class_backward', 'snsde_sample_resample',
            'snsde_sample_resample_backward',
            'snsde_sample_stats_weighted', 'snsde_sample_stats_weighted_backward', 'snsde_sample_crps_weighted',
-           'snsde_sample_crps_weighted_backward', 'snsde_sample_quantiles_weighted', 'snsde_sample_quantiles_weighted_backward')
+           'snsde_sample_crps_weighted_backward', 'snsde_sample_quantiles_weighted', 'snsde_sample_quantiles_weighted_backward',
+           'snsde_sample_energy_weighted', 'snsde_sample_energy_weighted_backward')
 
 
 MAX_AFFINE_JOBS = 12
@@ -235,6 +236,10 @@ def lib():
     levels = [C.c_int32, C.POINTER(C.c_float)]
     L.snsde_sample_quantiles_weighted.argtypes = [C.c_void_p] * 2 + dims + levels + [C.c_void_p] * 2
     L.snsde_sample_quantiles_weighted_backward.argtypes = [C.c_void_p] * 3 + dims + levels + [C.c_void_p] * 2
+    # (ys, target, logw, mask, dims, fair, path, nan_missing, energy, stream) /
+    # (grad_energy, ys, target, logw, mask, dims, fair, path, nan_missing, grad_ys, grad_target, stream)
+    L.snsde_sample_energy_weighted.argtypes = [C.c_void_p] * 4 + dims + [C.c_int32] * 3 + [C.c_void_p] * 2
+    L.snsde_sample_energy_weighted_backward.argtypes = [C.c_void_p] * 5 + dims + [C.c_int32] * 3 + [C.c_void_p] * 3
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

@@ -1447,7 +1447,7 @@ def _energy_dims(ys, samples, target, fair, members, path):
     return S, M, lead, G, W, N, ((G,) if path else lead + (G,))
 
 
-def sample_energy(ys, samples, target, fair=True, members=1, path=False):
+def sample_energy(ys, samples, target, fair=True, members=1, path=False, log_weight=None, mask=None):
     """Energy score of the sample paths of a solve against an observation: the multivariate generalisation of the CRPS, which
     also sees the dependence between the components of the vector.  ys, samples, members and target (..., B, W) as for
     `sample_crps`; the pooled samples x_n of an input row are vectors: of the W components of the last axis (path=False: the
@@ -1457,7 +1457,20 @@ def sample_energy(ys, samples, target, fair=True, members=1, path=False):
     every distance from differences (never a Gram matrix).  Differentiable in ys and target, d||d|| = d / ||d|| and 0 at d = 0.
     CUDA float32 inputs with N <= 256: one launch of snsde_sample_energy (no (.., N, N) intermediate, deterministic, capturable)
     - inside an autograd node whose backward is snsde_sample_energy_backward when an input requires grad.  Other tensors:
-    `sample_energy_tensor_ops`."""
+    `sample_energy_tensor_ops`.
+    log_weight (..., B, N) - under path (B, N): one log-weight per pooled path of a score - scores the weighted sample set: with
+    w = softmax(log_weight) and D = D' = sum w_n (1 - w_n) (fair) or 1,
+        energy = sum_n w_n ||x_n - y|| - sum_{n<j} w_n w_j ||x_n - x_j|| / D
+    with the dead samples and unusable weight sets of `normalised_weights`; the weights carry no gradient.  mask marks the
+    observed coordinates of a target with gaps: a tensor of the shape of target (bool, or a number: observed where != 0 - a
+    fractional value does not weigh), or 'nan' for "a NaN target is a gap".  Every norm is then taken over the observed
+    coordinates only; an unobserved one is selected out, never multiplied: NaN / Inf there in ys or target reaches nothing, and
+    the gradients there are exact zeros.  A score with nothing observed is 0.  mask=None is the call as it always was: a NaN
+    target poisons its score.  Either argument routes CUDA float32 inputs with N <= 256 to snsde_sample_energy_weighted / _backward
+    and everything else to `sample_energy_weighted_tensor_ops`.  A particle filter's result r scores as
+        sample_energy(filter_particles(r.ys, r.ancestor, S), S, target, log_weight=r.log_weight)"""
+    if log_weight is not None or mask is not None:
+        return _sample_energy_weighted(ys, samples, target, fair, members, path, log_weight, mask)
     fair, path = bool(fair), bool(path)
     S, M, lead, G, W, N, out_shape = _energy_dims(ys, samples, target, fair, members, path)
     if _score_native(ys, N, target):
@@ -2517,6 +2530,147 @@ class _SampleQuantilesWeighted(torch.autograd.Function):
     def backward(ctx, grad_out):
         ys, lw = ctx.saved_tensors
         return sample_quantiles_weighted_backward(grad_out.to(torch.float32).contiguous(), ys, lw, ctx.S, ctx.qs, ctx.M), None, None, None, None
+
+
+def _energy_weighted_args(ys, samples, target, fair, members, path, log_weight, mask):
+    """(S, M, lead, G, W, N, result shape, mask tensor or None, nan_missing) of a weighted / masked energy score; its argument
+    errors.  mask='nan': no tensor, nan_missing True.  A mask tensor of another dtype than ys becomes (mask != 0) in ys' dtype."""
+    S, M, lead, G, W, N, out_shape = _energy_dims(ys, samples, target, fair, members, path)
+    if log_weight is not None:
+        _check_log_weight(log_weight, ys, (G, N) if path else lead + (G, N))
+    nan_missing = False
+    if isinstance(mask, str):
+        if mask != 'nan':
+            raise ValueError(f"mask must be None, 'nan' (a NaN target is a gap) or a tensor of the shape of target, got {mask!r}")
+        mask, nan_missing = None, True
+    elif mask is not None:
+        if not isinstance(mask, torch.Tensor) or tuple(mask.shape) != tuple(target.shape):
+            raise ValueError(f'mask has shape {tuple(getattr(mask, "shape", ()))}, expected {tuple(target.shape)} (the shape of target)')
+        if mask.device != ys.device:
+            raise ValueError(f'mask is on {mask.device}, ys on {ys.device}')
+        mask = mask.detach()
+        if mask.dtype != ys.dtype:
+            mask = (mask != 0).to(ys.dtype)
+    return S, M, lead, G, W, N, out_shape, mask, nan_missing
+
+
+def _sample_energy_weighted(ys, samples, target, fair, members, path, log_weight, mask):
+    fair, path = bool(fair), bool(path)
+    S, M, lead, G, W, N, out_shape, mk, nan_missing = _energy_weighted_args(ys, samples, target, fair, members, path, log_weight, mask)
+    others = (target,) + (() if log_weight is None else (log_weight,)) + (() if mk is None else (mk,))
+    if _score_native(ys, N, *others):
+        lw = None if log_weight is None else log_weight.detach()
+        if (ys.requires_grad or target.requires_grad) and torch.is_grad_enabled():
+            return _SampleEnergyWeighted.apply(ys, target, lw, mk, S, M, fair, path, nan_missing)
+        return _sample_energy_weighted_launch(ys.contiguous(), target.contiguous(), None if lw is None else lw.contiguous(),
+                                              None if mk is None else mk.contiguous(), S, M, fair, path, nan_missing)
+    return sample_energy_weighted_tensor_ops(ys, S, target, log_weight, 'nan' if nan_missing else mk, fair, M, path)
+
+
+def sample_energy_weighted_tensor_ops(ys, samples, target, log_weight=None, mask=None, fair=True, members=1, path=False):
+    """`sample_energy(..., log_weight=, mask=)` stated in tensor ops (any device and floating dtype; autograd differentiates it in
+    ys and target).  torch.where on the mask puts exact zeros in the unobserved coordinates of every sample and of the
+    observation - selected, never multiplied, so NaN / Inf there reaches no value and the gradient there is an exact zero - and,
+    with (w, live, D') = normalised_weights(log_weight), in the rows of the dead samples; then, from direct differences
+    (torch.linalg.vector_norm, and torch.cdist in its direct-difference mode, sliced as in `sample_energy_tensor_ops`),
+        energy = sum_n w_n ||x_n - y|| - sum_{n,j} w_n w_j ||x_n - x_j|| / (2 D),  D = D' (fair) or 1
+    the dead pairs selected out; without log_weight w = 1 / N and D = (N - 1) / N or 1, written as / N and / (2 N D)."""
+    fair, path = bool(fair), bool(path)
+    S, M, lead, G, W, N, out_shape, mk, nan_missing = _energy_weighted_args(ys, samples, target, fair, members, path, log_weight, mask)
+    if ys.numel() == 0:
+        return ys.new_zeros(out_shape)
+    x, y = _pooled(ys, S, M, lead, G, W), target.to(ys.dtype)            # (..., G, N, W), (..., G, W)
+    obs = ~torch.isnan(y.detach()) if nan_missing else (None if mk is None else mk != 0)
+    if path:      # every leading axis joins the vector: (G, N, outer W)
+        O = _outer(lead)
+        x = x.reshape(O, G, N, W).permute(1, 2, 0, 3).reshape(G, N, O * W)
+        y = y.reshape(O, G, W).permute(1, 0, 2).reshape(G, O * W)
+        obs = None if obs is None else obs.reshape(O, G, W).permute(1, 0, 2).reshape(G, O * W)
+    zero = torch.zeros((), dtype=x.dtype, device=x.device)
+    if obs is not None:
+        x, y = torch.where(obs.unsqueeze(-2), x, zero), torch.where(obs, y, zero)
+    if log_weight is None:
+        w = pair = None
+    else:
+        w, live, Dp = normalised_weights(log_weight, x.dtype)
+        x = torch.where(live.unsqueeze(-1), x, zero)
+        pair = torch.where(live.unsqueeze(-1) & live.unsqueeze(-2), w.unsqueeze(-1) * w.unsqueeze(-2), zero)      # (..., G, N, N)
+    rn = torch.linalg.vector_norm(x - y.unsqueeze(-2), dim=-1)           # (..., G, N)
+    a = rn.sum(dim=-1) / N if w is None else torch.where(live, w * rn, zero).sum(dim=-1)
+    flat = x.reshape((-1, N, x.shape[-1]))
+    fpair = None if pair is None else pair.reshape((-1, N, N))
+    step = max(1, _CDIST_MAX_PLANE // (N * N))
+    sums = []
+    for i in range(0, flat.shape[0], step):
+        plane = torch.cdist(flat[i:i + step], flat[i:i + step], compute_mode='donot_use_mm_for_euclid_dist')
+        sums.append((plane if fpair is None else fpair[i:i + step] * plane).sum(dim=(-2, -1)))
+    b = (sums[0] if len(sums) == 1 else torch.cat(sums)).reshape(a.shape)
+    if w is None:
+        return a - b / (2 * N * (N - 1 if fair else N))
+    return a - (b / (2 * Dp) if fair else b / 2)
+
+
+def _sample_energy_weighted_launch(ys, target, logw, mask, S, M, fair, path, nan_missing):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    energy = torch.empty((G,) if path else lead + (G,), device=ys.device, dtype=torch.float32)
+    _lib.check(_lib.lib().snsde_sample_energy_weighted(_ptr(ys), _ptr(target), _ptr(logw), _ptr(mask), _outer(lead), M, G, S, W, int(fair),
+                                                       int(path), int(nan_missing), _ptr(energy),
+                                                       C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_energy_weighted')
+    return energy
+
+
+def sample_energy_weighted_backward(grad_energy, ys, target, samples, log_weight=None, mask=None, fair=True, members=1, path=False,
+                                    grad_target=True):
+    """(dL/d ys, dL/d target) of `sample_energy(..., log_weight=, mask=)` from dL/d energy, the weights fixed: one launch of
+    snsde_sample_energy_weighted_backward (dL/d target None when grad_target=False).  Contiguous float32 CUDA tensors, ys
+    (..., B S, W) or (..., M, B S, W), target (..., B, W), grad_energy (..., B) or, under path, (B,); log_weight (..., B, N) or,
+    under path, (B, N), or None; mask a float32 tensor of the shape of target, 'nan', or None."""
+    S, M, lead, G, W = _score_dims(ys, samples, members)
+    path, nan_missing = bool(path), isinstance(mask, str) and mask == 'nan'
+    if isinstance(mask, str) and not nan_missing:
+        raise ValueError(f"mask must be None, 'nan' or a tensor of the shape of target, got {mask!r}")
+    mask = None if nan_missing else mask
+    _check_f32('ys', ys)
+    _check_f32('target', target, lead + (G, W))
+    _check_f32('grad_energy', grad_energy, (G,) if path else lead + (G,))
+    if log_weight is not None:
+        _check_f32('log_weight', log_weight, (G, M * S) if path else lead + (G, M * S))
+    if mask is not None:
+        _check_f32('mask', mask, lead + (G, W))
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    _lib.check(_lib.lib().snsde_sample_energy_weighted_backward(_ptr(grad_energy), _ptr(ys), _ptr(target), _ptr(log_weight), _ptr(mask),
+                                                                _outer(lead), M, G, S, W, int(bool(fair)), int(path), int(nan_missing),
+                                                                _ptr(gys), _ptr(gt),
+                                                                C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_energy_weighted_backward')
+    return gys, gt
+
+
+class _SampleEnergyWeighted(torch.autograd.Function):
+    """The weighted / masked sample_energy of CUDA float32 tensors of which one requires grad: snsde_sample_energy_weighted and its
+    _backward."""
+
+    @staticmethod
+    def forward(ctx, ys, target, logw, mask, S, M, fair, path, nan_missing):
+        ysc, tc = ys.detach().contiguous(), target.detach().contiguous()
+        lw, mk = None if logw is None else logw.contiguous(), None if mask is None else mask.contiguous()
+        ctx.S, ctx.M, ctx.fair, ctx.path, ctx.nan_missing = S, M, fair, path, nan_missing
+        ctx.has = (lw is not None, mk is not None)
+        ctx.save_for_backward(ysc, tc, *(t for t in (lw, mk) if t is not None))
+        return _sample_energy_weighted_launch(ysc, tc, lw, mk, S, M, fair, path, nan_missing)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_energy):
+        ys, target, *rest = ctx.saved_tensors
+        lw = rest.pop(0) if ctx.has[0] else None
+        mk = rest.pop(0) if ctx.has[1] else None
+        gys, gt = sample_energy_weighted_backward(grad_energy.to(torch.float32).contiguous(), ys, target, ctx.S, lw,
+                                                  'nan' if ctx.nan_missing else mk, ctx.fair, ctx.M, ctx.path,
+                                                  grad_target=ctx.needs_input_grad[1])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, None, None, None, None, None, None
 
 
 def filter_particles(ys, ancestor, samples):

@@ -78,25 +78,34 @@ def crps_loss(samples, fair=True, members=1):
     return loss_fn
 
 
-def energy_loss(samples, fair=True, members=1):
+def energy_loss(samples, fair=True, members=1, masked=False):
     """loss_fn(pred, true) for `train_loop` / `GraphedStep` / `evaluate_metrics`: the mean energy score (engine.sample_energy)
     of a model solved with options={'samples': S} - the multivariate score, which also judges the dependence between the
     components of a forecast.  pred and true as for `crps_loss`: (B S, ...) or (M, B S, ...), and (B, ...).  Trailing axes are
     flattened into the vector, so a wrapper that returns (B S, T, out) is scored on the whole forecast path; the result is the
-    mean over the rows of true."""
+    mean over the rows of true.  masked=True scores a target with gaps, `iwae_loss`'s convention: a NaN in true marks a missing
+    entry, and data that carries its own mask is passed as true = (values, mask); the norms then run over the observed entries
+    of a row only, and a row with nothing observed adds 0."""
     from . import engine
     S = engine.check_samples(samples)
 
     lead = 1 if members > 1 else 0      # (an Ensemble's leading member axis)
 
     def loss_fn(pred_y, true_y):
+        mask = None
+        if masked:
+            true_y, mask = true_y if isinstance(true_y, (tuple, list)) else (true_y, None)
         want = ((members,) if lead else ()) + (S * true_y.shape[0],) if true_y.dim() else None
         if want is None or tuple(pred_y.shape[:lead + 1]) != want:
             raise ValueError(f'energy_loss(samples={S}, members={members}): pred has shape {tuple(pred_y.shape)} for a target of shape '
                              f'{tuple(true_y.shape)}: expected {"(members, " if lead else "("}samples x target rows, ...)')
+        if mask is not None and tuple(mask.shape) != tuple(true_y.shape):
+            raise ValueError(f'energy_loss: the mask has shape {tuple(mask.shape)} for a target of shape {tuple(true_y.shape)}')
         pred = pred_y.reshape(want + (-1,))
         true = true_y.reshape(true_y.shape[0], -1).to(pred.dtype)
-        return engine.sample_energy(pred, S, true, fair=fair, members=members).mean()
+        if not masked:
+            return engine.sample_energy(pred, S, true, fair=fair, members=members).mean()
+        return engine.sample_energy(pred, S, true, fair=fair, members=members, mask='nan' if mask is None else mask.reshape(true.shape)).mean()
     return loss_fn
 
 
