@@ -943,10 +943,10 @@ SNSDE_API int snsde_sample_energy_backward(const float* grad_energy, const float
                                            int64_t groups, int32_t samples, int32_t width, int32_t fair, int32_t path, float* grad_ys,
                                            float* grad_target, void* hip_stream);
 
-/* Energy score of a WEIGHTED and / or PARTIALLY OBSERVED sample set: a sibling kernel of snsde_sample_energy
- * (csrc/snsde_energy_weighted.hip); the unweighted, unmasked call keeps its kernels and its bits.  Layout, pooling (n = m S + s,
- * N = M S <= 256), `path` and `fair` as for snsde_sample_energy.  Weights and mask are compile-time variants of one kernel; a call
- * with neither runs the masked variant with every coordinate observed.
+/* Energy score of a WEIGHTED and / or PARTIALLY OBSERVED sample set: the kernel of snsde_sample_energy
+ * (csrc/snsde_energy.hip), of which weights and mask are compile-time variants; the unweighted, unmasked call keeps its bits.
+ * Layout, pooling (n = m S + s, N = M S <= 256), `path` and `fair` as for snsde_sample_energy.  A call with neither weights nor
+ * mask runs the variant snsde_sample_energy runs, and gives its bits.
  * Mask.  mask (NULL = none) has the shape of target, (outer, groups, width); a coordinate is observed where mask != 0 - the value
  * is a flag, a fractional value does NOT weigh.  With mask NULL and nan_missing != 0 a coordinate is observed where target is not
  * NaN.  Both are decided inside the kernel by the thread that stages the column: no extra launch, no mask tensor made from isnan.

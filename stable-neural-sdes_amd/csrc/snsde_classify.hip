@@ -36,11 +36,11 @@
 
 #include "snsde.h"
 #include "snsde_internal.h"
+#include "snsde_sample_set.h"      // MAX_N, pooled_row, pooled_dims_ok
 
 namespace {
 
 constexpr int TH = 256;             // threads of a workgroup
-constexpr int MAX_N = 256;          // pooled samples (engine.SCORE_MAX_POOLED)
 constexpr int SLAB_MAX = 24576;     // floats of a pack's slab staged in LDS
 constexpr int RS_MAX = 16;          // row parts of the column sums
 constexpr int FIXED = 7 * TH + 8;   // floats of LDS in front of the slab: m, ls, a, w, and the part sums p, q, e; 8 wave sums
@@ -57,8 +57,7 @@ __device__ __forceinline__ int64_t group_base(int64_t gi, const CDims& d) {
 
 __device__ __forceinline__ int64_t row_of(int n, const CDims& d) {
     if (d.S == d.N) return (int64_t)n * d.C;      // (uniform: one member)
-    const int m = n / d.S, s = n - m * d.S;
-    return m * d.mstride + (int64_t)s * d.C;
+    return pooled_row(n, d.S, d.C, d.mstride);
 }
 
 __device__ __forceinline__ float team_sum(float x, int lanes) {
@@ -380,12 +379,8 @@ int shift_of(int p) {
 
 // (outer, M, G, S, C): positive, the element count fits 63 bits, N = M S within the cap, binary only at width 1
 bool class_dims(int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t binary, CDims* d) {
-    if (outer <= 0 || members <= 0 || groups <= 0 || samples <= 0 || width <= 0) return false;
-    if ((int64_t)members * samples > MAX_N) return false;
-    if (binary && width != 1) return false;
-    if (groups > INT64_MAX / samples / width) return false;
-    const int64_t per = groups * samples * width;
-    if (outer > INT64_MAX / members / per) return false;
+    int64_t per;
+    if (!pooled_dims_ok(outer, members, groups, samples, width, &per) || (binary && width != 1)) return false;
     d->G = groups; d->OG = outer * groups; d->mstride = per; d->ostride = members * per;
     d->S = samples; d->C = width; d->N = members * samples;
     int L = 1;

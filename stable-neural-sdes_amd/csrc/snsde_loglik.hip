@@ -28,11 +28,11 @@
 
 #include "snsde.h"
 #include "snsde_internal.h"
+#include "snsde_sample_set.h"      // MAX_N, row_of_short, pooled_dims_ok
 
 namespace {
 
 constexpr int TH = 256;             // threads of a workgroup
-constexpr int MAX_N = 256;          // pooled samples (engine.SCORE_MAX_POOLED)
 constexpr int MAX_L = 32;           // lanes per sample
 constexpr float LOG_2PI = 1.8378770664093453f;
 
@@ -64,19 +64,14 @@ __device__ __forceinline__ Col col_of(int64_t g, int64_t v, const LDims& d) {
     return c;
 }
 
-__device__ __forceinline__ int64_t row_of(int n, const LDims& d) {
-    if (d.S == d.N) return (int64_t)n * d.W;      // (uniform: one member)
-    const int m = n / d.S, s = n - m * d.S;
-    return m * d.mstride + (int64_t)s * d.W;
-}
-
-__device__ __forceinline__ float wave_sum(float x) {
+// The butterflies of this file run xor 1, 2, .., 32 (the summation order above), those of snsde_sample_set.h 32, .., 1: other bits
+__device__ __forceinline__ float wave_sum_up(float x) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) x += __shfl_xor(x, m, 64);
     return x;
 }
 
-__device__ __forceinline__ float wave_max(float x) {
+__device__ __forceinline__ float wave_max_up(float x) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) x = fmaxf(x, __shfl_xor(x, m, 64));
     return x;
@@ -140,7 +135,7 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_kernel(const float* __
             }
 #pragma unroll UNR
             for (int n = r0; n < r1; ++n) {
-                const int64_t off = row_of(n, d);
+                const int64_t off = row_of_short(n, d);
 #pragma unroll
                 for (int i = 0; i < CPT; ++i) {
                     const float dd = obs[i] ? y[i] - ys[cl[i].ys + off] : 0.0f;
@@ -188,7 +183,7 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_kernel(const float* __
             logpx[at] = lp;
             abuf[sn] = logw ? lp + logw[at] : lp;
         }
-        sq = wave_sum(sq);
+        sq = wave_sum_up(sq);
         if (lane == 0) red[wave] = sq;
         __syncthreads();
         if (wave == 0) {
@@ -199,7 +194,7 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_kernel(const float* __
                 bad = bad || a != a;
                 mx = fmaxf(mx, a);
             }
-            mx = wave_max(mx);
+            mx = wave_max_up(mx);
             bad = __any(bad);
             float r;
             if (bad) {
@@ -209,7 +204,7 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_kernel(const float* __
             } else {
                 float sum = 0.0f;
                 for (int n = lane; n < d.N; n += 64) sum += expf(abuf[n] - mx);
-                sum = wave_sum(sum);
+                sum = wave_sum_up(sum);
                 r = mx + logf(sum) - logf(fN);
             }
             if (lane == 0) {
@@ -240,13 +235,13 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_backward_kernel(const 
         float a = -INFINITY, p = 0.0f;
         if (gbound) {      // (uniform: the softmax is needed only by grad_bound)
             if (have) a = logw ? logpx[at] + logw[at] : logpx[at];
-            float mx = wave_max(a);
+            float mx = wave_max_up(a);
             __syncthreads();      // (red of the last unit has been read)
             if (lane == 0) red[wave] = mx;
             __syncthreads();
             mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
             const float ex = have ? expf(a - mx) : 0.0f;
-            float sum = wave_sum(ex);
+            float sum = wave_sum_up(ex);
             __syncthreads();
             if (lane == 0) red[wave] = sum;
             __syncthreads();
@@ -276,7 +271,7 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_backward_kernel(const 
                 float s = 0.0f;
 #pragma unroll 8
                 for (int n = 0; n < d.N; ++n) {
-                    const int64_t r = row_of(n, d);
+                    const int64_t r = row_of_short(n, d);
                     const float gr = (cs[n] * m) * (y - src[r]);
                     dst[r] = gr;
                     s += gr;
@@ -284,20 +279,16 @@ __global__ void __launch_bounds__(TH) snsde_sample_loglik_backward_kernel(const 
                 if (gtarget) gtarget[cl.tg] = -s;
             } else {
                 float* dst = gys + cl.ys;
-                for (int n = 0; n < d.N; ++n) dst[row_of(n, d)] = 0.0f;
+                for (int n = 0; n < d.N; ++n) dst[row_of_short(n, d)] = 0.0f;
                 if (gtarget) gtarget[cl.tg] = 0.0f;
             }
         }
     }
 }
 
-// (outer, M, G, S, W): positive, the element count fits 63 bits, N = M S within the cap (as snsde_energy.hip: energy_dims)
 bool loglik_dims(int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width, int32_t norm, LDims* d) {
-    if (outer <= 0 || members <= 0 || groups <= 0 || samples <= 0 || width <= 0) return false;
-    if ((int64_t)members * samples > MAX_N) return false;
-    if (groups > INT64_MAX / samples / width) return false;
-    const int64_t per = groups * samples * width;
-    if (outer > INT64_MAX / members / per) return false;
+    int64_t per;
+    if (!pooled_dims_ok(outer, members, groups, samples, width, &per)) return false;
     d->G = groups; d->mstride = per; d->ostride = members * per;
     d->S = samples; d->W = width; d->N = members * samples; d->norm = norm ? 1 : 0;
     d->V = outer * width;

@@ -24,11 +24,12 @@
 
 #include "snsde.h"
 #include "snsde_internal.h"
+#include "snsde_sample_set.h"      // MAX_N
 
 namespace {
 
 constexpr int TH = 256;             // threads of a workgroup
-constexpr int MAX_S = 256;          // particles of a group (engine.SCORE_MAX_POOLED)
+constexpr int MAX_S = MAX_N;        // particles of a group
 constexpr int SLAB_MAX = 4096;      // floats of state a pack moves at most, where it holds more than one group
 constexpr int GRID_MAX = 2048;      // workgroups; the kernel strides over the packs beyond
 

@@ -14,57 +14,20 @@
 #include <stdint.h>
 
 #include "snsde.h"
+#include "snsde_sample_set.h"      // the column tiles (ST, LANES, WAVES, Dims, Tile, tile_of, row_of, stage, dims_ok), MAX_N (x 256 B = 64 KB of LDS), sign0
 
 namespace {
 
-constexpr int ST = 256;             // threads per block
-constexpr int LANES = 64;           // columns of a tile
-constexpr int WAVES = ST / LANES;   // waves sharing a tile
 constexpr int RB = 4;               // x_n held in registers per walk over the slab
-constexpr int MAX_N = 256;          // pooled samples: MAX_N * 256 B = 64 KB of LDS
 constexpr int MAX_Q = 8;            // quantiles per call (their k / frac travel in the kernel's argument struct)
 constexpr int XROWS = MAX_Q * 2;    // rows of the exchange area (MAX_Q * 2 * 64 floats), which aliases the slab
 constexpr int MIN_ROWS = XROWS + WAVES;   // slab rows allocated at least: the exchange area and one row of NaN flags per wave
-
-struct Dims {
-    int64_t outer, G, mstride, wtiles, tiles;      // mstride = G S W; tiles = outer G wtiles, wtiles = ceil(W / 64)
-    int32_t M, S, W, N;
-};
 
 struct QArgs {
     int32_t n_q;
     int32_t k[MAX_Q];
     float frac[MAX_Q];
 };
-
-struct Tile {
-    int64_t og;        // o G + g
-    int64_t base;      // float offset of x_0 of this lane's column
-    int64_t out;       // float offset of this lane's element in an (outer, G, W) plane
-    bool live;         // column < W (lanes of the tail tile are guarded, not clamped)
-};
-
-__device__ __forceinline__ Tile tile_of(int64_t t, const Dims& d, int lane) {
-    Tile r;
-    r.og = t / d.wtiles;
-    const int col = (int)(t - r.og * d.wtiles) * LANES + lane;
-    const int64_t o = r.og / d.G, g = r.og - o * d.G;
-    r.live = col < d.W;
-    r.base = o * d.M * d.mstride + (g * d.S) * (int64_t)d.W + col;
-    r.out = r.og * d.W + col;
-    return r;
-}
-
-// float offset of x_n from x_0 in this lane's column
-__device__ __forceinline__ int64_t row_of(int n, const Dims& d) {
-    const int m = n / d.S, s = n - m * d.S;
-    return m * d.mstride + (int64_t)s * d.W;
-}
-
-// the waves of the block stage the slab: wave k rows k, k + 4, ..; dead lanes hold zeros
-__device__ __forceinline__ void stage(const float* __restrict__ ys, const Tile& t, const Dims& d, float* slab, int wave, int lane) {
-    for (int n = wave; n < d.N; n += WAVES) slab[n * LANES + lane] = t.live ? ys[t.base + row_of(n, d)] : 0.0f;
-}
 
 // strict counts of RB samples against the whole column: lt[r] = #{j : x_j < xn[r]}, gt[r] = #{j : x_j > xn[r]}
 __device__ __forceinline__ void strict_counts(const float* col, int N, const float (&xn)[RB], int (&lt)[RB], int (&gt)[RB]) {
@@ -95,8 +58,6 @@ __device__ __forceinline__ void perm_ranks(const float* col, int N, const float 
 #pragma unroll
     for (int r = 0; r < RB; ++r) rk[r] = xn[r] != xn[r] ? -1 : rk[r];
 }
-
-__device__ __forceinline__ float sign0(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
 
 // crps = (sum |d_n|) / N - (sum c_n d_n) / (N D);  rank = #{x_n < y}, ties = #{x_n == y}
 __global__ void __launch_bounds__(ST) snsde_sample_crps_kernel(const float* __restrict__ ys, const float* __restrict__ target, Dims d, int32_t D,
@@ -310,20 +271,6 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_backward_kernel(con
             }
         }
     }
-}
-
-// (outer, M, G, S, W): positive, the element count fits 63 bits, N = M S within the slab
-bool dims_ok(int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width, Dims* d) {
-    if (outer <= 0 || members <= 0 || groups <= 0 || samples <= 0 || width <= 0) return false;
-    if ((int64_t)members * samples > MAX_N) return false;
-    if (groups > INT64_MAX / samples / width) return false;
-    const int64_t per = groups * samples * width;
-    if (outer > INT64_MAX / members / per) return false;
-    d->outer = outer; d->G = groups; d->mstride = per;
-    d->M = members; d->S = samples; d->W = width; d->N = members * samples;
-    d->wtiles = ((int64_t)width + LANES - 1) / LANES;
-    d->tiles = outer * groups * d->wtiles;      // (<= outer G W)
-    return true;
 }
 
 bool quantiles_ok(int32_t N, int32_t n_q, const int32_t* k, const float* frac, QArgs* qa) {

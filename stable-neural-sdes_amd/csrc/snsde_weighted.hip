@@ -2,7 +2,7 @@
 // fixed (include/snsde.h: snsde_sample_stats_weighted, snsde_sample_crps_weighted, snsde_sample_quantiles_weighted and their
 // _backward).  ys is (outer, M, G, S, W) as in snsde_scores.hip - the pooled set of an output element (o, g, w) is x_n, n = m S + s,
 // N = M S <= 256 - and logw is (outer, G, N): one log-weight per pooled path, shared by the W columns of the group.
-// Weights.  One wave normalises a group's weights on chip before any sample is read (normalise(), below): lane l holds a_n for
+// Weights.  One wave normalises a group's weights on chip before any sample is read (normalise(), snsde_sample_set.h): lane l holds a_n for
 // n = l, 64 + l, 128 + l, 192 + l (-Inf past N), mx by fmaxf, e_n = expf(a_n - mx), P and D' = sum w_n (1 - w_n) over one fixed
 // 256-leaf tree (zeros past N), w_n = e_n / P.  w_n and a live mark (0, NaN where dead) go to two 1 KB LDS rows that every lane then reads by broadcast.
 // A sample is dead where e_n == 0 and P is a number: it is selected out by a branch that is uniform over the workgroup, never
@@ -19,110 +19,19 @@
 
 #include "snsde.h"
 #include "snsde_internal.h"
+#include "snsde_sample_set.h"      // the column tiles (ST, LANES, WAVES, Dims, Tile, tile_of, row_of, stage, dims_ok), sign0, Norm, normalise
 
 namespace {
 
-constexpr int ST = 256;             // threads per block
-constexpr int LANES = 64;           // columns of a tile
-constexpr int WAVES = ST / LANES;   // waves of a block
 constexpr int RB = 4;               // x_n held in registers per walk over the slab
-constexpr int MAX_N = 256;          // pooled samples
 constexpr int MAX_Q = 8;            // quantile levels per call
 constexpr int SUM_ROWS = 4 * WAVES; // slab rows the CRPS kernels reuse for the quarter sums
 constexpr int META = 64;            // floats after the two weight rows: D', P, F
-
-struct Dims {
-    int64_t outer, G, mstride, wtiles, tiles;      // mstride = G S W; tiles = outer G wtiles, wtiles = ceil(W / 64)
-    int32_t M, S, W, N;
-};
 
 struct QLevels {
     int32_t n_q;
     float q[MAX_Q];
 };
-
-struct Tile {
-    int64_t og;        // o G + g
-    int64_t base;      // float offset of x_0 of this lane's column
-    int64_t out;       // float offset of this lane's element in an (outer, G, W) plane
-    bool live;         // column < W
-};
-
-__device__ __forceinline__ Tile tile_of(int64_t t, const Dims& d, int lane) {
-    Tile r;
-    r.og = t / d.wtiles;
-    const int col = (int)(t - r.og * d.wtiles) * LANES + lane;
-    const int64_t o = r.og / d.G, g = r.og - o * d.G;
-    r.live = col < d.W;
-    r.base = o * d.M * d.mstride + (g * d.S) * (int64_t)d.W + col;
-    r.out = r.og * d.W + col;
-    return r;
-}
-
-__device__ __forceinline__ int64_t row_of(int n, const Dims& d) {
-    const int m = n / d.S, s = n - m * d.S;
-    return m * d.mstride + (int64_t)s * d.W;
-}
-
-__device__ __forceinline__ void stage(const float* __restrict__ ys, const Tile& t, const Dims& d, float* slab, int wave, int lane) {
-    for (int n = wave; n < d.N; n += WAVES) slab[n * LANES + lane] = t.live ? ys[t.base + row_of(n, d)] : 0.0f;
-}
-
-__device__ __forceinline__ float sign0(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
-
-// v_l <- v_l + v_(l xor s), s = 32, 16, 8, 4, 2, 1: every lane ends with the same bits (the addition commutes)
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) v = __fadd_rn(v, __shfl_xor(v, s, LANES));
-    return v;
-}
-
-struct Norm {
-    float Dp;      // D' = sum_n w_n (1 - w_n)
-    float P;       // sum_n e_n (NaN: an unusable weight set)
-    int F;         // live samples
-};
-
-// One whole wave normalises the N log-weights at `a` into wrow (w_n) and lrow (0 live / NaN dead: added to a sample it
-// leaves a live one as it is and makes a dead one compare with nobody); every lane returns the same Norm.
-//   mx = fmaxf over all a_n;  e_n = expf(a_n - mx), the difference rounded once
-//   P  = ((T_0 + T_1) + T_2) + T_3,  T_i = the butterfly wave_sum of e_(64 i + l) over the lanes l, zeros past N
-//   w_n = e_n / P;  D' by the same tree over t_n = w_n (1 - w_n), each of the two operations rounded once
-__device__ __forceinline__ Norm normalise(const float* __restrict__ a, int N, float* wrow, float* lrow, int lane) {
-    float av[4], e[4];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = i * LANES + lane;
-        av[i] = n < N ? a[n] : -INFINITY;
-        mx = fmaxf(mx, av[i]);
-    }
-#pragma unroll
-    for (int s = 32; s >= 1; s >>= 1) mx = fmaxf(mx, __shfl_xor(mx, s, LANES));
-    float T[4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        e[i] = i * LANES + lane < N ? expf(__fsub_rn(av[i], mx)) : 0.0f;
-        T[i] = wave_sum(e[i]);
-    }
-    Norm r;
-    r.P = __fadd_rn(__fadd_rn(__fadd_rn(T[0], T[1]), T[2]), T[3]);
-    r.F = 0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int n = i * LANES + lane;
-        const float w = __fdiv_rn(e[i], r.P);
-        const bool alive = n < N && !(e[i] == 0.0f && r.P == r.P);
-        r.F += __popcll(__ballot(alive));
-        T[i] = wave_sum(n < N ? __fmul_rn(w, __fsub_rn(1.0f, w)) : 0.0f);
-        if (n < N) {
-            wrow[n] = w;
-            lrow[n] = alive ? 0.0f : __builtin_nanf("");
-        }
-    }
-    r.Dp = __fadd_rn(__fadd_rn(__fadd_rn(T[0], T[1]), T[2]), T[3]);
-    return r;
-}
 
 // wave 0 normalises the tile's group into the block's rows and leaves (D', P, F) behind them
 __device__ __forceinline__ void normalise_block(const float* __restrict__ logw, const Tile& tl, const Dims& d, float* wrow, int wave, int lane) {
@@ -542,20 +451,6 @@ __global__ void __launch_bounds__(ST) snsde_sample_quantiles_weighted_backward_k
             if (tl.live) gys[tl.base + row_of(n, d)] = acc;
         }
     }
-}
-
-// (outer, M, G, S, W): positive, the element count fits 63 bits, N = M S within the slab
-bool dims_ok(int64_t outer, int32_t members, int64_t groups, int32_t samples, int32_t width, Dims* d) {
-    if (outer <= 0 || members <= 0 || groups <= 0 || samples <= 0 || width <= 0) return false;
-    if ((int64_t)members * samples > MAX_N) return false;
-    if (groups > INT64_MAX / samples / width) return false;
-    const int64_t per = groups * samples * width;
-    if (outer > INT64_MAX / members / per) return false;
-    d->outer = outer; d->G = groups; d->mstride = per;
-    d->M = members; d->S = samples; d->W = width; d->N = members * samples;
-    d->wtiles = ((int64_t)width + LANES - 1) / LANES;
-    d->tiles = outer * groups * d->wtiles;      // (<= outer G W)
-    return true;
 }
 
 bool levels_ok(int32_t n_q, const float* q, QLevels* ql) {

@@ -1287,7 +1287,7 @@ class _EnsembleStats(torch.autograd.Function):
         return ensemble_stats_backward(gm, gw, gb, ys, ctx.M, ctx.S), None, None, None, None
 
 
-SCORE_MAX_POOLED = 256      # pooled samples N = members * samples the score kernels stage in LDS (csrc/snsde_scores.hip: MAX_N)
+SCORE_MAX_POOLED = 256      # pooled samples N = members * samples the score kernels stage in LDS (csrc/snsde_sample_set.h: MAX_N)
 SCORE_MAX_QUANTILES = 8     # quantile levels per launch (they travel in the kernel's argument struct)
 
 

@@ -14,6 +14,7 @@ pairs enter as exact zeros, so the chain is never deeper than min(#terms - 1, 22
 N = 3: 2 and 2) - one division each and the subtraction: inside the 2 N + 8 the bound allows."""
 import copy
 import functools
+import os
 
 import numpy as np
 import pytest
@@ -116,6 +117,33 @@ def test_gradients_against_the_float64_formula_with_planted_ties(shape, fair):
     # engine.sample_energy_backward: the same launch without autograd
     hx, hy = engine.sample_energy_backward(_dev(c['g']), xd.detach(), yd.detach(), N, fair)
     assert torch.equal(hx, gx) and torch.equal(hy, gy)
+
+
+@functools.lru_cache(maxsize=None)
+def _bits():
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'sample_energy_bits.npz')
+    with np.load(path) as z:
+        return {k: z[k] for k in z.files}
+
+
+BIT_CASES = ['n2', 'n39', 'n40', 'n87', 'n88', 'n151', 'n152', 'n256', 'n40_unfair', 'n88_m2', 'path_o3_w7']
+
+
+@pytest.mark.parametrize('name', BIT_CASES)
+def test_the_bits_recorded_before_the_two_energy_kernels_became_one(name):
+    """tests/golden/sample_energy_bits.npz (make_sample_energy_bits.py): the energy and both gradients that the unweighted kernels
+    of csrc/snsde_energy.hip gave, with neither weights nor mask, before csrc/snsde_energy_weighted.hip was folded into it - N on
+    both sides of every bucket edge, V = 17 (a chunk and a tail of one), two members, fair both ways, a path whose chunk straddles
+    the outer axis, a zero distance in group 0.  torch.equal: the one kernel template computes what the unweighted kernel did."""
+    z = _bits()
+    assert sorted({k.split('/')[0] for k in z}) == sorted(BIT_CASES)
+    M, Sn, fair, path = (int(v) for v in z[f'{name}/cfg'])
+    x, y, g = (_dev(z[f'{name}/{k}']) for k in ('x', 'y', 'g'))
+    e = engine.sample_energy(x, Sn, y, fair=bool(fair), members=M, path=bool(path))
+    gx, gy = engine.sample_energy_backward(g, x, y, Sn, bool(fair), M, bool(path))
+    for key, got in (('energy', e), ('gx', gx), ('gy', gy)):
+        want = torch.from_numpy(z[f'{name}/{key}'])
+        assert got.dtype == want.dtype and torch.equal(got.cpu(), want), (name, key)
 
 
 def test_exact_zeros_where_every_direction_is_u_of_zero():

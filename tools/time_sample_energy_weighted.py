@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""The energy score of weighted, partially observed sample sets: the sibling kernels (snsde_sample_energy_weighted /
+"""The energy score of weighted, partially observed sample sets: the weighted and masked variants of the kernel (snsde_sample_energy_weighted /
 _backward) against the unweighted kernel at the same shape and against the new tensor-op statement.  Same process, HIP events, the
 variants alternating; medians.
 
