@@ -1046,6 +1046,65 @@ SNSDE_API int snsde_sample_loglik_backward(const float* grad_logpx, const float*
                                            int32_t members, int64_t groups, int32_t samples, int32_t width, float logvar, float inv_var,
                                            int32_t norm, float* grad_ys, float* grad_target, float* grad_logw, void* hip_stream);
 
+/* snsde_sample_loglik under a log standard deviation per channel or per entry in place of the one scalar variance.  ys, target,
+ * mask, logw, the outputs and the pooled layout exactly as there.  log_std holds ls = log(std):
+ *     noise_mode = SNSDE_NOISE_CHANNEL: (width); column v = o width + w of the path vector reads entry w
+ *     noise_mode = SNSDE_NOISE_ENTRY:   (outer, groups, width), the shape of target and mask
+ *     logpx[g, n] = sum_{v observed} m_v (-1/2) (log 2 pi + 2 ls_v + (y_v - x_nv)^2 exp(-2 ls_v))           (groups, N)
+ * count, norm, bound and sqerr as for snsde_sample_loglik (sqerr is not weighed by the noise); count has that call's bits.
+ * Select, never multiply, covers the noise: ls_v is loaded only where m_v != 0, so NaN or Inf at an unobserved entry reaches
+ * nothing; a NaN ls_v at an observed entry makes every logpx[g, .], bound[g] of its group NaN (in channel mode: of every group
+ * that observes the channel) and touches no other group.  The values of log_std are not checked.
+ * The decomposition of snsde_sample_loglik; the thread that stages a column forms iv_v = expf(-2 ls_v), u_v = m_v iv_v and
+ * t_v = m_v fmaf(2, ls_v, (float)log 2 pi) once per column (+0 where unobserved) into LDS beside m_v.  Summation order, a
+ * function of (N, V) only:
+ *   q_n = sum_v u_v d_nv^2: sub-lane l a chain q = fmaf(u_v d, d, q) over v = l (mod L) ascending, the L chains by a butterfly
+ *   (xor 1, .., L / 2); count = sum m_v and lv = sum t_v by the same chains and butterfly, additions;
+ *   logpx = -0.5f (q_n + lv), then the division under norm; sqerr and bound as for snsde_sample_loglik.
+ * The two modes run the same arithmetic: channel mode gives the bits of entry mode on the broadcast plane.  No atomics, no
+ * workspace, the same bits on every launch and for every pointer alignment; a pooled call gives the bits of the members = 1 call on
+ * the permuted tensor.  Every element of logpx, count, bound and sqerr is written and no other byte; the inputs are only read.
+ * Enqueue-only, capturable.  All pointers device, fp32, contiguous.  SNSDE_ERR_NULL: ys, target, mask, log_std, logpx, count,
+ * bound or sqerr NULL.  SNSDE_ERR_DIMS: a non-positive extent, N > 256, a noise_mode other than the two, an element count
+ * beyond 63 bits. */
+#define SNSDE_NOISE_CHANNEL 0
+#define SNSDE_NOISE_ENTRY 1
+SNSDE_API int snsde_sample_loglik_noise(const float* ys, const float* target, const float* mask, const float* logw,
+                                        const float* log_std, int64_t outer, int32_t members, int64_t groups, int32_t samples,
+                                        int32_t width, int32_t noise_mode, int32_t norm, float* logpx, float* count, float* bound,
+                                        float* sqerr, void* hip_stream);
+
+/* Adjoint of snsde_sample_loglik_noise, the log-std included.  grad_logpx, grad_bound, p_n and c[g, n] as for
+ * snsde_sample_loglik_backward; with d = y_v - x_nv, iv_v = expf(-2 ls_v), u_v = m_v iv_v:
+ *     grad_ys[n, v]     = (c_n u_v) d                                      (as ys; every element is written)
+ *     grad_target[v]    = -sum_n grad_ys[n, v], n ascending               (optional, NULL = not wanted)
+ *     grad_logw[g, n]   = grad_bound[g] p_n                               (optional, NULL = not wanted)
+ *     grad_log_std[v]   = m_v r_v, r_v the chain r = fmaf(c_n, fmaf(d iv_v, d, -1), r) over n ascending
+ *                         (optional, NULL = not wanted; ALWAYS the per-entry plane (outer, groups, width), in both modes)
+ * The lane that owns a column forms all of them in one walk.  Unobserved elements of grad_ys, grad_target and grad_log_std are
+ * exact +0 and their ls_v is not loaded.  In channel mode the gradient of the (width) vector is the column sum of grad_log_std:
+ * snsde_sample_loglik_noise_reduce.  Every element of each output given is written and no other byte; no atomics; the same
+ * bits on every launch.  A workgroup per (group, 256 adjacent columns).  The errors of the forward; SNSDE_ERR_NULL: ys, target,
+ * mask, log_std, logpx, count or grad_ys NULL. */
+SNSDE_API int snsde_sample_loglik_noise_backward(const float* grad_logpx, const float* grad_bound, const float* ys, const float* target,
+                                                 const float* mask, const float* logw, const float* log_std, const float* logpx,
+                                                 const float* count, int64_t outer, int32_t members, int64_t groups, int32_t samples,
+                                                 int32_t width, int32_t noise_mode, int32_t norm, float* grad_ys, float* grad_target,
+                                                 float* grad_logw, float* grad_log_std, void* hip_stream);
+
+/* grad_channel[w] = sum_r grad_entry[r, w]: the (rows, width) plane grad_log_std of snsde_sample_loglik_noise_backward
+ * (rows = outer groups) summed to the (width) gradient of a per-channel log_std, in a fixed order that depends on rows and
+ * width alone.  With R = SNSDE_LOGLIK_NOISE_REDUCE_ROWS and P = ceil(rows / R): stage 1, partial[k, w] = the rows
+ * [k R, min(rows, (k + 1) R)) of column w added ascending, k < P; stage 2, grad_channel[w] = partial[0, w] + partial[1, w] + ..
+ * ascending.  partial is the caller's (P, width) floats - the library allocates nothing; where P == 1 stage 1 writes
+ * grad_channel itself and partial may be NULL.  Every element of grad_channel (and of partial, where P > 1) is written and no
+ * other byte; grad_entry is only read.  No atomics: deterministic, independent of alignment, enqueue-only, capturable (one or
+ * two launches).  SNSDE_ERR_NULL: grad_entry or grad_channel NULL, partial NULL where P > 1.  SNSDE_ERR_DIMS: rows or width
+ * not positive, rows width beyond 63 bits. */
+#define SNSDE_LOGLIK_NOISE_REDUCE_ROWS 64
+SNSDE_API int snsde_sample_loglik_noise_reduce(const float* grad_entry, int64_t rows, int32_t width, float* partial,
+                                               float* grad_channel, void* hip_stream);
+
 /* Classification with sample paths: the predictive (model-average) negative log-likelihood of a label, the expected
  * cross-entropy, the predictive distribution and the split of its entropy.  logits viewed as (outer, M, G, S, C) exactly as ys
  * for snsde_sample_crps: pooled path n = m S + s, N = M S <= 256; one result per (o, g).  labels are int32 (outer, groups) or

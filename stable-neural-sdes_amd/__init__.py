@@ -7,7 +7,7 @@ from .modules import (Diffusion_model, Ensemble, IstsNeuralSDE, NeuralSDE, Neura
                       make_sde_model, prepare_sde_solver_kwargs)
 from .engine import (ensemble_stats, filter_particles, filter_paths, sample_class, sample_crps, sample_energy, sample_loglik,  # noqa: F401
                      sample_quantiles, sample_resample, sample_stats)
-from .train import crps_loss, energy_loss, iwae_loss, mc_class_loss  # noqa: F401
+from .train import ObservationNoise, crps_loss, energy_loss, iwae_loss, mc_class_loss  # noqa: F401
 from .torchsde import sdeint, sdeint_ensemble, sdeint_filter  # noqa: F401
 
 __version__ = '0.1.0'

@@ -119,7 +119,10 @@ EXPORTS = ('snsde_version', 'snsde_abi_check', 'snsde_strerror', 'snsde_param_co
            'snsde_sample_resample_backward',
            'snsde_sample_stats_weighted', 'snsde_sample_stats_weighted_backward', 'snsde_sample_crps_weighted',
            'snsde_sample_crps_weighted_backward', 'snsde_sample_quantiles_weighted', 'snsde_sample_quantiles_weighted_backward',
-           'snsde_sample_energy_weighted', 'snsde_sample_energy_weighted_backward')
+           'snsde_sample_energy_weighted', 'snsde_sample_energy_weighted_backward',
+           'snsde_sample_loglik_noise', 'snsde_sample_loglik_noise_backward', 'snsde_sample_loglik_noise_reduce')
+NOISE_CHANNEL, NOISE_ENTRY = 0, 1      # snsde_sample_loglik_noise: log_std is (width) / the (outer, groups, width) plane
+LOGLIK_NOISE_REDUCE_ROWS = 64          # SNSDE_LOGLIK_NOISE_REDUCE_ROWS: rows per partial of snsde_sample_loglik_noise_reduce
 
 
 MAX_AFFINE_JOBS = 12
@@ -240,6 +243,12 @@ def lib():
     # (grad_energy, ys, target, logw, mask, dims, fair, path, nan_missing, grad_ys, grad_target, stream)
     L.snsde_sample_energy_weighted.argtypes = [C.c_void_p] * 4 + dims + [C.c_int32] * 3 + [C.c_void_p] * 2
     L.snsde_sample_energy_weighted_backward.argtypes = [C.c_void_p] * 5 + dims + [C.c_int32] * 3 + [C.c_void_p] * 3
+    # (ys, target, mask, logw, log_std, dims, noise_mode, norm, logpx, count, bound, sqerr, stream) /
+    # (grad_logpx, grad_bound, ys, target, mask, logw, log_std, logpx, count, dims, noise_mode, norm, grad_ys, grad_target, grad_logw,
+    #  grad_log_std, stream) / (grad_entry, rows, width, partial, grad_channel, stream)
+    L.snsde_sample_loglik_noise.argtypes = [C.c_void_p] * 5 + dims + [C.c_int32] * 2 + [C.c_void_p] * 5
+    L.snsde_sample_loglik_noise_backward.argtypes = [C.c_void_p] * 9 + dims + [C.c_int32] * 2 + [C.c_void_p] * 5
+    L.snsde_sample_loglik_noise_reduce.argtypes = [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
     L.snsde_abi_check.argtypes = [C.c_int, C.c_size_t, C.c_size_t, C.c_size_t, C.c_size_t]
     rc = L.snsde_abi_check(ABI_VERSION, C.sizeof(Model), C.sizeof(Solve), C.sizeof(Backward), C.sizeof(Head))
     if rc != 0:

@@ -1571,7 +1571,7 @@ def _loglik_args(ys, samples, target, mask, std, members, log_weight):
     return S, M, lead, G, W, N, mask, logvar, math.exp(-logvar)
 
 
-def sample_loglik(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False):
+def sample_loglik(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False, log_std=None):
     """Masked Gaussian log-likelihood of the sample paths of a solve against a partially observed target, and its
     importance-weighted (IWAE) bound: the objective that trains options={'samples': S} on data with gaps.  ys is
     (..., B S, W) or (..., M, B S, W) as for `sample_energy(path=True)`: the pooled samples x_n (n = m S + s, N = M S) of an
@@ -1591,11 +1591,29 @@ def sample_loglik(ys, samples, target, mask=None, std=0.1, members=1, log_weight
     exact-zero gradient, whatever target or ys hold there.  NaN-marked targets (the convention of torchcde and of
     natural_cubic_spline_coeffs) are accepted as they are; the reference multiplies by the mask and needs them zero-filled.
     Fractional mask values act as weights.  A NaN in an observed element of path n makes logpx[b, n], bound[b] and sqerr[b] NaN
-    and touches no other row.  Differentiable in ys, target and log_weight; not in mask or std.
+    and touches no other row.  Differentiable in ys, target and log_weight; not in mask or a float std.
     CUDA float32 inputs with N <= 256: one launch of snsde_sample_loglik (the slab read once, no intermediate, deterministic,
     capturable) - inside an autograd node whose backward is snsde_sample_loglik_backward when an input requires grad.  Other
-    tensors: `sample_loglik_tensor_ops`."""
+    tensors: `sample_loglik_tensor_ops`.
+    Noise per channel or per entry, learned or known.  std may be a tensor instead, or log_std = log(std) may be given - the
+    parametrisation of a learnable parameter; exactly one of them describes the noise, so log_std together with a std other than
+    the default float is a ValueError.  With W = ys.shape[-1] the tensor is (W,): per channel, component v = o W + w of the vector
+    uses entry w; or the shape of target (..., B, W): per entry, a known error bar for every measurement; a 0-dim tensor is the
+    (W,) vector of that one value.  With ls_v the log-std of component v of row b,
+        logpx[b, n] = sum_{v observed} m_v (-1/2) (log 2 pi + 2 ls_v + (y_v - x_nv)^2 exp(-2 ls_v))
+    and count, norm, bound, sqerr, log_weight and members as above.  The call is differentiable in the noise tensor too:
+    d logpx[b, n] / d ls_v = m_v ((y_v - x_nv)^2 exp(-2 ls_v) - 1); a tensor std enters as std.log() in tensor ops, so autograd
+    chains through it.  Select, never multiply covers the noise: at an unobserved element ls_v is never read into a sum - NaN
+    or Inf there reaches no value and no gradient - and its own gradient is an exact +0; a NaN ls_v at an observed element makes
+    the logpx and bound of the rows that observe it NaN and no other.  A tensor std must be > 0: that is checked for a CPU
+    tensor, where the check costs no device synchronisation, and NOT for a CUDA tensor - a std <= 0 there gives NaN (or, at 0,
+    infinite) results in the rows that observe it, like any NaN ls_v.  log_std is never checked.
+    CUDA float32 tensors on one device with N <= 256 run snsde_sample_loglik_noise, and snsde_sample_loglik_noise_backward
+    (followed, for a per-channel tensor, by snsde_sample_loglik_noise_reduce: a fixed-order column sum) as the backward; everything
+    else `sample_loglik_tensor_ops`.  A float std with log_std=None is the scalar call above: its code path, kernel and bits."""
     norm, stats = bool(norm), bool(stats)
+    if log_std is not None or isinstance(std, torch.Tensor):
+        return _sample_loglik_noise(ys, samples, target, mask, std, members, log_weight, norm, stats, log_std)
     S, M, lead, G, W, N, mask, logvar, inv_var = _loglik_args(ys, samples, target, mask, std, members, log_weight)
     others = (target, mask) if log_weight is None else (target, mask, log_weight)
     if _score_native(ys, N, *others):
@@ -1608,11 +1626,17 @@ def sample_loglik(ys, samples, target, mask=None, std=0.1, members=1, log_weight
     return sample_loglik_tensor_ops(ys, S, target, mask, std, M, log_weight, norm, stats)
 
 
-def sample_loglik_tensor_ops(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False):
+def sample_loglik_tensor_ops(ys, samples, target, mask=None, std=0.1, members=1, log_weight=None, norm=False, stats=False,
+                             log_std=None):
     """`sample_loglik` stated in tensor ops (any device and dtype; autograd differentiates it): torch.where on the mask selects
     the observed residuals - never a product with the mask - so NaN and Inf at unobserved positions reach neither a value nor a
-    gradient.  What `sample_loglik` runs off the kernels' domain, and the baseline the kernels are timed against."""
+    gradient; a tensor std / log_std is selected the same way.  What `sample_loglik` runs off the kernels' domain, and the
+    baseline the kernels are timed against."""
     norm, stats = bool(norm), bool(stats)
+    noise = log_std is not None or isinstance(std, torch.Tensor)
+    if noise:
+        ls, entry = _loglik_noise_arg(std, log_std, target)
+        std = LOGLIK_DEFAULT_STD
     S, M, lead, G, W, N, mask, logvar, inv_var = _loglik_args(ys, samples, target, mask, std, members, log_weight)
     O = _outer(lead)
     x = _pooled(ys, S, M, lead, G, W).reshape(O, G, N, W).permute(1, 2, 0, 3).reshape(G, N, O * W)      # (G, N, V)
@@ -1620,7 +1644,13 @@ def sample_loglik_tensor_ops(ys, samples, target, mask=None, std=0.1, members=1,
     m = mask.detach().to(x.dtype).reshape(O, G, W).permute(1, 0, 2).reshape(G, 1, O * W)
     obs = m != 0
     d = torch.where(obs, y - x, x.new_zeros(()))                                  # (G, N, V): exact zeros where unobserved
-    logpx = (-0.5 * m * ((math.log(2.0 * math.pi) + logvar) + d * d * inv_var)).sum(dim=-1)
+    if noise:
+        lsv = ls.to(x.dtype)
+        lsv = lsv.reshape(O, G, W).permute(1, 0, 2).reshape(G, 1, O * W) if entry else lsv.expand(O, W).reshape(1, 1, O * W)
+        lsv = torch.where(obs, lsv, x.new_zeros(()))                              # (G, 1, V): selected like the residuals
+        logpx = (-0.5 * m * ((math.log(2.0 * math.pi) + 2.0 * lsv) + d * d * torch.exp(-2.0 * lsv))).sum(dim=-1)
+    else:
+        logpx = (-0.5 * m * ((math.log(2.0 * math.pi) + logvar) + d * d * inv_var)).sum(dim=-1)
     count = m.sum(dim=-1)                                                         # (G, 1)
     if norm:
         some = count > 0
@@ -1703,6 +1733,150 @@ class _SampleLoglik(torch.autograd.Function):
         gys, gt, glw = _sample_loglik_backward_launch(gl, gb, ys, target, mask, lw, logpx, count, ctx.S, ctx.M, ctx.logvar, ctx.inv_var,
                                                       ctx.norm, ctx.needs_input_grad[1], ctx.has_logw and ctx.needs_input_grad[3])
         return (gys if ctx.needs_input_grad[0] else None), gt, None, glw, None, None, None, None, None
+
+
+LOGLIK_DEFAULT_STD = 0.1      # sample_loglik's std when the noise is a tensor (log_std, or a tensor std)
+
+
+def _loglik_noise_arg(std, log_std, target):
+    """(log_std, entry) of a tensor noise: log_std as a tensor of shape (W,) (entry False: per channel) or target's (entry True);
+    the argument errors of the noise.  A 0-dim tensor is expanded to (W,)."""
+    if log_std is not None:
+        if isinstance(std, torch.Tensor) or isinstance(std, bool) or std != LOGLIK_DEFAULT_STD:
+            raise ValueError(f'std and log_std both describe the observation noise: give one of them (std is {std!r} with log_std set)')
+        if not isinstance(log_std, torch.Tensor) or not log_std.dtype.is_floating_point:
+            raise ValueError(f'log_std must be a floating-point tensor (the log standard deviation of the observation noise), got '
+                             f'{log_std!r}')
+        ls = log_std
+    else:
+        if not std.dtype.is_floating_point:
+            raise ValueError(f'a tensor std must be floating point, got {std.dtype}')
+        if not std.is_cuda and not bool((std > 0).all()):      # (free on the host; a CUDA tensor is not read back)
+            raise ValueError('a tensor std must be > 0 everywhere (the standard deviation of the observation noise)')
+        ls = std.log()
+    if target.dim() < 2:
+        raise ValueError(f'target has shape {tuple(target.shape)}, expected (..., B, W)')
+    W = target.shape[-1]
+    if ls.dim() == 0:
+        return ls.expand(W), False
+    if tuple(ls.shape) == (W,):
+        return ls, False
+    if tuple(ls.shape) == tuple(target.shape):
+        return ls, True
+    raise ValueError(f'the noise tensor has shape {tuple(ls.shape)}, expected {(W,)} (per channel) or {tuple(target.shape)} (per '
+                     f'entry: the shape of target)')
+
+
+def _sample_loglik_noise(ys, samples, target, mask, std, members, log_weight, norm, stats, log_std):
+    """`sample_loglik` with a tensor noise: the kernels' route or the tensor-op statement."""
+    ls, entry = _loglik_noise_arg(std, log_std, target)
+    S, M, lead, G, W, N, mask, _, _ = _loglik_args(ys, samples, target, mask, LOGLIK_DEFAULT_STD, members, log_weight)
+    others = (target, mask, ls) if log_weight is None else (target, mask, ls, log_weight)
+    if _score_native(ys, N, *others):
+        if any(t.requires_grad for t in (ys,) + others) and torch.is_grad_enabled():
+            out = _SampleLoglikNoise.apply(ys, target, mask, log_weight, ls, S, M, entry, norm)
+        else:
+            out = _sample_loglik_noise_launch(ys.contiguous(), target.contiguous(), mask.contiguous(),
+                                              None if log_weight is None else log_weight.contiguous(), ls.contiguous(), S, M, entry, norm)
+        return out if stats else out[0]
+    return sample_loglik_tensor_ops(ys, S, target, mask, LOGLIK_DEFAULT_STD, M, log_weight, norm, stats, log_std=ls)
+
+
+def _sample_loglik_noise_launch(ys, target, mask, logw, ls, S, M, entry, norm):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    N = M * S
+    logpx = torch.empty((G, N), device=ys.device, dtype=torch.float32)
+    count, bound, sqerr = (torch.empty((G,), device=ys.device, dtype=torch.float32) for _ in range(3))
+    _lib.check(_lib.lib().snsde_sample_loglik_noise(_ptr(ys), _ptr(target), _ptr(mask), _ptr(logw), _ptr(ls), _outer(lead), M, G, S, W,
+                                                    _lib.NOISE_ENTRY if entry else _lib.NOISE_CHANNEL, int(norm), _ptr(logpx), _ptr(count),
+                                                    _ptr(bound), _ptr(sqerr), C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_loglik_noise')
+    return bound, logpx, count, sqerr
+
+
+def sample_loglik_noise_reduce(grad_entry):
+    """The (W,) column sum of a per-entry gradient plane (..., B, W) in the fixed order of snsde_sample_loglik_noise_reduce: the
+    rows in blocks of 64, each block ascending, then the blocks ascending.  A contiguous float32 CUDA tensor; the partial sums are
+    allocated here (torch.empty), not by the library."""
+    _check_f32('grad_entry', grad_entry)
+    W = grad_entry.shape[-1]
+    rows = grad_entry.numel() // W
+    parts = -(-rows // _lib.LOGLIK_NOISE_REDUCE_ROWS)
+    partial = torch.empty((parts, W), device=grad_entry.device, dtype=torch.float32) if parts > 1 else None
+    out = torch.empty((W,), device=grad_entry.device, dtype=torch.float32)
+    _lib.check(_lib.lib().snsde_sample_loglik_noise_reduce(_ptr(grad_entry), rows, W, _ptr(partial), _ptr(out),
+                                                           C.c_void_p(torch.cuda.current_stream(grad_entry.device).cuda_stream)),
+               'snsde_sample_loglik_noise_reduce')
+    return out
+
+
+def sample_loglik_noise_backward(grad_logpx, grad_bound, ys, target, mask, log_std, logpx, count, samples, members=1, log_weight=None,
+                                 norm=False, grad_target=True, grad_log_weight=True, grad_log_std=True):
+    """`sample_loglik_backward` for a tensor noise: (dL/d ys, dL/d target, dL/d log_weight, dL/d log_std) from dL/d logpx and
+    dL/d bound and the forward's logpx and count, bypassing autograd: one launch of snsde_sample_loglik_noise_backward and, for a
+    (W,) log_std, `sample_loglik_noise_reduce` of its per-entry plane.  dL/d log_std has log_std's shape (for a 0-dim log_std: (W,), the gradient of its expansion); each optional gradient
+    is None when not wanted.  Contiguous float32 CUDA tensors; log_std is (W,) or target's shape."""
+    ls, entry = _loglik_noise_arg(LOGLIK_DEFAULT_STD, log_std, target)
+    ls = ls.contiguous()      # (a 0-dim log_std arrives as a stride-0 view of W elements)
+    S, M, lead, G, W, N, mask, _, _ = _loglik_args(ys, samples, target, mask, LOGLIK_DEFAULT_STD, members, log_weight)
+    _check_f32('ys', ys)
+    _check_f32('target', target)
+    _check_f32('mask', mask)
+    _check_f32('log_std', ls)
+    _check_f32('logpx', logpx, (G, N))
+    _check_f32('count', count, (G,))
+    for name, t, shape in (('grad_logpx', grad_logpx, (G, N)), ('grad_bound', grad_bound, (G,)), ('log_weight', log_weight, (G, N))):
+        if t is not None:
+            _check_f32(name, t, shape)
+    return _sample_loglik_noise_backward_launch(grad_logpx, grad_bound, ys, target, mask, log_weight, ls, logpx, count, S, M, entry,
+                                                bool(norm), grad_target, grad_log_weight, grad_log_std)
+
+
+def _sample_loglik_noise_backward_launch(grad_logpx, grad_bound, ys, target, mask, logw, ls, logpx, count, S, M, entry, norm,
+                                         grad_target, grad_logw, grad_ls):
+    S_, M_, lead, G, W = _score_dims(ys, S, M)
+    gys = torch.empty_like(ys)
+    gt = torch.empty_like(target) if grad_target else None
+    glw = torch.empty_like(logpx) if grad_logw else None
+    gls = torch.empty_like(target) if grad_ls else None      # (the per-entry plane, in both modes)
+    _lib.check(_lib.lib().snsde_sample_loglik_noise_backward(_ptr(grad_logpx), _ptr(grad_bound), _ptr(ys), _ptr(target), _ptr(mask),
+                                                             _ptr(logw), _ptr(ls), _ptr(logpx), _ptr(count), _outer(lead), M, G, S, W,
+                                                             _lib.NOISE_ENTRY if entry else _lib.NOISE_CHANNEL, int(norm), _ptr(gys),
+                                                             _ptr(gt), _ptr(glw), _ptr(gls),
+                                                             C.c_void_p(torch.cuda.current_stream(ys.device).cuda_stream)),
+               'snsde_sample_loglik_noise_backward')
+    if grad_ls and not entry:
+        gls = sample_loglik_noise_reduce(gls)
+    return gys, gt, glw, gls
+
+
+class _SampleLoglikNoise(torch.autograd.Function):
+    """sample_loglik with a tensor noise, of CUDA float32 tensors of which one requires grad: snsde_sample_loglik_noise, and
+    snsde_sample_loglik_noise_backward (plus the fixed-order reduce for a per-channel log_std) as its backward, from the saved
+    logpx and count.  count and sqerr carry no gradient; mask receives none."""
+
+    @staticmethod
+    def forward(ctx, ys, target, mask, logw, ls, S, M, entry, norm):
+        ysc, tc, mc, lsc = (t.detach().contiguous() for t in (ys, target, mask, ls))
+        lw = None if logw is None else logw.detach().contiguous()
+        bound, logpx, count, sqerr = _sample_loglik_noise_launch(ysc, tc, mc, lw, lsc, S, M, entry, norm)
+        ctx.S, ctx.M, ctx.entry, ctx.norm, ctx.has_logw = S, M, entry, norm, lw is not None
+        ctx.save_for_backward(ysc, tc, mc, lsc, logpx, count, *(() if lw is None else (lw,)))
+        ctx.mark_non_differentiable(count, sqerr)
+        ctx.set_materialize_grads(False)
+        return bound, logpx, count, sqerr
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_bound, grad_logpx, grad_count, grad_sqerr):
+        ys, target, mask, ls, logpx, count = ctx.saved_tensors[:6]
+        lw = ctx.saved_tensors[6] if ctx.has_logw else None
+        gb = None if grad_bound is None else grad_bound.to(torch.float32).contiguous()
+        gl = None if grad_logpx is None else grad_logpx.to(torch.float32).contiguous()
+        gys, gt, glw, gls = _sample_loglik_noise_backward_launch(gl, gb, ys, target, mask, lw, ls, logpx, count, ctx.S, ctx.M, ctx.entry,
+                                                                 ctx.norm, ctx.needs_input_grad[1],
+                                                                 ctx.has_logw and ctx.needs_input_grad[3], ctx.needs_input_grad[4])
+        return (gys if ctx.needs_input_grad[0] else None), gt, None, glw, gls, None, None, None, None
 
 
 SampleClass = collections.namedtuple('SampleClass', 'nll xent logp probs entropy expected_entropy mutual_information')

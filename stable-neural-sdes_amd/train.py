@@ -109,15 +109,67 @@ def energy_loss(samples, fair=True, members=1, masked=False):
     return loss_fn
 
 
-def iwae_loss(samples, std=0.1, members=1, norm=False):
+class ObservationNoise(torch.nn.Module):
+    """A model together with the observation noise it is scored under: `forward` is the wrapped model's, and `log_std` is an
+    nn.Parameter of shape (channels,) - the log standard deviation of the noise per output channel, initialised to log(std) -
+    which `iwae_loss(S, noise=this)` reads at every call.  Because the module wraps the model, a `make_model()` given to `main`
+    can return (ObservationNoise(model, channels), vector_field): `net.parameters()` reaches the noise, the optimizer (and a
+    recorded `GraphedStep`) updates it in place, and `main` needs no further argument.  The wrapped model's entries of
+    `state_dict()` carry the prefix `model.` (`model.<name>`), beside `log_std`.  per_step=T (an integer; default False) gives
+    every one of the T output times its own scale: log_std is then (T, channels), for a model that returns (B S, T, channels)."""
+
+    def __init__(self, model, channels, std=0.1, per_step=False):
+        super().__init__()
+        if isinstance(channels, bool) or not isinstance(channels, int) or channels < 1:
+            raise ValueError(f'channels must be an integer >= 1 (the output channels of the model), got {channels!r}')
+        if isinstance(std, bool) or not isinstance(std, (int, float)) or not math.isfinite(std) or std <= 0:
+            raise ValueError(f'std must be a finite number > 0 (the initial standard deviation of the noise), got {std!r}')
+        if per_step is not False and (isinstance(per_step, bool) or not isinstance(per_step, int) or per_step < 1):
+            raise ValueError(f'per_step must be False or the number of output times (an integer >= 1), got {per_step!r}')
+        self.model = model
+        shape = (channels,) if per_step is False else (per_step, channels)
+        self.log_std = torch.nn.Parameter(torch.full(shape, math.log(float(std)), dtype=torch.float32))
+
+    def forward(self, *args, **kwargs):
+        return self.model(*args, **kwargs)
+
+    @property
+    def std(self):
+        return self.log_std.detach().exp()
+
+
+def _flat_log_std(noise, trailing, width):
+    """noise.log_std as the (width,) vector of a prediction whose trailing axes `trailing` are flattened into the width: a tensor
+    of the trailing shape (or already flat) as it is, (channels,) = trailing[-1:] repeated over the axes in front of it."""
+    ls = noise.log_std
+    if tuple(ls.shape) in (tuple(trailing), (width,)):
+        return ls.reshape(width)
+    if trailing and tuple(ls.shape) == (trailing[-1],):
+        return ls.expand(trailing).reshape(width)
+    raise ValueError(f'iwae_loss: noise.log_std has shape {tuple(ls.shape)} for a prediction of {tuple(trailing)} per path: expected '
+                     f'{tuple(trailing[-1:])} (per channel) or {tuple(trailing)}')
+
+
+def iwae_loss(samples, std=0.1, members=1, norm=False, noise=None):
     """loss_fn(pred, true) for `train_loop` / `GraphedStep` / `evaluate_metrics`: minus the mean importance-weighted bound
     (engine.sample_loglik) of a model solved with options={'samples': S} against a partially observed target - the multi-sample
     ELBO / IWAE objective on data with gaps.  pred and true as for `energy_loss`: (B S, ...) or (M, B S, ...), and (B, ...);
     trailing axes are flattened into the vector.  A NaN in true marks a missing entry (the mask is ~isnan(true)); data that
     carries its own mask is passed as true = (values, mask).  std is the standard deviation of the observation noise; norm
-    divides each row's likelihood by its number of observed entries."""
+    divides each row's likelihood by its number of observed entries.
+    noise: an `ObservationNoise`, or any object with a tensor `.log_std`, replaces the constant std by a learned scale per
+    output channel (sample_loglik(log_std=)); it is read at every call, not captured by value, so a parameter that the optimizer
+    updates in place is followed - also inside a recorded `GraphedStep`.  The trailing axes (T, out) of a prediction are
+    flattened into the vector, component t out + c, so the (out,) log_std is tiled T times into a (T out,) vector - T out
+    floats; the slab and the (B, T out) planes are not copied - and scored in the kernel's per-channel mode at width T out.
+    noise together with a std other than the default is a ValueError."""
     from . import engine
     S = engine.check_samples(samples)
+    if noise is not None:
+        if isinstance(std, bool) or std != engine.LOGLIK_DEFAULT_STD:
+            raise ValueError(f'iwae_loss: noise and std both describe the observation noise: give one of them (std is {std!r})')
+        if not isinstance(getattr(noise, 'log_std', None), torch.Tensor):
+            raise ValueError(f'iwae_loss: noise must have a tensor attribute log_std (an ObservationNoise), got {noise!r}')
 
     lead = 1 if members > 1 else 0      # (an Ensemble's leading member axis)
 
@@ -132,7 +184,10 @@ def iwae_loss(samples, std=0.1, members=1, norm=False):
         pred = pred_y.reshape(want + (-1,))
         true = true_y.reshape(true_y.shape[0], -1).to(pred.dtype)
         mask = None if mask is None else mask.reshape(true.shape).to(pred.dtype)
-        return -engine.sample_loglik(pred, S, true, mask=mask, std=std, members=members, norm=norm).mean()
+        if noise is None:
+            return -engine.sample_loglik(pred, S, true, mask=mask, std=std, members=members, norm=norm).mean()
+        ls = _flat_log_std(noise, tuple(pred_y.shape[lead + 1:]), pred.shape[-1]).to(pred.dtype)
+        return -engine.sample_loglik(pred, S, true, mask=mask, members=members, norm=norm, log_std=ls).mean()
     return loss_fn
 
 
